@@ -6,7 +6,15 @@ One *step* = one greedy decode token of Gemma-2B Q4_0 at batch 1 through the dev
 one hipGraph replay), after a 128-token synthetic prompt.  Weights are synthetic (seeded, Gemma-2B
 shapes, generated on the GPU; DESIGN.md §Synthetic weights) — no checkpoint is available offline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu] [--profile-out PATH]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu]]
+
+A plain run does what the headline needs and nothing else: engine setup (weights, measured launch
+plan), the prompt, W warmup steps, the K timed steps, then ONE JSON line (`value` tok/s,
+`ms_per_step`).  --full adds every other leg to the same line: the Gemma-7B row-split leg, the Q8_0 /
+Q6_K-output / Q4_K_M decodes, batched prefill, the ggml-API path, the K-quant matvecs, the per-kernel
+HBM roofline with its probes, and the CPU baseline (--no-cpu skips that one).  --dump-outputs DIR
+writes the timed call's results as DIR/<name>.npy (dump_outputs below); weights, prompt and greedy
+sampling are seeded and fixed, so two builds run with the same arguments can be compared file by file.
 
 N > 1: one process per GPU (torch.distributed.run).  The headline `value` is ONE Gemma-2B Q4_0
 decode stream with every weight matrix row-split across the N GPUs and RCCL all-gathers inside the
@@ -396,6 +404,26 @@ def merge_legs(rccl, p2p):
     return best
 
 
+def dump_outputs(eng, steps, out_dir):
+    """--dump-outputs: what the timed `eng.step(steps)` call handed its caller, as float64 .npy files.
+
+    tokens.npy            [steps]    the greedy token of every timed step, in order (the last entry is
+                                     the last timed step's); the call returns no logits, the tokens
+                                     are its whole result (ids < 2^24: exact in floating point)
+    next_step_logits.npy  [n_vocab]  the logits row of ONE further replay of the same decode graph,
+                                     which consumes the last timed token: the full-width fingerprint
+                                     of the state the timed steps left (KV cache, position, token)
+    Runs after the timed region; the files total ~2 MB."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    seq = eng.tokens()
+    files = {"tokens": np.asarray(seq[len(seq) - steps:], dtype=np.float64),
+             "next_step_logits": eng.step(1, want_logits=True, use_graph=True)[0].astype(np.float64)}
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in files.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -404,15 +432,23 @@ def main():
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--ctx", type=int, default=512)
     ap.add_argument("--wtype", choices=["q4_0", "q8_0"], default="q4_0")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (other formats, prefill, 7B row-split, ggml path, "
+                         "K-quant matvecs, per-kernel roofline, CPU baseline); off: only setup, warmup and the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed call's results to DIR/<name>.npy after the timed steps (see dump_outputs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--kernel-iters", type=int, default=50)
-    ap.add_argument("--prefill", type=int, default=2048, help="prefill leg prompt length (0 = skip)")
-    ap.add_argument("--ggml-steps", type=int, default=64, help="decode steps of the ggml-API drop-in leg (0 = skip)")
+    ap.add_argument("--prefill", type=int, default=2048, help="with --full: prefill leg prompt length (0 = skip)")
+    ap.add_argument("--ggml-steps", type=int, default=64, help="with --full: decode steps of the ggml-API drop-in leg (0 = skip)")
     ap.add_argument("--no-tune", action="store_true", help="default launch plan instead of the measured one")
-    ap.add_argument("--tp-steps", type=int, default=48, help="Gemma-7B row-split decode leg steps (0 = skip)")
-    ap.add_argument("--q8-steps", type=int, default=48, help="Gemma-2B Q8_0 decode leg steps (0 = skip)")
+    ap.add_argument("--tp-steps", type=int, default=48, help="with --full: Gemma-7B row-split decode leg steps (0 = skip)")
+    ap.add_argument("--q8-steps", type=int, default=48, help="with --full: Gemma-2B Q8_0 decode leg steps (0 = skip)")
     ap.add_argument("--tp-timeout", type=int, default=360, help="time limit of the TP leg's child processes (s)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline only, every other leg off
+        args.tp_steps = args.q8_steps = args.prefill = args.ggml_steps = 0
+        args.no_cpu = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -472,6 +508,10 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        log(f'outputs of the timed steps -> {args.dump_outputs}')
+        dumped = dump_outputs(eng, args.steps, args.dump_outputs)
 
     # row-split TP leg (BASELINE config 4): Gemma-7B Q4_0 batch-1 decode, weights row-split across
     # the job's GPUs with RCCL all-gathers (one rank per GPU; at N = 1 the same engine unsplit)
@@ -651,7 +691,7 @@ def main():
     # K-quant leg: Q4_K / Q6_K x Q8_K matvec alone at Gemma-2B shapes, cold weights
     log('kquant matvec leg')
     kquant = {}
-    for t, name in ((G.GGML_TYPE_Q4_K, "q4_K"), (G.GGML_TYPE_Q6_K, "q6_K")):
+    for t, name in ((G.GGML_TYPE_Q4_K, "q4_K"), (G.GGML_TYPE_Q6_K, "q6_K")) if args.full else ():
         for rows, K, nm in ((16384, 2048, "gate"), (2048, 16384, "down"), (256000, 2048, "output")):
             ab = C.c_double()
             us = G.lib().gemma_kq_time(t, rows, K, 30, C.byref(ab))
@@ -660,17 +700,36 @@ def main():
 
     # roofline leg: each hot matvec timed alone with hipEvents on the engine stream
     log('roofline leg')
-    kern = {}
-    for k in (0, 1, 2, 3, 4):
-        us, algo = eng.time_kernel(k, args.kernel_iters)
-        kern[k] = (us, algo)
-    dominant = max(kern, key=lambda k: kern[k][0] * KERNEL_CALLS_PER_TOKEN[k])
-    us, algo = kern[dominant]
-    achieved = algo / (us * 1e-6) / 1e9
-    traffic = load_traffic(dominant)
-    # measured HBM read roofline on this box: streaming read of 4 GiB (defeats the Infinity Cache)
-    hbm_probes = [eng.L.gemma_hbm_read_probe(local_rank, 4 << 30, 5, v) for v in (0, 1)]
-    hbm_measured = max(hbm_probes)
+    kern, roofline, hbm_measured = {}, None, 0.0
+    if args.full:
+        for k in (0, 1, 2, 3, 4):
+            us, algo = eng.time_kernel(k, args.kernel_iters)
+            kern[k] = (us, algo)
+        dominant = max(kern, key=lambda k: kern[k][0] * KERNEL_CALLS_PER_TOKEN[k])
+        us, algo = kern[dominant]
+        achieved = algo / (us * 1e-6) / 1e9
+        traffic = load_traffic(dominant)
+        # measured HBM read roofline of this GPU: streaming read of 4 GiB (defeats the Infinity Cache)
+        hbm_probes = [eng.L.gemma_hbm_read_probe(local_rank, 4 << 30, 5, v) for v in (0, 1)]
+        hbm_measured = max(hbm_probes)
+        roofline = {"bound": "hbm", "kernel": KERNEL_NAMES[dominant], "achieved": round(achieved, 1),
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                    "traffic": traffic, "avg_us": round(us, 3), "algo_bytes": int(algo),
+                    "measured_peak": round(hbm_measured, 1),
+                    "measured_peak_probes": {"vgpr_loads_nt": round(hbm_probes[0], 1), "lds_dma_nt": round(hbm_probes[1], 1),
+                                             "what": "4 GiB streaming reads; measured_peak = the faster (a plain "
+                                                     "float4 copy kernel: 6.29 TB/s)"},
+                    "frac_of_measured": round(achieved / hbm_measured, 4) if hbm_measured > 0 else None,
+                    "timing": "hipEvents over back-to-back launches rotating over the 18 layers' matrices",
+                    "graph_profile": load_graph_profile(),
+                    "classes": {KERNEL_NAMES[k]: {"avg_us": round(v[0], 3), "algo_bytes": int(v[1]),
+                                                  "GB/s": round(v[1] / (v[0] * 1e-6) / 1e9, 1),
+                                                  "frac": round(v[1] / (v[0] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+                                                  "frac_of_measured": (round(v[1] / (v[0] * 1e-6) / 1e9 / hbm_measured, 4)
+                                                                       if hbm_measured > 0 else None),
+                                                  "launches_per_token": KERNEL_CALLS_PER_TOKEN[k],
+                                                  "traffic": load_traffic(k)}
+                                for k, v in kern.items()}}
 
     log('cpu baseline')
     cpu = None
@@ -704,7 +763,7 @@ def main():
             "launches_per_token": launches,
             "prefill_tok_s": prefill["tok_s"] if prefill else None,
             "prefill": prefill,
-            "kquant_matvec": kquant,
+            "kquant_matvec": kquant if args.full else None,
             "q8_0_decode": q8,
             "q4_0_q6k_output_decode": q6o,
             "q4_k_m_decode": kqm,
@@ -714,25 +773,10 @@ def main():
             "launch_plan": {k: ({"k_split": v[0], "rows_per_wg": v[1], "image": v[2]} if isinstance(v, tuple) else
                                 ("split" if v else "per_head")) for k, v in plan.items()},
             "prefill_serial_tok_s": round(args.prompt / prefill_serial_s, 2),
-            "roofline": {"bound": "hbm", "kernel": KERNEL_NAMES[dominant], "achieved": round(achieved, 1),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": traffic, "avg_us": round(us, 3), "algo_bytes": int(algo),
-                         "measured_peak": round(hbm_measured, 1),
-                         "measured_peak_probes": {"vgpr_loads_nt": round(hbm_probes[0], 1), "lds_dma_nt": round(hbm_probes[1], 1),
-                                                  "what": "4 GiB streaming reads; measured_peak = the faster (the guide's "
-                                                          "float4 copy: 6.29 TB/s)"},
-                         "frac_of_measured": round(achieved / hbm_measured, 4) if hbm_measured > 0 else None,
-                         "timing": "hipEvents over back-to-back launches rotating over the 18 layers' matrices",
-                         "graph_profile": load_graph_profile(),
-                         "classes": {KERNEL_NAMES[k]: {"avg_us": round(v[0], 3), "algo_bytes": int(v[1]),
-                                                       "GB/s": round(v[1] / (v[0] * 1e-6) / 1e9, 1),
-                                                       "frac": round(v[1] / (v[0] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
-                                                       "frac_of_measured": (round(v[1] / (v[0] * 1e-6) / 1e9 / hbm_measured, 4)
-                                                                            if hbm_measured > 0 else None),
-                                                       "launches_per_token": KERNEL_CALLS_PER_TOKEN[k],
-                                                       "traffic": load_traffic(k)}
-                                     for k, v in kern.items()}},
-            "kernels_us": {KERNEL_NAMES[k]: round(v[0], 3) for k, v in kern.items()},
+            "full": args.full,
+            "outputs": dumped,
+            "roofline": roofline,
+            "kernels_us": {KERNEL_NAMES[k]: round(v[0], 3) for k, v in kern.items()} if args.full else None,
             "token_weight_bytes": 1409679360 if args.wtype == "q4_0" else 2662727680,
             "cpu_baseline": cpu,
         }

@@ -3,7 +3,7 @@
 # time limit, the script stops at the first failure):
 #   bash scripts/gpu_check.sh TAG "MODE ..."
 #   tests      pytest -m gpu (thread timeouts, so a hang names its test)
-#   bench      python bench.py (the driver's line)
+#   bench      python bench.py --full (every leg in one line)
 #   prof       the bench under rocprofv3 --kernel-trace --stats (csv kernel stats)
 #   profgraph  the fixed-plan decode (scripts/decode_prof.py) as hipGraph replays under rocprofv3
 #              --kernel-trace --stats -> decode_kernels_graph.md (per-class table of the benched path)
@@ -23,8 +23,8 @@ for w in $WHAT; do
   case $w in
     tests) timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $OUT/pytest_gpu.log 2>&1 || { tail -30 $OUT/pytest_gpu.log; exit 1; } ; tail -2 $OUT/pytest_gpu.log ;;
     smoke) timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; } ; cat $OUT/smoke.log ;;
-    bench) timeout -k 10 500 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; } ; cat $OUT/bench.json ;;
-    prof) timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --no-cpu --steps 32 > $OUT/prof.log 2>&1 || { tail -20 $OUT/prof.log; exit 1; } ;
+    bench) timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; } ; cat $OUT/bench.json ;;
+    prof) timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --full --no-cpu --steps 32 > $OUT/prof.log 2>&1 || { tail -20 $OUT/prof.log; exit 1; } ;
           find $OUT/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/kernel_stats.csv ; head -12 $OUT/kernel_stats.csv | cut -c1-200 ;;
     profgraph) TORCH_FIRST=${TORCH_FIRST:-1} PROF_MAPS=$OUT/maps_profg.txt GHIP_PROF_GRAPH=1 PLAN=$PLAN timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profg -o run -- python3 scripts/decode_prof.py 48 > $OUT/profg.log 2>&1 || { tail -40 $OUT/profg.log; exit 1; } ;
           python3 scripts/decode_classes.py $(find $OUT/profg -name "run_kernel_trace.csv" | head -1) 128 48 "$PLAN (hipGraph replay)" $OUT/decode_kernels_graph.json > $OUT/decode_kernels_graph.md && cat $OUT/decode_kernels_graph.md ;;

@@ -51,7 +51,7 @@ stats = glob.glob(os.path.join(src, "prof", "**", "*kernel_stats.csv"), recursiv
 if stats:
     rows = list(csv.DictReader(open(stats[0])))
     with open(os.path.join(out, "kernel_stats.md"), "w") as f:
-        f.write("# rocprofv3 --kernel-trace --stats: `python3 bench.py --no-cpu --steps 32`\n\n")
+        f.write("# rocprofv3 --kernel-trace --stats: `python3 bench.py --full --no-cpu --steps 32`\n\n")
         f.write("| kernel | calls | total ms | avg us | min us | max us | % |\n|---|---|---|---|---|---|---|\n")
         for r in rows[:40]:
             f.write(f"| `{short(r['Name'])}` | {r['Calls']} | {float(r['TotalDurationNs'])/1e6:.3f} | "
