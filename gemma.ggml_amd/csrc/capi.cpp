@@ -286,7 +286,7 @@ extern "C" void mul_mat(int64_t ne01, int64_t ne11, int64_t ne12, int64_t nb01, 
         if (hipMemcpyAsync((void *)dev_w, wdata, w_bytes, hipMemcpyHostToDevice, s.stream) != hipSuccess)
             return fail("mul_mat: wdata upload failed");
         mv_args a;
-        a.qs = W->qs; a.sc = W->sc; a.rows = W->rows; a.n_rt = W->n_rt; a.n_bt = W->n_bt; a.nb = W->nb;
+        set_mat(a, *W);
         a.x = dev_w; a.x_col_stride = (int64_t)row_size;
         a.y = dev_dst; a.y_col_stride = ne01;
         a.ncols = (int)col_num;
@@ -400,7 +400,7 @@ static int test_gemm(bool exact, int type, int64_t rows, int64_t K, int64_t T, c
     qa.x = d_x; qa.ldx = K; qa.K = K; qa.q = d_q; qa.qh = exact ? d_h : nullptr; qa.ldq = ldq; qa.da = d_da; qa.ldd = ldd;
     if (r == 0) r = launch_quant_rows(QR_F32, qa, (int)T, nullptr);
     gemm_args g;
-    g.qs = m.qs; g.sc = m.sc; g.rows = rows; g.n_rt = m.n_rt; g.n_bt = m.n_bt; g.nb = m.nb;
+    set_mat(g, m);
     g.xq = d_q; g.xh = d_h; g.ldq = ldq; g.da = d_da; g.ldd = ldd; g.T = T; g.y = d_y; g.ldy = rows;
     if (r == 0) r = exact ? launch_gemm_exact(type, EPI_STORE, g, nullptr) : launch_gemm_q(type, EPI_STORE, g, nullptr);
     if (r == 0) GHIP_CHECK(hipDeviceSynchronize());

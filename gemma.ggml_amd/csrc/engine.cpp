@@ -3,25 +3,14 @@
 // Keeps the whole token on the GPU: weights tiled in HBM, the activation never leaves the device,
 // the greedy token is fed back on the device, and one decode step (18 layers x 5 kernels + the
 // logits/argmax kernel + the advance kernel) is captured once in a hipGraph and replayed.
-// It computes exactly the graph src/gemma_model.cpp:665-747 builds, op for op (see the per-kernel
-// citations in kernels.h / matvec.hip / ops.hip), with the fusions listed in DESIGN.md §Kernels.
-#include <math.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <rccl/rccl.h>
-
-#include <algorithm>
+// This file is the engine's lifecycle: create (synthetic, GGUF, external weights, row-split), free,
+// begin, step, the tensor read-back and the TP / p2p set-up.  The decode step itself is
+// engine_decode.cpp, the prefill engine_prefill.cpp, timing / tuning / taps engine_diag.cpp; the
+// engine struct and what the units share is engine_impl.h.
 #include <chrono>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <vector>
 
-#include "../../include/gemma_hpc.h"
 #include "../../include/ggml.h"
-#include "engine_ext.h"
-#include "kernels.h"
+#include "engine_impl.h"
 
 namespace ghip {
 
@@ -129,276 +118,8 @@ void free_tiled(tiled_mat &m) {
     if (m.sc) (void)hipFree(m.sc);
     m.qs = m.sc = nullptr;
 }
-// rows [r0, r0+n) of a tiled matrix (r0, n multiples of 8) as its own tiled_mat view
-static tiled_mat sub_rows(const tiled_mat &m, int64_t r0, int64_t n) {
-    tiled_mat v = m;
-    const int sb = m.type == T_Q4_0 ? 16 : 8;
-    v.rows = n;
-    v.n_rt = (n + 7) / 8;
-    v.qs = m.qs + (r0 / 8) * m.n_bt * 1024;
-    v.sc = m.sc + (r0 / 8) * m.n_bt * 8 * sb;
-    return v;
-}
 
 }  // namespace ghip
-
-using namespace ghip;
-using ghip::host_weights;
-
-struct layer_dev {
-    float *attn_norm = nullptr, *ffn_norm = nullptr;
-    tiled_mat qkv, o, gate, up, down;
-};
-
-// K-quant layer matrices (wtype GGML_TYPE_Q4_K: llama.cpp's Q4_K_M files): raw ggml rows, each
-// matrix Q4_K or Q6_K, multiplied by the K-quant matvec against the Q8_K INIT of its input
-struct kq_mat {
-    uint8_t *w = nullptr;
-    int type = 0;
-    int64_t rows = 0, K = 0, rb = 0;
-    bool tiled = false;  // lane-contiguous layout (launch_kq_retile), else ggml rows
-};
-struct kq_layer {
-    kq_mat q, k, v, o, gate, up, down;
-    bool qk_fused = false;  // q and k share one allocation (k's rows right after q's, same type)
-};
-
-struct gemma_engine;
-static bool att_img_ok(const gemma_engine *e);
-
-// matrix classes of a decode step and their launch plan (K split, row-tile groups per workgroup)
-enum { MC_QKV = 0, MC_O, MC_GU, MC_DOWN, MC_LOGITS, MC_N };
-struct launch_plan {
-    int ks = 1, rpw = 1;
-    int img = 0;  // attn-out / down: read the producer-written Q8_0 image (PRO_IMG) instead of f32
-};
-
-struct gemma_engine {
-    gemma_hip_config cfg{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int qw = 0, kvw = 0, qkv_rows = 0;
-    tiled_mat embd;
-    // token_embd / tied output in Q6_K (llama.cpp's Q4_0 / Q8_0 Gemma files): raw ggml rows, the
-    // embedding dequantized by k_embed_q6K and the logits through the K-quant matvec
-    int out_type = 0;
-    bool kq = false;              // K-quant layers (kql) instead of the tiled Q4_0 / Q8_0 ones
-    std::vector<kq_layer> kql;
-    uint8_t *kq_x = nullptr;      // Q8_K INIT of the current matvec input (max(E, qw, F) / 256 blocks)
-    // hand-off mode (kq_fuse == 2): the Q8_K images each producer writes for its consumer, one
-    // buffer per hand-off so no launch overwrites the image it reads (kq_x = the attn-norm image,
-    // kq_xa = attention output, kq_xf = ffn-norm image, kq_xh = gelu(gate)*up); counters zeroed once
-    uint8_t *kq_xa = nullptr, *kq_xf = nullptr, *kq_xh = nullptr;
-    unsigned *kq_cnt = nullptr;
-    int kq_cnt_cap = 0;
-    float *kq_g = nullptr;        // ffn gate output (n_ff), consumed by the up matvec's gelu*mul epilogue
-    uint8_t *embd_q6k = nullptr;
-    bool embd_tiled = false;  // embd_q6k in the lane-contiguous layout (launch_kq_retile)
-    int64_t embd_row_bytes = 0;
-    uint8_t *xq8k = nullptr;  // Q8_K rows of rms_norm(x)*out_norm (decode: 1 row; prefill: T rows)
-    int64_t xq8k_rows = 0;
-    float *out_norm = nullptr;
-    std::vector<layer_dev> layers;
-    uint16_t *kc = nullptr, *vc = nullptr;  // [L][ctx][kvw], [L][kvw][ctx]
-    std::vector<uint16_t *> kc_ext, vc_ext;  // external per-layer caches (ggml executor), else empty
-    float *ext_stage = nullptr;               // pinned logits row (ggml executor path)
-    int *ext_err = nullptr;                   // pinned copy of the persistent launch's sticky word (same path)
-    int att_mode = ATTN_PER_HEAD;
-    // row-split tensor parallelism: this rank's contiguous row range of every
-    // matrix; activations are full vectors, each matvec writes its shard in place and an in-place
-    // RCCL all-gather completes them
-    int tp_n = 1, tp_rank = 0;
-    int n_virtual = 1;  // > 1: all tp_n ranks' shards in this one engine (single-GPU parity mode, no RCCL)
-    bool tp_n_keys = false;  // logits through per-rank argmax keys (row split: virtual ranks or an RCCL comm)
-    ncclComm_t comm = nullptr;
-    int64_t sh_qkv = 0, sh_e = 0, sh_ff = 0, sh_v = 0;  // rows per rank (qkv, n_embd, n_ff, n_vocab)
-    // GEMMA_TP_REP_ATTN: Wq|Wk|Wv and Wo whole on every rank (sh_qkv = all rows, sh_o = n_embd), so
-    // a layer needs 2 all-gathers (h, x) instead of 4; the FFN and the output head stay row-split
-    bool rep_attn = false;
-    int64_t sh_o = 0;
-    // GEMMA_TP_P2P: the all-gathers by peer-to-peer pushes (p2p.hip) instead of RCCL: an uncached
-    // arena of inboxes + flags per rank, shared by IPC handles (gemma_engine_p2p_handle / _open)
-    bool p2p = false, p2p_ready = false;
-    uint8_t *p2p_arena = nullptr;
-    uint8_t *p2p_peer[P2P_MAX_RANKS] = {};
-    unsigned *p2p_seq = nullptr, *p2p_err = nullptr;
-    int64_t ib_qkv = 0, ib_sa = 0, ib_h = 0, ib_x = 0, ib_hact = 0, ib_hda = 0, ib_logits = 0, ib_keys = 0, ib_flags = 0;
-    unsigned long long *rank_keys = nullptr;           // [tp_n] one argmax key per rank
-    attn_geom ag;                           // split-attention geometry and its scratch
-    float *att_sbuf = nullptr;
-    int *att_sync = nullptr;                // hand-off counters [Hkv][2] + sticky error word
-    uint16_t *exp_tab = nullptr, *gelu_tab = nullptr;
-    float *rope_cos = nullptr, *rope_sin = nullptr, *rope_cur = nullptr;
-    // activations
-    float *x = nullptr, *qkv = nullptr, *attn = nullptr, *sa = nullptr, *h = nullptr, *logits = nullptr;
-    // Q8_0 activation images written by their producers (attention, gate/up) for attn-out and down
-    // (DESIGN.md §Activation image); null when a shape does not allow them (then PRO_F32)
-    // fused layer front (layer_front.hip): qkv -> attention -> attn-out in one launch per layer;
-    // hand-off counters [n_layer][16] zeroed once per token (memset node), sticky timeout word
-    // K-quant layers: kq_fuse = the plan for where ggml's Q8_K INIT runs (enqueue_step_kq, 0..6);
-    // kq_dual: gate+up in one launch
-    // K-quant step options (gemma_engine_set_option): the Q8_K INIT plan, gate+up in one launch, q|k
-    // and v in one launch
-    int kq_fuse = 5, kq_dual = 1, kq_pair = 1;
-    // per-head decode attention: workgroups per head (each the KQ/softmax, 1/att_dsplit of the KQV
-    // dims; option "att_dsplit"). Same box, decode tok/s: 1 / 2 / 4 -> 1,443 / 1,458 / 1,458; after the
-    // batched K/V step loads 2 / 4 / 8 -> 1,470-1,482 / 1,491 / 1,355-1,369 (scripts/env_ab.sh)
-    int att_dsplit = 4;
-    int kq_abl = 0;  // option "kq_abl": hand-off timing ablation (kq_args::q8_abl; wrong results)
-    int att_mx = 1;  // option "att_mx": exact prefill attention on the f32 matrix cores (0: the row form)
-    int time_hot = 0, ablate = 0;  // gemma_engine_time diagnostics: one layer's matrix repeated; ablations
-    // the whole token's layers as ONE persistent launch (token.hip) when the shapes
-    // allow it (GHIP_PERSIST=1 or gemma_engine_set_persist(e, 1)); off by default until it beats
-    // the per-layer launches on the bench
-    int persist = 0;
-    std::string persist_why;           // why the persistent launch cannot run ("" = it can)
-    tok_args tok{};                    // its arguments (host copy; tok_dev: the copy the kernel reads)
-    tok_args *tok_dev = nullptr;
-    tok_layer *tok_tab = nullptr;      // per-layer pointer table
-    unsigned long long *tok_gran = nullptr;  // hand-off granules (zeroed once; tags carry the epoch)
-    unsigned *epoch = nullptr;         // bumped by k_advance / k_set_position once per token
-    int *tok_err = nullptr;            // sticky hand-off timeout [flag, site, layer]
-    unsigned persist_timeout = 2000000u;  // per-wait bound of the launch (100 MHz ticks; tests shorten it)
-    int fuse_front = 0;  // measured: 727 vs 672 us/token (the in-launch hand-offs cost as much as the
-                         // launch boundaries they replace; DESIGN.md perf log) — kept as an option
-    unsigned *front_cnt = nullptr;
-    int *front_err = nullptr;
-    // attention + attn-out in one launch (layer_front.hip k_attn_o): on / off, its per-layer hand-off
-    // counters (8 replicas + done, 128 B apart; the launch leaves them zero) and sticky error words
-    int att_o = 0;
-    unsigned *ao_cnt = nullptr;
-    int *ao_err = nullptr;
-    uint32_t *att_act = nullptr, *h_act = nullptr;
-    float *att_da = nullptr, *h_da = nullptr;
-    unsigned long long *key = nullptr;
-    int *pos = nullptr, *token = nullptr, *hist = nullptr, *nfix = nullptr;
-    int n_prompt = 0;
-    int host_pos = 0;  // mirror of *pos (steps are deterministic)
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    // flow control of gemma_engine_step: an event every FC_EVERY graph launches, FC_SLOTS of them
-    hipEvent_t fc_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    // launch geometry: one plan per matrix class (defaults below; gemma_engine_tune measures)
-    int ks_small = KS_RR, ks_down = KS_RR;  // round-pipelined form where the shape allows (pick_ks falls back)
-    int grid_big = 2048;
-    int grid_big_cap = 2048;  // workgroups the argmax key buffer holds
-    launch_plan plan[MC_N];
-    // prefill scratch (lazily allocated)
-    // prefill buffers (lazily sized for the prompt length)
-    struct {
-        int T = 0;
-        int64_t ldq = 0, ldd = 0;
-        float *X = nullptr, *SA = nullptr, *QKV = nullptr, *ATT = nullptr, *G = nullptr, *U = nullptr, *LG = nullptr;
-        float *DA = nullptr;
-        uint16_t *Q16 = nullptr;
-        int8_t *XQ = nullptr;
-        uint16_t *XH = nullptr;  // f16 image of the quantized activations (exact GEMM operand)
-        uint16_t *XM = nullptr;  // K-quant prefill: the Q4_K mins operand of the Q8_K image (k_q8k_expand)
-        void *keys = nullptr;
-    } pf;
-    float *dbg = nullptr;  // per-layer taps [L][qkv_rows + qw + E] (debug steps only)
-    unsigned long long *stamp = nullptr;  // phase stamps of one layer's kernels (diagnostic steps only)
-    int stamp_layer = -1;
-};
-
-static constexpr size_t kStampRegion = 4096 * 16;  // u64 per kernel: <= 4096 workgroups x 16 stamps
-static unsigned long long *stamp_region(gemma_engine *e, int il, int k) {
-    return (e->stamp && il == e->stamp_layer) ? e->stamp + (size_t)k * kStampRegion : nullptr;
-}
-
-// attention can hand attn-out the Q8_0 image of its output (per-head form; split form with 32-dim slices)
-static bool att_img_ok(const gemma_engine *e) { return e->att_mode == ATTN_PER_HEAD || e->ag.img; }
-
-// workgroups of a matvec launch: a KS = 1 workgroup runs 4 waves on 4 row tiles at a time, a
-// KS > 1 workgroup its KS waves on one row tile; each workgroup repeats for rpw row-tile groups
-static int mv_grid(const gemma_engine *e, int cls, int64_t n_rt) {
-    const launch_plan &p = e->plan[cls];
-    const int64_t per = (p.ks == 1 || cls == MC_GU ? 4 : 1) * (int64_t)std::max(p.rpw, 1);  // gate/up ks 2: 4 row tiles
-    int64_t g = (n_rt + per - 1) / per;
-    if (cls == MC_LOGITS || cls == MC_GU) g = std::min<int64_t>(g, e->grid_big);  // key slots
-    return (int)std::max<int64_t>(g, 1);
-}
-
-// largest power-of-two K split <= target that divides the block-tile count and whose LDS image
-// (activation + carry stash) fits the 160 KiB of a CU (Gemma-7B's down, K = 24576, steps to KS 1)
-static int pick_ks(int wtype, int64_t n_bt, int target) {
-    if (target == KS_RR) return matvec_rr_supported(wtype, n_bt) ? KS_RR : pick_ks(wtype, n_bt, 8);
-    int ks = target;
-    while (ks > 1 && (n_bt % ks || matvec_lds_bytes(wtype, ks, n_bt, n_bt / ks) > 160 * 1024)) ks >>= 1;
-    return ks;
-}
-
-// the inbox of a gathered working vector in every rank's p2p arena
-static int64_t p2p_inbox(const gemma_engine *e, const void *work) {
-    if (work == e->qkv) return e->ib_qkv;
-    if (work == e->sa) return e->ib_sa;
-    if (work == e->h) return e->ib_h;
-    if (work == e->x) return e->ib_x;
-    if (work == e->h_act) return e->ib_hact;
-    if (work == e->h_da) return e->ib_hda;
-    if (work == e->logits) return e->ib_logits;
-    if (work == e->rank_keys) return e->ib_keys;
-    return -1;
-}
-
-// one peer-to-peer gather of up to two segments (working vector, bytes per rank)
-static int p2p_gather(gemma_engine *e, void *w0, int64_t b0, void *w1 = nullptr, int64_t b1 = 0, hipStream_t s = nullptr) {
-    p2p_args a;
-    a.nseg = w1 ? 2 : 1;
-    a.seg[0].work = (uint8_t *)w0; a.seg[0].inbox = p2p_inbox(e, w0); a.seg[0].shard = b0;
-    if (w1) { a.seg[1].work = (uint8_t *)w1; a.seg[1].inbox = p2p_inbox(e, w1); a.seg[1].shard = b1; }
-    if (a.seg[0].inbox < 0 || (w1 && a.seg[1].inbox < 0)) {
-        set_error("p2p_gather: not a gathered vector");
-        return -1;
-    }
-    a.rank = e->tp_rank; a.n = e->tp_n;
-    for (int r = 0; r < e->tp_n; ++r) a.peer[r] = e->p2p_peer[r];
-    a.flags = e->ib_flags; a.seq = e->p2p_seq; a.err = e->p2p_err;
-    return launch_p2p_gather(a, s ? s : e->stream);
-}
-
-// in-place all-gather of a full vector whose rank-r shard [r*cnt, (r+1)*cnt) was just written
-static int tp_gather(gemma_engine *e, float *full, int64_t cnt) {
-    if (e->p2p) return p2p_gather(e, full, cnt * 4);
-    if (!e->comm) return 0;  // one unsplit engine, or virtual ranks (shards already in place)
-    const ncclResult_t r = ncclAllGather(full + (size_t)e->tp_rank * cnt, full, (size_t)cnt, ncclFloat, e->comm, e->stream);
-    if (r != ncclSuccess) {
-        set_error(std::string("ncclAllGather: ") + ncclGetErrorString(r));
-        return -1;
-    }
-    return 0;
-}
-
-// in-place all-gather of the h image: per rank `act_bytes` of act (u32 groups) and `nda` scales
-static int tp_gather_bytes(gemma_engine *e, uint32_t *act, int64_t act_bytes, float *da, int64_t nda) {
-    if (e->p2p) return p2p_gather(e, act, act_bytes, da, nda * 4);
-    if (!e->comm) return 0;
-    ncclGroupStart();
-    ncclResult_t r = ncclAllGather((uint8_t *)act + (size_t)e->tp_rank * act_bytes, act, (size_t)act_bytes, ncclUint8,
-                                   e->comm, e->stream);
-    const ncclResult_t r2 = ncclAllGather(da + (size_t)e->tp_rank * nda, da, (size_t)nda, ncclFloat, e->comm, e->stream);
-    const ncclResult_t r3 = ncclGroupEnd();
-    if (r == ncclSuccess) r = r2;
-    if (r == ncclSuccess) r = r3;
-    if (r != ncclSuccess) {
-        set_error(std::string("ncclAllGather(image): ") + ncclGetErrorString(r));
-        return -1;
-    }
-    return 0;
-}
-
-// layer il's shards of (virtual) rank slot vr, and the rank that slot stands for
-static inline layer_dev &layer_of(gemma_engine *e, int il, int vr) { return e->layers[(size_t)il * e->n_virtual + vr]; }
-static inline int rank_of(const gemma_engine *e, int vr) { return e->n_virtual > 1 ? vr : e->tp_rank; }
-// layer il's caches: K [ctx][kvw], V [kvw][ctx]
-static inline uint16_t *kc_of(const gemma_engine *e, int il) {
-    return e->kc_ext.empty() ? e->kc + (size_t)il * e->cfg.n_ctx * e->kvw : e->kc_ext[il];
-}
-static inline uint16_t *vc_of(const gemma_engine *e, int il) {
-    return e->vc_ext.empty() ? e->vc + (size_t)il * e->cfg.n_ctx * e->kvw : e->vc_ext[il];
-}
-
-static inline int wfmt_scale(int wt) { return wt == T_Q4_0 ? 16 : 8; }  // scale bytes per row and tile
 
 // ggml K-quant rows -> the lane-contiguous layout, in place (through a scratch copy).  Q6_K needs
 // K % 2048 == 0 (else the rows stay as they are).
@@ -415,487 +136,6 @@ static int kq_retile_inplace(uint8_t *w, int type, int64_t rows, int64_t K, hipS
     *tiled = true;
     return 0;
 }
-
-static int enqueue_step_kq(gemma_engine *e, const rope_row &rr);
-
-// the persistent token launch's arguments and per-layer table (device copies the kernel reads);
-// sets persist_why to the reason when the launch cannot run this engine
-static int tok_prepare(gemma_engine *e) {
-    const gemma_hip_config &c = e->cfg;
-    e->persist_why.clear();
-    if (e->kq) e->persist_why = "K-quant layers";
-    else if (e->out_type == T_Q6_K) e->persist_why = "Q6_K token_embd (the launch dequantizes the layer type)";
-    else if (e->tp_n != 1 || e->n_virtual != 1 || e->comm) e->persist_why = "row-split TP";
-    if (!e->persist_why.empty() || !e->tok_gran) {
-        if (e->persist_why.empty()) e->persist_why = "no buffers";
-        return 0;
-    }
-    std::vector<tok_layer> tab(c.n_layer);
-    for (int il = 0; il < c.n_layer; ++il) {
-        const layer_dev &L = e->layers[il];
-        tok_layer &T = tab[il];
-        T.qkv_qs = L.qkv.qs; T.qkv_sc = L.qkv.sc; T.o_qs = L.o.qs; T.o_sc = L.o.sc;
-        T.g_qs = L.gate.qs; T.g_sc = L.gate.sc; T.u_qs = L.up.qs; T.u_sc = L.up.sc; T.d_qs = L.down.qs; T.d_sc = L.down.sc;
-        T.attn_norm = L.attn_norm; T.ffn_norm = L.ffn_norm;
-        T.kc = kc_of(e, il); T.vc = vc_of(e, il);
-    }
-    GHIP_CHECK(hipMemcpy(e->tok_tab, tab.data(), tab.size() * sizeof(tok_layer), hipMemcpyHostToDevice));
-    tok_args &a = e->tok;
-    a = tok_args{};
-    a.layers = e->tok_tab;
-    a.n_layer = c.n_layer;
-    a.E = c.n_embd; a.F = c.n_ff; a.H = c.n_head; a.Hkv = c.n_head_kv; a.hd = c.head_dim; a.ctx = c.n_ctx;
-    a.qkv_rows = e->qkv_rows;
-    a.att_split = e->att_dsplit;
-    a.eps = c.eps; a.emb_scale = sqrtf((float)c.n_embd); a.q_scale = 1.0f / sqrtf((float)c.head_dim);
-    a.emb_qs = e->embd.qs; a.emb_sc = e->embd.sc; a.emb_n_bt = e->embd.n_bt;
-    a.hist = e->hist; a.pos = e->pos; a.rope_cur = e->rope_cur;
-    a.exp_tab = e->exp_tab; a.gelu_tab = e->gelu_tab; a.gelu_clamp = c.gelu_clamp;
-    const tok_gran_sizes g = token_gran_sizes(c.n_embd, c.n_ff, e->qkv_rows);
-    unsigned long long *p = e->tok_gran;
-    a.gx = p; p += g.gx;
-    a.gqkv = p; p += g.gqkv;
-    a.gatt = p; p += g.gatt;
-    a.gatt_da = p; p += g.gatt_da;
-    a.gsa = p; p += g.gsa;
-    a.gh = p; p += g.gh;
-    a.gh_da = p;
-    a.epoch = e->epoch; a.x_out = e->x; a.att_out = e->attn; a.err = e->tok_err;
-    a.timeout = e->persist_timeout;
-    e->persist_why = token_unsupported(c.wtype, a);
-    GHIP_CHECK(hipMemcpy(e->tok_dev, &a, sizeof(tok_args), hipMemcpyHostToDevice));
-    return 0;
-}
-static bool persist_on(const gemma_engine *e) {
-    return e->persist && e->persist_why.empty() && !e->dbg && !e->stamp && e->att_mode == ATTN_PER_HEAD &&
-           !e->fuse_front;
-}
-
-// After a stream sync that covers persistent-launch steps: a hand-off that timed out (a workgroup
-// not co-resident, the CUs shared with another stream or process) leaves the sticky word set and the
-// step's numbers wrong.  Report it, clear it and fall back to the per-layer launches for later steps
-// (ADVICE r3); returns 1 when a timeout was seen.
-static void drop_graph(gemma_engine *e);
-// w = the persistent launch's sticky words [flag, site, layer] read back after the step
-static int persist_report(gemma_engine *e, const int *w) {
-    if (!w[0]) return 0;
-    (void)hipMemset(e->tok_err, 0, 64);
-    e->persist = 0;
-    drop_graph(e);
-    set_error("persistent token launch: hand-off timeout (site " + std::to_string(w[1]) + ", layer " +
-              std::to_string(w[2]) + "): the step's logits and KV rows are invalid; the engine now runs the "
-              "per-layer launches");
-    return 1;
-}
-
-// After a stream sync that covers k_attn_o launches: a hand-off poll that timed out leaves the sticky
-// word set and the step's numbers wrong.  Report it, clear it and run the two launches from then on.
-static int att_o_check(gemma_engine *e) {
-    if (!e->att_o || !e->ao_err) return 0;
-    int w[5] = {0, 0, 0, 0, 0};
-    if (hipMemcpy(w, e->ao_err, 20, hipMemcpyDeviceToHost) != hipSuccess || !w[0]) return 0;
-    (void)hipMemset(e->ao_err, 0, 64);
-    (void)hipMemset(e->ao_cnt, 0, (size_t)e->cfg.n_layer * 16 * 32 * 4);
-    e->att_o = 0;
-    drop_graph(e);
-    set_error("attention + attn-out launch: hand-off timeout (counter " + std::to_string(w[2]) + " of " +
-              std::to_string(w[3]) + "): the step's logits and KV rows are invalid; the engine now runs the two "
-              "launches");
-    return 1;
-}
-
-static int persist_check(gemma_engine *e) {
-    if (!persist_on(e) || !e->tok_err) return 0;
-    int w[3] = {0, 0, 0};
-    if (hipMemcpy(w, e->tok_err, 12, hipMemcpyDeviceToHost) != hipSuccess) return 0;
-    return persist_report(e, w);
-}
-
-static int enqueue_step(gemma_engine *e) {
-    const gemma_hip_config &c = e->cfg;
-    const int wt = c.wtype;
-    hipStream_t s = e->stream;
-    const int E = c.n_embd;
-    if (e->kq) {
-        rope_row rr;
-        rr.cos = e->rope_cos; rr.sin = e->rope_sin; rr.cur = e->rope_cur; rr.half = c.head_dim / 2; rr.ctx = c.n_ctx;
-        rr.epoch = e->epoch;
-        return enqueue_step_kq(e, rr);
-    }
-    if (e->out_type == T_Q6_K &&
-        launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, e->hist, e->pos, 1, E, sqrtf((float)E), e->x, s, e->embd_tiled))
-        return -1;
-    if (persist_on(e)) {  // every layer in one launch (token.hip), then the logits below
-        if (launch_token(wt, e->tok, e->tok_dev, s)) return -1;
-        goto logits;
-    }
-    {
-    const bool front_ok = e->front_cnt && e->fuse_front && e->tp_n == 1 && !e->comm && e->n_virtual == 1 &&
-                          e->att_mode == ATTN_PER_HEAD && e->att_act && e->plan[MC_QKV].ks == KS_RR &&
-                          e->plan[MC_O].ks == KS_RR && e->plan[MC_O].img;
-    if (front_ok) GHIP_CHECK(hipMemsetAsync(e->front_cnt, 0, (size_t)c.n_layer * 16 * 32 * 4, s));
-    for (int il = 0; il < c.n_layer; ++il) {
-        // fused front (layers > 0, or a Q6_K embedding that ran before layer 0): one launch for
-        // K1 + K2 + K3 below, same arithmetic (layer_front.hip)
-        if (front_ok && (il > 0 || e->out_type == T_Q6_K)) {
-            const layer_dev &L = e->layers[il];
-            front_args f;
-            f.q.qs = L.qkv.qs; f.q.sc = L.qkv.sc; f.q.rows = L.qkv.rows; f.q.n_rt = L.qkv.n_rt; f.q.n_bt = L.qkv.n_bt;
-            f.q.nb = L.qkv.nb; f.q.norm_w = L.attn_norm; f.q.eps = c.eps; f.q.x = e->x; f.q.y = e->qkv;
-            attn_args &t = f.t;
-            t.qkv = e->qkv;
-            t.kc = kc_of(e, il);
-            t.vc = vc_of(e, il);
-            t.rope_cos = e->rope_cos; t.rope_sin = e->rope_sin; t.rope_cur = e->rope_cur; t.exp_tab = e->exp_tab;
-            t.pos = e->pos; t.out = e->attn; t.out_act = e->att_act; t.out_da = e->att_da;
-            t.H = c.n_head; t.Hkv = c.n_head_kv; t.hd = c.head_dim; t.ctx = c.n_ctx;
-            t.q_scale = 1.0f / sqrtf((float)c.head_dim);
-            t.mode = ATTN_PER_HEAD;
-            f.o.qs = L.o.qs; f.o.sc = L.o.sc; f.o.rows = L.o.rows; f.o.n_rt = L.o.n_rt; f.o.n_bt = L.o.n_bt; f.o.nb = L.o.nb;
-            f.o.x = e->att_act; f.o.x_da = e->att_da; f.o.y = e->sa; f.o.resid = e->x;
-            f.cnt = e->front_cnt + (size_t)il * 16 * 32;  // 16 counters of 128 B
-            f.err = e->front_err;
-            f.dbg_t = stamp_region(e, il, 0);
-            if (layer_front_supported(wt, f.q, f.t, f.o)) {
-                if (launch_layer_front(wt, f, s)) return -1;
-                const size_t tap = (size_t)il * (e->qkv_rows + e->qw + E);
-                if (e->dbg) GHIP_CHECK(hipMemcpyAsync(e->dbg + tap, e->qkv, (size_t)e->qkv_rows * 4, hipMemcpyDeviceToDevice, s));
-                if (e->dbg)
-                    GHIP_CHECK(hipMemcpyAsync(e->dbg + tap + e->qkv_rows, e->attn, (size_t)e->qw * 4, hipMemcpyDeviceToDevice, s));
-                goto ffn;
-            }
-        }
-        {
-        // K1: [embed | rms_norm*attn_norm] + quantize -> Wq|Wk|Wv   (:677-696); each rank its rows
-        for (int vr = 0; vr < (e->rep_attn ? 1 : e->n_virtual); ++vr) {
-            layer_dev &L = layer_of(e, il, vr);
-            mv_args a;
-            a.qs = L.qkv.qs; a.sc = L.qkv.sc; a.rows = L.qkv.rows; a.n_rt = L.qkv.n_rt; a.n_bt = L.qkv.n_bt;
-            a.nb = L.qkv.nb;
-            a.norm_w = L.attn_norm; a.eps = c.eps;
-            int pro = PRO_NORM;
-            if (il == 0 && e->out_type != T_Q6_K) {
-                pro = PRO_EMBED;
-                a.x = e->hist; a.tok_pos = e->pos;
-                a.emb_qs = e->embd.qs; a.emb_sc = e->embd.sc; a.emb_n_bt = e->embd.n_bt;
-                a.emb_scale = sqrtf((float)E);
-                a.emb_out = e->x;
-            } else {
-                a.x = e->x;
-            }
-            a.dbg_t = stamp_region(e, il, 0);
-            a.y = e->qkv + (e->rep_attn ? 0 : (size_t)rank_of(e, vr) * e->sh_qkv);  // this rank's rows of q|k|v
-            if (launch_matvec(wt, pick_ks(wt, L.qkv.n_bt, e->plan[MC_QKV].ks), pro, EPI_STORE, a, mv_grid(e, MC_QKV, L.qkv.n_rt), s)) return -1;
-        }
-        if (!e->rep_attn && tp_gather(e, e->qkv, e->sh_qkv)) return -1;
-        // K2: rope + scale + kv store + KQ + softmax + KQV  (:698-718, :454-518); replicated
-        attn_args t;
-        t.qkv = e->qkv;
-        t.kc = kc_of(e, il);
-        t.vc = vc_of(e, il);
-        t.rope_cos = e->rope_cos; t.rope_sin = e->rope_sin; t.rope_cur = e->rope_cur; t.exp_tab = e->exp_tab;
-        t.pos = e->pos; t.out = e->attn;
-        const bool att_img = e->att_act && att_img_ok(e) && e->plan[MC_O].img;
-        if (att_img) { t.out_act = e->att_act; t.out_da = e->att_da; }
-        t.H = c.n_head; t.Hkv = c.n_head_kv; t.hd = c.head_dim; t.ctx = c.n_ctx;
-        t.q_scale = 1.0f / sqrtf((float)c.head_dim);
-        t.mode = e->att_mode;
-        t.nwg = e->ag.nwg; t.sbuf = e->att_sbuf; t.sync = e->att_sync; t.err = e->att_sync + e->ag.sync_ints;
-        t.dbg_t = stamp_region(e, il, 1);
-        if (t.mode == ATTN_PER_HEAD) t.dsplit = e->att_dsplit;
-        // attention + attn-out in one launch (k_attn_o): the attention's idle workgroups run attn-out
-        if (e->att_o && att_img && e->n_virtual == 1 && e->ao_cnt && e->plan[MC_O].ks == KS_RR) {
-            const layer_dev &L = layer_of(e, il, 0);
-            const size_t r0 = e->rep_attn ? 0 : (size_t)rank_of(e, 0) * e->sh_o;
-            attn_o_args f;
-            f.t = t;
-            f.o.qs = L.o.qs; f.o.sc = L.o.sc; f.o.rows = L.o.rows; f.o.n_rt = L.o.n_rt; f.o.n_bt = L.o.n_bt; f.o.nb = L.o.nb;
-            f.o.x = e->att_act; f.o.x_da = e->att_da; f.o.y = e->sa + r0; f.o.resid = e->x + r0;
-            f.cnt = e->ao_cnt + (size_t)il * 16 * 32;
-            f.err = e->ao_err;
-            f.t.dbg_t = nullptr;  // (the fused kernel's stamps: 16 per workgroup in the attention region)
-            f.dbg_t = stamp_region(e, il, 1);
-            if (attn_o_supported(wt, f.t, f.o)) {
-                if (launch_attn_o(wt, f, s)) return -1;
-                const size_t tap = (size_t)il * (e->qkv_rows + e->qw + E);
-                if (e->dbg) GHIP_CHECK(hipMemcpyAsync(e->dbg + tap, e->qkv, (size_t)e->qkv_rows * 4, hipMemcpyDeviceToDevice, s));
-                if (e->dbg)
-                    GHIP_CHECK(hipMemcpyAsync(e->dbg + tap + e->qkv_rows, e->attn, (size_t)e->qw * 4, hipMemcpyDeviceToDevice, s));
-                if (!e->rep_attn && tp_gather(e, e->sa, e->sh_o)) return -1;
-                goto ffn;
-            }
-        }
-        if (launch_attn_decode(t, s)) return -1;
-        const size_t tap = (size_t)il * (e->qkv_rows + e->qw + E);
-        if (e->dbg) GHIP_CHECK(hipMemcpyAsync(e->dbg + tap, e->qkv, (size_t)e->qkv_rows * 4, hipMemcpyDeviceToDevice, s));
-        if (e->dbg)
-            GHIP_CHECK(hipMemcpyAsync(e->dbg + tap + e->qkv_rows, e->attn, (size_t)e->qw * 4, hipMemcpyDeviceToDevice, s));
-        // K3: quantize(attn) -> Wo, + inpL  (:493, :723)
-        for (int vr = 0; vr < (e->rep_attn ? 1 : e->n_virtual); ++vr) {
-            layer_dev &L = layer_of(e, il, vr);
-            const size_t r0 = e->rep_attn ? 0 : (size_t)rank_of(e, vr) * e->sh_o;
-            mv_args b;
-            b.qs = L.o.qs; b.sc = L.o.sc; b.rows = L.o.rows; b.n_rt = L.o.n_rt; b.n_bt = L.o.n_bt; b.nb = L.o.nb;
-            b.x = e->attn; b.y = e->sa + r0; b.resid = e->x + r0;
-            if (att_img) { b.x = e->att_act; b.x_da = e->att_da; }
-            b.dbg_t = stamp_region(e, il, 2);
-            if (launch_matvec(wt, pick_ks(wt, L.o.n_bt, e->plan[MC_O].ks), att_img ? PRO_IMG : PRO_F32, EPI_ADD, b,
-                              mv_grid(e, MC_O, L.o.n_rt), s))
-                return -1;
-        }
-        if (!e->rep_attn && tp_gather(e, e->sa, e->sh_o)) return -1;
-        }
-    ffn:
-        // K4: rms_norm*ffn_norm + quantize -> gate & up -> gelu(gate)*up  (:724, :446-449)
-        const bool h_img = e->h_act && e->plan[MC_DOWN].img;
-        for (int vr = 0; vr < e->n_virtual; ++vr) {
-            layer_dev &L = layer_of(e, il, vr);
-            mv_args g;
-            g.qs = L.gate.qs; g.sc = L.gate.sc; g.qs2 = L.up.qs; g.sc2 = L.up.sc;
-            g.rows = L.gate.rows; g.n_rt = L.gate.n_rt; g.n_bt = L.gate.n_bt; g.nb = L.gate.nb;
-            g.x = e->sa; g.norm_w = L.ffn_norm; g.eps = c.eps; g.y = e->h + (size_t)rank_of(e, vr) * e->sh_ff;
-            g.gelu_tab = e->gelu_tab; g.gelu_clamp = c.gelu_clamp;
-            if (h_img) {  // this rank's blocks of the image (shard offsets are whole 4-block groups)
-                const size_t b0 = (size_t)rank_of(e, vr) * e->sh_ff / 32;
-                g.out_act = e->h_act + b0 * 8;
-                g.out_da = e->h_da + b0;
-            }
-            g.dbg_t = stamp_region(e, il, 3);
-            if (launch_matvec(wt, e->plan[MC_GU].ks, PRO_NORM, EPI_GELU_MUL, g, mv_grid(e, MC_GU, L.gate.n_rt), s))
-                return -1;
-        }
-        if (h_img) {
-            if (tp_gather_bytes(e, e->h_act, e->sh_ff, e->h_da, e->sh_ff / 32)) return -1;
-        } else if (tp_gather(e, e->h, e->sh_ff)) {
-            return -1;
-        }
-        // K5: quantize(h) -> Wdown, + sa  (:450, :731)
-        for (int vr = 0; vr < e->n_virtual; ++vr) {
-            layer_dev &L = layer_of(e, il, vr);
-            const size_t r0 = (size_t)rank_of(e, vr) * e->sh_e;
-            mv_args d;
-            d.qs = L.down.qs; d.sc = L.down.sc; d.rows = L.down.rows; d.n_rt = L.down.n_rt; d.n_bt = L.down.n_bt;
-            d.nb = L.down.nb;
-            d.x = e->h; d.y = e->x + r0; d.resid = e->sa + r0;
-            if (h_img) { d.x = e->h_act; d.x_da = e->h_da; }
-            d.dbg_t = stamp_region(e, il, 4);
-            if (launch_matvec(wt, pick_ks(wt, L.down.n_bt, e->plan[MC_DOWN].ks), h_img ? PRO_IMG : PRO_F32, EPI_ADD, d,
-                              mv_grid(e, MC_DOWN, L.down.n_rt), s))
-                return -1;
-        }
-        if (tp_gather(e, e->x, e->sh_e)) return -1;
-        if (e->dbg)
-            GHIP_CHECK(hipMemcpyAsync(e->dbg + (size_t)il * (e->qkv_rows + e->qw + E) + e->qkv_rows + e->qw, e->x,
-                                      (size_t)E * 4, hipMemcpyDeviceToDevice, s));
-    }
-    }
-logits:
-    // K6: rms_norm*output_norm + quantize -> tied output -> logits + argmax  (:736-740, :532-546)
-    // K7: token feedback (greedy_sample -> input.push_back, :282-285), position += 1; the prompt is
-    // never overwritten: hist writes only land at positions >= n_prompt
-    rope_row rr;
-    rr.cos = e->rope_cos; rr.sin = e->rope_sin; rr.cur = e->rope_cur; rr.half = c.head_dim / 2; rr.ctx = c.n_ctx;
-    rr.epoch = e->epoch;
-    if (e->out_type == T_Q6_K) {  // rms_norm*out_norm -> Q8_K -> Q6_K tied output -> argmax
-        if (launch_norm_q8K(e->x, E, e->out_norm, E, c.eps, 1, e->xq8k, (E / 256) * 292, s)) return -1;
-        kq_args k;
-        k.w = e->embd_q6k; k.tiled = e->embd_tiled; k.row_bytes = e->embd_row_bytes; k.rows = c.n_vocab; k.nsb = E / 256;
-        k.x = e->xq8k; k.x_col_stride = (E / 256) * 292; k.y = e->logits; k.y_col_stride = c.n_vocab; k.ncols = 1;
-        if (launch_matvec_kq(T_Q6_K, k, s)) return -1;
-        if (launch_row_argmax(e->logits, c.n_vocab, e->key, 256, s)) return -1;
-        if (launch_advance(e->key, 256, e->token, e->pos, e->hist, c.n_ctx, e->nfix, rr, s)) return -1;
-        return 0;
-    }
-    int lg_grid = 0;
-    for (int vr = 0; vr < e->n_virtual; ++vr) {
-        const int rk = rank_of(e, vr);
-        const tiled_mat out_rows = sub_rows(e->embd, (int64_t)rk * e->sh_v, e->sh_v);  // tied output, this rank's vocab
-        mv_args o;
-        o.qs = out_rows.qs; o.sc = out_rows.sc; o.rows = out_rows.rows; o.n_rt = out_rows.n_rt; o.n_bt = out_rows.n_bt;
-        o.nb = out_rows.nb;
-        o.x = e->x; o.norm_w = e->out_norm; o.eps = c.eps; o.y = e->logits + (size_t)rk * e->sh_v;
-        o.argmax_key = e->key;
-        lg_grid = mv_grid(e, MC_LOGITS, out_rows.n_rt);
-        o.dbg_t = e->stamp ? e->stamp + 5 * kStampRegion : nullptr;
-        if (launch_matvec(wt, 1, PRO_NORM, EPI_ARGMAX, o, lg_grid, s)) return -1;
-        // TP: one key per rank, its index made global
-        if (e->tp_n_keys && launch_reduce_keys(e->key, lg_grid, (int64_t)rk * e->sh_v, e->rank_keys + rk, s)) return -1;
-    }
-    if (!e->tp_n_keys) {
-        if (launch_advance(e->key, lg_grid, e->token, e->pos, e->hist, c.n_ctx, e->nfix, rr, s)) return -1;
-        return 0;
-    }
-    if (e->p2p && p2p_gather(e, e->rank_keys, 8, nullptr, 0, s)) return -1;
-    if (e->comm) {
-        const ncclResult_t nr = ncclAllGather(e->rank_keys + e->tp_rank, e->rank_keys, 1, ncclUint64, e->comm, s);
-        if (nr != ncclSuccess) {
-            set_error(std::string("ncclAllGather(keys): ") + ncclGetErrorString(nr));
-            return -1;
-        }
-    }
-    return launch_advance(e->rank_keys, e->tp_n, e->token, e->pos, e->hist, c.n_ctx, e->nfix, rr, s);
-}
-
-// One decode token with K-quant layer matrices (src/gemma_model.cpp:665-747 on a Q4_K_M file):
-// per layer rms_norm*attn_norm -> Q8_K -> Wq, Wk, Wv (K-quant dots) -> attention (the same kernel)
-// -> Q8_K(attn) -> Wo (+inpL) -> rms_norm*ffn_norm -> Q8_K -> Wgate, Wup (gelu(gate)*up epilogue)
-// -> Q8_K(h) -> Wdown (+sa); then the Q6_K tied output.  ggml's INIT and vec_dot order throughout.
-static int enqueue_step_kq(gemma_engine *e, const rope_row &rr) {
-    const gemma_hip_config &c = e->cfg;
-    hipStream_t s = e->stream;
-    const int E = c.n_embd;
-    // Where ggml's Q8_K INIT of each matvec input runs (all write the same bytes):
-    //   LAUNCH   a k_norm_q8K / k_quant_q8_K launch;
-    //   PROLOGUE the consumer's prologue from f32 (KQP_NORM / KQP_F32, every workgroup);
-    //   HANDOFF  the producer's tail (kq_handoff; attention: each head's super-block).
-    // Images: A = attn-norm(x) -> q|k, v; B = attention out -> o; C = ffn-norm(sa) -> gate/up;
-    // D = gelu(gate)*up -> down; each in its own buffer.  e->kq_fuse picks the plan:
-    //   0 all LAUNCH; 1 all PROLOGUE; 2 all HANDOFF (measured: the norm tails cost more than a
-    //   launch); 3 norms PROLOGUE, quantizations HANDOFF; 4 as 3 with C a LAUNCH; 5 (default) all
-    //   PROLOGUE but D (the attention then keeps two workgroups per head); 6 as 5 with B a LAUNCH.
-    //   Same box, Q4_K_M decode: plan 3 / 5 / 6 -> 997 / 1,017 / 980 tok/s.
-    enum { LAUNCH, PROLOGUE, HANDOFF };
-    static const int plan[7][4] = {{LAUNCH, LAUNCH, LAUNCH, LAUNCH},
-                                   {PROLOGUE, PROLOGUE, PROLOGUE, PROLOGUE},
-                                   {HANDOFF, HANDOFF, HANDOFF, HANDOFF},
-                                   {PROLOGUE, HANDOFF, PROLOGUE, HANDOFF},
-                                   {PROLOGUE, HANDOFF, LAUNCH, HANDOFF},
-                                   {PROLOGUE, PROLOGUE, PROLOGUE, HANDOFF},
-                                   {PROLOGUE, LAUNCH, PROLOGUE, HANDOFF}};
-    const int mode = e->kq_fuse >= 0 && e->kq_fuse <= 6 ? e->kq_fuse : 5;
-    int srcA = plan[mode][0], srcB = plan[mode][1], srcC = plan[mode][2], srcD = plan[mode][3];
-    if (E > 2048) {  // the norm hand-off holds <= 2048 values in one wave
-        if (srcA == HANDOFF) srcA = PROLOGUE;
-        if (srcC == HANDOFF) srcC = PROLOGUE;
-    }
-    if (srcB == HANDOFF && !(e->att_mode == ATTN_PER_HEAD && c.head_dim == 256)) srcB = LAUNCH;
-    struct img {
-        int src;
-        uint8_t *x;  // the Q8_K image (LAUNCH / HANDOFF)
-        int pro;     // PROLOGUE: mode and f32 input
-        const float *xf, *norm_w;
-    };
-    struct out {
-        int mode = KQO_NONE;  // a HANDOFF this launch writes
-        uint8_t *q8 = nullptr;
-        const float *norm = nullptr;
-    };
-    unsigned long long *mv_dbg = nullptr;  // stamps build: the launch's phase stamps (tests/stamp_step.py KQ=1)
-    auto args = [&](const kq_mat &W, float *y, const float *resid, const float *gate_in, const img &in, const out &o,
-                    const kq_mat *up) {
-        kq_args k;
-        k.dbg_t = mv_dbg;
-        k.w = W.w; k.row_bytes = W.rb; k.rows = W.rows; k.nsb = (int)(W.K / 256);
-        k.x = in.x; k.x_col_stride = (W.K / 256) * 292; k.y = y; k.y_col_stride = W.rows; k.ncols = 1;
-        k.tiled = W.tiled;
-        k.resid = resid; k.gate_in = gate_in; k.gelu_tab = e->gelu_tab; k.gelu_clamp = c.gelu_clamp;
-        k.eps = c.eps;
-        if (in.src == PROLOGUE) {
-            k.pro = in.pro; k.xf = in.xf; k.xf_col_stride = W.K; k.norm_w = in.norm_w;
-        }
-        if (o.mode != KQO_NONE) {
-            k.q8_mode = o.mode; k.q8_out = o.q8; k.q8_norm = o.norm; k.q8_cnt = e->kq_cnt; k.q8_cnt_cap = e->kq_cnt_cap;
-            k.q8_abl = e->kq_abl;
-        }
-        if (up) k.w2 = up->w;
-        return k;
-    };
-    auto mv = [&](const kq_mat &W, float *y, const float *resid, const float *gate_in, const img &in, const out &o,
-                  const kq_mat *up) { return launch_matvec_kq(W.type, args(W, y, resid, gate_in, in, o, up), s); };
-    auto launch_img = [&](const img &in, int K) {
-        if (in.src != LAUNCH) return 0;
-        if (in.norm_w) return launch_norm_q8K(in.xf, K, in.norm_w, K, c.eps, 1, in.x, (K / 256) * 292, s);
-        return launch_quant_q8_K(in.xf, K, K, 1, in.x, (K / 256) * 292, s);
-    };
-    if (launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, e->hist, e->pos, 1, E, sqrtf((float)E), e->x, s, e->embd_tiled)) return -1;
-    for (int il = 0; il < c.n_layer; ++il) {
-        const layer_dev &L = e->layers[il];
-        const kq_layer &K = e->kql[il];
-        // layer 0's image A has no producing down: a launch when the plan hands it off
-        const img in_a{srcA == HANDOFF && il == 0 ? LAUNCH : srcA, e->kq_x, KQP_NORM, e->x, L.attn_norm};
-        if (launch_img(in_a, E)) return -1;
-        const bool pair = e->kq_pair && K.qk_fused && E % 2048 == 0 && E <= 4096 && K.q.tiled == K.v.tiled &&
-                          (K.q.rows + K.k.rows) % 8 == 0;
-        if (pair) {  // q|k and v (their own types) in one launch
-            kq_mat qk = K.q;
-            qk.rows = K.q.rows + K.k.rows;
-            if (launch_matvec_kq2(qk.type, args(qk, e->qkv, nullptr, nullptr, in_a, out{}, nullptr), K.v.type,
-                                  args(K.v, e->qkv + e->qw + e->kvw, nullptr, nullptr, in_a, out{}, nullptr), s))
-                return -1;
-        } else {
-            if (K.qk_fused) {  // q|k in one allocation (same type): one launch for both
-                kq_mat qk = K.q;
-                qk.rows = K.q.rows + K.k.rows;
-                if (mv(qk, e->qkv, nullptr, nullptr, in_a, out{}, nullptr)) return -1;
-            } else if (mv(K.q, e->qkv, nullptr, nullptr, in_a, out{}, nullptr) ||
-                       mv(K.k, e->qkv + e->qw, nullptr, nullptr, in_a, out{}, nullptr)) {
-                return -1;
-            }
-            if (mv(K.v, e->qkv + e->qw + e->kvw, nullptr, nullptr, in_a, out{}, nullptr)) return -1;
-        }
-        attn_args t;
-        t.qkv = e->qkv;
-        t.kc = kc_of(e, il);
-        t.vc = vc_of(e, il);
-        t.rope_cos = e->rope_cos; t.rope_sin = e->rope_sin; t.rope_cur = e->rope_cur; t.exp_tab = e->exp_tab;
-        t.pos = e->pos; t.out = e->attn;
-        t.H = c.n_head; t.Hkv = c.n_head_kv; t.hd = c.head_dim; t.ctx = c.n_ctx;
-        t.q_scale = 1.0f / sqrtf((float)c.head_dim);
-        t.mode = e->att_mode;
-        t.nwg = e->ag.nwg; t.sbuf = e->att_sbuf; t.sync = e->att_sync; t.err = e->att_sync + e->ag.sync_ints;
-        if (srcB == HANDOFF) t.out_q8k = e->kq_xa;  // each head's 256 outputs are one super-block
-        else if (t.mode == ATTN_PER_HEAD) t.dsplit = e->att_dsplit;
-        t.dbg_t = stamp_region(e, il, 1);  // diagnostics (stamps build): the attention's phases
-        if (launch_attn_decode(t, s)) return -1;
-        const img in_b{srcB, e->kq_xa, KQP_F32, e->attn, nullptr};
-        if (launch_img(in_b, e->qw)) return -1;
-        out o_c;
-        if (srcC == HANDOFF) {
-            o_c.mode = KQO_NORM; o_c.q8 = e->kq_xf; o_c.norm = L.ffn_norm;
-        }
-        mv_dbg = stamp_region(e, il, 2);
-        if (mv(K.o, e->sa, e->x, nullptr, in_b, o_c, nullptr)) return -1;  // + inpL (:723)
-        mv_dbg = nullptr;
-        const img in_c{srcC, e->kq_xf, KQP_NORM, e->sa, L.ffn_norm};
-        if (launch_img(in_c, E)) return -1;
-        out o_d;
-        if (srcD == HANDOFF) {
-            o_d.mode = KQO_QUANT; o_d.q8 = e->kq_xh;
-        }
-        if (K.gate.type == K.up.type && K.gate.rows == K.up.rows && K.gate.K == K.up.K && e->kq_dual) {
-            // gate and up in one launch, gelu(gate)*up in registers (:446-449)
-            mv_dbg = stamp_region(e, il, 3);
-            if (mv(K.gate, e->h, nullptr, nullptr, in_c, o_d, &K.up)) return -1;
-            mv_dbg = nullptr;
-        } else if (mv(K.gate, e->kq_g, nullptr, nullptr, in_c, out{}, nullptr) ||
-                   mv(K.up, e->h, nullptr, e->kq_g, in_c, o_d, nullptr)) {
-            return -1;
-        }
-        const img in_d{srcD, e->kq_xh, KQP_F32, e->h, nullptr};
-        if (launch_img(in_d, c.n_ff)) return -1;
-        // down (+ sa, :731); under a HANDOFF plan for A it writes the next layer's image A (or the
-        // output norm's)
-        out o_a;
-        if (srcA == HANDOFF) {
-            o_a.mode = KQO_NORM;
-            o_a.q8 = il + 1 < c.n_layer ? e->kq_x : e->xq8k;
-            o_a.norm = il + 1 < c.n_layer ? e->layers[il + 1].attn_norm : e->out_norm;
-        }
-        if (mv(K.down, e->x, e->sa, nullptr, in_d, o_a, nullptr)) return -1;
-    }
-    // the tied output's INIT: handed over by the last down, else its own launch (256k rows over
-    // thousands of workgroups would each redo the norm in a prologue)
-    if (srcA != HANDOFF && launch_norm_q8K(e->x, E, e->out_norm, E, c.eps, 1, e->xq8k, (E / 256) * 292, s)) return -1;
-    kq_args k;
-    k.w = e->embd_q6k; k.tiled = e->embd_tiled; k.row_bytes = e->embd_row_bytes; k.rows = c.n_vocab; k.nsb = E / 256;
-    k.x = e->xq8k; k.x_col_stride = (E / 256) * 292; k.y = e->logits; k.y_col_stride = c.n_vocab; k.ncols = 1;
-    if (launch_matvec_kq(T_Q6_K, k, s)) return -1;
-    if (launch_row_argmax(e->logits, c.n_vocab, e->key, 256, s)) return -1;
-    if (launch_advance(e->key, 256, e->token, e->pos, e->hist, c.n_ctx, e->nfix, rr, s)) return -1;
-    return 0;
-}
-
-// real weights in ggml row-major layout (a GGUF file's tensors, src/gemma_model.cpp:145-182)
 
 // rows [r0, r0 + dst.rows) of a host row-major Q4_0 / Q8_0 matrix into the tiled layout; from the
 // C-ABI weight cache's tiled copy (device to device) when the host weight was registered
@@ -919,38 +159,30 @@ static int upload_rows(const tiled_mat &dst, const void *host, int64_t r0, hipSt
     return rc;
 }
 
-static gemma_engine *engine_create(const gemma_hip_config *cfg, int device, int tp_n, int tp_rank, const void *nccl_id,
-                                   const host_weights *hw = nullptr, const std::vector<uint16_t *> *kc_ext = nullptr,
-                                   const std::vector<uint16_t *> *vc_ext = nullptr, int tp_flags = 0) {
-    set_error("");
-    const gemma_hip_config &c = *cfg;
+// ---- engine_create, phase by phase ----------------------------------------------------------------
+static bool config_ok(const gemma_hip_config &c, int tp_n, const void *nccl_id) {
     const bool kq_layers = c.wtype == T_Q4_K;  // K-quant layers (Q4_K / Q6_K per matrix) + Q6_K output
     if (c.head_dim % 32 || c.n_embd % 32 || c.n_ff % 32 || c.n_ctx % 32 || c.n_head % c.n_head_kv ||
         (c.wtype != T_Q4_0 && c.wtype != T_Q8_0 && !kq_layers) ||
         (c.out_type != 0 && c.out_type != c.wtype && c.out_type != T_Q6_K)) {
         set_error("gemma_engine_create: unsupported config");
-        return nullptr;
+        return false;
     }
     if (kq_layers && (c.n_embd % 256 || c.n_ff % 256 || (c.n_head * c.head_dim) % 256 || c.n_embd > 4096 || tp_n > 1 ||
                       nccl_id)) {
         set_error("gemma_engine_create: K-quant layers need n_embd, n_ff, n_head*head_dim % 256 == 0, n_embd <= 4096, one rank");
-        return nullptr;
+        return false;
     }
     if ((c.out_type == T_Q6_K || kq_layers) && (c.n_embd % 256 || c.n_embd > 4096 || tp_n > 1 || nccl_id)) {
         set_error("gemma_engine_create: a Q6_K output needs n_embd % 256 == 0, n_embd <= 4096 and one rank");
-        return nullptr;
+        return false;
     }
-    if (hipSetDevice(device) != hipSuccess) {
-        set_error("gemma_engine_create: hipSetDevice failed");
-        return nullptr;
-    }
-    constexpr bool cprof = false;  // engine-creation phase timings to stderr (diagnostics build: set true)
-    auto cnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double ct0 = cprof ? cnow() : 0.0;
-    auto *e = new gemma_engine();
-    e->cfg = c;
-    e->device = device;
-    GHIP_FATAL(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+    return true;
+}
+
+// the row split: every split matrix is cut into tp_n contiguous row ranges of whole 8-row tiles
+static bool set_shards(gemma_engine *e, int tp_n, int tp_rank, const void *nccl_id, int tp_flags) {
+    const gemma_hip_config &c = e->cfg;
     e->qw = c.n_head * c.head_dim;
     e->kvw = c.n_head_kv * c.head_dim;
     e->qkv_rows = e->qw + 2 * e->kvw;
@@ -958,26 +190,27 @@ static gemma_engine *engine_create(const gemma_hip_config *cfg, int device, int 
     e->tp_rank = tp_rank;
     e->rep_attn = tp_n > 1 && (tp_flags & GEMMA_TP_REP_ATTN);
     e->p2p = tp_n > 1 && !nccl_id && (tp_flags & GEMMA_TP_P2P);
-    // every split matrix is cut into tp_n contiguous row ranges of whole 8-row tiles
     if (tp_n < 1 || tp_rank < 0 || tp_rank >= tp_n || (!e->rep_attn && e->qkv_rows % (8 * tp_n)) ||
         c.n_embd % (8 * tp_n) || c.n_ff % (8 * tp_n) || c.n_vocab % (8 * tp_n) ||
         (tp_flags & ~(GEMMA_TP_REP_ATTN | GEMMA_TP_P2P)) || (e->p2p && tp_n > P2P_MAX_RANKS)) {
         set_error("gemma_engine_create: row split needs every matrix's rows to divide into 8-row tiles per rank");
-        delete e;
-        return nullptr;
+        return false;
     }
     e->sh_qkv = e->rep_attn ? e->qkv_rows : e->qkv_rows / tp_n;
     e->sh_e = c.n_embd / tp_n;
     e->sh_o = e->rep_attn ? c.n_embd : e->sh_e;
     e->sh_ff = c.n_ff / tp_n;
     e->sh_v = c.n_vocab / tp_n;
-    const int wt = c.wtype;
-    const uint64_t seed = c.seed;
+    e->n_virtual = (tp_n > 1 && !nccl_id && !e->p2p) ? tp_n : 1;
+    return true;
+}
+
+// token_embd / tied output and the output norm: uploaded, or the synthetic generator straight into
+// the device layout (matches oracle/gemma_cpu.cpp); returns true when an upload failed
+static bool create_embeddings(gemma_engine *e, const host_weights *hw) {
+    const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
-    // weights: synthetic generator straight into the tiled layout (matches oracle/gemma_cpu.cpp)
-    bool up_fail = false;  // a host-weight upload failed (last_error says which)
-    e->kq = kq_layers;
-    e->out_type = (c.out_type == T_Q6_K || kq_layers) ? T_Q6_K : wt;
+    bool fail = false;
     const double emb_std = (c.out_gain > 0.0f ? (double)c.out_gain : 1.0) / sqrt((double)c.n_embd);
     if (e->out_type == T_Q6_K) {  // oracle make_kmat(TID_EMBD, Q6_K, out_gain/sqrt(E)) on the device
         e->embd_row_bytes = (int64_t)c.n_embd / 256 * 210;
@@ -985,140 +218,148 @@ static gemma_engine *engine_create(const gemma_hip_config *cfg, int device, int 
         GHIP_FATAL(hipMalloc(&e->xq8k, (size_t)c.n_embd / 256 * 292));
         e->xq8k_rows = 1;
         if (!hw)
-            launch_synth_kquant(T_Q6_K, e->embd_q6k, c.n_vocab, c.n_embd, tensor_key(seed, TID_EMBD),
+            launch_synth_kquant(T_Q6_K, e->embd_q6k, c.n_vocab, c.n_embd, tensor_key(c.seed, TID_EMBD),
                                 (float)(emb_std / 0.68), s);
     } else {
-        e->embd = alloc_tiled(wt, c.n_vocab, c.n_embd, s);
-        if (!hw) launch_synth_tiled(e->embd, tensor_key(seed, TID_EMBD), synth_scale(emb_std), 0, s);
+        e->embd = alloc_tiled(c.wtype, c.n_vocab, c.n_embd, s);
+        if (!hw) launch_synth_tiled(e->embd, tensor_key(c.seed, TID_EMBD), synth_scale(emb_std), 0, s);
     }
     GHIP_FATAL(hipMalloc(&e->out_norm, (size_t)c.n_embd * 4));
     if (hw) {
         if (e->out_type == T_Q6_K)
             GHIP_FATAL(hipMemcpy(e->embd_q6k, hw->embd, (size_t)(e->embd_row_bytes * c.n_vocab), hipMemcpyHostToDevice));
         else
-            up_fail |= upload_rows(e->embd, hw->embd, 0, s) != 0;
+            fail |= upload_rows(e->embd, hw->embd, 0, s) != 0;
         GHIP_FATAL(hipMemcpy(e->out_norm, hw->out_norm, (size_t)c.n_embd * 4, hipMemcpyHostToDevice));
     } else {
-        launch_synth_norm(e->out_norm, c.n_embd, tensor_key(seed, TID_OUT_NORM), synth_scale(0.05), s);
+        launch_synth_norm(e->out_norm, c.n_embd, tensor_key(c.seed, TID_OUT_NORM), synth_scale(0.05), s);
     }
-    if (e->out_type == T_Q6_K && kq_retile_inplace(e->embd_q6k, T_Q6_K, c.n_vocab, c.n_embd, s, &e->embd_tiled)) up_fail = true;
-    e->n_virtual = (tp_n > 1 && !nccl_id && !e->p2p) ? tp_n : 1;
-    e->layers.resize((size_t)c.n_layer * e->n_virtual);
+    if (e->out_type == T_Q6_K && kq_retile_inplace(e->embd_q6k, T_Q6_K, c.n_vocab, c.n_embd, s, &e->embd_tiled)) fail = true;
+    return fail;
+}
+
+// a layer's norms: replicated, the slot-0 copy serves every virtual rank
+static void create_layer_norms(gemma_engine *e, int il, int vr, const host_weights *hw) {
+    const gemma_hip_config &c = e->cfg;
+    layer_dev &L = layer_of(e, il, vr);
+    if (vr > 0) {
+        L.attn_norm = layer_of(e, il, 0).attn_norm;
+        L.ffn_norm = layer_of(e, il, 0).ffn_norm;
+        return;
+    }
+    GHIP_FATAL(hipMalloc(&L.attn_norm, (size_t)c.n_embd * 4));
+    GHIP_FATAL(hipMalloc(&L.ffn_norm, (size_t)c.n_embd * 4));
+    if (hw) {
+        GHIP_FATAL(hipMemcpy(L.attn_norm, hw->layers[il].attn_norm, (size_t)c.n_embd * 4, hipMemcpyHostToDevice));
+        GHIP_FATAL(hipMemcpy(L.ffn_norm, hw->layers[il].ffn_norm, (size_t)c.n_embd * 4, hipMemcpyHostToDevice));
+    } else {
+        launch_synth_norm(L.attn_norm, c.n_embd, tensor_key(c.seed, tid_layer(il, L_ATTN_NORM)), synth_scale(0.05), e->stream);
+        launch_synth_norm(L.ffn_norm, c.n_embd, tensor_key(c.seed, tid_layer(il, L_FFN_NORM)), synth_scale(0.05), e->stream);
+    }
+}
+
+// layer il's K-quant matrices, raw rows: uploaded, or the oracle's make_kmat on the device; returns
+// true when an allocation or upload failed
+static bool create_layer_kq(gemma_engine *e, int il, const host_weights *hw) {
+    const gemma_hip_config &c = e->cfg;
+    hipStream_t s = e->stream;
+    bool fail = false;
+    if (e->kql.empty()) e->kql.resize(c.n_layer);
+    kq_layer &K = e->kql[il];
+    const host_weights::layer *H = hw ? &hw->layers[il] : nullptr;
+    // q and k of one type share one allocation (k's rows right after q's): one launch for q|k
+    const int tq = H ? H->tq : T_Q4_K, tk = H ? H->tk : T_Q4_K;
+    uint8_t *qk_buf = nullptr;
+    if (tq == tk) {
+        const int64_t rb = c.n_embd / 256 * (tq == T_Q4_K ? 144 : 210);
+        if (hipMalloc(&qk_buf, (size_t)(rb * (e->qw + e->kvw))) != hipSuccess) {
+            set_error("gemma_engine_create: weight alloc failed");
+            fail = true;
+        }
+    }
+    auto make = [&](kq_mat &m, int type, int64_t rows, int64_t k, int tid, double stdv, const void *host) {
+        m.type = type;
+        m.rows = rows;
+        m.K = k;
+        m.rb = k / 256 * (type == T_Q4_K ? 144 : 210);
+        if (qk_buf && (&m == &K.q || &m == &K.k)) {
+            m.w = qk_buf + (&m == &K.k ? m.rb * e->qw : 0);
+        } else if (hipMalloc(&m.w, (size_t)(m.rb * rows)) != hipSuccess) {
+            set_error("gemma_engine_create: weight alloc failed");
+            fail = true;
+            return;
+        }
+        if (host) {
+            fail |= hipMemcpy(m.w, host, (size_t)(m.rb * rows), hipMemcpyHostToDevice) != hipSuccess;
+        } else {
+            launch_synth_kquant(type, m.w, rows, k, tensor_key(c.seed, tid_layer(il, tid)),
+                                (float)(stdv / (type == T_Q4_K ? 0.8 : 0.68)), s);
+        }
+        if (!fail && kq_retile_inplace(m.w, type, rows, k, s, &m.tiled)) fail = true;
+    };
     const double se = 1.0 / sqrt((double)c.n_embd), sq = 1.0 / sqrt((double)e->qw), sf = 1.0 / sqrt((double)c.n_ff);
-    for (int il = 0; il < c.n_layer; ++il)
-    for (int vr = 0; vr < e->n_virtual; ++vr) {
-        layer_dev &L = layer_of(e, il, vr);
-        const int tp_rank = rank_of(e, vr);
-        if (vr == 0) {
-            GHIP_FATAL(hipMalloc(&L.attn_norm, (size_t)c.n_embd * 4));
-            GHIP_FATAL(hipMalloc(&L.ffn_norm, (size_t)c.n_embd * 4));
-            if (hw) {
-                GHIP_FATAL(hipMemcpy(L.attn_norm, hw->layers[il].attn_norm, (size_t)c.n_embd * 4, hipMemcpyHostToDevice));
-                GHIP_FATAL(hipMemcpy(L.ffn_norm, hw->layers[il].ffn_norm, (size_t)c.n_embd * 4, hipMemcpyHostToDevice));
-            } else {
-                launch_synth_norm(L.attn_norm, c.n_embd, tensor_key(seed, tid_layer(il, L_ATTN_NORM)), synth_scale(0.05), s);
-                launch_synth_norm(L.ffn_norm, c.n_embd, tensor_key(seed, tid_layer(il, L_FFN_NORM)), synth_scale(0.05), s);
-            }
-        } else {  // norms are replicated: the slot-0 copy serves every virtual rank
-            L.attn_norm = layer_of(e, il, 0).attn_norm;
-            L.ffn_norm = layer_of(e, il, 0).ffn_norm;
+    make(K.q, H ? H->tq : T_Q4_K, e->qw, c.n_embd, L_Q, se, H ? H->q : nullptr);
+    make(K.k, H ? H->tk : T_Q4_K, e->kvw, c.n_embd, L_K, se, H ? H->k : nullptr);
+    K.qk_fused = qk_buf != nullptr;
+    make(K.v, H ? H->tv : T_Q6_K, e->kvw, c.n_embd, L_V, se, H ? H->v : nullptr);
+    make(K.o, H ? H->to : T_Q4_K, c.n_embd, e->qw, L_O, 4.0 * sq, H ? H->o : nullptr);
+    make(K.gate, H ? H->tg : T_Q4_K, c.n_ff, c.n_embd, L_GATE, se, H ? H->gate : nullptr);
+    make(K.up, H ? H->tu : T_Q4_K, c.n_ff, c.n_embd, L_UP, se, H ? H->up : nullptr);
+    make(K.down, H ? H->td : T_Q6_K, c.n_embd, c.n_ff, L_DOWN, 4.0 * sf, H ? H->down : nullptr);
+    return fail;
+}
+
+// layer il's tiled matrices for (virtual) rank slot vr: this rank's rows of each, uploaded or from
+// the synthetic generator straight into the tiled layout; returns true when an upload failed
+static bool create_layer_tiled(gemma_engine *e, int il, int vr, const host_weights *hw) {
+    const gemma_hip_config &c = e->cfg;
+    const int wt = c.wtype;
+    hipStream_t s = e->stream;
+    bool fail = false;
+    layer_dev &L = layer_of(e, il, vr);
+    const int tp_rank = rank_of(e, vr);
+    const host_weights::layer *H = hw ? &hw->layers[il] : nullptr;
+    const double se = 1.0 / sqrt((double)c.n_embd), sq = 1.0 / sqrt((double)e->qw), sf = 1.0 / sqrt((double)c.n_ff);
+    // replicated attention block: one whole copy in slot 0 (virtual slots > 0 hold none)
+    const bool att_here = !e->rep_attn || vr == 0;
+    // this rank's rows [r0, r0 + n) of the fused [Wq | Wk | Wv]: the pieces of each source tensor
+    const int64_t q0 = e->rep_attn ? 0 : (int64_t)tp_rank * e->sh_qkv, qn = att_here ? e->sh_qkv : 0;
+    if (att_here) L.qkv = alloc_tiled(wt, qn, c.n_embd, s);
+    const int64_t src_start[3] = {0, e->qw, e->qw + e->kvw}, src_rows[3] = {e->qw, e->kvw, e->kvw};
+    const int src_tid[3] = {L_Q, L_K, L_V};
+    const void *src_host[3] = {H ? H->q : nullptr, H ? H->k : nullptr, H ? H->v : nullptr};
+    for (int k = 0; k < 3; ++k) {
+        const int64_t a0 = std::max(q0, src_start[k]), a1 = std::min(q0 + qn, src_start[k] + src_rows[k]);
+        if (a1 > a0 && hw) {
+            fail |= upload_rows(sub_rows(L.qkv, a0 - q0, a1 - a0), src_host[k], a0 - src_start[k], s) != 0;
+        } else if (a1 > a0) {
+            launch_synth_tiled(sub_rows(L.qkv, a0 - q0, a1 - a0), tensor_key(c.seed, tid_layer(il, src_tid[k])),
+                               synth_scale(se), a0 - src_start[k], s);
         }
-        if (kq_layers) {  // raw K-quant rows: uploaded, or the oracle's make_kmat on the device
-            if (e->kql.empty()) e->kql.resize(c.n_layer);
-            kq_layer &K = e->kql[il];
-            const host_weights::layer *H = hw ? &hw->layers[il] : nullptr;
-            // q and k of one type share one allocation (k's rows right after q's): one launch for q|k
-            const int tq = H ? H->tq : T_Q4_K, tk = H ? H->tk : T_Q4_K;
-            uint8_t *qk_buf = nullptr;
-            if (tq == tk) {
-                const int64_t rb = c.n_embd / 256 * (tq == T_Q4_K ? 144 : 210);
-                if (hipMalloc(&qk_buf, (size_t)(rb * (e->qw + e->kvw))) != hipSuccess) {
-                    set_error("gemma_engine_create: weight alloc failed");
-                    up_fail = true;
-                }
-            }
-            auto make = [&](kq_mat &m, int type, int64_t rows, int64_t k, int tid, double stdv, const void *host) {
-                m.type = type;
-                m.rows = rows;
-                m.K = k;
-                m.rb = k / 256 * (type == T_Q4_K ? 144 : 210);
-                if (qk_buf && (&m == &K.q || &m == &K.k)) {
-                    m.w = qk_buf + (&m == &K.k ? m.rb * e->qw : 0);
-                } else if (hipMalloc(&m.w, (size_t)(m.rb * rows)) != hipSuccess) {
-                    set_error("gemma_engine_create: weight alloc failed");
-                    up_fail = true;
-                    return;
-                }
-                if (host) {
-                    up_fail |= hipMemcpy(m.w, host, (size_t)(m.rb * rows), hipMemcpyHostToDevice) != hipSuccess;
-                } else {
-                    launch_synth_kquant(type, m.w, rows, k, tensor_key(seed, tid_layer(il, tid)),
-                                        (float)(stdv / (type == T_Q4_K ? 0.8 : 0.68)), s);
-                }
-                if (!up_fail && kq_retile_inplace(m.w, type, rows, k, s, &m.tiled)) up_fail = true;
-            };
-            make(K.q, H ? H->tq : T_Q4_K, e->qw, c.n_embd, L_Q, se, H ? H->q : nullptr);
-            make(K.k, H ? H->tk : T_Q4_K, e->kvw, c.n_embd, L_K, se, H ? H->k : nullptr);
-            K.qk_fused = qk_buf != nullptr;
-            make(K.v, H ? H->tv : T_Q6_K, e->kvw, c.n_embd, L_V, se, H ? H->v : nullptr);
-            make(K.o, H ? H->to : T_Q4_K, c.n_embd, e->qw, L_O, 4.0 * sq, H ? H->o : nullptr);
-            make(K.gate, H ? H->tg : T_Q4_K, c.n_ff, c.n_embd, L_GATE, se, H ? H->gate : nullptr);
-            make(K.up, H ? H->tu : T_Q4_K, c.n_ff, c.n_embd, L_UP, se, H ? H->up : nullptr);
-            make(K.down, H ? H->td : T_Q6_K, c.n_embd, c.n_ff, L_DOWN, 4.0 * sf, H ? H->down : nullptr);
-            continue;
-        }
-        // replicated attention block: one whole copy in slot 0 (virtual slots > 0 hold none)
-        const bool att_here = !e->rep_attn || vr == 0;
-        const int64_t o0 = e->rep_attn ? 0 : (int64_t)tp_rank * e->sh_o;
-        // this rank's rows [r0, r0 + n) of the fused [Wq | Wk | Wv]: the pieces of each source tensor
-        const int64_t q0 = e->rep_attn ? 0 : (int64_t)tp_rank * e->sh_qkv, qn = att_here ? e->sh_qkv : 0;
-        if (att_here) L.qkv = alloc_tiled(wt, qn, c.n_embd, s);
-        const int64_t src_start[3] = {0, e->qw, e->qw + e->kvw}, src_rows[3] = {e->qw, e->kvw, e->kvw};
-        const int src_tid[3] = {L_Q, L_K, L_V};
-        const void *src_host[3] = {hw ? hw->layers[il].q : nullptr, hw ? hw->layers[il].k : nullptr,
-                                   hw ? hw->layers[il].v : nullptr};
-        for (int k = 0; k < 3; ++k) {
-            const int64_t a0 = std::max(q0, src_start[k]), a1 = std::min(q0 + qn, src_start[k] + src_rows[k]);
-            if (a1 > a0 && hw) {
-                up_fail |= upload_rows(sub_rows(L.qkv, a0 - q0, a1 - a0), src_host[k], a0 - src_start[k], s) != 0;
-            } else if (a1 > a0) {
-                launch_synth_tiled(sub_rows(L.qkv, a0 - q0, a1 - a0), tensor_key(seed, tid_layer(il, src_tid[k])),
-                                   synth_scale(se), a0 - src_start[k], s);
-            }
-        }
-        if (hw) {
-            const host_weights::layer &H = hw->layers[il];
-            if (att_here) L.o = alloc_tiled(wt, e->sh_o, e->qw, s);
-            L.gate = alloc_tiled(wt, e->sh_ff, c.n_embd, s);
-            L.up = alloc_tiled(wt, e->sh_ff, c.n_embd, s);
-            L.down = alloc_tiled(wt, e->sh_e, c.n_ff, s);
-            if (att_here) up_fail |= upload_rows(L.o, H.o, o0, s) != 0;
-            up_fail |= upload_rows(L.gate, H.gate, (int64_t)tp_rank * e->sh_ff, s) != 0;
-            up_fail |= upload_rows(L.up, H.up, (int64_t)tp_rank * e->sh_ff, s) != 0;
-            up_fail |= upload_rows(L.down, H.down, (int64_t)tp_rank * e->sh_e, s) != 0;
-            continue;
-        }
-        if (att_here) {
-            L.o = alloc_tiled(wt, e->sh_o, e->qw, s);
-            launch_synth_tiled(L.o, tensor_key(seed, tid_layer(il, L_O)), synth_scale(4.0 * sq), o0, s);
-        }
-        L.gate = alloc_tiled(wt, e->sh_ff, c.n_embd, s);
-        launch_synth_tiled(L.gate, tensor_key(seed, tid_layer(il, L_GATE)), synth_scale(se), (int64_t)tp_rank * e->sh_ff, s);
-        L.up = alloc_tiled(wt, e->sh_ff, c.n_embd, s);
-        launch_synth_tiled(L.up, tensor_key(seed, tid_layer(il, L_UP)), synth_scale(se), (int64_t)tp_rank * e->sh_ff, s);
-        L.down = alloc_tiled(wt, e->sh_e, c.n_ff, s);
-        launch_synth_tiled(L.down, tensor_key(seed, tid_layer(il, L_DOWN)), synth_scale(4.0 * sf), (int64_t)tp_rank * e->sh_e,
-                           s);
     }
-    if (up_fail) {
-        gemma_engine_free(e);
-        return nullptr;
-    }
-    if (cprof) {
-        (void)hipStreamSynchronize(s);
-        fprintf(stderr, "[gemma_hip] engine create: weights %.2f ms\n", cnow() - ct0);
-    }
-    // caches, tables, activations
+    // rows [r0, r0 + rows) of one source tensor as its own matrix
+    auto make = [&](tiled_mat &m, int64_t rows, int64_t K, const void *host, int tid, double stdv, int64_t r0) {
+        m = alloc_tiled(wt, rows, K, s);
+        if (hw) fail |= upload_rows(m, host, r0, s) != 0;
+        else launch_synth_tiled(m, tensor_key(c.seed, tid_layer(il, tid)), synth_scale(stdv), r0, s);
+    };
+    if (att_here) make(L.o, e->sh_o, e->qw, H ? H->o : nullptr, L_O, 4.0 * sq, e->rep_attn ? 0 : (int64_t)tp_rank * e->sh_o);
+    make(L.gate, e->sh_ff, c.n_embd, H ? H->gate : nullptr, L_GATE, se, (int64_t)tp_rank * e->sh_ff);
+    make(L.up, e->sh_ff, c.n_embd, H ? H->up : nullptr, L_UP, se, (int64_t)tp_rank * e->sh_ff);
+    make(L.down, e->sh_e, c.n_ff, H ? H->down : nullptr, L_DOWN, 4.0 * sf, (int64_t)tp_rank * e->sh_e);
+    return fail;
+}
+
+template <typename T> static void alloc_zeroed(T **p, size_t bytes) {
+    GHIP_FATAL(hipMalloc(p, bytes));
+    GHIP_FATAL(hipMemset(*p, 0, bytes));
+}
+
+// caches, tables, activations, hand-off counters and the decode state; -1 (last_error set) when
+// the attention geometry is unsupported
+static int create_buffers(gemma_engine *e, const std::vector<uint16_t *> *kc_ext, const std::vector<uint16_t *> *vc_ext) {
+    const gemma_hip_config &c = e->cfg;
+    hipStream_t s = e->stream;
     const size_t kv_elems = (size_t)c.n_layer * c.n_ctx * e->kvw;
     if (kc_ext && vc_ext) {
         e->kc_ext = *kc_ext;
@@ -1138,8 +379,7 @@ static gemma_engine *engine_create(const gemma_hip_config *cfg, int device, int 
     e->ag = attn_geometry(c.n_head, c.n_head_kv, c.head_dim, c.n_ctx);
     if (e->att_mode == ATTN_SPLIT && !e->ag.nwg) {
         set_error("gemma_engine_create: unsupported attention geometry");
-        gemma_engine_free(e);
-        return nullptr;
+        return -1;
     }
     GHIP_FATAL(hipMalloc(&e->att_sbuf, std::max<size_t>(e->ag.sbuf_floats, 1) * 4));
     GHIP_FATAL(hipMalloc(&e->att_sync, (e->ag.sync_ints + 1) * 4));
@@ -1165,21 +405,17 @@ static gemma_engine *engine_create(const gemma_hip_config *cfg, int device, int 
     if (e->qw % 128 == 0) {  // whole 4-block groups
         GHIP_FATAL(hipMalloc(&e->att_act, (size_t)e->qw));
         GHIP_FATAL(hipMalloc(&e->att_da, (size_t)e->qw / 32 * 4));
-        GHIP_FATAL(hipMalloc(&e->front_cnt, (size_t)c.n_layer * 16 * 32 * 4));
-        GHIP_FATAL(hipMalloc(&e->front_err, 64));
-        GHIP_FATAL(hipMemset(e->front_cnt, 0, (size_t)c.n_layer * 16 * 32 * 4));
-        GHIP_FATAL(hipMemset(e->front_err, 0, 64));
-        GHIP_FATAL(hipMalloc(&e->ao_cnt, (size_t)c.n_layer * 16 * 32 * 4));
-        GHIP_FATAL(hipMalloc(&e->ao_err, 64));
-        GHIP_FATAL(hipMemset(e->ao_cnt, 0, (size_t)c.n_layer * 16 * 32 * 4));
-        GHIP_FATAL(hipMemset(e->ao_err, 0, 64));
+        alloc_zeroed(&e->front_cnt, (size_t)c.n_layer * 16 * 32 * 4);
+        alloc_zeroed(&e->front_err, 64);
+        alloc_zeroed(&e->ao_cnt, (size_t)c.n_layer * 16 * 32 * 4);
+        alloc_zeroed(&e->ao_err, 64);
     }
     if (e->sh_ff % 128 == 0) {  // every rank's shard is whole 4-block groups
         GHIP_FATAL(hipMalloc(&e->h_act, (size_t)c.n_ff));
         GHIP_FATAL(hipMalloc(&e->h_da, (size_t)c.n_ff / 32 * 4));
     }
     GHIP_FATAL(hipMalloc(&e->logits, (size_t)c.n_vocab * 4));
-    if (kq_layers) {
+    if (e->kq) {
         const int64_t kmax = std::max<int64_t>(std::max<int64_t>(c.n_embd, e->qw), c.n_ff);
         const size_t img = (size_t)(kmax / 256 * 292 + 255) & ~(size_t)255;
         GHIP_FATAL(hipMalloc(&e->kq_x, 4 * img));
@@ -1189,21 +425,17 @@ static gemma_engine *engine_create(const gemma_hip_config *cfg, int device, int 
         // counters: a quantize hand-off takes rows/256 (gate/up: n_ff/256), a norm hand-off rows/256 + 1
         // (down, attn-out: n_embd/256 + 1 — more than n_ff/256 when n_ff <= n_embd)
         e->kq_cnt_cap = (int)std::max<int64_t>(std::max<int64_t>(c.n_ff / 256, c.n_embd / 256 + 1), 1);
-        GHIP_FATAL(hipMalloc(&e->kq_cnt, (size_t)e->kq_cnt_cap * 128));
-        GHIP_FATAL(hipMemset(e->kq_cnt, 0, (size_t)e->kq_cnt_cap * 128));
+        alloc_zeroed(&e->kq_cnt, (size_t)e->kq_cnt_cap * 128);
         GHIP_FATAL(hipMalloc(&e->kq_g, (size_t)c.n_ff * 4));
     }
     {  // the persistent token launch: granules, epoch, error word, argument copies
         const tok_gran_sizes g = token_gran_sizes(c.n_embd, c.n_ff, e->qkv_rows);
         const size_t n = g.gx + g.gqkv + g.gatt + g.gatt_da + g.gsa + g.gh + g.gh_da;
-        GHIP_FATAL(hipMalloc(&e->tok_gran, n * 8));
-        GHIP_FATAL(hipMemset(e->tok_gran, 0, n * 8));
-        GHIP_FATAL(hipMalloc(&e->epoch, 64));
+        alloc_zeroed(&e->tok_gran, n * 8);
+        alloc_zeroed(&e->epoch, 64);
         const unsigned one = 1;
-        GHIP_FATAL(hipMemset(e->epoch, 0, 64));
         GHIP_FATAL(hipMemcpy(e->epoch, &one, 4, hipMemcpyHostToDevice));
-        GHIP_FATAL(hipMalloc(&e->tok_err, 64));
-        GHIP_FATAL(hipMemset(e->tok_err, 0, 64));
+        alloc_zeroed(&e->tok_err, 64);
         GHIP_FATAL(hipMalloc(&e->tok_dev, sizeof(tok_args)));
         GHIP_FATAL(hipMalloc(&e->tok_tab, (size_t)c.n_layer * sizeof(tok_layer)));
     }
@@ -1214,28 +446,75 @@ static gemma_engine *engine_create(const gemma_hip_config *cfg, int device, int 
     GHIP_FATAL(hipMalloc(&e->hist, (size_t)(c.n_ctx + 1) * 4));
     GHIP_FATAL(hipMemsetAsync(e->key, 0, (size_t)e->grid_big * 8, s));
     GHIP_FATAL(hipMemsetAsync(e->hist, 0, (size_t)(c.n_ctx + 1) * 4, s));
-    GHIP_FATAL(hipMalloc(&e->rank_keys, (size_t)tp_n * 8));
-    if (e->p2p) {  // inboxes mirroring every gathered vector, then one flag word per source rank
-        size_t off = 0;
-        auto take = [&](int64_t &ib, size_t bytes) { ib = (int64_t)off; off += (bytes + 255) & ~(size_t)255; };
-        take(e->ib_qkv, (size_t)e->qkv_rows * 4);
-        take(e->ib_sa, (size_t)c.n_embd * 4);
-        take(e->ib_h, (size_t)c.n_ff * 4);
-        take(e->ib_x, (size_t)c.n_embd * 4);
-        take(e->ib_hact, e->h_act ? (size_t)c.n_ff : 0);
-        take(e->ib_hda, e->h_act ? (size_t)c.n_ff / 32 * 4 : 0);
-        take(e->ib_logits, (size_t)c.n_vocab * 4);
-        take(e->ib_keys, (size_t)tp_n * 8);
-        take(e->ib_flags, (size_t)P2P_MAX_RANKS * 4);
-        GHIP_FATAL(hipExtMallocWithFlags((void **)&e->p2p_arena, off, hipDeviceMallocUncached));
-        GHIP_FATAL(hipMemset(e->p2p_arena, 0, off));
-        GHIP_FATAL(hipMalloc(&e->p2p_seq, 64));
-        GHIP_FATAL(hipMemset(e->p2p_seq, 0, 64));
-        GHIP_FATAL(hipMalloc(&e->p2p_err, 64));
-        GHIP_FATAL(hipMemset(e->p2p_err, 0, 64));
-        e->p2p_peer[tp_rank] = e->p2p_arena;
+    GHIP_FATAL(hipMalloc(&e->rank_keys, (size_t)e->tp_n * 8));
+    return 0;
+}
+
+// GEMMA_TP_P2P: inboxes mirroring every gathered vector, then one flag word per source rank
+static void create_p2p_arena(gemma_engine *e) {
+    const gemma_hip_config &c = e->cfg;
+    size_t off = 0;
+    auto take = [&](int64_t &ib, size_t bytes) { ib = (int64_t)off; off += (bytes + 255) & ~(size_t)255; };
+    take(e->ib_qkv, (size_t)e->qkv_rows * 4);
+    take(e->ib_sa, (size_t)c.n_embd * 4);
+    take(e->ib_h, (size_t)c.n_ff * 4);
+    take(e->ib_x, (size_t)c.n_embd * 4);
+    take(e->ib_hact, e->h_act ? (size_t)c.n_ff : 0);
+    take(e->ib_hda, e->h_act ? (size_t)c.n_ff / 32 * 4 : 0);
+    take(e->ib_logits, (size_t)c.n_vocab * 4);
+    take(e->ib_keys, (size_t)e->tp_n * 8);
+    take(e->ib_flags, (size_t)P2P_MAX_RANKS * 4);
+    GHIP_FATAL(hipExtMallocWithFlags((void **)&e->p2p_arena, off, hipDeviceMallocUncached));
+    GHIP_FATAL(hipMemset(e->p2p_arena, 0, off));
+    alloc_zeroed(&e->p2p_seq, 64);
+    alloc_zeroed(&e->p2p_err, 64);
+    e->p2p_peer[e->tp_rank] = e->p2p_arena;
+}
+
+static gemma_engine *engine_create(const gemma_hip_config *cfg, int device, int tp_n, int tp_rank, const void *nccl_id,
+                                   const host_weights *hw = nullptr, const std::vector<uint16_t *> *kc_ext = nullptr,
+                                   const std::vector<uint16_t *> *vc_ext = nullptr, int tp_flags = 0) {
+    set_error("");
+    const gemma_hip_config &c = *cfg;
+    if (!config_ok(c, tp_n, nccl_id)) return nullptr;
+    if (hipSetDevice(device) != hipSuccess) {
+        set_error("gemma_engine_create: hipSetDevice failed");
+        return nullptr;
     }
-    GHIP_FATAL(hipStreamSynchronize(s));
+    constexpr bool cprof = false;  // engine-creation phase timings to stderr (diagnostics build: set true)
+    auto cnow = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double ct0 = cprof ? cnow() : 0.0;
+    auto *e = new gemma_engine();
+    e->cfg = c;
+    e->device = device;
+    GHIP_FATAL(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+    if (!set_shards(e, tp_n, tp_rank, nccl_id, tp_flags)) {
+        delete e;
+        return nullptr;
+    }
+    e->kq = c.wtype == T_Q4_K;
+    e->out_type = (c.out_type == T_Q6_K || e->kq) ? T_Q6_K : c.wtype;
+    bool up_fail = create_embeddings(e, hw);  // a host-weight upload failed (last_error says which)
+    e->layers.resize((size_t)c.n_layer * e->n_virtual);
+    for (int il = 0; il < c.n_layer; ++il)
+        for (int vr = 0; vr < e->n_virtual; ++vr) {
+            create_layer_norms(e, il, vr, hw);
+            up_fail |= e->kq ? create_layer_kq(e, il, hw) : create_layer_tiled(e, il, vr, hw);
+        }
+    if (up_fail) {
+        gemma_engine_free(e);
+        return nullptr;
+    }
+    if (cprof) {
+        (void)hipStreamSynchronize(e->stream);
+        fprintf(stderr, "[gemma_hip] engine create: weights %.2f ms\n", cnow() - ct0);
+    }
+    if (create_buffers(e, kc_ext, vc_ext)) {
+        gemma_engine_free(e);
+        return nullptr;
+    }
+    if (e->p2p) create_p2p_arena(e);
+    GHIP_FATAL(hipStreamSynchronize(e->stream));
     // a communicator whenever an id is given, also for ONE rank: every gather, the key gather and
     // RCCL inside the captured hipGraph then run exactly as on N GPUs (a 1-rank all-gather in place)
     if (nccl_id) {
@@ -1245,15 +524,13 @@ static gemma_engine *engine_create(const gemma_hip_config *cfg, int device, int 
         if (nr != ncclSuccess) set_error(std::string("ncclCommInitRank: ") + ncclGetErrorString(nr));
     }
     e->tp_n_keys = tp_n > 1 || e->comm;
-    {
-        // default launch plan (the shapes of every rank's shards are equal)
-        const layer_dev &L0 = e->layers[0];
-        e->plan[MC_QKV] = {pick_ks(wt, L0.qkv.n_bt, e->ks_small), 1, 0};
-        e->plan[MC_O] = {pick_ks(wt, L0.o.n_bt, e->ks_small), 1, e->att_act ? 1 : 0};  // the image feeds the fused front
-        e->plan[MC_GU] = {1, 1, 0};
-        e->plan[MC_DOWN] = {pick_ks(wt, L0.down.n_bt, e->ks_down), 1, 0};
-        e->plan[MC_LOGITS] = {1, 8, 0};  // 8 row tiles per workgroup: the round-5 bench lines' best
-    }
+    // default launch plan (the shapes of every rank's shards are equal)
+    const layer_dev &L0 = e->layers[0];
+    e->plan[MC_QKV] = {pick_ks(c.wtype, L0.qkv.n_bt, e->ks_small), 1, 0};
+    e->plan[MC_O] = {pick_ks(c.wtype, L0.o.n_bt, e->ks_small), 1, e->att_act ? 1 : 0};  // the image feeds the fused front
+    e->plan[MC_GU] = {1, 1, 0};
+    e->plan[MC_DOWN] = {pick_ks(c.wtype, L0.down.n_bt, e->ks_down), 1, 0};
+    e->plan[MC_LOGITS] = {1, 8, 0};  // 8 row tiles per workgroup: the round-5 bench lines' best
     if (last_error().empty()) (void)tok_prepare(e);  // K-quant engines: persist_why = "K-quant layers"
     if (!last_error().empty()) {
         gemma_engine_free(e);
@@ -1331,8 +608,9 @@ extern "C" gemma_engine *gemma_engine_create_from_gguf(const char *path, int n_c
         }
     }
     const bool kqm = c.wtype == T_Q4_K;
-    // K-quant layers: each matrix Q4_K or Q6_K; returns the data and records the type
-    auto ktensor = [&](const std::string &name, int64_t ne0, int64_t ne1, int &type) -> const void * {
+    // a layer matrix of the layer type; K-quant layers: each Q4_K or Q6_K, the type recorded
+    auto mat = [&](const std::string &name, int64_t ne0, int64_t ne1, int &type) -> const void * {
+        if (!kqm) return tensor(name, c.wtype, ne0, ne1);
         const void *d = tensor(name, -1, ne0, ne1);
         if (!d) return nullptr;
         const int t = (int)ggml_get_tensor(w, name.c_str())->type;
@@ -1350,24 +628,13 @@ extern "C" gemma_engine *gemma_engine_create_from_gguf(const char *path, int n_c
         host_weights::layer L;
         L.attn_norm = (const float *)tensor(b + "attn_norm.weight", GGML_TYPE_F32, c.n_embd, 1);
         L.ffn_norm = (const float *)tensor(b + "ffn_norm.weight", GGML_TYPE_F32, c.n_embd, 1);
-        if (kqm) {
-            L.q = ktensor(b + "attn_q.weight", c.n_embd, qw, L.tq);
-            L.k = ktensor(b + "attn_k.weight", c.n_embd, kvw, L.tk);
-            L.v = ktensor(b + "attn_v.weight", c.n_embd, kvw, L.tv);
-            L.o = ktensor(b + "attn_output.weight", qw, c.n_embd, L.to);
-            L.gate = ktensor(b + "ffn_gate.weight", c.n_embd, c.n_ff, L.tg);
-            L.up = ktensor(b + "ffn_up.weight", c.n_embd, c.n_ff, L.tu);
-            L.down = ktensor(b + "ffn_down.weight", c.n_ff, c.n_embd, L.td);
-            hw.layers.push_back(L);
-            continue;
-        }
-        L.q = tensor(b + "attn_q.weight", c.wtype, c.n_embd, qw);
-        L.k = tensor(b + "attn_k.weight", c.wtype, c.n_embd, kvw);
-        L.v = tensor(b + "attn_v.weight", c.wtype, c.n_embd, kvw);
-        L.o = tensor(b + "attn_output.weight", c.wtype, qw, c.n_embd);
-        L.gate = tensor(b + "ffn_gate.weight", c.wtype, c.n_embd, c.n_ff);
-        L.up = tensor(b + "ffn_up.weight", c.wtype, c.n_embd, c.n_ff);
-        L.down = tensor(b + "ffn_down.weight", c.wtype, c.n_ff, c.n_embd);
+        L.q = mat(b + "attn_q.weight", c.n_embd, qw, L.tq);
+        L.k = mat(b + "attn_k.weight", c.n_embd, kvw, L.tk);
+        L.v = mat(b + "attn_v.weight", c.n_embd, kvw, L.tv);
+        L.o = mat(b + "attn_output.weight", qw, c.n_embd, L.to);
+        L.gate = mat(b + "ffn_gate.weight", c.n_embd, c.n_ff, L.tg);
+        L.up = mat(b + "ffn_up.weight", c.n_embd, c.n_ff, L.tu);
+        L.down = mat(b + "ffn_down.weight", c.n_ff, c.n_embd, L.td);
         hw.layers.push_back(L);
     }
     gemma_engine *e = nullptr;
@@ -1480,8 +747,6 @@ extern "C" int gemma_engine_tp_flags(const gemma_engine *e) {
     return e ? (e->rep_attn ? GEMMA_TP_REP_ATTN : 0) | (e->p2p ? GEMMA_TP_P2P : 0) : -1;
 }
 
-static void drop_graph(gemma_engine *e);
-
 extern "C" void gemma_engine_free(gemma_engine *e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
@@ -1559,7 +824,8 @@ extern "C" int gemma_engine_begin(gemma_engine *e, const int32_t *prompt, int n_
     return 0;
 }
 
-static int ensure_graph(gemma_engine *e) {
+// the decode step captured once in a hipGraph (after a first eager step has set the kernels' LDS attributes)
+int ensure_graph(gemma_engine *e) {
     if (e->graph_exec) return 0;
     GHIP_CHECK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeRelaxed));
     const int r = enqueue_step(e);
@@ -1705,940 +971,13 @@ extern "C" int64_t gemma_engine_tensor(gemma_engine *e, int tid, void *dst, int6
     return -1;
 }
 
-// ---- hipEvent timing of one hot kernel on the engine stream (bench.py roofline leg) -----------
-extern "C" double gemma_engine_time(gemma_engine *e, int which, int iters, double *algo_bytes) {
-    set_error("");
-    (void)hipSetDevice(e->device);
-    const gemma_hip_config &c = e->cfg;
-    const int wt = c.wtype;
-    const double act_q8 = 34.0 / 32.0;  // bytes per activation element after quantization
-    // launches rotate over the layers' matrices, as in a decode step: each launch reads its weights
-    // cold (18 x the FFN matrices exceed the 256 MB Infinity Cache)
-    int layer = 0;
-    mv_args a;
-    int ks = 1, pro = PRO_F32, epi = EPI_STORE, grid = 1;
-    double bytes = 0;
-    auto set_mat = [&](const tiled_mat &m) {
-        a.qs = m.qs; a.sc = m.sc; a.rows = m.rows; a.n_rt = m.n_rt; a.n_bt = m.n_bt; a.nb = m.nb;
-    };
-    auto setup = [&](layer_dev &L) {
-    switch (which) {
-        case 0:
-            set_mat(L.gate);
-            a.qs2 = L.up.qs; a.sc2 = L.up.sc;
-            a.x = e->sa; a.norm_w = L.ffn_norm; a.eps = c.eps; a.y = e->h; a.gelu_tab = e->gelu_tab;
-            pro = PRO_NORM; epi = EPI_GELU_MUL; ks = e->plan[MC_GU].ks;  // 2 = gate and up on separate waves
-            grid = mv_grid(e, MC_GU, L.gate.n_rt);
-            bytes = (double)L.gate.algo_bytes() + L.up.algo_bytes() + c.n_embd * 4.0 * 2 + c.n_ff * 4.0;
-            break;
-        case 1:
-            set_mat(L.down);
-            a.x = e->h; a.y = e->x; a.resid = e->sa; ks = pick_ks(wt, L.down.n_bt, e->plan[MC_DOWN].ks); epi = EPI_ADD;
-            if (e->h_act && e->plan[MC_DOWN].img) { a.x = e->h_act; a.x_da = e->h_da; pro = PRO_IMG; }
-            grid = mv_grid(e, MC_DOWN, L.down.n_rt);
-            bytes = (double)L.down.algo_bytes() + c.n_ff * (e->h_act ? 36.0 / 32 : 4.0) + c.n_embd * 8.0;
-            break;
-        case 2:
-            set_mat(L.qkv);
-            a.x = e->x; a.norm_w = L.attn_norm; a.eps = c.eps; a.y = e->qkv; ks = pick_ks(wt, L.qkv.n_bt, e->plan[MC_QKV].ks); pro = PRO_NORM;
-            grid = mv_grid(e, MC_QKV, L.qkv.n_rt);
-            bytes = (double)L.qkv.algo_bytes() + c.n_embd * 8.0 + e->qkv_rows * 4.0;
-            break;
-        case 3:
-            set_mat(L.o);
-            a.x = e->attn; a.y = e->sa; a.resid = e->x; ks = pick_ks(wt, L.o.n_bt, e->plan[MC_O].ks); epi = EPI_ADD;
-            if (e->att_act && att_img_ok(e) && e->plan[MC_O].img) { a.x = e->att_act; a.x_da = e->att_da; pro = PRO_IMG; }
-            grid = mv_grid(e, MC_O, L.o.n_rt);
-            bytes = (double)L.o.algo_bytes() + e->qw * (pro == PRO_IMG ? 36.0 / 32 : 4.0) + c.n_embd * 8.0;
-            break;
-        case 4:
-            set_mat(e->embd);
-            a.x = e->x; a.norm_w = e->out_norm; a.eps = c.eps; a.y = e->logits; a.argmax_key = e->key;
-            pro = PRO_NORM; epi = EPI_ARGMAX;
-            grid = mv_grid(e, MC_LOGITS, e->embd.n_rt);
-            bytes = (double)e->embd.algo_bytes() + c.n_embd * 8.0 + c.n_vocab * 4.0;
-            break;
-        default:
-            break;
-    }
-    };
-    if (e->kq) {
-        set_error("gemma_engine_time: K-quant layer engines time their matvecs with gemma_kq_time");
-        return -1.0;
-    }
-    if (which == 4 && e->out_type == T_Q6_K) {
-        set_error("gemma_engine_time: the logits kernel of a Q6_K output is the K-quant matvec (gemma_kq_time)");
-        return -1.0;
-    }
-    if (which < 0 || which > 5) {
-        set_error("gemma_engine_time: bad kernel id");
-        return -1.0;
-    }
-    setup(e->layers[0]);
-    (void)act_q8;
-    const bool hot = e->time_hot != 0;
-    a.ablate = e->ablate;
-    hipEvent_t t0, t1;
-    GHIP_FATAL(hipEventCreate(&t0));
-    GHIP_FATAL(hipEventCreate(&t1));
-    auto run = [&]() -> int {
-        if (which == 5) {
-            if (ensure_graph(e)) return -1;
-            GHIP_CHECK(hipGraphLaunch(e->graph_exec, e->stream));
-            return 0;
-        }
-        if (which < 4) {
-            setup(e->layers[layer]);
-            if (!hot) layer = (layer + 1) % c.n_layer;  // hot: the same matrix (Infinity-Cache resident)
-        }
-        return launch_matvec(wt, ks, pro, epi, a, grid, e->stream);
-    };
-    if (which == 5) {
-        // whole step replays advance the position: keep within the context
-        if (e->host_pos + 2 * iters + 4 >= c.n_ctx) {
-            set_error("gemma_engine_time: context too small for step timing");
-            return -1.0;
-        }
-    }
-    for (int i = 0; i < 3; ++i)
-        if (run()) return -1.0;
-    GHIP_FATAL(hipEventRecord(t0, e->stream));
-    for (int i = 0; i < iters; ++i)
-        if (run()) return -1.0;
-    GHIP_FATAL(hipEventRecord(t1, e->stream));
-    GHIP_FATAL(hipEventSynchronize(t1));
-    if (which == 5) e->host_pos += iters + 3;
-    float ms = 0;
-    GHIP_FATAL(hipEventElapsedTime(&ms, t0, t1));
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
-    if (algo_bytes) *algo_bytes = bytes;
-    return (double)ms * 1000.0 / iters;
-}
-
-// ---- launch-plan tuning -----------------------------------------------------------------------
-// Coordinate descent over the matrix classes: for each class every feasible (K split, row-tile
-// groups per workgroup) is timed as whole decode steps (hipGraph replays on a fresh context), the
-// other classes held at their current best.  Whole steps keep the cache state of real decoding
-// (a matrix timed alone would be served from the 256 MB Infinity Cache).  Every candidate computes
-// the same bits (the K split keeps the block order), so tuning changes speed only.  The decode
-// state is clobbered: call gemma_engine_begin afterwards.  In a TP job every rank runs the same
-// candidate sequence (same collectives per step); ranks may settle on different plans.
-static void drop_graph(gemma_engine *e) {
+// the captured decode graph is stale (a plan, option or launch form changed): re-captured at the next step
+void drop_graph(gemma_engine *e) {
     if (e->graph_exec) (void)hipGraphExecDestroy(e->graph_exec);
     if (e->graph) (void)hipGraphDestroy(e->graph);
     e->graph_exec = nullptr;
     e->graph = nullptr;
 }
-
-extern "C" int gemma_engine_tune(gemma_engine *e, int iters) {
-    set_error("");
-    if (e->kq) return 0;  // K-quant layers: no launch plan to measure
-    (void)hipSetDevice(e->device);
-    const gemma_hip_config &c = e->cfg;
-    const int wt = c.wtype;
-    const int32_t prompt[4] = {2, 2, 2, 2};
-    iters = std::max(2, std::min(iters, c.n_ctx - 12));
-    if (iters < 2 || c.n_ctx < 16) {
-        set_error("gemma_engine_tune: context too small");
-        return -1;
-    }
-    hipEvent_t t0, t1;
-    GHIP_CHECK(hipEventCreate(&t0));
-    GHIP_CHECK(hipEventCreate(&t1));
-    auto trial = [&]() -> double {
-        drop_graph(e);
-        if (gemma_engine_begin(e, prompt, 4)) return -1.0;
-        if (gemma_engine_step(e, 1, nullptr, 1)) return -1.0;  // eager step + capture
-        for (int i = 0; i < 2; ++i)
-            if (hipGraphLaunch(e->graph_exec, e->stream) != hipSuccess) return -1.0;
-        // the minimum of three timed runs: one run's box noise (±1 %) exceeded the differences
-        // between neighbouring plans, so single samples picked plans by luck (round 5: the bench's
-        // logits plan varied run to run between 1, 2 and 8 row tiles per workgroup, ±2 µs)
-        double tmin = 1e30;
-        for (int rep = 0; rep < 3; ++rep) {
-            if (hipEventRecord(t0, e->stream) != hipSuccess) return -1.0;
-            for (int i = 0; i < iters; ++i)
-                if (hipGraphLaunch(e->graph_exec, e->stream) != hipSuccess) return -1.0;
-            if (hipEventRecord(t1, e->stream) != hipSuccess || hipEventSynchronize(t1) != hipSuccess) return -1.0;
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, t0, t1);
-            tmin = std::min(tmin, (double)ms * 1000.0 / iters);
-        }
-        return tmin;
-    };
-    const layer_dev &L0 = e->layers[0];
-    const int64_t nbt[MC_N] = {L0.qkv.n_bt, L0.o.n_bt, L0.gate.n_bt, L0.down.n_bt, e->embd.n_bt};
-    int rc = 0;
-    double best = trial();
-    if (best < 0) rc = -1;
-    const int order[MC_N] = {MC_DOWN, MC_GU, MC_QKV, MC_O, MC_LOGITS};
-    for (int oi = 0; oi < MC_N && rc == 0; ++oi) {
-        const int cls = order[oi];
-        if (cls == MC_LOGITS && e->out_type == T_Q6_K) continue;  // the K-quant matvec has no plan
-        std::vector<launch_plan> cands;
-        const bool splits = cls == MC_QKV || cls == MC_O || cls == MC_DOWN || cls == MC_GU;
-        for (int ks = 1; ks <= (cls == MC_GU ? 2 : splits ? 8 : 1); ks *= 2) {
-            if (pick_ks(wt, nbt[cls], ks) != ks) continue;  // not a divisor, or the LDS image overflows
-            const int rmax = cls == MC_LOGITS ? 16 : ks == 1 ? 2 : 4;
-            for (int rpw = 1; rpw <= rmax; rpw *= 2) cands.push_back({ks, rpw, e->plan[cls].img});
-        }
-        // the round-pipelined form (one workgroup per row tile)
-        if (splits && cls != MC_GU && pick_ks(wt, nbt[cls], KS_RR) == KS_RR) cands.push_back({KS_RR, 1, e->plan[cls].img});
-        const launch_plan keep = e->plan[cls];
-        launch_plan win = keep;
-        // whole steps for every class.  (Timing the logits launch alone picked 1 row tile per
-        // workgroup, whose back-to-back launches overlap their tails; inside the step, where k_advance
-        // waits for it, 8 measured 52.3-52.7 vs 53.2-54.4 µs — round 5, driver-style bench lines.)
-        auto measure = [&]() -> double { return trial(); };
-        double best_cls;
-        {  // the incumbent re-measured beside its challengers (not a sample from an earlier class)
-            const double t = measure();
-            if (t < 0) {
-                rc = -1;
-                break;
-            }
-            best_cls = t;
-        }
-        for (const launch_plan &p : cands) {
-            if (p.ks == keep.ks && p.rpw == keep.rpw && p.img == keep.img) continue;
-            e->plan[cls] = p;
-            const double t = measure();
-            if (t < 0) {
-                rc = -1;
-                break;
-            }
-            if (t < best_cls * 0.998) {  // a challenger must beat the incumbent past the noise floor
-                best_cls = t;
-                win = p;
-            }
-        }
-        e->plan[cls] = win;
-        if (cls != MC_LOGITS) best = best_cls;
-        // on / off switches: the incumbent re-measured beside the challenger and the same 0.2 %
-        // hysteresis as the plans (a bare t < best flipped on noise).  Every condition is
-        // structural, never a measured outcome, so every rank of a TP job runs the same trials.
-        auto toggle = [&](auto flip) {
-            if (rc) return;
-            const double inc = trial();
-            flip();
-            const double t = inc < 0 ? -1.0 : trial();
-            if (t < 0) rc = -1;
-            if (t >= 0 && t < inc * 0.998) best = t;
-            else flip();
-        };
-        if (cls == MC_O && e->ag.nwg && e->cfg.n_ctx <= 2048 && e->cfg.head_dim <= 256)
-            toggle([&] { e->att_mode ^= 1; });  // attention form: one workgroup per head vs the split
-        // the producer-written activation image, at the winning launch shape
-        if ((cls == MC_O && e->att_act) || (cls == MC_DOWN && e->h_act)) toggle([&] { e->plan[cls].img ^= 1; });
-        // attention + attn-out in one launch (takes effect with the image and the rr attn-out form)
-        if (cls == MC_O && e->ao_cnt && e->n_virtual == 1) toggle([&] { e->att_o ^= 1; });
-    }
-    drop_graph(e);
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
-    e->host_pos = 0;
-    return rc;
-}
-
-// the current plan, 3 ints per class (qkv, o, gate/up, down, logits): K split, row-tile groups per
-// workgroup, activation image (o, down); returns the number of ints written
-extern "C" int gemma_engine_plan(gemma_engine *e, int *out, int cap) {
-    int n = 0;
-    for (int cls = 0; cls < MC_N && n + 3 <= cap; ++cls) {
-        out[n++] = e->plan[cls].ks;
-        out[n++] = e->plan[cls].rpw;
-        out[n++] = e->plan[cls].img;
-    }
-    if (n < cap) out[n++] = e->att_mode;  // attention form: 0 per head, 1 split
-    return n;
-}
-
-// kernel launches per decode token: the kernel nodes of the captured decode graph (captured on
-// first use if needed); -1 on error
-extern "C" int gemma_engine_graph_kernels(gemma_engine *e) {
-    set_error("");
-    (void)hipSetDevice(e->device);
-    if (!e->graph) {
-        set_error("gemma_engine_graph_kernels: no decode graph yet (run a gemma_engine_step with use_graph first)");
-        return -1;
-    }
-    size_t n = 0;
-    GHIP_CHECK(hipGraphGetNodes(e->graph, nullptr, &n));
-    std::vector<hipGraphNode_t> nodes(n);
-    GHIP_CHECK(hipGraphGetNodes(e->graph, nodes.data(), &n));
-    int k = 0;
-    for (size_t i = 0; i < n; ++i) {
-        hipGraphNodeType t;
-        GHIP_CHECK(hipGraphNodeGetType(nodes[i], &t));
-        k += t == hipGraphNodeTypeKernel;
-    }
-    return k;
-}
-
-// the persistent token launch on/off (-1 = keep); returns 1 when it runs this engine's decode
-// steps, 0 when not (hpc_last_error says why if it was asked for)
-extern "C" int gemma_engine_set_persist(gemma_engine *e, int on) {
-    set_error("");
-    (void)hipSetDevice(e->device);
-    if (on >= 0 && on != e->persist) {
-        e->persist = on;
-        drop_graph(e);
-    }
-    if (tok_prepare(e)) return -1;
-    if (e->persist && !e->persist_why.empty()) set_error("persistent token launch: " + e->persist_why);
-    return persist_on(e) ? 1 : 0;
-}
-
-// tests: the persistent launch's per-wait bound in 100 MHz ticks (0 = the default 20 ms); a tiny
-// bound forces hand-off timeouts so that their reporting can be checked
-extern "C" int gemma_engine_set_persist_timeout(gemma_engine *e, unsigned ticks) {
-    set_error("");
-    (void)hipSetDevice(e->device);
-    e->persist_timeout = ticks ? ticks : 2000000u;
-    drop_graph(e);
-    return tok_prepare(e);
-}
-
-// the persistent launch's sticky hand-off timeout words [flag, site, layer] (0 = none seen);
-// reset = 1 clears them
-extern "C" int gemma_engine_persist_err(gemma_engine *e, int *out3, int reset) {
-    (void)hipSetDevice(e->device);
-    int w[3] = {0, 0, 0};
-    if (e->tok_err) GHIP_CHECK(hipMemcpy(w, e->tok_err, 12, hipMemcpyDeviceToHost));
-    if (out3) memcpy(out3, w, 12);
-    if (reset && e->tok_err) GHIP_CHECK(hipMemset(e->tok_err, 0, 64));
-    return w[0];
-}
-
-// Engine options (tests, A/B): the measured variants that stay selectable, set through the API so a
-// stray environment variable on a box can never change the benched kernels.  Returns 0, or -1 for an
-// unknown name.  The decode graph is dropped (re-captured at the next step).
-extern "C" int gemma_engine_set_option(gemma_engine *e, const char *name, int value) {
-    set_error("");
-    const std::string n = name ? name : "";
-    int *f = n == "kq_fuse" ? &e->kq_fuse : n == "kq_dual" ? &e->kq_dual : n == "kq_pair" ? &e->kq_pair
-           : n == "kq_abl" ? &e->kq_abl : n == "att_mx" ? &e->att_mx : n == "time_hot" ? &e->time_hot
-           : n == "ablate" ? &e->ablate : n == "ks_small" ? &e->ks_small : n == "ks_down" ? &e->ks_down : nullptr;
-    if (n == "att_dsplit") {
-        if (value < 1 || value > 8 || (value & (value - 1)) || e->cfg.head_dim % (32 * value)) {
-            set_error("gemma_engine_set_option: att_dsplit must be 1, 2, 4 or 8 and divide head_dim / 32");
-            return -1;
-        }
-        f = &e->att_dsplit;
-    }
-    if (n == "grid_big") {
-        if (value < 1 || value > e->grid_big_cap) {
-            set_error("gemma_engine_set_option: grid_big out of range (1 .. the argmax key buffer)");
-            return -1;
-        }
-        f = &e->grid_big;
-    }
-    if (!f) {
-        set_error("gemma_engine_set_option: unknown option '" + n + "'");
-        return -1;
-    }
-    *f = value;
-    drop_graph(e);
-    return 0;
-}
-
-// attention + attn-out in one launch on (1) / off (0) / unchanged (-1); returns the setting
-extern "C" int gemma_engine_set_att_o(gemma_engine *e, int on) {
-    if (on >= 0 && (on != 0) != (e->att_o != 0)) {
-        e->att_o = on != 0 && e->ao_cnt;
-        drop_graph(e);
-    }
-    return e->att_o;
-}
-
-// fused layer front on/off (tests, A/B); returns the sticky hand-off timeout word (0 = none seen)
-extern "C" int gemma_engine_set_fuse(gemma_engine *e, int fuse_front) {
-    if (fuse_front >= 0) {
-        e->fuse_front = fuse_front;
-        drop_graph(e);
-    }
-    int err = 0;
-    if (e->front_err) (void)hipMemcpy(&err, e->front_err, 4, hipMemcpyDeviceToHost);
-    return err;
-}
-
-extern "C" int gemma_engine_set_plan(gemma_engine *e, const int *in, int n) {
-    const gemma_hip_config &c = e->cfg;
-    const layer_dev &L0 = e->layers[0];
-    const int64_t nbt[MC_N] = {L0.qkv.n_bt, L0.o.n_bt, L0.gate.n_bt, L0.down.n_bt, e->embd.n_bt};
-    for (int cls = 0; cls < MC_N && 3 * cls + 2 < n; ++cls) {
-        const int ks = in[3 * cls], rpw = in[3 * cls + 1], img = in[3 * cls + 2];
-        const bool splits = cls == MC_QKV || cls == MC_O || cls == MC_DOWN || cls == MC_GU;
-        const bool img_ok = (cls == MC_O && e->att_act) || (cls == MC_DOWN && e->h_act);
-        if (ks < 1 || (!splits && ks != 1) || (cls == MC_GU && ks > 2) || pick_ks(c.wtype, nbt[cls], ks) != ks || rpw < 1 || rpw > 64 ||
-            (img && !img_ok)) {
-            set_error("gemma_engine_set_plan: infeasible plan");
-            return -1;
-        }
-        e->plan[cls] = {ks, rpw, img ? 1 : 0};
-    }
-    if (n > 3 * MC_N) {
-        const int mode = in[3 * MC_N];
-        if ((mode != ATTN_PER_HEAD && mode != ATTN_SPLIT) || (mode == ATTN_SPLIT && !e->ag.nwg) ||
-            (mode == ATTN_PER_HEAD && (c.head_dim > 256 || c.n_ctx > 2048))) {
-            set_error("gemma_engine_set_plan: infeasible attention form");
-            return -1;
-        }
-        e->att_mode = mode;
-    }
-    drop_graph(e);
-    return 0;
-}
-
-static int prefill_alloc(gemma_engine *e, int T) {
-    auto &p = e->pf;
-    if (p.T >= T) return 0;
-    void *bufs[] = {p.X, p.SA, p.QKV, p.ATT, p.G, p.U, p.LG, p.DA, p.Q16, p.XQ, p.XH, p.XM, p.keys};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    const gemma_hip_config &c = e->cfg;
-    const int64_t E = c.n_embd, F = c.n_ff;
-    p.ldq = (std::max(std::max(E, F), (int64_t)e->qw) + 255) / 256 * 256;
-    p.ldd = p.ldq / 32;
-    GHIP_CHECK(hipMalloc(&p.X, (size_t)T * E * 4));
-    GHIP_CHECK(hipMalloc(&p.SA, (size_t)T * E * 4));
-    GHIP_CHECK(hipMalloc(&p.QKV, (size_t)T * e->qkv_rows * 4));
-    GHIP_CHECK(hipMalloc(&p.ATT, (size_t)T * e->qw * 4));
-    GHIP_CHECK(hipMalloc(&p.G, (size_t)T * F * 4));
-    GHIP_CHECK(hipMalloc(&p.U, (size_t)T * F * 4));
-    GHIP_CHECK(hipMalloc(&p.LG, (size_t)T * c.n_vocab * 4));  // all rows, as the reference computes them
-    GHIP_CHECK(hipMalloc(&p.DA, (size_t)T * p.ldd * 4));
-    GHIP_CHECK(hipMalloc(&p.Q16, (size_t)T * e->qw * 2));
-    // K-quant layers: XQ holds T Q8_K columns (292 B per 256 values) instead of the int8 image
-    GHIP_CHECK(hipMalloc(&p.XQ, (size_t)T * (e->kq ? p.ldq / 256 * 292 : p.ldq)));
-    GHIP_CHECK(hipMalloc(&p.XH, (size_t)T * p.ldq * 2));
-    GHIP_CHECK(hipMalloc(&p.XM, (size_t)T * (p.ldq / 256) * 32));
-    GHIP_CHECK(hipMalloc(&p.keys, 256 * 8));
-    p.T = T;
-    return 0;
-}
-
-static int enqueue_prefill_kq(gemma_engine *e, int T);
-
-// the K-quant prefill's MFMA GEMM (prefill_kq.hip) for T prompt rows (kq_gemm_min: default 8)
-static bool kq_prefill_mfma(int T) { return T >= kq_gemm_min(); }
-// T Q8_K columns of K values (ld bytes apart) -> the GEMM's f16 image in the prefill scratch
-static int kq_expand(gemma_engine *e, const uint8_t *x, int64_t ld, int64_t K, int T) {
-    auto &p = e->pf;
-    q8kx_args a;
-    a.x = x; a.x_col_stride = ld; a.nsb = (int)(K / 256); a.T = T;
-    a.xh = p.XH; a.ldh = p.ldq; a.xd = p.DA; a.ldd = p.ldd; a.xm = p.XM; a.ldm = p.ldq / 256;
-    return launch_q8k_expand(a, e->stream);
-}
-
-// The exact prefill attention: on the f32 matrix cores where the shapes allow it (attn_mx.hip:
-// v_mfma_f32_16x16x4_f32 is an fmaf chain over K, so vec_dot_f16's chains ride it bit for bit),
-// else per row with v_fma_mix (k_attn_rows).  Option "att_mx" 0 forces the row form (tests, A/B).
-// The form is resolved once per prefill (att_mx_form): the option and the shape check do not
-// change between its layers.
-static bool att_mx_form(const gemma_engine *e, const attnp_args &at) {
-    return e->att_mx && !attn_mx_unsupported(at);
-}
-static int launch_attn_exact(const attnp_args &at, bool mx, hipStream_t s) {
-    return mx ? launch_attn_mx(at, s) : launch_attn_rows(at, s);
-}
-
-static int enqueue_prefill(gemma_engine *e, int T, bool exact, float *taps = nullptr) {
-    const gemma_hip_config &c = e->cfg;
-    hipStream_t s = e->stream;
-    int mx_form = -1;  // the exact attention's form, resolved at the first layer
-    auto &p = e->pf;
-    const int wt = c.wtype;
-    const int64_t E = c.n_embd, F = c.n_ff;
-    auto gemm = [&](const tiled_mat &m, int epi, const float *resid, float *y, int64_t ldy) {
-        gemm_args g;
-        g.qs = m.qs; g.sc = m.sc; g.rows = m.rows; g.n_rt = m.n_rt; g.n_bt = m.n_bt; g.nb = m.nb;
-        g.xq = p.XQ; g.xh = p.XH; g.ldq = p.ldq; g.da = p.DA; g.ldd = p.ldd; g.T = T; g.y = y; g.resid = resid; g.ldy = ldy;
-        return exact ? launch_gemm_exact(wt, epi, g, s) : launch_gemm_q(wt, epi, g, s);
-    };
-    auto quant = [&](int mode, const float *x, const float *x2, int64_t K, const float *norm_w) {
-        qrow_args a;
-        a.x = x; a.x2 = x2; a.ldx = K; a.K = K; a.norm_w = norm_w; a.eps = c.eps;
-        const bool i8img = exact && gemm_x4_i8();  // the int8-staged exact GEMM reads the int8 image
-        a.q = (!exact || i8img) ? p.XQ : nullptr; a.qh = (exact && !i8img) ? p.XH : nullptr; a.ldq = p.ldq; a.da = p.DA; a.ldd = p.ldd;
-        a.gelu_tab = e->gelu_tab; a.gelu_clamp = c.gelu_clamp;
-        if (mode == QR_EMBED_NORM) {
-            a.tokens = e->hist; a.emb_qs = e->embd.qs; a.emb_sc = e->embd.sc; a.emb_type = wt;
-            a.emb_n_bt = e->embd.n_bt; a.emb_scale = sqrtf((float)E); a.emb_out = p.X; a.ldx = E;
-        }
-        return launch_quant_rows(mode, a, T, s);
-    };
-    int n_kv = 32 * (T / 32 + 1);  // src/gemma_model.cpp:429 with n_total = T
-    if (n_kv > c.n_ctx) n_kv = c.n_ctx;
-    const bool q6 = e->out_type == T_Q6_K;
-    if (e->kq) {
-        if (!exact) {
-            set_error("gemma_engine_prefill_fast: K-quant layer engines have the exact batched prefill only");
-            return -1;
-        }
-        if (enqueue_prefill_kq(e, T)) return -1;
-    } else if (q6 && launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, e->hist, nullptr, T, (int)E, sqrtf((float)E), p.X, s, e->embd_tiled)) {
-        return -1;
-    }
-    for (int il = 0; il < (e->kq ? 0 : c.n_layer); ++il) {
-        layer_dev &L = e->layers[il];
-        if (quant(il == 0 && !q6 ? QR_EMBED_NORM : QR_NORM, p.X, nullptr, E, L.attn_norm)) return -1;
-        if (gemm(L.qkv, EPI_STORE, nullptr, p.QKV, e->qkv_rows)) return -1;
-        ropekv_args r;
-        r.qkv = p.QKV; r.ldqkv = e->qkv_rows; r.rope_cos = e->rope_cos; r.rope_sin = e->rope_sin; r.q16 = p.Q16;
-        r.kc = kc_of(e, il); r.vc = vc_of(e, il);
-        r.H = c.n_head; r.Hkv = c.n_head_kv; r.hd = c.head_dim; r.ctx = c.n_ctx; r.p0 = 0;
-        r.q_scale = 1.0f / sqrtf((float)c.head_dim);
-        if (launch_rope_kv_prefill(r, T, s)) return -1;
-        attnp_args at;
-        at.q16 = p.Q16; at.kc = r.kc; at.vc = r.vc; at.out = p.ATT; at.ldo = e->qw;
-        at.T = T; at.H = c.n_head; at.Hkv = c.n_head_kv; at.hd = c.head_dim; at.ctx = c.n_ctx; at.n_kv = n_kv;
-        if (mx_form < 0) mx_form = att_mx_form(e, at);
-        if (exact ? launch_attn_exact(at, mx_form == 1, s) : launch_attn_prefill(at, s)) return -1;
-        if (quant(QR_F32, p.ATT, nullptr, e->qw, nullptr)) return -1;
-        if (gemm(L.o, EPI_ADD, p.X, p.SA, E)) return -1;
-        if (quant(QR_NORM, p.SA, nullptr, E, L.ffn_norm)) return -1;
-        if (gemm(L.gate, EPI_STORE, nullptr, p.G, F)) return -1;
-        if (gemm(L.up, EPI_STORE, nullptr, p.U, F)) return -1;
-        if (quant(QR_GELU, p.G, p.U, F, nullptr)) return -1;
-        if (gemm(L.down, EPI_ADD, p.SA, p.X, E)) return -1;
-        if (taps) GHIP_CHECK(hipMemcpyAsync(taps + (size_t)il * T * E, p.X, (size_t)T * E * 4, hipMemcpyDeviceToDevice, s));
-    }
-    if (q6) {  // Q6_K tied output: Q8_K INIT of every row, then the K-quant dot per (vocab row, position)
-        const int64_t ld = E / 256 * 292;
-        if (e->xq8k_rows < T) {
-            GHIP_CHECK(hipFree(e->xq8k));
-            GHIP_CHECK(hipMalloc(&e->xq8k, (size_t)(ld * T)));
-            e->xq8k_rows = T;
-        }
-        if (launch_norm_q8K(p.X, E, e->out_norm, (int)E, c.eps, T, e->xq8k, ld, s)) return -1;
-        if (exact && kq_prefill_mfma(T) && e->embd_tiled && E % 2048 == 0) {  // the MFMA GEMM (prefill_kq.hip)
-            if (kq_expand(e, e->xq8k, ld, E, T)) return -1;
-            kqg_args g;
-            g.w = e->embd_q6k; g.row_bytes = e->embd_row_bytes; g.rows = c.n_vocab; g.nsb = (int)(E / 256); g.T = T;
-            g.xh = p.XH; g.ldh = p.ldq; g.xd = p.DA; g.ldd = p.ldd; g.xm = p.XM; g.ldm = p.ldq / 256;
-            g.y = p.LG; g.ldy = c.n_vocab;
-            if (launch_gemm_kq(T_Q6_K, g, s)) return -1;
-        } else {
-            kq_args k;
-            k.w = e->embd_q6k; k.tiled = e->embd_tiled; k.row_bytes = e->embd_row_bytes; k.rows = c.n_vocab; k.nsb = (int)(E / 256);
-            k.x = e->xq8k; k.x_col_stride = ld; k.y = p.LG; k.y_col_stride = c.n_vocab; k.ncols = T;
-            if (launch_matvec_kq(T_Q6_K, k, s)) return -1;
-        }
-    } else {
-        if (quant(QR_NORM, p.X, nullptr, E, e->out_norm)) return -1;
-        if (gemm(e->embd, EPI_STORE, nullptr, p.LG, c.n_vocab)) return -1;
-    }
-    // greedy token from the last row; position T-1 -> T, token appended at hist[T]
-    if (launch_row_argmax(p.LG + (size_t)(T - 1) * c.n_vocab, c.n_vocab, (unsigned long long *)p.keys, 256, s)) return -1;
-    const int last = T - 1;
-    GHIP_CHECK(hipMemcpyAsync(e->pos, &last, 4, hipMemcpyHostToDevice, s));
-    rope_row rr;
-    rr.cos = e->rope_cos; rr.sin = e->rope_sin; rr.cur = e->rope_cur; rr.half = c.head_dim / 2; rr.ctx = c.n_ctx;
-    rr.epoch = e->epoch;
-    return launch_advance((const unsigned long long *)p.keys, 256, e->token, e->pos, e->hist, c.n_ctx, e->nfix, rr, s);
-}
-
-// Batched prefill for K-quant layers (the reference's shipped Q4_K_M model, src/app.cpp:36): the
-// same T-column MUL_MATs the reference runs through mul_mat (src/hpc.cpp:216-273 with col_num = T),
-// each (row, column) the decode dot (vec_dot_q{4,6}_K_q8_K in ggml's AVX2 lane order) against the
-// column's Q8_K INIT — every K-quant launch covers all T columns (grid.y) — and the exact per-row
-// attention of the Q4_0 prefill (k_rope_kv_prefill + k_attn_rows).  Bit-identical to the token
-// loop and to the CPU path: no operation depends on the batching.
-static int enqueue_prefill_kq(gemma_engine *e, int T) {
-    const gemma_hip_config &c = e->cfg;
-    hipStream_t s = e->stream;
-    int mx_form = -1;  // the exact attention's form, resolved at the first layer
-    auto &p = e->pf;
-    const int64_t E = c.n_embd, F = c.n_ff;
-    const int64_t ldk = p.ldq / 256 * 292;  // Q8_K column stride in XQ
-    uint8_t *img = (uint8_t *)p.XQ;
-    // T >= kq_gemm_min() (default 8): the lane-tiled matrices go through the MFMA GEMM
-    // (prefill_kq.hip) against the f16 image each Q8_K INIT is expanded to; below, or with
-    // GHIP_KQ_MFMA=0, the dot4 T-column kernel.  Same bytes either way (tests/test_gpu_engine_gguf.py).
-    const bool mfma = kq_prefill_mfma(T);
-    auto mfma_ok = [&](const kq_mat &W) { return mfma && W.tiled && (W.type == T_Q4_K || W.K % 2048 == 0); };
-    auto expand = [&](int64_t K) { return mfma ? kq_expand(e, img, ldk, K, T) : 0; };
-    auto mv = [&](const kq_mat &W, float *y, int64_t ldy, const float *resid, const float *gate_in, const kq_mat *up) {
-        if (!up && mfma_ok(W)) {
-            kqg_args g;
-            g.w = W.w; g.row_bytes = W.rb; g.rows = W.rows; g.nsb = (int)(W.K / 256); g.T = T;
-            g.xh = p.XH; g.ldh = p.ldq; g.xd = p.DA; g.ldd = p.ldd; g.xm = p.XM; g.ldm = p.ldq / 256;
-            g.y = y; g.ldy = ldy; g.resid = resid; g.gate_in = gate_in; g.gelu_tab = e->gelu_tab; g.gelu_clamp = c.gelu_clamp;
-            return launch_gemm_kq(W.type, g, s);
-        }
-        kq_args k;
-        k.w = W.w; k.row_bytes = W.rb; k.rows = W.rows; k.nsb = (int)(W.K / 256);
-        k.x = img; k.x_col_stride = ldk; k.y = y; k.y_col_stride = ldy; k.ncols = T;
-        k.tiled = W.tiled;
-        k.resid = resid; k.gate_in = gate_in; k.gelu_tab = e->gelu_tab; k.gelu_clamp = c.gelu_clamp;
-        if (up) k.w2 = up->w;
-        return launch_matvec_kq(W.type, k, s);
-    };
-    int n_kv = 32 * (T / 32 + 1);  // src/gemma_model.cpp:429 with n_total = T
-    if (n_kv > c.n_ctx) n_kv = c.n_ctx;
-    if (launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, e->hist, nullptr, T, (int)E, sqrtf((float)E), p.X, s, e->embd_tiled)) return -1;
-    for (int il = 0; il < c.n_layer; ++il) {
-        const layer_dev &L = e->layers[il];
-        const kq_layer &K = e->kql[il];
-        if (launch_norm_q8K(p.X, E, L.attn_norm, (int)E, c.eps, T, img, ldk, s) || expand(E)) return -1;
-        const int64_t ldqkv = e->qkv_rows;
-        if (K.qk_fused) {
-            kq_mat qk = K.q;
-            qk.rows = K.q.rows + K.k.rows;
-            if (mv(qk, p.QKV, ldqkv, nullptr, nullptr, nullptr)) return -1;
-        } else if (mv(K.q, p.QKV, ldqkv, nullptr, nullptr, nullptr) ||
-                   mv(K.k, p.QKV + e->qw, ldqkv, nullptr, nullptr, nullptr)) {
-            return -1;
-        }
-        if (mv(K.v, p.QKV + e->qw + e->kvw, ldqkv, nullptr, nullptr, nullptr)) return -1;
-        ropekv_args r;
-        r.qkv = p.QKV; r.ldqkv = e->qkv_rows; r.rope_cos = e->rope_cos; r.rope_sin = e->rope_sin; r.q16 = p.Q16;
-        r.kc = kc_of(e, il); r.vc = vc_of(e, il);
-        r.H = c.n_head; r.Hkv = c.n_head_kv; r.hd = c.head_dim; r.ctx = c.n_ctx; r.p0 = 0;
-        r.q_scale = 1.0f / sqrtf((float)c.head_dim);
-        if (launch_rope_kv_prefill(r, T, s)) return -1;
-        attnp_args at;
-        at.q16 = p.Q16; at.kc = r.kc; at.vc = r.vc; at.out = p.ATT; at.ldo = e->qw;
-        at.T = T; at.H = c.n_head; at.Hkv = c.n_head_kv; at.hd = c.head_dim; at.ctx = c.n_ctx; at.n_kv = n_kv;
-        if (mx_form < 0) mx_form = att_mx_form(e, at);
-        if (launch_attn_exact(at, mx_form == 1, s)) return -1;
-        if (launch_quant_q8_K(p.ATT, e->qw, e->qw, T, img, ldk, s) || expand(e->qw)) return -1;
-        if (mv(K.o, p.SA, E, p.X, nullptr, nullptr)) return -1;  // + inpL
-        if (launch_norm_q8K(p.SA, E, L.ffn_norm, (int)E, c.eps, T, img, ldk, s) || expand(E)) return -1;
-        if (K.gate.type == K.up.type && K.gate.rows == K.up.rows && K.gate.K == K.up.K && e->kq_dual &&
-            !(mfma_ok(K.gate) && mfma_ok(K.up))) {
-            if (mv(K.gate, p.U, F, nullptr, nullptr, &K.up)) return -1;  // gelu(gate)*up
-        } else if (mv(K.gate, p.G, F, nullptr, nullptr, nullptr) || mv(K.up, p.U, F, nullptr, p.G, nullptr)) {
-            return -1;
-        }
-        if (launch_quant_q8_K(p.U, F, F, T, img, ldk, s) || expand(F)) return -1;
-        if (mv(K.down, p.X, E, p.SA, nullptr, nullptr)) return -1;  // + sa
-    }
-    return 0;
-}
-
-// Batched prefill of the prompt given to gemma_engine_begin: all prompt
-// positions in one pass, KV cache filled, logits for every row as the reference computes them
-// (src/gemma_model.cpp:740); returns the greedy token and leaves the engine at position T, ready
-// for gemma_engine_step.  exact: ggml-lane-order GEMMs + per-row decode-arithmetic attention,
-// bit-identical to the CPU path; otherwise int8 MFMA GEMMs + f16 MFMA attention, which differ from
-// it in fp32 summation order.
-static int prefill_run(gemma_engine *e, bool exact, float *logits_last, float *logits_all) {
-    (void)hipSetDevice(e->device);
-    const gemma_hip_config &c = e->cfg;
-    const int T = e->n_prompt;
-    if (T <= 0 || e->host_pos != 0) {
-        set_error("gemma_engine_prefill: call right after gemma_engine_begin");
-        return -1;
-    }
-    if (e->tp_n > 1 || e->comm) {
-        set_error("gemma_engine_prefill: the MFMA prefill is single-GPU (row-split engines prefill token by token)");
-        return -1;
-    }
-    if (prefill_alloc(e, T)) return -1;
-    if (enqueue_prefill(e, T, exact)) return -1;
-    GHIP_CHECK(hipStreamSynchronize(e->stream));
-    if (logits_last)
-        GHIP_CHECK(hipMemcpy(logits_last, e->pf.LG + (size_t)(T - 1) * c.n_vocab, (size_t)c.n_vocab * 4,
-                             hipMemcpyDeviceToHost));
-    if (logits_all) GHIP_CHECK(hipMemcpy(logits_all, e->pf.LG, (size_t)T * c.n_vocab * 4, hipMemcpyDeviceToHost));
-    int tok = -1;
-    GHIP_CHECK(hipMemcpy(&tok, e->token, 4, hipMemcpyDeviceToHost));
-    e->host_pos = T;
-    return tok;
-}
-
-extern "C" int gemma_engine_prefill(gemma_engine *e, float *logits_last, float *logits_all) {
-    set_error("");
-    return prefill_run(e, true, logits_last, logits_all);
-}
-
-extern "C" int gemma_engine_prefill_fast(gemma_engine *e, float *logits_last, float *logits_all) {
-    set_error("");
-    return prefill_run(e, false, logits_last, logits_all);
-}
-
-// one eager step with per-layer taps copied to host: [L][qkv | attn | x_out]
-// Diagnostic: one eager decode step with s_memrealtime phase stamps (100 MHz) for the five kernels
-// of `layer` (regions 0..4: qkv, attention, o, gate/up, down) and the logits kernel (region 5).
-// out: 6 * 4096 * 16 u64; unused slots are 0.
-extern "C" int gemma_engine_stamp_step(gemma_engine *e, int layer, unsigned long long *out) {
-    set_error("");
-    if (!GHIP_STAMPS) {
-        set_error("gemma_engine_stamp_step: library built without -DGHIP_STAMPS=1 (scripts/build_variant.sh)");
-        return -1;
-    }
-    (void)hipSetDevice(e->device);
-    const size_t n = 6 * kStampRegion;
-    GHIP_CHECK(hipMalloc(&e->stamp, n * 8));
-    GHIP_CHECK(hipMemsetAsync(e->stamp, 0, n * 8, e->stream));
-    e->stamp_layer = layer;
-    const int r = enqueue_step(e);
-    if (r == 0) {
-        GHIP_CHECK(hipStreamSynchronize(e->stream));
-        GHIP_CHECK(hipMemcpy(out, e->stamp, n * 8, hipMemcpyDeviceToHost));
-        e->host_pos += 1;
-    }
-    (void)hipFree(e->stamp);
-    e->stamp = nullptr;
-    e->stamp_layer = -1;
-    return r;
-}
-
-// diagnostics: one eager step through the persistent token launch with its phase stamps
-// (s_memrealtime, 100 MHz) -> out [grid = n_embd / 8][n_layer][16]; needs a -DGHIP_STAMPS=1 build
-// of token.hip and engine.cpp (scripts/build_variant.sh)
-extern "C" int gemma_engine_token_stamps(gemma_engine *e, unsigned long long *out) {
-    set_error("");
-    if (!GHIP_STAMPS) {
-        set_error("gemma_engine_token_stamps: library built without -DGHIP_STAMPS=1 (scripts/build_variant.sh)");
-        return -1;
-    }
-    (void)hipSetDevice(e->device);
-    if (!persist_on(e)) {
-        set_error("gemma_engine_token_stamps: the persistent launch is not active: " + e->persist_why);
-        return -1;
-    }
-    const size_t n = (size_t)(e->cfg.n_embd / 8) * e->cfg.n_layer * 16 + 256;  // + per-pop probes
-    unsigned long long *buf = nullptr;
-    GHIP_CHECK(hipStreamSynchronize(e->stream));
-    GHIP_CHECK(hipMalloc(&buf, n * 8));
-    GHIP_CHECK(hipMemset(buf, 0, n * 8));
-    tok_args a = e->tok;
-    a.dbg_t = buf;
-    GHIP_CHECK(hipMemcpy(e->tok_dev, &a, sizeof(a), hipMemcpyHostToDevice));
-    const int r = enqueue_step(e);
-    GHIP_CHECK(hipStreamSynchronize(e->stream));
-    GHIP_CHECK(hipMemcpy(e->tok_dev, &e->tok, sizeof(e->tok), hipMemcpyHostToDevice));
-    if (r == 0) {
-        GHIP_CHECK(hipMemcpy(out, buf, n * 8, hipMemcpyDeviceToHost));
-        e->host_pos += 1;
-    }
-    (void)hipFree(buf);
-    return r;
-}
-
-extern "C" int gemma_engine_debug_step(gemma_engine *e, float *host_taps, float *logits) {
-    set_error("");
-    (void)hipSetDevice(e->device);
-    const gemma_hip_config &c = e->cfg;
-    const size_t per = (size_t)e->qkv_rows + e->qw + c.n_embd;
-    GHIP_CHECK(hipMalloc(&e->dbg, per * c.n_layer * 4));
-    const int r = enqueue_step(e);
-    GHIP_CHECK(hipStreamSynchronize(e->stream));
-    if (r == 0) {
-        GHIP_CHECK(hipMemcpy(host_taps, e->dbg, per * c.n_layer * 4, hipMemcpyDeviceToHost));
-        if (logits) GHIP_CHECK(hipMemcpy(logits, e->logits, (size_t)c.n_vocab * 4, hipMemcpyDeviceToHost));
-        e->host_pos += 1;
-    }
-    GHIP_CHECK(hipFree(e->dbg));
-    e->dbg = nullptr;
-    return r;
-}
-
-// ---- per-op test entry: the decode attention kernel on host buffers ---------------------------
-// qkv [H*hd + 2*Hkv*hd] f32; kc [ctx][Hkv*hd], vc [Hkv*hd][ctx] f16 (updated in place at pos)
-extern "C" int gemma_test_attn_decode(const float *qkv, uint16_t *kc, uint16_t *vc, int pos, int H, int Hkv, int hd,
-                                      int ctx, float rope_base, float *out, float *dbg_w, uint16_t *dbg_p,
-                                      float *dbg_inv, unsigned long long *dbg_t, int mode) {
-    set_error("");
-    const size_t qkv_n = (size_t)(H + 2 * Hkv) * hd, cache_n = (size_t)ctx * Hkv * hd;
-    std::vector<uint16_t> et, gt;
-    build_f16_tables(et, gt);
-    std::vector<float> rc, rs;
-    build_rope(ctx, hd, rope_base, rc, rs);
-    float *d_qkv, *d_out, *d_c, *d_s;
-    uint16_t *d_k, *d_v, *d_e;
-    int *d_pos;
-    float *d_dw = nullptr, *d_di = nullptr;
-    unsigned long long *d_dt = nullptr;
-    const size_t n_stamps = (size_t)H * 8 * 8;  // >= workgroups x 8 stamps for any hd <= 512
-    if (dbg_t) GHIP_CHECK(hipMalloc(&d_dt, n_stamps * 8));
-    if (dbg_t) GHIP_CHECK(hipMemset(d_dt, 0, n_stamps * 8));
-    uint16_t *d_dp = nullptr;
-    if (dbg_w) GHIP_CHECK(hipMalloc(&d_dw, (size_t)H * ctx * 4));
-    if (dbg_p) GHIP_CHECK(hipMalloc(&d_dp, (size_t)H * ctx * 2));
-    if (dbg_inv) GHIP_CHECK(hipMalloc(&d_di, (size_t)H * 4));
-    GHIP_CHECK(hipMalloc(&d_qkv, qkv_n * 4));
-    GHIP_CHECK(hipMalloc(&d_out, (size_t)H * hd * 4));
-    GHIP_CHECK(hipMalloc(&d_c, rc.size() * 4));
-    GHIP_CHECK(hipMalloc(&d_s, rs.size() * 4));
-    GHIP_CHECK(hipMalloc(&d_k, cache_n * 2));
-    GHIP_CHECK(hipMalloc(&d_v, cache_n * 2));
-    GHIP_CHECK(hipMalloc(&d_e, 65536 * 2));
-    GHIP_CHECK(hipMalloc(&d_pos, 4));
-    GHIP_CHECK(hipMemcpy(d_qkv, qkv, qkv_n * 4, hipMemcpyHostToDevice));
-    GHIP_CHECK(hipMemcpy(d_c, rc.data(), rc.size() * 4, hipMemcpyHostToDevice));
-    GHIP_CHECK(hipMemcpy(d_s, rs.data(), rs.size() * 4, hipMemcpyHostToDevice));
-    GHIP_CHECK(hipMemcpy(d_k, kc, cache_n * 2, hipMemcpyHostToDevice));
-    GHIP_CHECK(hipMemcpy(d_v, vc, cache_n * 2, hipMemcpyHostToDevice));
-    GHIP_CHECK(hipMemcpy(d_e, et.data(), 65536 * 2, hipMemcpyHostToDevice));
-    GHIP_CHECK(hipMemcpy(d_pos, &pos, 4, hipMemcpyHostToDevice));
-    const attn_geom g = attn_geometry(H, Hkv, hd, ctx);
-    float *d_sb = nullptr;
-    int *d_sy = nullptr;
-    if (g.nwg) {
-        GHIP_CHECK(hipMalloc(&d_sb, g.sbuf_floats * 4));
-        GHIP_CHECK(hipMalloc(&d_sy, (g.sync_ints + 1) * 4));
-        GHIP_CHECK(hipMemset(d_sy, 0, (g.sync_ints + 1) * 4));
-    }
-    attn_args a;
-    a.qkv = d_qkv; a.kc = d_k; a.vc = d_v; a.rope_cos = d_c; a.rope_sin = d_s; a.exp_tab = d_e; a.pos = d_pos;
-    a.nwg = g.nwg; a.sbuf = d_sb; a.sync = d_sy; a.err = d_sy ? d_sy + g.sync_ints : nullptr;
-    float *d_rc = nullptr;
-    GHIP_CHECK(hipMalloc(&d_rc, (size_t)(hd + 4) * 4));
-    GHIP_CHECK(hipMemcpy(d_rc, rc.data() + (size_t)pos * (hd / 2), (size_t)(hd / 2) * 4, hipMemcpyHostToDevice));
-    GHIP_CHECK(hipMemcpy(d_rc + hd / 2, rs.data() + (size_t)pos * (hd / 2), (size_t)(hd / 2) * 4, hipMemcpyHostToDevice));
-    GHIP_CHECK(hipMemcpy(d_rc + hd, &pos, 4, hipMemcpyHostToDevice));
-    a.rope_cur = d_rc;
-    // mode 0 per-head, 1 split form; 2 / 3: per-head with 2 / 4 workgroups per head (dim split)
-    a.mode = mode >= 2 ? ATTN_PER_HEAD : mode;
-    a.dsplit = mode == 2 ? 2 : mode == 3 ? 4 : 1;
-    a.out = d_out; a.H = H; a.Hkv = Hkv; a.hd = hd; a.ctx = ctx; a.q_scale = 1.0f / sqrtf((float)hd);
-    a.dbg_w = d_dw; a.dbg_p = d_dp; a.dbg_inv = d_di; a.dbg_t = d_dt;
-    int r = 0;
-    for (int rep = 0; rep < (dbg_t ? 3 : 1) && r == 0; ++rep) r = launch_attn_decode(a, nullptr);
-    GHIP_CHECK(hipDeviceSynchronize());
-    if (r == 0) {
-        GHIP_CHECK(hipMemcpy(out, d_out, (size_t)H * hd * 4, hipMemcpyDeviceToHost));
-        GHIP_CHECK(hipMemcpy(kc, d_k, cache_n * 2, hipMemcpyDeviceToHost));
-        GHIP_CHECK(hipMemcpy(vc, d_v, cache_n * 2, hipMemcpyDeviceToHost));
-        if (dbg_w) GHIP_CHECK(hipMemcpy(dbg_w, d_dw, (size_t)H * ctx * 4, hipMemcpyDeviceToHost));
-        if (dbg_p) GHIP_CHECK(hipMemcpy(dbg_p, d_dp, (size_t)H * ctx * 2, hipMemcpyDeviceToHost));
-        if (dbg_inv) GHIP_CHECK(hipMemcpy(dbg_inv, d_di, (size_t)H * 4, hipMemcpyDeviceToHost));
-        if (dbg_t) GHIP_CHECK(hipMemcpy(dbg_t, d_dt, n_stamps * 8, hipMemcpyDeviceToHost));
-    }
-    if (r == 0 && d_sy) {
-        int err = 0;
-        GHIP_CHECK(hipMemcpy(&err, d_sy + g.sync_ints, 4, hipMemcpyDeviceToHost));
-        if (err) {
-            set_error("attn_decode: hand-off spin timed out");
-            r = -1;
-        }
-    }
-    void *bufs[] = {d_qkv, d_out, d_c, d_s, d_k, d_v, d_e, d_pos, d_dw, d_dp, d_di, d_dt, d_sb, d_sy, d_rc};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    return r;
-}
-
-extern "C" int gemma_test_exp_f16(uint16_t *out) {
-    set_error("");
-    uint16_t *d = nullptr;
-    GHIP_CHECK(hipMalloc(&d, 65536 * 2));
-    int r = launch_exp_f16_all(d, nullptr);
-    if (r == 0) GHIP_CHECK(hipMemcpy(out, d, 65536 * 2, hipMemcpyDeviceToHost));
-    (void)hipFree(d);
-    return r;
-}
-
-// Test hook: one rms_norm kernel on `rows` host rows of n f32.  kind 0: the ggml
-// executor's RMS_NORM (k_g_rms_norm), out = f32 rows x * scale; kind 1: k_norm_q8K (rms_norm * w then
-// quantize_row_q8_K, n a multiple of 256, <= 4096), out = Q8_K rows.
-extern "C" int gemma_test_rms_norm(int kind, const float *x, const float *w, int rows, int n, float eps, void *out) {
-    set_error("");
-    if (rows <= 0 || n <= 0 || (kind == 1 && (n % 256 || n > 4096)) || kind < 0 || kind > 1) {
-        set_error("gemma_test_rms_norm: unsupported shape or kind");
-        return -1;
-    }
-    const size_t in_b = (size_t)rows * n * 4, out_b = kind == 0 ? in_b : (size_t)rows * (n / 256) * 292;
-    float *dx = nullptr, *dw = nullptr;
-    uint8_t *dy = nullptr;
-    GHIP_CHECK(hipMalloc(&dx, in_b));
-    GHIP_CHECK(hipMalloc(&dw, (size_t)n * 4));
-    GHIP_CHECK(hipMalloc(&dy, out_b));
-    GHIP_CHECK(hipMemcpy(dx, x, in_b, hipMemcpyHostToDevice));
-    if (w) GHIP_CHECK(hipMemcpy(dw, w, (size_t)n * 4, hipMemcpyHostToDevice));
-    int r;
-    if (kind == 0) {
-        gt_desc a, d;
-        a.data = (char *)dx;
-        d.data = (char *)dy;
-        a.ne[0] = d.ne[0] = n;
-        a.ne[1] = d.ne[1] = rows;
-        a.nb[0] = d.nb[0] = 4;
-        a.nb[1] = d.nb[1] = (int64_t)n * 4;
-        a.nb[2] = d.nb[2] = a.nb[3] = d.nb[3] = (int64_t)n * rows * 4;
-        r = launch_g_rms_norm(a, d, eps, nullptr);
-    } else {
-        r = launch_norm_q8K(dx, n, dw, n, eps, rows, dy, (n / 256) * 292, nullptr);
-    }
-    if (r == 0) GHIP_CHECK(hipMemcpy(out, dy, out_b, hipMemcpyDeviceToHost));
-    (void)hipFree(dx);
-    (void)hipFree(dw);
-    (void)hipFree(dy);
-    return r;
-}
-
-// Measured HBM read roofline: a streaming read of `bytes` (>= 4 GB defeats the
-// Infinity Cache), `iters` passes timed with hipEvents; returns GB/s (negative on error).
-// measured HBM read rate (GB/s) of one probe: variant 0 = 16-B nontemporal loads into VGPRs (8 in
-// flight per lane), 1 = LDS-DMA (global_load_lds_dwordx4 nt, 16 KiB in flight per wave); a buffer
-// far beyond the 256 MB Infinity Cache
-extern "C" double gemma_hbm_read_probe(int device, size_t bytes, int iters, int variant) {
-    set_error("");
-    if (hipSetDevice(device) != hipSuccess) return -1.0;
-    void *buf = nullptr;
-    unsigned *sink = nullptr;
-    if (hipMalloc(&buf, bytes) != hipSuccess || hipMalloc(&sink, 4) != hipSuccess) {
-        set_error("gemma_hbm_read_gbs: allocation failed");
-        return -1.0;
-    }
-    (void)hipMemset(buf, 1, bytes);
-    hipStream_t s;
-    (void)hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    hipEvent_t t0, t1;
-    (void)hipEventCreate(&t0);
-    (void)hipEventCreate(&t1);
-    double gbs = -1.0;
-    if (launch_stream_read(buf, bytes, sink, s, variant) == 0) {
-        (void)hipEventRecord(t0, s);
-        for (int i = 0; i < iters; ++i) (void)launch_stream_read(buf, bytes, sink, s, variant);
-        (void)hipEventRecord(t1, s);
-        (void)hipEventSynchronize(t1);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, t0, t1);
-        gbs = (double)bytes * iters / (ms * 1e-3) / 1e9;
-    }
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
-    (void)hipStreamDestroy(s);
-    (void)hipFree(buf);
-    (void)hipFree(sink);
-    return gbs;
-}
-
-// the measured HBM read roofline: the faster of the two probes
-extern "C" double gemma_hbm_read_gbs(int device, size_t bytes, int iters) {
-    const double a = gemma_hbm_read_probe(device, bytes, iters, 0), b = gemma_hbm_read_probe(device, bytes, iters, 1);
-    return a > b ? a : b;
-}
-
-// diagnostics: the prefill (exact or MFMA) with the residual stream after every layer copied to host_taps
-// [n_layer][T][n_embd] (compare with the oracle's per-layer hidden states)
-extern "C" int gemma_engine_prefill_taps(gemma_engine *e, float *host_taps, int exact) {
-    set_error("");
-    (void)hipSetDevice(e->device);
-    const gemma_hip_config &c = e->cfg;
-    const int T = e->n_prompt;
-    if (T <= 0 || e->host_pos != 0) {
-        set_error("gemma_engine_prefill_taps: call right after gemma_engine_begin");
-        return -1;
-    }
-    if (prefill_alloc(e, T)) return -1;
-    float *d = nullptr;
-    const size_t n = (size_t)c.n_layer * T * c.n_embd;
-    GHIP_CHECK(hipMalloc(&d, n * 4));
-    int r = enqueue_prefill(e, T, exact != 0, d);
-    if (r == 0) GHIP_CHECK(hipStreamSynchronize(e->stream));
-    if (r == 0) GHIP_CHECK(hipMemcpy(host_taps, d, n * 4, hipMemcpyDeviceToHost));
-    (void)hipFree(d);
-    if (r == 0) e->host_pos = T;
-    return r;
-}
-
 // ---- the ggml executor's fast path (engine_ext.h) ------------------------------------------------
 gemma_engine *gemma_engine_create_ext(const gemma_hip_config *cfg, int device, const host_weights &hw,
                                       const std::vector<uint16_t *> &kc, const std::vector<uint16_t *> &vc) {
@@ -2647,94 +986,4 @@ gemma_engine *gemma_engine_create_ext(const gemma_hip_config *cfg, int device, c
         return nullptr;
     }
     return engine_create(cfg, device, 1, 0, nullptr, &hw, &kc, &vc);
-}
-
-// the device state a decode step reads: hist[pos] = token, *pos, the RoPE row of pos (k_advance
-// publishes it between steps of a device-fed sequence; here the host feeds every token)
-static int ext_set_position(gemma_engine *e, int token, int pos) {
-    const gemma_hip_config &c = e->cfg;
-    rope_row rr;
-    rr.cos = e->rope_cos; rr.sin = e->rope_sin; rr.cur = e->rope_cur; rr.half = c.head_dim / 2; rr.ctx = c.n_ctx;
-    rr.epoch = e->epoch;
-    // n_fixed past the history: k_advance must not overwrite hist (the host supplies every token)
-    return launch_set_position(token, pos, e->pos, e->hist, e->nfix, c.n_ctx + 1, rr, e->stream);
-}
-
-int gemma_engine_ext_decode(gemma_engine *e, int token, int pos, float *logits) {
-    set_error("");
-    const gemma_hip_config &c = e->cfg;
-    if (pos < 0 || pos + 1 >= c.n_ctx || token < 0 || token >= c.n_vocab) {
-        set_error("gemma_engine_ext_decode: token or position out of range");
-        return -1;
-    }
-    const bool prof = ghip_debug_level() >= 2;  // GHIP_GGML_DEBUG=2: per-step host phases to stderr
-    auto us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = prof ? us() : 0.0;
-    (void)hipSetDevice(e->device);
-    if (ext_set_position(e, token, pos)) return -1;
-    if (!e->graph_exec) {  // first step eager (sets the kernels' LDS attributes), then capture
-        if (enqueue_step(e)) return -1;
-        if (ensure_graph(e)) return -1;
-    } else {
-        GHIP_CHECK(hipGraphLaunch(e->graph_exec, e->stream));
-    }
-    if (prof) GHIP_CHECK(hipStreamSynchronize(e->stream));
-    const double t1 = prof ? us() : 0.0;
-    // logits through a pinned staging row (a pageable device-to-host copy stages through the driver);
-    // with the persistent launch its sticky timeout word rides along, so ONE sync covers both
-    const size_t lb = (size_t)c.n_vocab * 4;
-    const bool pchk = persist_on(e) && e->tok_err;
-    auto copy_out = [&]() -> int {
-        if (pchk) {
-            if (!e->ext_err) GHIP_CHECK(hipHostMalloc((void **)&e->ext_err, 16, hipHostMallocDefault));
-            GHIP_CHECK(hipMemcpyAsync(e->ext_err, e->tok_err, 12, hipMemcpyDeviceToHost, e->stream));
-        }
-        if (!e->ext_stage) GHIP_CHECK(hipHostMalloc((void **)&e->ext_stage, lb, hipHostMallocDefault));
-        GHIP_CHECK(hipMemcpyAsync(e->ext_stage, e->logits, lb, hipMemcpyDeviceToHost, e->stream));
-        GHIP_CHECK(hipStreamSynchronize(e->stream));
-        return 0;
-    };
-    if (copy_out()) return -1;
-    if (pchk && persist_report(e, e->ext_err)) {  // a hand-off timeout: redo the token on the per-layer launches
-        fprintf(stderr, "[gemma_hip] %s; token at position %d redone\n", last_error().c_str(), pos);
-        set_error("");
-        if (ext_set_position(e, token, pos) || enqueue_step(e)) return -1;
-        if (copy_out()) return -1;
-    }
-    const double t2 = prof ? us() : 0.0;
-    memcpy(logits, e->ext_stage, lb);
-    if (prof) fprintf(stderr, "[gemma_hip] ext_decode: launch+run %.1f us, copy %.1f us, host copy %.1f us\n", t1 - t0, t2 - t1, us() - t2);
-    e->host_pos = pos + 1;
-    return 0;
-}
-
-int gemma_engine_ext_prefill(gemma_engine *e, const int32_t *tokens, int T, float *logits_all) {
-    if (T <= 0 || T >= e->cfg.n_ctx) {
-        set_error("gemma_engine_ext_prefill: prompt length out of range");
-        return -1;
-    }
-    for (int i = 0; i < T; ++i)
-        if (tokens[i] < 0 || tokens[i] >= e->cfg.n_vocab) {
-            set_error("gemma_engine_ext_prefill: token id out of range");
-            return -1;
-        }
-    if (!e->graph_exec) {
-        // the decode step's first launches (code-object loading, LDS attributes) and its graph
-        // capture happen here, in the prompt's call, instead of in the first generated token: one
-        // eager step at position 0, whose cache row the prefill below rewrites (begin clears it)
-        (void)hipSetDevice(e->device);
-        if (ext_set_position(e, tokens[0], 0) || enqueue_step(e) || ensure_graph(e)) return -1;
-        GHIP_CHECK(hipGraphLaunch(e->graph_exec, e->stream));  // the graph's first launch uploads it
-        if (!e->ext_stage) GHIP_CHECK(hipHostMalloc((void **)&e->ext_stage, (size_t)e->cfg.n_vocab * 4, hipHostMallocDefault));
-        GHIP_CHECK(hipMemcpyAsync(e->ext_stage, e->logits, (size_t)e->cfg.n_vocab * 4, hipMemcpyDeviceToHost, e->stream));
-        GHIP_CHECK(hipStreamSynchronize(e->stream));
-    }
-    if (gemma_engine_begin(e, tokens, T)) return -1;
-    std::vector<float> last(e->cfg.n_vocab);
-    if (gemma_engine_prefill(e, last.data(), logits_all) < 0) return -1;
-    // measured: the first pinned-row copy after the prompt's large pageable copy takes ~10 ms; pay
-    // it here rather than in the first generated token
-    GHIP_CHECK(hipMemcpyAsync(e->ext_stage, e->logits, (size_t)e->cfg.n_vocab * 4, hipMemcpyDeviceToHost, e->stream));
-    GHIP_CHECK(hipStreamSynchronize(e->stream));
-    return 0;
 }

@@ -1,0 +1,633 @@
+// engine_diag.cpp — what measures, tunes and inspects the device-resident engine: per-kernel
+// timing, the launch-plan tuner, plan / option setters, phase stamps (the entry points that need a
+// -DGHIP_STAMPS=1 build of this file), per-layer taps, the per-op test hooks and the HBM probes.
+#include "engine_impl.h"
+
+// ---- hipEvent timing of one hot kernel on the engine stream (bench.py roofline leg) -----------
+extern "C" double gemma_engine_time(gemma_engine *e, int which, int iters, double *algo_bytes) {
+    set_error("");
+    (void)hipSetDevice(e->device);
+    const gemma_hip_config &c = e->cfg;
+    const int wt = c.wtype;
+    // launches rotate over the layers' matrices, as in a decode step: each launch reads its weights
+    // cold (18 x the FFN matrices exceed the 256 MB Infinity Cache)
+    int layer = 0;
+    mv_args a;
+    int ks = 1, pro = PRO_F32, epi = EPI_STORE, grid = 1;
+    double bytes = 0;
+    auto setup = [&](layer_dev &L) {
+    switch (which) {
+        case 0:
+            set_mat(a, L.gate);
+            a.qs2 = L.up.qs; a.sc2 = L.up.sc;
+            a.x = e->sa; a.norm_w = L.ffn_norm; a.eps = c.eps; a.y = e->h; a.gelu_tab = e->gelu_tab;
+            pro = PRO_NORM; epi = EPI_GELU_MUL; ks = e->plan[MC_GU].ks;  // 2 = gate and up on separate waves
+            grid = mv_grid(e, MC_GU, L.gate.n_rt);
+            bytes = (double)L.gate.algo_bytes() + L.up.algo_bytes() + c.n_embd * 4.0 * 2 + c.n_ff * 4.0;
+            break;
+        case 1:
+            set_mat(a, L.down);
+            a.x = e->h; a.y = e->x; a.resid = e->sa; ks = pick_ks(wt, L.down.n_bt, e->plan[MC_DOWN].ks); epi = EPI_ADD;
+            if (e->h_act && e->plan[MC_DOWN].img) { a.x = e->h_act; a.x_da = e->h_da; pro = PRO_IMG; }
+            grid = mv_grid(e, MC_DOWN, L.down.n_rt);
+            bytes = (double)L.down.algo_bytes() + c.n_ff * (e->h_act ? 36.0 / 32 : 4.0) + c.n_embd * 8.0;
+            break;
+        case 2:
+            set_mat(a, L.qkv);
+            a.x = e->x; a.norm_w = L.attn_norm; a.eps = c.eps; a.y = e->qkv; ks = pick_ks(wt, L.qkv.n_bt, e->plan[MC_QKV].ks); pro = PRO_NORM;
+            grid = mv_grid(e, MC_QKV, L.qkv.n_rt);
+            bytes = (double)L.qkv.algo_bytes() + c.n_embd * 8.0 + e->qkv_rows * 4.0;
+            break;
+        case 3:
+            set_mat(a, L.o);
+            a.x = e->attn; a.y = e->sa; a.resid = e->x; ks = pick_ks(wt, L.o.n_bt, e->plan[MC_O].ks); epi = EPI_ADD;
+            if (e->att_act && att_img_ok(e) && e->plan[MC_O].img) { a.x = e->att_act; a.x_da = e->att_da; pro = PRO_IMG; }
+            grid = mv_grid(e, MC_O, L.o.n_rt);
+            bytes = (double)L.o.algo_bytes() + e->qw * (pro == PRO_IMG ? 36.0 / 32 : 4.0) + c.n_embd * 8.0;
+            break;
+        case 4:
+            set_mat(a, e->embd);
+            a.x = e->x; a.norm_w = e->out_norm; a.eps = c.eps; a.y = e->logits; a.argmax_key = e->key;
+            pro = PRO_NORM; epi = EPI_ARGMAX;
+            grid = mv_grid(e, MC_LOGITS, e->embd.n_rt);
+            bytes = (double)e->embd.algo_bytes() + c.n_embd * 8.0 + c.n_vocab * 4.0;
+            break;
+        default:
+            break;
+    }
+    };
+    if (e->kq) {
+        set_error("gemma_engine_time: K-quant layer engines time their matvecs with gemma_kq_time");
+        return -1.0;
+    }
+    if (which == 4 && e->out_type == T_Q6_K) {
+        set_error("gemma_engine_time: the logits kernel of a Q6_K output is the K-quant matvec (gemma_kq_time)");
+        return -1.0;
+    }
+    if (which < 0 || which > 5) {
+        set_error("gemma_engine_time: bad kernel id");
+        return -1.0;
+    }
+    setup(e->layers[0]);
+    const bool hot = e->time_hot != 0;
+    a.ablate = e->ablate;
+    hipEvent_t t0, t1;
+    GHIP_FATAL(hipEventCreate(&t0));
+    GHIP_FATAL(hipEventCreate(&t1));
+    auto run = [&]() -> int {
+        if (which == 5) {
+            if (ensure_graph(e)) return -1;
+            GHIP_CHECK(hipGraphLaunch(e->graph_exec, e->stream));
+            return 0;
+        }
+        if (which < 4) {
+            setup(e->layers[layer]);
+            if (!hot) layer = (layer + 1) % c.n_layer;  // hot: the same matrix (Infinity-Cache resident)
+        }
+        return launch_matvec(wt, ks, pro, epi, a, grid, e->stream);
+    };
+    if (which == 5) {
+        // whole step replays advance the position: keep within the context
+        if (e->host_pos + 2 * iters + 4 >= c.n_ctx) {
+            set_error("gemma_engine_time: context too small for step timing");
+            return -1.0;
+        }
+    }
+    for (int i = 0; i < 3; ++i)
+        if (run()) return -1.0;
+    GHIP_FATAL(hipEventRecord(t0, e->stream));
+    for (int i = 0; i < iters; ++i)
+        if (run()) return -1.0;
+    GHIP_FATAL(hipEventRecord(t1, e->stream));
+    GHIP_FATAL(hipEventSynchronize(t1));
+    if (which == 5) e->host_pos += iters + 3;
+    float ms = 0;
+    GHIP_FATAL(hipEventElapsedTime(&ms, t0, t1));
+    (void)hipEventDestroy(t0);
+    (void)hipEventDestroy(t1);
+    if (algo_bytes) *algo_bytes = bytes;
+    return (double)ms * 1000.0 / iters;
+}
+
+// ---- launch-plan tuning -----------------------------------------------------------------------
+// Coordinate descent over the matrix classes: for each class every feasible (K split, row-tile
+// groups per workgroup) is timed as whole decode steps (hipGraph replays on a fresh context), the
+// other classes held at their current best.  Whole steps keep the cache state of real decoding
+// (a matrix timed alone would be served from the 256 MB Infinity Cache).  Every candidate computes
+// the same bits (the K split keeps the block order), so tuning changes speed only.  The decode
+// state is clobbered: call gemma_engine_begin afterwards.  In a TP job every rank runs the same
+// candidate sequence (same collectives per step); ranks may settle on different plans.
+extern "C" int gemma_engine_tune(gemma_engine *e, int iters) {
+    set_error("");
+    if (e->kq) return 0;  // K-quant layers: no launch plan to measure
+    (void)hipSetDevice(e->device);
+    const gemma_hip_config &c = e->cfg;
+    const int wt = c.wtype;
+    const int32_t prompt[4] = {2, 2, 2, 2};
+    iters = std::max(2, std::min(iters, c.n_ctx - 12));
+    if (iters < 2 || c.n_ctx < 16) {
+        set_error("gemma_engine_tune: context too small");
+        return -1;
+    }
+    hipEvent_t t0, t1;
+    GHIP_CHECK(hipEventCreate(&t0));
+    GHIP_CHECK(hipEventCreate(&t1));
+    auto trial = [&]() -> double {
+        drop_graph(e);
+        if (gemma_engine_begin(e, prompt, 4)) return -1.0;
+        if (gemma_engine_step(e, 1, nullptr, 1)) return -1.0;  // eager step + capture
+        for (int i = 0; i < 2; ++i)
+            if (hipGraphLaunch(e->graph_exec, e->stream) != hipSuccess) return -1.0;
+        // the minimum of three timed runs: one run's box noise (±1 %) exceeded the differences
+        // between neighbouring plans, so single samples picked plans by luck (round 5: the bench's
+        // logits plan varied run to run between 1, 2 and 8 row tiles per workgroup, ±2 µs)
+        double tmin = 1e30;
+        for (int rep = 0; rep < 3; ++rep) {
+            if (hipEventRecord(t0, e->stream) != hipSuccess) return -1.0;
+            for (int i = 0; i < iters; ++i)
+                if (hipGraphLaunch(e->graph_exec, e->stream) != hipSuccess) return -1.0;
+            if (hipEventRecord(t1, e->stream) != hipSuccess || hipEventSynchronize(t1) != hipSuccess) return -1.0;
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, t0, t1);
+            tmin = std::min(tmin, (double)ms * 1000.0 / iters);
+        }
+        return tmin;
+    };
+    const layer_dev &L0 = e->layers[0];
+    const int64_t nbt[MC_N] = {L0.qkv.n_bt, L0.o.n_bt, L0.gate.n_bt, L0.down.n_bt, e->embd.n_bt};
+    int rc = 0;
+    double best = trial();
+    if (best < 0) rc = -1;
+    const int order[MC_N] = {MC_DOWN, MC_GU, MC_QKV, MC_O, MC_LOGITS};
+    for (int oi = 0; oi < MC_N && rc == 0; ++oi) {
+        const int cls = order[oi];
+        if (cls == MC_LOGITS && e->out_type == T_Q6_K) continue;  // the K-quant matvec has no plan
+        std::vector<launch_plan> cands;
+        const bool splits = cls == MC_QKV || cls == MC_O || cls == MC_DOWN || cls == MC_GU;
+        for (int ks = 1; ks <= (cls == MC_GU ? 2 : splits ? 8 : 1); ks *= 2) {
+            if (pick_ks(wt, nbt[cls], ks) != ks) continue;  // not a divisor, or the LDS image overflows
+            const int rmax = cls == MC_LOGITS ? 16 : ks == 1 ? 2 : 4;
+            for (int rpw = 1; rpw <= rmax; rpw *= 2) cands.push_back({ks, rpw, e->plan[cls].img});
+        }
+        // the round-pipelined form (one workgroup per row tile)
+        if (splits && cls != MC_GU && pick_ks(wt, nbt[cls], KS_RR) == KS_RR) cands.push_back({KS_RR, 1, e->plan[cls].img});
+        const launch_plan keep = e->plan[cls];
+        launch_plan win = keep;
+        // whole steps for every class.  (Timing the logits launch alone picked 1 row tile per
+        // workgroup, whose back-to-back launches overlap their tails; inside the step, where k_advance
+        // waits for it, 8 measured 52.3-52.7 vs 53.2-54.4 µs — round 5, driver-style bench lines.)
+        auto measure = [&]() -> double { return trial(); };
+        double best_cls;
+        {  // the incumbent re-measured beside its challengers (not a sample from an earlier class)
+            const double t = measure();
+            if (t < 0) {
+                rc = -1;
+                break;
+            }
+            best_cls = t;
+        }
+        for (const launch_plan &p : cands) {
+            if (p.ks == keep.ks && p.rpw == keep.rpw && p.img == keep.img) continue;
+            e->plan[cls] = p;
+            const double t = measure();
+            if (t < 0) {
+                rc = -1;
+                break;
+            }
+            if (t < best_cls * 0.998) {  // a challenger must beat the incumbent past the noise floor
+                best_cls = t;
+                win = p;
+            }
+        }
+        e->plan[cls] = win;
+        if (cls != MC_LOGITS) best = best_cls;
+        // on / off switches: the incumbent re-measured beside the challenger and the same 0.2 %
+        // hysteresis as the plans (a bare t < best flipped on noise).  Every condition is
+        // structural, never a measured outcome, so every rank of a TP job runs the same trials.
+        auto toggle = [&](auto flip) {
+            if (rc) return;
+            const double inc = trial();
+            flip();
+            const double t = inc < 0 ? -1.0 : trial();
+            if (t < 0) rc = -1;
+            if (t >= 0 && t < inc * 0.998) best = t;
+            else flip();
+        };
+        if (cls == MC_O && e->ag.nwg && e->cfg.n_ctx <= 2048 && e->cfg.head_dim <= 256)
+            toggle([&] { e->att_mode ^= 1; });  // attention form: one workgroup per head vs the split
+        // the producer-written activation image, at the winning launch shape
+        if ((cls == MC_O && e->att_act) || (cls == MC_DOWN && e->h_act)) toggle([&] { e->plan[cls].img ^= 1; });
+        // attention + attn-out in one launch (takes effect with the image and the rr attn-out form)
+        if (cls == MC_O && e->ao_cnt && e->n_virtual == 1) toggle([&] { e->att_o ^= 1; });
+    }
+    drop_graph(e);
+    (void)hipEventDestroy(t0);
+    (void)hipEventDestroy(t1);
+    e->host_pos = 0;
+    return rc;
+}
+
+// the current plan, 3 ints per class (qkv, o, gate/up, down, logits): K split, row-tile groups per
+// workgroup, activation image (o, down); returns the number of ints written
+extern "C" int gemma_engine_plan(gemma_engine *e, int *out, int cap) {
+    int n = 0;
+    for (int cls = 0; cls < MC_N && n + 3 <= cap; ++cls) {
+        out[n++] = e->plan[cls].ks;
+        out[n++] = e->plan[cls].rpw;
+        out[n++] = e->plan[cls].img;
+    }
+    if (n < cap) out[n++] = e->att_mode;  // attention form: 0 per head, 1 split
+    return n;
+}
+
+// kernel launches per decode token: the kernel nodes of the captured decode graph (captured on
+// first use if needed); -1 on error
+extern "C" int gemma_engine_graph_kernels(gemma_engine *e) {
+    set_error("");
+    (void)hipSetDevice(e->device);
+    if (!e->graph) {
+        set_error("gemma_engine_graph_kernels: no decode graph yet (run a gemma_engine_step with use_graph first)");
+        return -1;
+    }
+    size_t n = 0;
+    GHIP_CHECK(hipGraphGetNodes(e->graph, nullptr, &n));
+    std::vector<hipGraphNode_t> nodes(n);
+    GHIP_CHECK(hipGraphGetNodes(e->graph, nodes.data(), &n));
+    int k = 0;
+    for (size_t i = 0; i < n; ++i) {
+        hipGraphNodeType t;
+        GHIP_CHECK(hipGraphNodeGetType(nodes[i], &t));
+        k += t == hipGraphNodeTypeKernel;
+    }
+    return k;
+}
+
+// the persistent token launch on/off (-1 = keep); returns 1 when it runs this engine's decode
+// steps, 0 when not (hpc_last_error says why if it was asked for)
+extern "C" int gemma_engine_set_persist(gemma_engine *e, int on) {
+    set_error("");
+    (void)hipSetDevice(e->device);
+    if (on >= 0 && on != e->persist) {
+        e->persist = on;
+        drop_graph(e);
+    }
+    if (tok_prepare(e)) return -1;
+    if (e->persist && !e->persist_why.empty()) set_error("persistent token launch: " + e->persist_why);
+    return persist_on(e) ? 1 : 0;
+}
+
+// tests: the persistent launch's per-wait bound in 100 MHz ticks (0 = the default 20 ms); a tiny
+// bound forces hand-off timeouts so that their reporting can be checked
+extern "C" int gemma_engine_set_persist_timeout(gemma_engine *e, unsigned ticks) {
+    set_error("");
+    (void)hipSetDevice(e->device);
+    e->persist_timeout = ticks ? ticks : 2000000u;
+    drop_graph(e);
+    return tok_prepare(e);
+}
+
+// the persistent launch's sticky hand-off timeout words [flag, site, layer] (0 = none seen);
+// reset = 1 clears them
+extern "C" int gemma_engine_persist_err(gemma_engine *e, int *out3, int reset) {
+    (void)hipSetDevice(e->device);
+    int w[3] = {0, 0, 0};
+    if (e->tok_err) GHIP_CHECK(hipMemcpy(w, e->tok_err, 12, hipMemcpyDeviceToHost));
+    if (out3) memcpy(out3, w, 12);
+    if (reset && e->tok_err) GHIP_CHECK(hipMemset(e->tok_err, 0, 64));
+    return w[0];
+}
+
+// Engine options (tests, A/B): the measured variants that stay selectable, set through the API so a
+// stray environment variable on a box can never change the benched kernels.  Returns 0, or -1 for an
+// unknown name.  The decode graph is dropped (re-captured at the next step).
+extern "C" int gemma_engine_set_option(gemma_engine *e, const char *name, int value) {
+    set_error("");
+    const std::string n = name ? name : "";
+    int *f = n == "kq_fuse" ? &e->kq_fuse : n == "kq_dual" ? &e->kq_dual : n == "kq_pair" ? &e->kq_pair
+           : n == "kq_abl" ? &e->kq_abl : n == "att_mx" ? &e->att_mx : n == "time_hot" ? &e->time_hot
+           : n == "ablate" ? &e->ablate : n == "ks_small" ? &e->ks_small : n == "ks_down" ? &e->ks_down : nullptr;
+    if (n == "att_dsplit") {
+        if (value < 1 || value > 8 || (value & (value - 1)) || e->cfg.head_dim % (32 * value)) {
+            set_error("gemma_engine_set_option: att_dsplit must be 1, 2, 4 or 8 and divide head_dim / 32");
+            return -1;
+        }
+        f = &e->att_dsplit;
+    }
+    if (n == "grid_big") {
+        if (value < 1 || value > e->grid_big_cap) {
+            set_error("gemma_engine_set_option: grid_big out of range (1 .. the argmax key buffer)");
+            return -1;
+        }
+        f = &e->grid_big;
+    }
+    if (!f) {
+        set_error("gemma_engine_set_option: unknown option '" + n + "'");
+        return -1;
+    }
+    *f = value;
+    drop_graph(e);
+    return 0;
+}
+
+// attention + attn-out in one launch on (1) / off (0) / unchanged (-1); returns the setting
+extern "C" int gemma_engine_set_att_o(gemma_engine *e, int on) {
+    if (on >= 0 && (on != 0) != (e->att_o != 0)) {
+        e->att_o = on != 0 && e->ao_cnt;
+        drop_graph(e);
+    }
+    return e->att_o;
+}
+
+// fused layer front on/off (tests, A/B); returns the sticky hand-off timeout word (0 = none seen)
+extern "C" int gemma_engine_set_fuse(gemma_engine *e, int fuse_front) {
+    if (fuse_front >= 0) {
+        e->fuse_front = fuse_front;
+        drop_graph(e);
+    }
+    int err = 0;
+    if (e->front_err) (void)hipMemcpy(&err, e->front_err, 4, hipMemcpyDeviceToHost);
+    return err;
+}
+
+extern "C" int gemma_engine_set_plan(gemma_engine *e, const int *in, int n) {
+    const gemma_hip_config &c = e->cfg;
+    const layer_dev &L0 = e->layers[0];
+    const int64_t nbt[MC_N] = {L0.qkv.n_bt, L0.o.n_bt, L0.gate.n_bt, L0.down.n_bt, e->embd.n_bt};
+    for (int cls = 0; cls < MC_N && 3 * cls + 2 < n; ++cls) {
+        const int ks = in[3 * cls], rpw = in[3 * cls + 1], img = in[3 * cls + 2];
+        const bool splits = cls == MC_QKV || cls == MC_O || cls == MC_DOWN || cls == MC_GU;
+        const bool img_ok = (cls == MC_O && e->att_act) || (cls == MC_DOWN && e->h_act);
+        if (ks < 1 || (!splits && ks != 1) || (cls == MC_GU && ks > 2) || pick_ks(c.wtype, nbt[cls], ks) != ks || rpw < 1 || rpw > 64 ||
+            (img && !img_ok)) {
+            set_error("gemma_engine_set_plan: infeasible plan");
+            return -1;
+        }
+        e->plan[cls] = {ks, rpw, img ? 1 : 0};
+    }
+    if (n > 3 * MC_N) {
+        const int mode = in[3 * MC_N];
+        if ((mode != ATTN_PER_HEAD && mode != ATTN_SPLIT) || (mode == ATTN_SPLIT && !e->ag.nwg) ||
+            (mode == ATTN_PER_HEAD && (c.head_dim > 256 || c.n_ctx > 2048))) {
+            set_error("gemma_engine_set_plan: infeasible attention form");
+            return -1;
+        }
+        e->att_mode = mode;
+    }
+    drop_graph(e);
+    return 0;
+}
+// Diagnostic: one eager decode step with s_memrealtime phase stamps (100 MHz) for the five kernels
+// of `layer` (regions 0..4: qkv, attention, o, gate/up, down) and the logits kernel (region 5).
+// out: 6 * 4096 * 16 u64; unused slots are 0.
+extern "C" int gemma_engine_stamp_step(gemma_engine *e, int layer, unsigned long long *out) {
+    set_error("");
+    if (!GHIP_STAMPS) {
+        set_error("gemma_engine_stamp_step: library built without -DGHIP_STAMPS=1 (scripts/build_variant.sh)");
+        return -1;
+    }
+    (void)hipSetDevice(e->device);
+    const size_t n = 6 * kStampRegion;
+    GHIP_CHECK(hipMalloc(&e->stamp, n * 8));
+    GHIP_CHECK(hipMemsetAsync(e->stamp, 0, n * 8, e->stream));
+    e->stamp_layer = layer;
+    const int r = enqueue_step(e);
+    if (r == 0) {
+        GHIP_CHECK(hipStreamSynchronize(e->stream));
+        GHIP_CHECK(hipMemcpy(out, e->stamp, n * 8, hipMemcpyDeviceToHost));
+        e->host_pos += 1;
+    }
+    (void)hipFree(e->stamp);
+    e->stamp = nullptr;
+    e->stamp_layer = -1;
+    return r;
+}
+
+// diagnostics: one eager step through the persistent token launch with its phase stamps
+// (s_memrealtime, 100 MHz) -> out [grid = n_embd / 8][n_layer][16]; needs a -DGHIP_STAMPS=1 build
+// of token.hip and engine_diag.cpp (scripts/build_variant.sh)
+extern "C" int gemma_engine_token_stamps(gemma_engine *e, unsigned long long *out) {
+    set_error("");
+    if (!GHIP_STAMPS) {
+        set_error("gemma_engine_token_stamps: library built without -DGHIP_STAMPS=1 (scripts/build_variant.sh)");
+        return -1;
+    }
+    (void)hipSetDevice(e->device);
+    if (!persist_on(e)) {
+        set_error("gemma_engine_token_stamps: the persistent launch is not active: " + e->persist_why);
+        return -1;
+    }
+    const size_t n = (size_t)(e->cfg.n_embd / 8) * e->cfg.n_layer * 16 + 256;  // + per-pop probes
+    unsigned long long *buf = nullptr;
+    GHIP_CHECK(hipStreamSynchronize(e->stream));
+    GHIP_CHECK(hipMalloc(&buf, n * 8));
+    GHIP_CHECK(hipMemset(buf, 0, n * 8));
+    tok_args a = e->tok;
+    a.dbg_t = buf;
+    GHIP_CHECK(hipMemcpy(e->tok_dev, &a, sizeof(a), hipMemcpyHostToDevice));
+    const int r = enqueue_step(e);
+    GHIP_CHECK(hipStreamSynchronize(e->stream));
+    GHIP_CHECK(hipMemcpy(e->tok_dev, &e->tok, sizeof(e->tok), hipMemcpyHostToDevice));
+    if (r == 0) {
+        GHIP_CHECK(hipMemcpy(out, buf, n * 8, hipMemcpyDeviceToHost));
+        e->host_pos += 1;
+    }
+    (void)hipFree(buf);
+    return r;
+}
+
+// one eager step with per-layer taps copied to host: [L][qkv | attn | x_out]
+extern "C" int gemma_engine_debug_step(gemma_engine *e, float *host_taps, float *logits) {
+    set_error("");
+    (void)hipSetDevice(e->device);
+    const gemma_hip_config &c = e->cfg;
+    const size_t per = (size_t)e->qkv_rows + e->qw + c.n_embd;
+    GHIP_CHECK(hipMalloc(&e->dbg, per * c.n_layer * 4));
+    const int r = enqueue_step(e);
+    GHIP_CHECK(hipStreamSynchronize(e->stream));
+    if (r == 0) {
+        GHIP_CHECK(hipMemcpy(host_taps, e->dbg, per * c.n_layer * 4, hipMemcpyDeviceToHost));
+        if (logits) GHIP_CHECK(hipMemcpy(logits, e->logits, (size_t)c.n_vocab * 4, hipMemcpyDeviceToHost));
+        e->host_pos += 1;
+    }
+    GHIP_CHECK(hipFree(e->dbg));
+    e->dbg = nullptr;
+    return r;
+}
+
+// ---- per-op test entry: the decode attention kernel on host buffers ---------------------------
+// qkv [H*hd + 2*Hkv*hd] f32; kc [ctx][Hkv*hd], vc [Hkv*hd][ctx] f16 (updated in place at pos)
+extern "C" int gemma_test_attn_decode(const float *qkv, uint16_t *kc, uint16_t *vc, int pos, int H, int Hkv, int hd,
+                                      int ctx, float rope_base, float *out, float *dbg_w, uint16_t *dbg_p,
+                                      float *dbg_inv, unsigned long long *dbg_t, int mode) {
+    set_error("");
+    const size_t qkv_n = (size_t)(H + 2 * Hkv) * hd, cache_n = (size_t)ctx * Hkv * hd;
+    std::vector<uint16_t> et, gt;
+    build_f16_tables(et, gt);
+    std::vector<float> rc, rs;
+    build_rope(ctx, hd, rope_base, rc, rs);
+    float *d_qkv, *d_out, *d_c, *d_s;
+    uint16_t *d_k, *d_v, *d_e;
+    int *d_pos;
+    float *d_dw = nullptr, *d_di = nullptr;
+    unsigned long long *d_dt = nullptr;
+    const size_t n_stamps = (size_t)H * 8 * 8;  // >= workgroups x 8 stamps for any hd <= 512
+    if (dbg_t) GHIP_CHECK(hipMalloc(&d_dt, n_stamps * 8));
+    if (dbg_t) GHIP_CHECK(hipMemset(d_dt, 0, n_stamps * 8));
+    uint16_t *d_dp = nullptr;
+    if (dbg_w) GHIP_CHECK(hipMalloc(&d_dw, (size_t)H * ctx * 4));
+    if (dbg_p) GHIP_CHECK(hipMalloc(&d_dp, (size_t)H * ctx * 2));
+    if (dbg_inv) GHIP_CHECK(hipMalloc(&d_di, (size_t)H * 4));
+    GHIP_CHECK(hipMalloc(&d_qkv, qkv_n * 4));
+    GHIP_CHECK(hipMalloc(&d_out, (size_t)H * hd * 4));
+    GHIP_CHECK(hipMalloc(&d_c, rc.size() * 4));
+    GHIP_CHECK(hipMalloc(&d_s, rs.size() * 4));
+    GHIP_CHECK(hipMalloc(&d_k, cache_n * 2));
+    GHIP_CHECK(hipMalloc(&d_v, cache_n * 2));
+    GHIP_CHECK(hipMalloc(&d_e, 65536 * 2));
+    GHIP_CHECK(hipMalloc(&d_pos, 4));
+    GHIP_CHECK(hipMemcpy(d_qkv, qkv, qkv_n * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_c, rc.data(), rc.size() * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_s, rs.data(), rs.size() * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_k, kc, cache_n * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_v, vc, cache_n * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_e, et.data(), 65536 * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_pos, &pos, 4, hipMemcpyHostToDevice));
+    const attn_geom g = attn_geometry(H, Hkv, hd, ctx);
+    float *d_sb = nullptr;
+    int *d_sy = nullptr;
+    if (g.nwg) {
+        GHIP_CHECK(hipMalloc(&d_sb, g.sbuf_floats * 4));
+        GHIP_CHECK(hipMalloc(&d_sy, (g.sync_ints + 1) * 4));
+        GHIP_CHECK(hipMemset(d_sy, 0, (g.sync_ints + 1) * 4));
+    }
+    attn_args a;
+    a.qkv = d_qkv; a.kc = d_k; a.vc = d_v; a.rope_cos = d_c; a.rope_sin = d_s; a.exp_tab = d_e; a.pos = d_pos;
+    a.nwg = g.nwg; a.sbuf = d_sb; a.sync = d_sy; a.err = d_sy ? d_sy + g.sync_ints : nullptr;
+    float *d_rc = nullptr;
+    GHIP_CHECK(hipMalloc(&d_rc, (size_t)(hd + 4) * 4));
+    GHIP_CHECK(hipMemcpy(d_rc, rc.data() + (size_t)pos * (hd / 2), (size_t)(hd / 2) * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_rc + hd / 2, rs.data() + (size_t)pos * (hd / 2), (size_t)(hd / 2) * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_rc + hd, &pos, 4, hipMemcpyHostToDevice));
+    a.rope_cur = d_rc;
+    // mode 0 per-head, 1 split form; 2 / 3: per-head with 2 / 4 workgroups per head (dim split)
+    a.mode = mode >= 2 ? ATTN_PER_HEAD : mode;
+    a.dsplit = mode == 2 ? 2 : mode == 3 ? 4 : 1;
+    a.out = d_out; a.H = H; a.Hkv = Hkv; a.hd = hd; a.ctx = ctx; a.q_scale = 1.0f / sqrtf((float)hd);
+    a.dbg_w = d_dw; a.dbg_p = d_dp; a.dbg_inv = d_di; a.dbg_t = d_dt;
+    int r = 0;
+    for (int rep = 0; rep < (dbg_t ? 3 : 1) && r == 0; ++rep) r = launch_attn_decode(a, nullptr);
+    GHIP_CHECK(hipDeviceSynchronize());
+    if (r == 0) {
+        GHIP_CHECK(hipMemcpy(out, d_out, (size_t)H * hd * 4, hipMemcpyDeviceToHost));
+        GHIP_CHECK(hipMemcpy(kc, d_k, cache_n * 2, hipMemcpyDeviceToHost));
+        GHIP_CHECK(hipMemcpy(vc, d_v, cache_n * 2, hipMemcpyDeviceToHost));
+        if (dbg_w) GHIP_CHECK(hipMemcpy(dbg_w, d_dw, (size_t)H * ctx * 4, hipMemcpyDeviceToHost));
+        if (dbg_p) GHIP_CHECK(hipMemcpy(dbg_p, d_dp, (size_t)H * ctx * 2, hipMemcpyDeviceToHost));
+        if (dbg_inv) GHIP_CHECK(hipMemcpy(dbg_inv, d_di, (size_t)H * 4, hipMemcpyDeviceToHost));
+        if (dbg_t) GHIP_CHECK(hipMemcpy(dbg_t, d_dt, n_stamps * 8, hipMemcpyDeviceToHost));
+    }
+    if (r == 0 && d_sy) {
+        int err = 0;
+        GHIP_CHECK(hipMemcpy(&err, d_sy + g.sync_ints, 4, hipMemcpyDeviceToHost));
+        if (err) {
+            set_error("attn_decode: hand-off spin timed out");
+            r = -1;
+        }
+    }
+    void *bufs[] = {d_qkv, d_out, d_c, d_s, d_k, d_v, d_e, d_pos, d_dw, d_dp, d_di, d_dt, d_sb, d_sy, d_rc};
+    for (void *p : bufs)
+        if (p) (void)hipFree(p);
+    return r;
+}
+
+extern "C" int gemma_test_exp_f16(uint16_t *out) {
+    set_error("");
+    uint16_t *d = nullptr;
+    GHIP_CHECK(hipMalloc(&d, 65536 * 2));
+    int r = launch_exp_f16_all(d, nullptr);
+    if (r == 0) GHIP_CHECK(hipMemcpy(out, d, 65536 * 2, hipMemcpyDeviceToHost));
+    (void)hipFree(d);
+    return r;
+}
+
+// Test hook: one rms_norm kernel on `rows` host rows of n f32.  kind 0: the ggml
+// executor's RMS_NORM (k_g_rms_norm), out = f32 rows x * scale; kind 1: k_norm_q8K (rms_norm * w then
+// quantize_row_q8_K, n a multiple of 256, <= 4096), out = Q8_K rows.
+extern "C" int gemma_test_rms_norm(int kind, const float *x, const float *w, int rows, int n, float eps, void *out) {
+    set_error("");
+    if (rows <= 0 || n <= 0 || (kind == 1 && (n % 256 || n > 4096)) || kind < 0 || kind > 1) {
+        set_error("gemma_test_rms_norm: unsupported shape or kind");
+        return -1;
+    }
+    const size_t in_b = (size_t)rows * n * 4, out_b = kind == 0 ? in_b : (size_t)rows * (n / 256) * 292;
+    float *dx = nullptr, *dw = nullptr;
+    uint8_t *dy = nullptr;
+    GHIP_CHECK(hipMalloc(&dx, in_b));
+    GHIP_CHECK(hipMalloc(&dw, (size_t)n * 4));
+    GHIP_CHECK(hipMalloc(&dy, out_b));
+    GHIP_CHECK(hipMemcpy(dx, x, in_b, hipMemcpyHostToDevice));
+    if (w) GHIP_CHECK(hipMemcpy(dw, w, (size_t)n * 4, hipMemcpyHostToDevice));
+    int r;
+    if (kind == 0) {
+        gt_desc a, d;
+        a.data = (char *)dx;
+        d.data = (char *)dy;
+        a.ne[0] = d.ne[0] = n;
+        a.ne[1] = d.ne[1] = rows;
+        a.nb[0] = d.nb[0] = 4;
+        a.nb[1] = d.nb[1] = (int64_t)n * 4;
+        a.nb[2] = d.nb[2] = a.nb[3] = d.nb[3] = (int64_t)n * rows * 4;
+        r = launch_g_rms_norm(a, d, eps, nullptr);
+    } else {
+        r = launch_norm_q8K(dx, n, dw, n, eps, rows, dy, (n / 256) * 292, nullptr);
+    }
+    if (r == 0) GHIP_CHECK(hipMemcpy(out, dy, out_b, hipMemcpyDeviceToHost));
+    (void)hipFree(dx);
+    (void)hipFree(dw);
+    (void)hipFree(dy);
+    return r;
+}
+
+// Measured HBM read roofline: a streaming read of `bytes` (>= 4 GB defeats the
+// Infinity Cache), `iters` passes timed with hipEvents; returns GB/s (negative on error).
+// measured HBM read rate (GB/s) of one probe: variant 0 = 16-B nontemporal loads into VGPRs (8 in
+// flight per lane), 1 = LDS-DMA (global_load_lds_dwordx4 nt, 16 KiB in flight per wave); a buffer
+// far beyond the 256 MB Infinity Cache
+extern "C" double gemma_hbm_read_probe(int device, size_t bytes, int iters, int variant) {
+    set_error("");
+    if (hipSetDevice(device) != hipSuccess) return -1.0;
+    void *buf = nullptr;
+    unsigned *sink = nullptr;
+    if (hipMalloc(&buf, bytes) != hipSuccess || hipMalloc(&sink, 4) != hipSuccess) {
+        set_error("gemma_hbm_read_gbs: allocation failed");
+        return -1.0;
+    }
+    (void)hipMemset(buf, 1, bytes);
+    hipStream_t s;
+    (void)hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    hipEvent_t t0, t1;
+    (void)hipEventCreate(&t0);
+    (void)hipEventCreate(&t1);
+    double gbs = -1.0;
+    if (launch_stream_read(buf, bytes, sink, s, variant) == 0) {
+        (void)hipEventRecord(t0, s);
+        for (int i = 0; i < iters; ++i) (void)launch_stream_read(buf, bytes, sink, s, variant);
+        (void)hipEventRecord(t1, s);
+        (void)hipEventSynchronize(t1);
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, t0, t1);
+        gbs = (double)bytes * iters / (ms * 1e-3) / 1e9;
+    }
+    (void)hipEventDestroy(t0);
+    (void)hipEventDestroy(t1);
+    (void)hipStreamDestroy(s);
+    (void)hipFree(buf);
+    (void)hipFree(sink);
+    return gbs;
+}
+
+// the measured HBM read roofline: the faster of the two probes
+extern "C" double gemma_hbm_read_gbs(int device, size_t bytes, int iters) {
+    const double a = gemma_hbm_read_probe(device, bytes, iters, 0), b = gemma_hbm_read_probe(device, bytes, iters, 1);
+    return a > b ? a : b;
+}

@@ -1,4 +1,4 @@
-// engine_ext.h — internal interface between the device-resident Gemma engine (engine.cpp) and the
+// engine_ext.h — internal interface between the device-resident Gemma engine (engine.cpp, engine_prefill.cpp) and the
 // ggml graph executor (ggml_api.cpp): an engine built over the host weights a ggml graph references,
 // whose per-layer KV caches are the executor's device mirrors of the graph's cache tensors.
 #pragma once

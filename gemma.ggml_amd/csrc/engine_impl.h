@@ -1,0 +1,282 @@
+// engine_impl.h — the device-resident engine's state and what its translation units share
+// (internal: included only by engine.cpp, engine_decode.cpp, engine_prefill.cpp, engine_diag.cpp).
+//   engine.cpp          lifecycle: create / free / begin / step / tensor, TP and p2p set-up
+//   engine_decode.cpp   one decode token: enqueue_step (+ K-quant), the persistent launch's
+//                       arguments, the all-gathers
+//   engine_prefill.cpp  batched prefill and the ggml executor's entry points
+//   engine_diag.cpp     timing, tuning, plan and option setters, stamps, taps, per-op test hooks
+#pragma once
+
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <rccl/rccl.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/gemma_hpc.h"
+#include "engine_ext.h"
+#include "kernels.h"
+
+using namespace ghip;
+using ghip::host_weights;
+
+struct layer_dev {
+    float *attn_norm = nullptr, *ffn_norm = nullptr;
+    tiled_mat qkv, o, gate, up, down;
+};
+
+// K-quant layer matrices (wtype GGML_TYPE_Q4_K: llama.cpp's Q4_K_M files): raw ggml rows, each
+// matrix Q4_K or Q6_K, multiplied by the K-quant matvec against the Q8_K INIT of its input
+struct kq_mat {
+    uint8_t *w = nullptr;
+    int type = 0;
+    int64_t rows = 0, K = 0, rb = 0;
+    bool tiled = false;  // lane-contiguous layout (launch_kq_retile), else ggml rows
+};
+struct kq_layer {
+    kq_mat q, k, v, o, gate, up, down;
+    bool qk_fused = false;  // q and k share one allocation (k's rows right after q's, same type)
+};
+
+// matrix classes of a decode step and their launch plan (K split, row-tile groups per workgroup)
+enum { MC_QKV = 0, MC_O, MC_GU, MC_DOWN, MC_LOGITS, MC_N };
+struct launch_plan {
+    int ks = 1, rpw = 1;
+    int img = 0;  // attn-out / down: read the producer-written Q8_0 image (PRO_IMG) instead of f32
+};
+
+struct gemma_engine {
+    gemma_hip_config cfg{};
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int qw = 0, kvw = 0, qkv_rows = 0;
+    // ---- weights ----
+    tiled_mat embd;
+    std::vector<layer_dev> layers;
+    float *out_norm = nullptr;
+    // token_embd / tied output in Q6_K (llama.cpp's Q4_0 / Q8_0 Gemma files): raw ggml rows, the
+    // embedding dequantized by k_embed_q6K and the logits through the K-quant matvec
+    int out_type = 0;
+    uint8_t *embd_q6k = nullptr;
+    bool embd_tiled = false;  // embd_q6k in the lane-contiguous layout (launch_kq_retile)
+    int64_t embd_row_bytes = 0;
+    uint8_t *xq8k = nullptr;  // Q8_K rows of rms_norm(x)*out_norm (decode: 1 row; prefill: T rows)
+    int64_t xq8k_rows = 0;
+    // ---- K-quant layers ----
+    bool kq = false;              // K-quant layers (kql) instead of the tiled Q4_0 / Q8_0 ones
+    std::vector<kq_layer> kql;
+    uint8_t *kq_x = nullptr;      // Q8_K INIT of the current matvec input (max(E, qw, F) / 256 blocks)
+    // hand-off mode (kq_fuse == 2): the Q8_K images each producer writes for its consumer, one
+    // buffer per hand-off so no launch overwrites the image it reads (kq_x = the attn-norm image,
+    // kq_xa = attention output, kq_xf = ffn-norm image, kq_xh = gelu(gate)*up); counters zeroed once
+    uint8_t *kq_xa = nullptr, *kq_xf = nullptr, *kq_xh = nullptr;
+    unsigned *kq_cnt = nullptr;
+    int kq_cnt_cap = 0;
+    float *kq_g = nullptr;        // ffn gate output (n_ff), consumed by the up matvec's gelu*mul epilogue
+    // K-quant step options (gemma_engine_set_option): kq_fuse = the plan for where ggml's Q8_K INIT
+    // runs (enqueue_step_kq, 0..6); kq_dual: gate+up in one launch; kq_pair: q|k and v in one launch
+    int kq_fuse = 5, kq_dual = 1, kq_pair = 1;
+    int kq_abl = 0;  // option "kq_abl": hand-off timing ablation (kq_args::q8_abl; wrong results)
+    // ---- TP + p2p ----
+    // row-split tensor parallelism: this rank's contiguous row range of every
+    // matrix; activations are full vectors, each matvec writes its shard in place and an in-place
+    // RCCL all-gather completes them
+    int tp_n = 1, tp_rank = 0;
+    int n_virtual = 1;  // > 1: all tp_n ranks' shards in this one engine (single-GPU parity mode, no RCCL)
+    bool tp_n_keys = false;  // logits through per-rank argmax keys (row split: virtual ranks or an RCCL comm)
+    ncclComm_t comm = nullptr;
+    int64_t sh_qkv = 0, sh_e = 0, sh_ff = 0, sh_v = 0;  // rows per rank (qkv, n_embd, n_ff, n_vocab)
+    // GEMMA_TP_REP_ATTN: Wq|Wk|Wv and Wo whole on every rank (sh_qkv = all rows, sh_o = n_embd), so
+    // a layer needs 2 all-gathers (h, x) instead of 4; the FFN and the output head stay row-split
+    bool rep_attn = false;
+    int64_t sh_o = 0;
+    // GEMMA_TP_P2P: the all-gathers by peer-to-peer pushes (p2p.hip) instead of RCCL: an uncached
+    // arena of inboxes + flags per rank, shared by IPC handles (gemma_engine_p2p_handle / _open)
+    bool p2p = false, p2p_ready = false;
+    uint8_t *p2p_arena = nullptr;
+    uint8_t *p2p_peer[P2P_MAX_RANKS] = {};
+    unsigned *p2p_seq = nullptr, *p2p_err = nullptr;
+    int64_t ib_qkv = 0, ib_sa = 0, ib_h = 0, ib_x = 0, ib_hact = 0, ib_hda = 0, ib_logits = 0, ib_keys = 0, ib_flags = 0;
+    unsigned long long *rank_keys = nullptr;           // [tp_n] one argmax key per rank
+    // ---- attention ----
+    uint16_t *kc = nullptr, *vc = nullptr;  // [L][ctx][kvw], [L][kvw][ctx]
+    std::vector<uint16_t *> kc_ext, vc_ext;  // external per-layer caches (ggml executor), else empty
+    int att_mode = ATTN_PER_HEAD;
+    attn_geom ag;                           // split-attention geometry and its scratch
+    float *att_sbuf = nullptr;
+    int *att_sync = nullptr;                // hand-off counters [Hkv][2] + sticky error word
+    uint16_t *exp_tab = nullptr, *gelu_tab = nullptr;
+    float *rope_cos = nullptr, *rope_sin = nullptr, *rope_cur = nullptr;
+    // per-head decode attention: workgroups per head (each the KQ/softmax, 1/att_dsplit of the KQV
+    // dims; option "att_dsplit"). Same box, decode tok/s: 1 / 2 / 4 -> 1,443 / 1,458 / 1,458; after the
+    // batched K/V step loads 2 / 4 / 8 -> 1,470-1,482 / 1,491 / 1,355-1,369 (scripts/env_ab.sh)
+    int att_dsplit = 4;
+    int att_mx = 1;  // option "att_mx": exact prefill attention on the f32 matrix cores (0: the row form)
+    // ---- activations ----
+    float *x = nullptr, *qkv = nullptr, *attn = nullptr, *sa = nullptr, *h = nullptr, *logits = nullptr;
+    // Q8_0 activation images written by their producers (attention, gate/up) for attn-out and down
+    // (DESIGN.md §Activation image); null when a shape does not allow them (then PRO_F32)
+    uint32_t *att_act = nullptr, *h_act = nullptr;
+    float *att_da = nullptr, *h_da = nullptr;
+    // ---- persistent launch ----
+    // the whole token's layers as ONE persistent launch (token.hip) when the shapes
+    // allow it (GHIP_PERSIST=1 or gemma_engine_set_persist(e, 1)); off by default until it beats
+    // the per-layer launches on the bench
+    int persist = 0;
+    std::string persist_why;           // why the persistent launch cannot run ("" = it can)
+    tok_args tok{};                    // its arguments (host copy; tok_dev: the copy the kernel reads)
+    tok_args *tok_dev = nullptr;
+    tok_layer *tok_tab = nullptr;      // per-layer pointer table
+    unsigned long long *tok_gran = nullptr;  // hand-off granules (zeroed once; tags carry the epoch)
+    unsigned *epoch = nullptr;         // bumped by k_advance / k_set_position once per token
+    int *tok_err = nullptr;            // sticky hand-off timeout [flag, site, layer]
+    unsigned persist_timeout = 2000000u;  // per-wait bound of the launch (100 MHz ticks; tests shorten it)
+    // ---- fused launches ----
+    // fused layer front (layer_front.hip): qkv -> attention -> attn-out in one launch per layer;
+    // hand-off counters [n_layer][16] zeroed once per token (memset node), sticky timeout word
+    int fuse_front = 0;  // measured: 727 vs 672 us/token (the in-launch hand-offs cost as much as the
+                         // launch boundaries they replace; DESIGN.md perf log) — kept as an option
+    unsigned *front_cnt = nullptr;
+    int *front_err = nullptr;
+    // attention + attn-out in one launch (layer_front.hip k_attn_o): on / off, its per-layer hand-off
+    // counters (8 replicas + done, 128 B apart; the launch leaves them zero) and sticky error words
+    int att_o = 0;
+    unsigned *ao_cnt = nullptr;
+    int *ao_err = nullptr;
+    // ---- decode state ----
+    unsigned long long *key = nullptr;
+    int *pos = nullptr, *token = nullptr, *hist = nullptr, *nfix = nullptr;
+    int n_prompt = 0;
+    int host_pos = 0;  // mirror of *pos (steps are deterministic)
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t graph_exec = nullptr;
+    // flow control of gemma_engine_step: an event every FC_EVERY graph launches, FC_SLOTS of them
+    hipEvent_t fc_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    float *ext_stage = nullptr;               // pinned logits row (ggml executor path)
+    int *ext_err = nullptr;                   // pinned copy of the persistent launch's sticky word (same path)
+    // ---- plan ----
+    // launch geometry: one plan per matrix class (defaults below; gemma_engine_tune measures)
+    int ks_small = KS_RR, ks_down = KS_RR;  // round-pipelined form where the shape allows (pick_ks falls back)
+    int grid_big = 2048;
+    int grid_big_cap = 2048;  // workgroups the argmax key buffer holds
+    launch_plan plan[MC_N];
+    // ---- prefill ----
+    // prefill buffers (lazily sized for the prompt length)
+    struct {
+        int T = 0;
+        int64_t ldq = 0, ldd = 0;
+        float *X = nullptr, *SA = nullptr, *QKV = nullptr, *ATT = nullptr, *G = nullptr, *U = nullptr, *LG = nullptr;
+        float *DA = nullptr;
+        uint16_t *Q16 = nullptr;
+        int8_t *XQ = nullptr;
+        uint16_t *XH = nullptr;  // f16 image of the quantized activations (exact GEMM operand)
+        uint16_t *XM = nullptr;  // K-quant prefill: the Q4_K mins operand of the Q8_K image (k_q8k_expand)
+        void *keys = nullptr;
+    } pf;
+    // ---- diagnostics ----
+    int time_hot = 0, ablate = 0;  // gemma_engine_time diagnostics: one layer's matrix repeated; ablations
+    float *dbg = nullptr;  // per-layer taps [L][qkv_rows + qw + E] (debug steps only)
+    unsigned long long *stamp = nullptr;  // phase stamps of one layer's kernels (diagnostic steps only)
+    int stamp_layer = -1;
+};
+
+// ---- small accessors ---------------------------------------------------------------------------
+static constexpr size_t kStampRegion = 4096 * 16;  // u64 per kernel: <= 4096 workgroups x 16 stamps
+static inline unsigned long long *stamp_region(gemma_engine *e, int il, int k) {
+    return (e->stamp && il == e->stamp_layer) ? e->stamp + (size_t)k * kStampRegion : nullptr;
+}
+
+// layer il's shards of (virtual) rank slot vr, and the rank that slot stands for
+static inline layer_dev &layer_of(gemma_engine *e, int il, int vr) { return e->layers[(size_t)il * e->n_virtual + vr]; }
+static inline int rank_of(const gemma_engine *e, int vr) { return e->n_virtual > 1 ? vr : e->tp_rank; }
+// layer il's caches: K [ctx][kvw], V [kvw][ctx]
+static inline uint16_t *kc_of(const gemma_engine *e, int il) {
+    return e->kc_ext.empty() ? e->kc + (size_t)il * e->cfg.n_ctx * e->kvw : e->kc_ext[il];
+}
+static inline uint16_t *vc_of(const gemma_engine *e, int il) {
+    return e->vc_ext.empty() ? e->vc + (size_t)il * e->cfg.n_ctx * e->kvw : e->vc_ext[il];
+}
+
+// attention can hand attn-out the Q8_0 image of its output (per-head form; split form with 32-dim slices)
+static inline bool att_img_ok(const gemma_engine *e) { return e->att_mode == ATTN_PER_HEAD || e->ag.img; }
+
+// workgroups of a matvec launch: a KS = 1 workgroup runs 4 waves on 4 row tiles at a time, a
+// KS > 1 workgroup its KS waves on one row tile; each workgroup repeats for rpw row-tile groups
+static inline int mv_grid(const gemma_engine *e, int cls, int64_t n_rt) {
+    const launch_plan &p = e->plan[cls];
+    const int64_t per = (p.ks == 1 || cls == MC_GU ? 4 : 1) * (int64_t)std::max(p.rpw, 1);  // gate/up ks 2: 4 row tiles
+    int64_t g = (n_rt + per - 1) / per;
+    if (cls == MC_LOGITS || cls == MC_GU) g = std::min<int64_t>(g, e->grid_big);  // key slots
+    return (int)std::max<int64_t>(g, 1);
+}
+
+// largest power-of-two K split <= target that divides the block-tile count and whose LDS image
+// (activation + carry stash) fits the 160 KiB of a CU (Gemma-7B's down, K = 24576, steps to KS 1)
+static inline int pick_ks(int wtype, int64_t n_bt, int target) {
+    if (target == KS_RR) return matvec_rr_supported(wtype, n_bt) ? KS_RR : pick_ks(wtype, n_bt, 8);
+    int ks = target;
+    while (ks > 1 && (n_bt % ks || matvec_lds_bytes(wtype, ks, n_bt, n_bt / ks) > 160 * 1024)) ks >>= 1;
+    return ks;
+}
+
+// the persistent token launch runs this engine's decode steps
+static inline bool persist_on(const gemma_engine *e) {
+    return e->persist && e->persist_why.empty() && !e->dbg && !e->stamp && e->att_mode == ATTN_PER_HEAD &&
+           !e->fuse_front;
+}
+
+// rows [r0, r0+n) of a tiled matrix (r0, n multiples of 8) as its own tiled_mat view
+static inline tiled_mat sub_rows(const tiled_mat &m, int64_t r0, int64_t n) {
+    tiled_mat v = m;
+    const int sb = m.type == T_Q4_0 ? 16 : 8;
+    v.rows = n;
+    v.n_rt = (n + 7) / 8;
+    v.qs = m.qs + (r0 / 8) * m.n_bt * 1024;
+    v.sc = m.sc + (r0 / 8) * m.n_bt * 8 * sb;
+    return v;
+}
+
+// ---- argument builders -------------------------------------------------------------------------
+// the decode attention of layer il: everything but the output images, dsplit and the stamps
+static inline attn_args attn_of(gemma_engine *e, int il) {
+    const gemma_hip_config &c = e->cfg;
+    attn_args t;
+    t.qkv = e->qkv;
+    t.kc = kc_of(e, il);
+    t.vc = vc_of(e, il);
+    t.rope_cos = e->rope_cos; t.rope_sin = e->rope_sin; t.rope_cur = e->rope_cur; t.exp_tab = e->exp_tab;
+    t.pos = e->pos; t.out = e->attn;
+    t.H = c.n_head; t.Hkv = c.n_head_kv; t.hd = c.head_dim; t.ctx = c.n_ctx;
+    t.q_scale = 1.0f / sqrtf((float)c.head_dim);
+    t.mode = e->att_mode;
+    t.nwg = e->ag.nwg; t.sbuf = e->att_sbuf; t.sync = e->att_sync; t.err = e->att_sync + e->ag.sync_ints;
+    return t;
+}
+
+// the RoPE tables and the current-position row k_advance / k_set_position publish
+static inline rope_row rope_of(const gemma_engine *e) {
+    rope_row rr;
+    rr.cos = e->rope_cos; rr.sin = e->rope_sin; rr.cur = e->rope_cur; rr.half = e->cfg.head_dim / 2; rr.ctx = e->cfg.n_ctx;
+    rr.epoch = e->epoch;
+    return rr;
+}
+
+// ---- functions that cross translation units (internal: not part of the library's surface) -------
+#pragma GCC visibility push(hidden)
+// engine.cpp
+int ensure_graph(gemma_engine *e);
+void drop_graph(gemma_engine *e);
+// engine_decode.cpp
+int enqueue_step(gemma_engine *e);
+int tok_prepare(gemma_engine *e);
+int persist_report(gemma_engine *e, const int *w);
+int persist_check(gemma_engine *e);
+int att_o_check(gemma_engine *e);
+int tp_gather(gemma_engine *e, float *full, int64_t cnt);
+// ncols Q8_K columns x ((n_embd / 256) * 292 bytes apart) through the Q6_K tied output -> y [ncols][n_vocab]
+int enqueue_logits_q6k(gemma_engine *e, const uint8_t *x, int ncols, float *y);
+#pragma GCC visibility pop

@@ -413,7 +413,7 @@ int run_mul_mat(run_state &rs, ggml_tensor *node) {
     const char *x = dev_addr(rs, b);
     if (cols <= 4) {
         mv_args m;
-        m.qs = W->qs; m.sc = W->sc; m.rows = W->rows; m.n_rt = W->n_rt; m.n_bt = W->n_bt; m.nb = W->nb;
+        set_mat(m, *W);
         m.x = x; m.x_col_stride = (int64_t)b->nb[1];
         m.y = y; m.y_col_stride = a->ne[1];
         m.ncols = (int)cols;
@@ -432,7 +432,7 @@ int run_mul_mat(run_state &rs, ggml_tensor *node) {
     q.ldd = ldd;
     if (launch_quant_rows(QR_F32, q, (int)cols, e.stream)) return -1;
     gemm_args g;
-    g.qs = W->qs; g.sc = W->sc; g.rows = W->rows; g.n_rt = W->n_rt; g.n_bt = W->n_bt; g.nb = W->nb;
+    set_mat(g, *W);
     g.xq = q.q; g.xh = q.qh; g.ldq = ldq; g.da = q.da; g.ldd = ldd; g.T = cols; g.y = y; g.ldy = a->ne[1];
     return launch_gemm_exact(a->type, EPI_STORE, g, e.stream);
 }

@@ -7,6 +7,12 @@
 
 namespace ghip {
 
+// the tiled weight matrix (tiled_mat, common.h) of a launch: the six fields an mv_args, a gemm_args
+// or any other argument struct names it by
+template <typename A> inline void set_mat(A &a, const tiled_mat &m) {
+    a.qs = m.qs; a.sc = m.sc; a.rows = m.rows; a.n_rt = m.n_rt; a.n_bt = m.n_bt; a.nb = m.nb;
+}
+
 // ---- decode matvec (matvec.hip) ----------------------------------------------------------------
 // Prologue: how the activation column is turned into the LDS Q8_0 image.
 enum mv_pro : int {
