@@ -1,7 +1,8 @@
 // attn_mx.hip — the exact causal prefill attention on the f32 matrix cores.
 //
 // What it computes: rows i < T of the reference's prefill KQ -> soft_max_ext -> KQV
-// (src/gemma_model.cpp:454-497 with T tokens; mask -inf for j > i, scale 1.0), every dot product in
+// (src/gemma_model.cpp:454-497 with T tokens; mask -inf for j > i, scale 1.0; with p0 > 0 row i is
+// position p0 + i of a longer sequence whose first p0 K / V rows are in the caches), every dot product in
 // ggml's AVX/F16C vec_dot_f16 order: 32 fmaf chains per output — chain c = 8j + l
 // runs over elements 32s + c, s = 0, 1, ... — folded as ((c0+c16)+(c8+c24)) per l, then halves and
 // hadds.  The same arithmetic k_attn_rows runs with v_fma_mix, bit for bit.
@@ -78,7 +79,8 @@ __global__ void __launch_bounds__(MX_THREADS) k_attn_mx(attnp_args a) {
     const int kvw = a.Hkv * MX_HD;
     // this block's rows: m = p * G + g -> position i0 + p, head kvh * G + g
     const int i_last = min(i0 + P - 1, a.T - 1);
-    int L = 32 * ((i_last + 1) / 32 + 1);
+    const int s_last = a.p0 + i_last;  // its sequence position: the block's keys are 0 .. s_last
+    int L = 32 * ((s_last + 1) / 32 + 1);
     if (L > a.n_kv) L = a.n_kv;
     // S [16][LS], LS = L + 4: the 16 rows of an MFMA operand read sit 16 B apart in the banks
     const int LS = L + 4;
@@ -100,7 +102,7 @@ __global__ void __launch_bounds__(MX_THREADS) k_attn_mx(attnp_args a) {
         }
     }
     // ---- KQ: 16-position key tiles; wave w takes tiles w, w + 8, ... ----------------------------
-    const int n_keys = i_last + 1;  // positions past the block's last row are all masked
+    const int n_keys = s_last + 1;  // positions past the block's last row are all masked
     const int n_kt = (n_keys + 15) / 16;
     // this lane's 128 B of key row kt*16 + (lane & 15); the next tile's loads are issued before
     // the current tile's MFMAs
@@ -151,14 +153,15 @@ __global__ void __launch_bounds__(MX_THREADS) k_attn_mx(attnp_args a) {
             for (int j = lane; j < L; j += 64) Pr[j] = 0;
             continue;
         }
-        int n_kv = 32 * ((ip + 1) / 32 + 1);
+        const int sp = a.p0 + ip;  // the row's sequence position: keys j > sp are masked
+        int n_kv = 32 * ((sp + 1) / 32 + 1);
         if (n_kv > a.n_kv) n_kv = a.n_kv;
         float mx = -INFINITY;
-        for (int j = lane; j < n_kv; j += 64) mx = fmaxf(mx, j > ip ? -INFINITY : Sr[j]);
+        for (int j = lane; j < n_kv; j += 64) mx = fmaxf(mx, j > sp ? -INFINITY : Sr[j]);
         mx = wave_max(mx);
         unsigned long long isum = 0;
         for (int j = lane; j < n_kv; j += 64) {
-            const float w = j > ip ? -INFINITY : Sr[j];
+            const float w = j > sp ? -INFINITY : Sr[j];
             const float e = w != -INFINITY ? h2f(exp_f16_of(f2h(w - mx))) : 0.0f;
             isum += (unsigned long long)(uint32_t)(e * 16777216.0f);  // e * 2^24 <= 2^24: exact
         }
@@ -171,7 +174,7 @@ __global__ void __launch_bounds__(MX_THREADS) k_attn_mx(attnp_args a) {
         // its iteration's read whatever type-based alias analysis concludes
         for (int j = lane; j < L; j += 64) {
             float w = -INFINITY;
-            if (j <= ip && j < n_kv) w = Sr[j];
+            if (j <= sp && j < n_kv) w = Sr[j];
             asm volatile("" ::: "memory");
             const float e = w != -INFINITY ? h2f(exp_f16_of(f2h(w - mx))) : 0.0f;
             Pr[j] = (uint16_t)f2h(e * inv);
@@ -227,8 +230,8 @@ const char *attn_mx_unsupported(const attnp_args &a) {
     if (a.Hkv <= 0 || a.H % a.Hkv) return "heads";
     const int G = a.H / a.Hkv;
     if (G > 16 || 16 % G) return "query heads per kv head must divide 16";
-    if (a.ctx % 32 || a.n_kv % 32 || a.n_kv > a.ctx || a.T <= 0 || a.T > a.n_kv) return "context";
-    int L = 32 * (a.T / 32 + 1);  // the last row's padded n_kv
+    if (a.ctx % 32 || a.n_kv % 32 || a.n_kv > a.ctx || a.T <= 0 || a.p0 < 0 || a.p0 + a.T > a.n_kv) return "context";
+    int L = 32 * ((a.p0 + a.T) / 32 + 1);  // the last row's padded n_kv
     if (L > a.n_kv) L = a.n_kv;
     if ((size_t)16 * (L + 4) * 4 > 160 * 1024) return "scores of 16 rows exceed the LDS (n_kv > 2556)";
     return nullptr;
@@ -240,7 +243,7 @@ int launch_attn_mx(const attnp_args &a, hipStream_t s) {
         return -1;
     }
     const int G = a.H / a.Hkv, P = 16 / G;
-    int L = 32 * (a.T / 32 + 1);
+    int L = 32 * ((a.p0 + a.T) / 32 + 1);
     if (L > a.n_kv) L = a.n_kv;
     const size_t lds = (size_t)16 * (L + 4) * 4;
     if (allow_full_lds((const void *)k_attn_mx, LDS_SLOT_ATTN_MX)) return -1;

@@ -824,6 +824,46 @@ extern "C" int gemma_engine_begin(gemma_engine *e, const int32_t *prompt, int n_
     return 0;
 }
 
+// Continue or rewind: positions [0, keep) stay, everything from `keep` on is dropped and `tokens`
+// become the given-but-unprocessed positions keep .. keep+n-1.  The device state afterwards is byte
+// for byte what gemma_engine_begin with the same sequence plus `keep` processed positions leaves:
+// cache rows / columns >= keep and hist past the tokens zero, *pos, the RoPE row and *n_fixed
+// published as k_set_position does.  Every buffer keeps its address, so the captured decode graph
+// stays valid.
+extern "C" int gemma_engine_extend(gemma_engine *e, int keep, const int32_t *tokens, int n) {
+    set_error("");
+    const gemma_hip_config &c = e->cfg;
+    if (keep < 0 || keep > e->host_pos) {
+        set_error("gemma_engine_extend: keep = " + std::to_string(keep) + " outside [0, pos = " + std::to_string(e->host_pos) + "]");
+        return -1;
+    }
+    if (n <= 0 || !tokens || (int64_t)keep + n >= c.n_ctx) {
+        set_error("gemma_engine_extend: needs n >= 1 tokens with keep + n < n_ctx");
+        return -1;
+    }
+    for (int i = 0; i < n; ++i)  // the embedding kernels index token_embd rows unchecked
+        if (tokens[i] < 0 || tokens[i] >= c.n_vocab) {
+            set_error("gemma_engine_extend: token id " + std::to_string(tokens[i]) + " out of range [0, n_vocab)");
+            return -1;
+        }
+    (void)hipSetDevice(e->device);
+    hipStream_t s = e->stream;
+    const size_t ctx = (size_t)c.n_ctx, drop = ctx - (size_t)keep;
+    for (int il = 0; il < c.n_layer; ++il) {  // K [ctx][kvw]: rows >= keep; V [kvw][ctx]: columns >= keep
+        GHIP_CHECK(hipMemsetAsync(kc_of(e, il) + (size_t)keep * e->kvw, 0, drop * e->kvw * 2, s));
+        GHIP_CHECK(hipMemset2DAsync(vc_of(e, il) + keep, ctx * 2, 0, drop * 2, (size_t)e->kvw, s));
+    }
+    GHIP_CHECK(hipMemsetAsync(e->hist + keep, 0, (ctx + 1 - (size_t)keep) * 4, s));
+    GHIP_CHECK(hipMemcpyAsync(e->hist + keep, tokens, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    GHIP_CHECK(hipMemsetAsync(e->key, 0, (size_t)e->grid_big * 8, s));
+    // *pos = keep, its RoPE row with the position word, *n_fixed = keep + n, the epoch bump
+    if (launch_set_position(tokens[0], keep, e->pos, e->hist, e->nfix, keep + n, rope_of(e), s)) return -1;
+    GHIP_CHECK(hipStreamSynchronize(s));
+    e->n_prompt = keep + n;
+    e->host_pos = keep;
+    return 0;
+}
+
 // the decode step captured once in a hipGraph (after a first eager step has set the kernels' LDS attributes)
 int ensure_graph(gemma_engine *e) {
     if (e->graph_exec) return 0;

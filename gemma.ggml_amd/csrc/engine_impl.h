@@ -1,6 +1,6 @@
 // engine_impl.h — the device-resident engine's state and what its translation units share
 // (internal: included only by engine.cpp, engine_decode.cpp, engine_prefill.cpp, engine_diag.cpp).
-//   engine.cpp          lifecycle: create / free / begin / step / tensor, TP and p2p set-up
+//   engine.cpp          lifecycle: create / free / begin / extend / step / tensor, TP and p2p set-up
 //   engine_decode.cpp   one decode token: enqueue_step (+ K-quant), the persistent launch's
 //                       arguments, the all-gathers
 //   engine_prefill.cpp  batched prefill and the ggml executor's entry points
@@ -150,8 +150,8 @@ struct gemma_engine {
     // ---- decode state ----
     unsigned long long *key = nullptr;
     int *pos = nullptr, *token = nullptr, *hist = nullptr, *nfix = nullptr;
-    int n_prompt = 0;
-    int host_pos = 0;  // mirror of *pos (steps are deterministic)
+    int n_prompt = 0;  // host-given tokens: positions [0, n_prompt) of hist (begin / extend; *nfix mirrors it)
+    int host_pos = 0;  // mirror of *pos (steps are deterministic): processed positions, K / V rows in the caches
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     // flow control of gemma_engine_step: an event every FC_EVERY graph launches, FC_SLOTS of them

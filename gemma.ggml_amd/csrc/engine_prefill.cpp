@@ -5,7 +5,7 @@
 
 #include "engine_impl.h"
 
-// prefill buffers (lazily sized for the prompt length)
+// prefill buffers (lazily sized for the largest pass seen: the prompt, or a gemma_engine_prefill_next chunk)
 static int prefill_alloc(gemma_engine *e, int T) {
     auto &p = e->pf;
     if (p.T >= T) return 0;
@@ -34,7 +34,7 @@ static int prefill_alloc(gemma_engine *e, int T) {
     return 0;
 }
 
-static int enqueue_prefill_kq(gemma_engine *e, int T);
+static int enqueue_prefill_kq(gemma_engine *e, int T, int p0);
 
 // the K-quant prefill's MFMA GEMM (prefill_kq.hip) for T prompt rows (kq_gemm_min: default 8)
 static bool kq_prefill_mfma(int T) { return T >= kq_gemm_min(); }
@@ -59,27 +59,31 @@ static int launch_attn_exact(const attnp_args &at, bool mx, hipStream_t s) {
     return mx ? launch_attn_mx(at, s) : launch_attn_rows(at, s);
 }
 
-// layer il of a T-row prefill, from pf.QKV: RoPE + K/V store into the layer caches, then the causal
-// attention into pf.ATT (exact: the form *mx_form, resolved at the first layer; else f16 MFMA)
-static int prefill_attention(gemma_engine *e, int il, int T, bool exact, int *mx_form) {
+// layer il of a T-row prefill of positions p0 .. p0+T-1, from pf.QKV: RoPE + K/V store into the
+// layer caches (which hold the positions before p0), then the causal attention into pf.ATT (exact:
+// the form *mx_form, resolved at the first layer; else f16 MFMA)
+static int prefill_attention(gemma_engine *e, int il, int T, int p0, bool exact, int *mx_form) {
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
     auto &p = e->pf;
     ropekv_args r;
     r.qkv = p.QKV; r.ldqkv = e->qkv_rows; r.rope_cos = e->rope_cos; r.rope_sin = e->rope_sin; r.q16 = p.Q16;
     r.kc = kc_of(e, il); r.vc = vc_of(e, il);
-    r.H = c.n_head; r.Hkv = c.n_head_kv; r.hd = c.head_dim; r.ctx = c.n_ctx; r.p0 = 0;
+    r.H = c.n_head; r.Hkv = c.n_head_kv; r.hd = c.head_dim; r.ctx = c.n_ctx; r.p0 = p0;
     r.q_scale = 1.0f / sqrtf((float)c.head_dim);
     if (launch_rope_kv_prefill(r, T, s)) return -1;
     attnp_args at;
     at.q16 = p.Q16; at.kc = r.kc; at.vc = r.vc; at.out = p.ATT; at.ldo = e->qw;
-    at.T = T; at.H = c.n_head; at.Hkv = c.n_head_kv; at.hd = c.head_dim; at.ctx = c.n_ctx;
-    at.n_kv = std::min(32 * (T / 32 + 1), c.n_ctx);  // src/gemma_model.cpp:429 with n_total = T
+    at.T = T; at.H = c.n_head; at.Hkv = c.n_head_kv; at.hd = c.head_dim; at.ctx = c.n_ctx; at.p0 = p0;
+    at.n_kv = std::min(32 * ((p0 + T) / 32 + 1), c.n_ctx);  // src/gemma_model.cpp:429 with n_total = p0 + T
     if (*mx_form < 0) *mx_form = att_mx_form(e, at);
     return exact ? launch_attn_exact(at, *mx_form == 1, s) : launch_attn_prefill(at, s);
 }
 
-static int enqueue_prefill(gemma_engine *e, int T, bool exact, float *taps = nullptr) {
+// One batched pass over hist[p0 .. p0+T): the rows are sequence positions p0 .. p0+T-1, the caches
+// hold the positions before p0 (p0 = 0: the whole-prompt prefill).  Every scratch buffer is indexed
+// by the row t of the pass; only the token reads, RoPE, the cache stores and the attention know p0.
+static int enqueue_prefill(gemma_engine *e, int T, int p0, bool exact, float *taps = nullptr) {
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
     int mx_form = -1;  // the exact attention's form, resolved at the first layer
@@ -99,7 +103,7 @@ static int enqueue_prefill(gemma_engine *e, int T, bool exact, float *taps = nul
         a.q = (!exact || i8img) ? p.XQ : nullptr; a.qh = (exact && !i8img) ? p.XH : nullptr; a.ldq = p.ldq; a.da = p.DA; a.ldd = p.ldd;
         a.gelu_tab = e->gelu_tab; a.gelu_clamp = c.gelu_clamp;
         if (mode == QR_EMBED_NORM) {
-            a.tokens = e->hist; a.emb_qs = e->embd.qs; a.emb_sc = e->embd.sc; a.emb_type = wt;
+            a.tokens = e->hist + p0; a.emb_qs = e->embd.qs; a.emb_sc = e->embd.sc; a.emb_type = wt;
             a.emb_n_bt = e->embd.n_bt; a.emb_scale = sqrtf((float)E); a.emb_out = p.X; a.ldx = E;
         }
         return launch_quant_rows(mode, a, T, s);
@@ -110,15 +114,15 @@ static int enqueue_prefill(gemma_engine *e, int T, bool exact, float *taps = nul
             set_error("gemma_engine_prefill_fast: K-quant layer engines have the exact batched prefill only");
             return -1;
         }
-        if (enqueue_prefill_kq(e, T)) return -1;
-    } else if (q6 && launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, e->hist, nullptr, T, (int)E, sqrtf((float)E), p.X, s, e->embd_tiled)) {
+        if (enqueue_prefill_kq(e, T, p0)) return -1;
+    } else if (q6 && launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, e->hist + p0, nullptr, T, (int)E, sqrtf((float)E), p.X, s, e->embd_tiled)) {
         return -1;
     }
     for (int il = 0; il < (e->kq ? 0 : c.n_layer); ++il) {
         layer_dev &L = e->layers[il];
         if (quant(il == 0 && !q6 ? QR_EMBED_NORM : QR_NORM, p.X, nullptr, E, L.attn_norm)) return -1;
         if (gemm(L.qkv, EPI_STORE, nullptr, p.QKV, e->qkv_rows)) return -1;
-        if (prefill_attention(e, il, T, exact, &mx_form)) return -1;
+        if (prefill_attention(e, il, T, p0, exact, &mx_form)) return -1;
         if (quant(QR_F32, p.ATT, nullptr, e->qw, nullptr)) return -1;
         if (gemm(L.o, EPI_ADD, p.X, p.SA, E)) return -1;
         if (quant(QR_NORM, p.SA, nullptr, E, L.ffn_norm)) return -1;
@@ -150,9 +154,10 @@ static int enqueue_prefill(gemma_engine *e, int T, bool exact, float *taps = nul
         if (quant(QR_NORM, p.X, nullptr, E, e->out_norm)) return -1;
         if (gemm(e->embd, EPI_STORE, nullptr, p.LG, c.n_vocab)) return -1;
     }
-    // greedy token from the last row; position T-1 -> T, token appended at hist[T]
+    // greedy token from the last row; position p0+T-1 -> p0+T, token appended at hist[p0+T] unless
+    // that is still a given token (k_advance's p >= n_fixed guard: a pass that ends mid-prompt)
     if (launch_row_argmax(p.LG + (size_t)(T - 1) * c.n_vocab, c.n_vocab, (unsigned long long *)p.keys, 256, s)) return -1;
-    const int last = T - 1;
+    const int last = p0 + T - 1;
     GHIP_CHECK(hipMemcpyAsync(e->pos, &last, 4, hipMemcpyHostToDevice, s));
     return launch_advance((const unsigned long long *)p.keys, 256, e->token, e->pos, e->hist, c.n_ctx, e->nfix, rope_of(e), s);
 }
@@ -163,7 +168,7 @@ static int enqueue_prefill(gemma_engine *e, int T, bool exact, float *taps = nul
 // column's Q8_K INIT — every K-quant launch covers all T columns (grid.y) — and the exact per-row
 // attention of the Q4_0 prefill (k_rope_kv_prefill + k_attn_rows).  Bit-identical to the token
 // loop and to the CPU path: no operation depends on the batching.
-static int enqueue_prefill_kq(gemma_engine *e, int T) {
+static int enqueue_prefill_kq(gemma_engine *e, int T, int p0) {
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
     int mx_form = -1;  // the exact attention's form, resolved at the first layer
@@ -193,7 +198,7 @@ static int enqueue_prefill_kq(gemma_engine *e, int T) {
         if (up) k.w2 = up->w;
         return launch_matvec_kq(W.type, k, s);
     };
-    if (launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, e->hist, nullptr, T, (int)E, sqrtf((float)E), p.X, s, e->embd_tiled)) return -1;
+    if (launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, e->hist + p0, nullptr, T, (int)E, sqrtf((float)E), p.X, s, e->embd_tiled)) return -1;
     for (int il = 0; il < c.n_layer; ++il) {
         const layer_dev &L = e->layers[il];
         const kq_layer &K = e->kql[il];
@@ -208,7 +213,7 @@ static int enqueue_prefill_kq(gemma_engine *e, int T) {
             return -1;
         }
         if (mv(K.v, p.QKV + e->qw + e->kvw, ldqkv, nullptr, nullptr, nullptr)) return -1;
-        if (prefill_attention(e, il, T, true, &mx_form)) return -1;
+        if (prefill_attention(e, il, T, p0, true, &mx_form)) return -1;
         if (launch_quant_q8_K(p.ATT, e->qw, e->qw, T, img, ldk, s) || expand(e->qw)) return -1;
         if (mv(K.o, p.SA, E, p.X, nullptr, nullptr)) return -1;  // + inpL
         if (launch_norm_q8K(p.SA, E, L.ffn_norm, (int)E, c.eps, T, img, ldk, s) || expand(E)) return -1;
@@ -224,6 +229,23 @@ static int enqueue_prefill_kq(gemma_engine *e, int T) {
     return 0;
 }
 
+// one pass over rows [p0, p0+T) and its results: the last row's logits, all rows' [T][n_vocab], the
+// greedy token of the last row; the engine is left at position p0 + T
+static int prefill_pass(gemma_engine *e, int T, int p0, bool exact, float *logits_last, float *logits_all) {
+    const gemma_hip_config &c = e->cfg;
+    if (prefill_alloc(e, T)) return -1;
+    if (enqueue_prefill(e, T, p0, exact)) return -1;
+    GHIP_CHECK(hipStreamSynchronize(e->stream));
+    if (logits_last)
+        GHIP_CHECK(hipMemcpy(logits_last, e->pf.LG + (size_t)(T - 1) * c.n_vocab, (size_t)c.n_vocab * 4,
+                             hipMemcpyDeviceToHost));
+    if (logits_all) GHIP_CHECK(hipMemcpy(logits_all, e->pf.LG, (size_t)T * c.n_vocab * 4, hipMemcpyDeviceToHost));
+    int tok = -1;
+    GHIP_CHECK(hipMemcpy(&tok, e->token, 4, hipMemcpyDeviceToHost));
+    e->host_pos = p0 + T;
+    return tok;
+}
+
 // Batched prefill of the prompt given to gemma_engine_begin: all prompt
 // positions in one pass, KV cache filled, logits for every row as the reference computes them
 // (src/gemma_model.cpp:740); returns the greedy token and leaves the engine at position T, ready
@@ -232,7 +254,6 @@ static int enqueue_prefill_kq(gemma_engine *e, int T) {
 // it in fp32 summation order.
 static int prefill_run(gemma_engine *e, bool exact, float *logits_last, float *logits_all) {
     (void)hipSetDevice(e->device);
-    const gemma_hip_config &c = e->cfg;
     const int T = e->n_prompt;
     if (T <= 0 || e->host_pos != 0) {
         set_error("gemma_engine_prefill: call right after gemma_engine_begin");
@@ -242,17 +263,7 @@ static int prefill_run(gemma_engine *e, bool exact, float *logits_last, float *l
         set_error("gemma_engine_prefill: the MFMA prefill is single-GPU (row-split engines prefill token by token)");
         return -1;
     }
-    if (prefill_alloc(e, T)) return -1;
-    if (enqueue_prefill(e, T, exact)) return -1;
-    GHIP_CHECK(hipStreamSynchronize(e->stream));
-    if (logits_last)
-        GHIP_CHECK(hipMemcpy(logits_last, e->pf.LG + (size_t)(T - 1) * c.n_vocab, (size_t)c.n_vocab * 4,
-                             hipMemcpyDeviceToHost));
-    if (logits_all) GHIP_CHECK(hipMemcpy(logits_all, e->pf.LG, (size_t)T * c.n_vocab * 4, hipMemcpyDeviceToHost));
-    int tok = -1;
-    GHIP_CHECK(hipMemcpy(&tok, e->token, 4, hipMemcpyDeviceToHost));
-    e->host_pos = T;
-    return tok;
+    return prefill_pass(e, T, 0, exact, logits_last, logits_all);
 }
 
 extern "C" int gemma_engine_prefill(gemma_engine *e, float *logits_last, float *logits_all) {
@@ -263,6 +274,32 @@ extern "C" int gemma_engine_prefill(gemma_engine *e, float *logits_last, float *
 extern "C" int gemma_engine_prefill_fast(gemma_engine *e, float *logits_last, float *logits_all) {
     set_error("");
     return prefill_run(e, false, logits_last, logits_all);
+}
+
+// One batched pass over the next n given tokens, positions [pos, pos+n), against the caches of
+// [0, pos): enqueue_prefill with the row offset p0 = pos.  The given tokens are hist[.. n_prompt)
+// (gemma_engine_begin / gemma_engine_extend); steps and earlier passes may have consumed some.
+extern "C" int gemma_engine_prefill_next(gemma_engine *e, int n, int exact, float *logits_last, float *logits_all) {
+    set_error("");
+    (void)hipSetDevice(e->device);
+    const int p0 = e->host_pos, left = e->n_prompt - p0;
+    if (e->tp_n > 1 || e->comm) {
+        set_error("gemma_engine_prefill_next: the batched prefill is single-GPU (row-split engines prefill token by token)");
+        return -1;
+    }
+    if (left <= 0) {
+        set_error("gemma_engine_prefill_next: no given token is pending (gemma_engine_begin / gemma_engine_extend supply them)");
+        return -1;
+    }
+    if (n < 0 || n > left) {
+        set_error("gemma_engine_prefill_next: n = " + std::to_string(n) + " with " + std::to_string(left) + " given tokens pending");
+        return -1;
+    }
+    if (!exact && e->kq) {
+        set_error("gemma_engine_prefill_next: K-quant layer engines have the exact batched prefill only");
+        return -1;
+    }
+    return prefill_pass(e, n ? n : left, p0, exact != 0, logits_last, logits_all);
 }
 
 // diagnostics: the prefill (exact or MFMA) with the residual stream after every layer copied to host_taps
@@ -280,7 +317,7 @@ extern "C" int gemma_engine_prefill_taps(gemma_engine *e, float *host_taps, int 
     float *d = nullptr;
     const size_t n = (size_t)c.n_layer * T * c.n_embd;
     GHIP_CHECK(hipMalloc(&d, n * 4));
-    int r = enqueue_prefill(e, T, exact != 0, d);
+    int r = enqueue_prefill(e, T, 0, exact != 0, d);
     if (r == 0) GHIP_CHECK(hipStreamSynchronize(e->stream));
     if (r == 0) GHIP_CHECK(hipMemcpy(host_taps, d, n * 4, hipMemcpyDeviceToHost));
     (void)hipFree(d);

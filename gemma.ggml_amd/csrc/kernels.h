@@ -248,11 +248,14 @@ struct ropekv_args {  // RoPE q (-> f16, x q_scale) and k, store k/v of position
 };
 int launch_rope_kv_prefill(const ropekv_args &a, int T, hipStream_t s);
 struct attnp_args {  // causal attention of T prompt tokens against the layer caches
-    const uint16_t *q16 = nullptr;
+    const uint16_t *q16 = nullptr;  // [T][H][hd], row t of the launch
     const uint16_t *kc = nullptr, *vc = nullptr;
     float *out = nullptr;        // [T][ldo], head h at h*hd
     int64_t ldo = 0;
     int T = 0, H = 0, Hkv = 0, hd = 0, ctx = 0, n_kv = 0;
+    // row t is sequence position p0 + t and attends keys 0 .. p0 + t; the caches already hold the
+    // positions < p0 (a prefill continued mid-sequence); n_kv is the padded key count of row T - 1
+    int p0 = 0;
 };
 int launch_attn_prefill(const attnp_args &a, hipStream_t s);
 // exact rows: each prompt row with the decode attention's arithmetic (ops.hip)

@@ -525,7 +525,8 @@ __global__ void __launch_bounds__(AH_THREADS) k_attn_head(attn_args a) {
 // decode computation at position i: positions j > i are masked to -inf (e = 0), and the KQV terms
 // past the row's own padded n_kv multiply exact zeros, so each row runs k_attn_head's arithmetic
 // (vec_dot_f16 lane order via v_fma_mix, fp16 exp, integer-exact sum, (float)(1/sum)) over
-// n_kv(i) = 32*((i+1)/32+1) positions.  One 1024-thread workgroup per (row, kv head) serves the
+// n_kv(i) = 32*((i+1)/32+1) positions (row i of a launch with p0 > 0 is position p0 + i; the caches
+// hold the positions before p0).  One 1024-thread workgroup per (row, kv head) serves the
 // G <= 8 query heads of that kv head: quad q -> KQ position q (+ 256 per pass) and KQV dim q, each
 // for all G heads, so every K / V row is loaded once per row and 8 steps share one round trip
 // (the head-major mapping of round 1 paid a round trip per 256/G positions).  Rows are issued
@@ -549,7 +550,8 @@ __global__ void __launch_bounds__(AR_THREADS) k_attn_rows(attnp_args a) {
     uint16_t *P16 = AR_ALIAS ? (uint16_t *)S : (uint16_t *)(S + (size_t)G * nkp);
     const int p16s = AR_ALIAS ? 2 * nkp : nkp;     // P16 row stride (halfs)
     uint16_t *Q16 = (uint16_t *)(S + (size_t)G * nkp) + (AR_ALIAS ? 0 : (size_t)G * nkp);  // [G][hd]
-    int n_kv = 32 * ((i + 1) / 32 + 1);
+    const int ip = a.p0 + i;  // the row's sequence position (q16 / out stay indexed by i)
+    int n_kv = 32 * ((ip + 1) / 32 + 1);
     if (n_kv > nkp) n_kv = nkp;
     for (int k = tid; k < G * hd / 8; k += AR_THREADS) {
         const int gg = k / (hd / 8), o = (k % (hd / 8)) * 8;
@@ -561,7 +563,7 @@ __global__ void __launch_bounds__(AR_THREADS) k_attn_rows(attnp_args a) {
     // (head, position) dot is the same 32-accumulator vec_dot_f16 chain against that head's q
     for (int j0 = 0; j0 < n_kv; j0 += AR_THREADS / 4) {
         const int j = j0 + quad;
-        const int jl = j <= i ? j : i;  // masked positions load a valid row (result unused)
+        const int jl = j <= ip ? j : ip;  // masked positions load a valid row (result unused)
         const uint16_t *krow = a.kc + (int64_t)jl * kvw + (int64_t)kvh * hd + t4 * 8;
         uint4 kv[8];
 #pragma unroll
@@ -576,7 +578,7 @@ __global__ void __launch_bounds__(AR_THREADS) k_attn_rows(attnp_args a) {
             for (int s = 0; s < 8; ++s)
                 if (s * 32 < hd) f16_step8(acc, kv[s], *(const uint4 *)(Q16 + gg * hd + s * 32 + t4 * 8));
             const float kq = quad_reduce_f16(acc);
-            if (t4 == 0 && j < n_kv) S[gg * nkp + j] = (j > i) ? -INFINITY : kq * 1.0f + 0.0f;
+            if (t4 == 0 && j < n_kv) S[gg * nkp + j] = (j > ip) ? -INFINITY : kq * 1.0f + 0.0f;
         }
     }
     __syncthreads();
@@ -860,7 +862,7 @@ int launch_attn_rows(const attnp_args &a, hipStream_t s) {
     const int G = a.Hkv > 0 ? a.H / a.Hkv : 0;
     const size_t lds = (size_t)G * a.n_kv * (AR_ALIAS ? 4 : 6) + (size_t)G * a.hd * 2;
     if (G <= 0 || G > 8 || a.H % a.Hkv || (AR_THREADS / 4) % G || a.hd % 32 || a.hd > 256 || a.ctx % 32 || a.n_kv % 32 ||
-        a.n_kv > a.ctx || a.T <= 0 || a.T > a.n_kv || lds > 160 * 1024) {
+        a.n_kv > a.ctx || a.T <= 0 || a.p0 < 0 || a.p0 + a.T > a.n_kv || lds > 160 * 1024) {
         set_error("attn_rows: unsupported shape (head_dim <= 256, G <= 8, 256 % G == 0, G*(n_kv*6 + hd*2) B of LDS <= 160 KiB)");
         return -1;
     }

@@ -1047,11 +1047,11 @@ __global__ void __launch_bounds__(256) k_attn_prefill(attnp_args a) {
         const int h = kvh * G + m % G;
         *(uint4 *)(Qs + m * AP_QS + seg * 8) = *(const uint4 *)(a.q16 + ((int64_t)t * a.H + h) * AP_HD + seg * 8);
     }
-    // this wave's rows: 16*wave + kg*4 + v  ->  their query positions (for the causal mask)
+    // this wave's rows: 16*wave + kg*4 + v  ->  their sequence positions p0 + t (for the causal mask)
     int tr[4];
 #pragma unroll
-    for (int v = 0; v < 4; ++v) tr[v] = tq0 + (16 * wave + kg * 4 + v) / G;
-    const int t_last = min(tq0 + QBQ - 1, a.T - 1);
+    for (int v = 0; v < 4; ++v) tr[v] = a.p0 + tq0 + (16 * wave + kg * 4 + v) / G;
+    const int t_last = a.p0 + min(tq0 + QBQ - 1, a.T - 1);
     const int n_kb = t_last / AP_KB + 1;  // key blocks reaching the last query (keys j <= t only)
     float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     unsigned long long isum[4] = {0, 0, 0, 0};

@@ -26,7 +26,7 @@ GGML_TYPE_Q4_K, GGML_TYPE_Q6_K, GGML_TYPE_Q8_K = 12, 14, 15
 EXPORTS = ["mul_mat", "hpc_init", "hpc_shutdown", "hpc_register_weight", "hpc_last_error", "hpc_set_error_mode",
            "hpc_weight_cache_entries", "hpc_set_matvec_ks", "hpc_set_gemm_x4", "gemma_engine_debug_step", "gemma_engine_stamp_step", "gemma_engine_create", "gemma_engine_free", "gemma_engine_begin",
            "gemma_engine_step", "gemma_engine_tokens", "gemma_engine_pos", "gemma_engine_prefill",
-           "gemma_engine_prefill_fast", "gemma_engine_prefill_taps", "gemma_test_gemm", "gemma_test_gemm_exact", "gemma_kq_time", "hpc_graph_compute",
+           "gemma_engine_prefill_fast", "gemma_engine_prefill_taps", "gemma_engine_extend", "gemma_engine_prefill_next", "gemma_test_gemm", "gemma_test_gemm_exact", "gemma_kq_time", "hpc_graph_compute",
            "ggml_init", "ggml_free", "ggml_new_tensor_2d", "ggml_mul_mat", "ggml_graph_compute_with_ctx",
            "gemma_engine_tensor", "gemma_engine_time", "gemma_engine_sync", "gemma_engine_tune",
            "gemma_engine_plan", "gemma_engine_set_plan", "gemma_engine_set_fuse", "gemma_engine_set_att_o", "gemma_engine_set_option", "gemma_engine_set_persist", "gemma_engine_persist_err", "gemma_engine_graph_kernels", "gemma_hbm_read_gbs", "gemma_hbm_read_probe",
@@ -127,6 +127,10 @@ def lib():
     L.gemma_engine_prefill_fast.argtypes = [vp, vp, vp]
     L.gemma_engine_prefill_taps.restype = C.c_int
     L.gemma_engine_prefill_taps.argtypes = [vp, vp, C.c_int]
+    L.gemma_engine_extend.restype = C.c_int
+    L.gemma_engine_extend.argtypes = [vp, C.c_int, vp, C.c_int]
+    L.gemma_engine_prefill_next.restype = C.c_int
+    L.gemma_engine_prefill_next.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     L.gemma_engine_tensor.restype = C.c_int64
     L.gemma_engine_tensor.argtypes = [vp, C.c_int, vp, i64]
     L.gemma_engine_tune.argtypes = [vp, C.c_int]
@@ -268,6 +272,37 @@ class Engine:
     def begin(self, prompt):
         p = np.ascontiguousarray(prompt, dtype=np.int32)
         self._chk(self.L.gemma_engine_begin(self.h, _p(p), len(p)), "begin")
+        self._n_seq = len(p)  # host-given tokens (positions [0, n_seq)); extend() moves it
+
+    def pos(self):
+        """number of processed positions"""
+        return self.L.gemma_engine_pos(self.h)
+
+    def extend(self, tokens, keep=None):
+        """Continue or rewind: positions [0, keep) stay, `tokens` become the next given positions
+        (consumed by step() or prefill_next()).  keep=None keeps everything, the pending greedy
+        token included, and places `tokens` after it (the next turn of a conversation)."""
+        t = [int(x) for x in tokens]
+        if keep is None:
+            keep = self.pos()
+            if keep < getattr(self, "_n_seq", 0):
+                raise ValueError(f"extend(keep=None): {self._n_seq - keep} given tokens are not processed yet")
+            t = [int(self.tokens()[-1])] + t
+        a = np.ascontiguousarray(t, dtype=np.int32)
+        self._chk(self.L.gemma_engine_extend(self.h, int(keep), _p(a), len(a)), "extend")
+        self._n_seq = int(keep) + len(a)
+
+    def prefill_next(self, n=0, want_all=False, exact=True):
+        """One batched pass over the next n given tokens (0: all that remain) from the current
+        position; returns (token, last-row logits[, the pass's rows]) like prefill().  The token is
+        appended only when the pass reaches the end of the given tokens."""
+        rows = n if n > 0 else max(getattr(self, "_n_seq", 0) - self.pos(), 0)
+        last = np.zeros(self.cfg.n_vocab, dtype=np.float32)
+        allv = np.zeros((rows, self.cfg.n_vocab), dtype=np.float32) if want_all else None
+        tok = self.L.gemma_engine_prefill_next(self.h, int(n), 1 if exact else 0, _p(last), _p(allv) if want_all else None)
+        if tok < 0:
+            raise RuntimeError("prefill_next failed: " + last_error())
+        return (tok, last, allv) if want_all else (tok, last)
 
     def step(self, n, want_logits=False, use_graph=True):
         lg = np.zeros((n, self.cfg.n_vocab), dtype=np.float32) if want_logits else None

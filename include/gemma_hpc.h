@@ -124,6 +124,22 @@ int gemma_engine_pos(gemma_engine *e);
 int gemma_engine_prefill(gemma_engine *e, float *logits_last, float *logits_all);
 /* the same on int8/f16 MFMA: fp32 summation order differs from the CPU path (tolerance path) */
 int gemma_engine_prefill_fast(gemma_engine *e, float *logits_last, float *logits_all);
+/* Continue or rewind the sequence.  Positions [0, keep) stay (0 <= keep <= pos: their K/V rows are in
+ * the caches); everything from `keep` on is dropped, the pending greedy token included; `tokens`
+ * become positions keep .. keep+n-1, given but not yet processed (n >= 1, keep + n < n_ctx, ids in
+ * [0, n_vocab)).  keep == 0 is gemma_engine_begin.  Afterwards pos == keep and either
+ * gemma_engine_step consumes the tokens one by one or gemma_engine_prefill_next in batches.
+ * -1 with hpc_last_error and the state untouched on a bad argument. */
+int gemma_engine_extend(gemma_engine *e, int keep, const int32_t *tokens, int n);
+/* One batched pass over the next `n` given-but-unprocessed tokens, positions [pos, pos+n)
+ * (n == 0: all that remain; 1 <= n <= n_seq - pos), against the caches of [0, pos).  exact != 0:
+ * bit-identical to the CPU path and to the token-by-token steps; 0: the MFMA tolerance path.
+ * logits_last: the last row; logits_all: [n][n_vocab].  Returns the last row's greedy token; when
+ * the pass reaches the end of the given tokens that token is appended (as gemma_engine_prefill
+ * does) and the engine is ready for gemma_engine_step, otherwise nothing is appended and the
+ * next call continues the prompt.  Scratch is sized by the largest n seen, not by n_seq.
+ * Single-GPU engines only; K-quant layers have the exact form only. */
+int gemma_engine_prefill_next(gemma_engine *e, int n, int exact, float *logits_last, float *logits_all);
 /* weights back in ggml row-major layout (tests); tid as in DESIGN.md §Synthetic weights */
 int64_t gemma_engine_tensor(gemma_engine *e, int tid, void *dst, int64_t cap);
 /* time `iters` launches of one hot kernel with hipEvents on the engine stream; returns avg µs and
