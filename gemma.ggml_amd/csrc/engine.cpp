@@ -787,6 +787,8 @@ extern "C" void gemma_engine_free(gemma_engine *e) {
     for (hipEvent_t &ev : e->fc_ev)
         if (ev) (void)hipEventDestroy(ev);
     if (e->xq8k) (void)hipFree(e->xq8k);
+    if (e->smp_dev) (void)hipFree(e->smp_dev);
+    sample_ws_free(&e->smp_ws);
     (void)hipStreamDestroy(e->stream);
     delete e;
 }

@@ -160,6 +160,20 @@ int enqueue_logits_q6k(gemma_engine *e, const uint8_t *x, int ncols, float *y) {
     return launch_matvec_kq(T_Q6_K, k, e->stream);
 }
 
+// The one place a token is picked.  Sampling off: k_advance reduces the greedy argmax keys, launch
+// for launch as before.  Sampling on: the sampler's three launches on the logits row, then the
+// unchanged k_advance on its one key (the p >= n_fixed guard, the RoPE row and the epoch bump stay).
+int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *keys, int n_parts) {
+    const gemma_hip_config &c = e->cfg;
+    hipStream_t s = e->stream;
+    if (e->sampling) {
+        if (launch_sample(row, c.n_vocab, e->smp_dev, e->pos, e->smp_ws, sample_dbg{}, s)) return -1;
+        keys = e->smp_ws.key;
+        n_parts = 1;
+    }
+    return launch_advance(keys, n_parts, e->token, e->pos, e->hist, c.n_ctx, e->nfix, rope_of(e), s);
+}
+
 // the decode tail of a Q6_K tied output: rms_norm*out_norm -> Q8_K (have_img: the last down handed
 // that image over) -> logits -> row argmax -> token feedback, position += 1
 static int step_tail_q6k(gemma_engine *e, bool have_img) {
@@ -168,8 +182,8 @@ static int step_tail_q6k(gemma_engine *e, bool have_img) {
     const int E = c.n_embd;
     if (!have_img && launch_norm_q8K(e->x, E, e->out_norm, E, c.eps, 1, e->xq8k, (E / 256) * 292, s)) return -1;
     if (enqueue_logits_q6k(e, e->xq8k, 1, e->logits)) return -1;
-    if (launch_row_argmax(e->logits, c.n_vocab, e->key, 256, s)) return -1;
-    return launch_advance(e->key, 256, e->token, e->pos, e->hist, c.n_ctx, e->nfix, rope_of(e), s);
+    if (!e->sampling && launch_row_argmax(e->logits, c.n_vocab, e->key, 256, s)) return -1;
+    return enqueue_pick(e, e->logits, e->key, 256);
 }
 
 // One decode token with K-quant layer matrices (src/gemma_model.cpp:665-747 on a Q4_K_M file):
@@ -504,7 +518,7 @@ static int step_logits(gemma_engine *e) {
         // TP: one key per rank, its index made global
         if (e->tp_n_keys && launch_reduce_keys(e->key, lg_grid, (int64_t)rk * e->sh_v, e->rank_keys + rk, s)) return -1;
     }
-    if (!e->tp_n_keys) return launch_advance(e->key, lg_grid, e->token, e->pos, e->hist, c.n_ctx, e->nfix, rr, s);
+    if (!e->tp_n_keys) return enqueue_pick(e, e->logits, e->key, lg_grid);
     if (e->p2p && p2p_gather(e, e->rank_keys, 8, nullptr, 0, s)) return -1;
     if (e->comm) {
         const ncclResult_t nr = ncclAllGather(e->rank_keys + e->tp_rank, e->rank_keys, 1, ncclUint64, e->comm, s);

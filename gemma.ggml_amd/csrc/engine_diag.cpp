@@ -329,6 +329,121 @@ extern "C" int gemma_engine_set_option(gemma_engine *e, const char *name, int va
     return 0;
 }
 
+// On-device sampling on / off and its parameters (include/gemma_hpc.h).  The parameters live in a
+// device struct the sampler's kernels read, and their launch geometry depends on n_vocab only: a new
+// seed, temperature, top_k or top_p is a stream-ordered copy and the captured graph is kept; only
+// turning sampling on or off changes the node set and drops the graph.
+extern "C" int gemma_engine_set_sampler(gemma_engine *e, const gemma_sampler *sp) {
+    set_error("");
+    if (sp) {
+        const std::string why = sampler_invalid(*sp);
+        if (!why.empty()) {
+            set_error("gemma_engine_set_sampler: " + why);
+            return -1;
+        }
+    }
+    const bool on = sp && sp->temperature > 0.0f;
+    if (on && (e->tp_n > 1 || e->comm || e->n_virtual > 1 || e->tp_n_keys)) {
+        set_error("gemma_engine_set_sampler: row-split engines hold a vocabulary shard per rank; sampling needs the whole row "
+                  "(single-GPU engines only)");
+        return -1;
+    }
+    (void)hipSetDevice(e->device);
+    if (on) {
+        if (!e->smp_dev) {
+            sample_ws ws;
+            if (sample_ws_alloc(&ws, e->cfg.n_vocab, e->stream)) {
+                sample_ws_free(&ws);
+                return -1;
+            }
+            if (hipMalloc(&e->smp_dev, sizeof(sampler_params)) != hipSuccess) {
+                sample_ws_free(&ws);
+                e->smp_dev = nullptr;
+                set_error("gemma_engine_set_sampler: allocation failed");
+                return -1;
+            }
+            e->smp_ws = ws;
+        }
+        // the copy's source must outlive the call: wait for an earlier copy before rewriting it
+        GHIP_CHECK(hipStreamSynchronize(e->stream));
+        e->smp_host = sampler_params{};
+        e->smp_host.temperature = sp->temperature; e->smp_host.top_k = sp->top_k; e->smp_host.top_p = sp->top_p;
+        e->smp_host.seed = sp->seed;
+        GHIP_CHECK(hipMemcpyAsync(e->smp_dev, &e->smp_host, sizeof(sampler_params), hipMemcpyHostToDevice, e->stream));
+    }
+    e->smp = sp ? *sp : gemma_sampler{0.0f, 0, 1.0f, 0};
+    if (on != e->sampling) {
+        e->sampling = on;
+        drop_graph(e);
+    }
+    return 0;
+}
+
+extern "C" int gemma_engine_sampler(const gemma_engine *e, gemma_sampler *out) {
+    if (out) *out = e->smp;
+    return e->sampling ? 1 : 0;
+}
+
+// Test hook: the sampler's three launches on `rows` host rows of n_vocab logits, row r at sequence
+// index positions[r]; the same kernels, scratch and device parameter struct as the engine's step.
+extern "C" int gemma_test_sample(const float *logits, int rows, int n_vocab, const gemma_sampler *sp, const int32_t *positions,
+                                 int32_t *tokens, int32_t *cand, int32_t *n_cand, int32_t *n_kept) {
+    set_error("");
+    if (!logits || !sp || !positions || rows <= 0) {
+        set_error("gemma_test_sample: logits, sampler, positions and rows >= 1 are required");
+        return -1;
+    }
+    if (n_vocab <= 0) {
+        set_error("gemma_test_sample: n_vocab must be >= 1");
+        return -1;
+    }
+    std::string why = sampler_invalid(*sp);
+    if (why.empty() && !(sp->temperature > 0.0f)) why = "temperature must be > 0 (the sampler is off otherwise)";
+    for (int r = 0; why.empty() && r < rows; ++r)
+        if (positions[r] < 0 || positions[r] == INT32_MAX) why = "positions must be in [0, 2^31 - 1)";
+    if (!why.empty()) {
+        set_error("gemma_test_sample: " + why);
+        return -1;
+    }
+    sample_ws ws;
+    sampler_params hp, *dp = nullptr;
+    hp.temperature = sp->temperature; hp.top_k = sp->top_k; hp.top_p = sp->top_p; hp.seed = sp->seed;
+    float *dl = nullptr;
+    int *dpos = nullptr, *dtok = nullptr, *dcand = nullptr, *dnc = nullptr, *dnk = nullptr;
+    std::vector<int> pm1(positions, positions + rows);
+    for (int &v : pm1) v -= 1;  // the kernels read *pos + 1, as k_advance does
+    const size_t row_b = (size_t)n_vocab * 4;
+    auto run = [&]() -> int {
+        if (sample_ws_alloc(&ws, n_vocab, nullptr)) return -1;
+        GHIP_CHECK(hipMalloc(&dp, sizeof(hp)));
+        GHIP_CHECK(hipMalloc(&dl, row_b * rows));
+        GHIP_CHECK(hipMalloc(&dpos, (size_t)rows * 4));
+        GHIP_CHECK(hipMalloc(&dtok, (size_t)rows * 4));
+        GHIP_CHECK(hipMalloc(&dnc, (size_t)rows * 4));
+        GHIP_CHECK(hipMalloc(&dnk, (size_t)rows * 4));
+        GHIP_CHECK(hipMalloc(&dcand, (size_t)rows * SAMPLE_MAX_K * 4));
+        GHIP_CHECK(hipMemcpy(dp, &hp, sizeof(hp), hipMemcpyHostToDevice));
+        GHIP_CHECK(hipMemcpy(dl, logits, row_b * rows, hipMemcpyHostToDevice));
+        GHIP_CHECK(hipMemcpy(dpos, pm1.data(), (size_t)rows * 4, hipMemcpyHostToDevice));
+        for (int r = 0; r < rows; ++r) {
+            sample_dbg d;
+            d.token = dtok + r; d.cand = dcand + (size_t)r * SAMPLE_MAX_K; d.n_cand = dnc + r; d.n_kept = dnk + r;
+            if (launch_sample(dl + (size_t)r * n_vocab, n_vocab, dp, dpos + r, ws, d, nullptr)) return -1;
+        }
+        GHIP_CHECK(hipDeviceSynchronize());
+        if (tokens) GHIP_CHECK(hipMemcpy(tokens, dtok, (size_t)rows * 4, hipMemcpyDeviceToHost));
+        if (n_cand) GHIP_CHECK(hipMemcpy(n_cand, dnc, (size_t)rows * 4, hipMemcpyDeviceToHost));
+        if (n_kept) GHIP_CHECK(hipMemcpy(n_kept, dnk, (size_t)rows * 4, hipMemcpyDeviceToHost));
+        if (cand) GHIP_CHECK(hipMemcpy(cand, dcand, (size_t)rows * SAMPLE_MAX_K * 4, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    const int r = run();
+    sample_ws_free(&ws);
+    for (void *p : {(void *)dp, (void *)dl, (void *)dpos, (void *)dtok, (void *)dnc, (void *)dnk, (void *)dcand})
+        if (p) (void)hipFree(p);
+    return r;
+}
+
 // attention + attn-out in one launch on (1) / off (0) / unchanged (-1); returns the setting
 extern "C" int gemma_engine_set_att_o(gemma_engine *e, int on) {
     if (on >= 0 && (on != 0) != (e->att_o != 0)) {

@@ -14,6 +14,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -150,6 +151,12 @@ struct gemma_engine {
     // ---- decode state ----
     unsigned long long *key = nullptr;
     int *pos = nullptr, *token = nullptr, *hist = nullptr, *nfix = nullptr;
+    // on-device sampling (gemma_engine_set_sampler; sample.hip): off = greedy, nothing below is used
+    bool sampling = false;
+    gemma_sampler smp{0.0f, 0, 1.0f, 0};  // the parameters as given
+    sampler_params smp_host;              // their device form (source of the stream-ordered copy)
+    sampler_params *smp_dev = nullptr;
+    sample_ws smp_ws;                     // allocated when sampling is first turned on
     int n_prompt = 0;  // host-given tokens: positions [0, n_prompt) of hist (begin / extend; *nfix mirrors it)
     int host_pos = 0;  // mirror of *pos (steps are deterministic): processed positions, K / V rows in the caches
     hipGraph_t graph = nullptr;
@@ -265,6 +272,14 @@ static inline rope_row rope_of(const gemma_engine *e) {
     return rr;
 }
 
+// what is wrong with a sampler's fields ("" = valid); the message names the field
+static inline std::string sampler_invalid(const gemma_sampler &s) {
+    if (!std::isfinite(s.temperature)) return "temperature is not finite";
+    if (s.top_k < 0 || s.top_k > SAMPLE_MAX_K) return "top_k outside [0, " + std::to_string(SAMPLE_MAX_K) + "]";
+    if (!std::isfinite(s.top_p) || !(s.top_p > 0.0f) || s.top_p > 1.0f) return "top_p outside (0, 1]";
+    return "";
+}
+
 // ---- functions that cross translation units (internal: not part of the library's surface) -------
 #pragma GCC visibility push(hidden)
 // engine.cpp
@@ -272,6 +287,9 @@ int ensure_graph(gemma_engine *e);
 void drop_graph(gemma_engine *e);
 // engine_decode.cpp
 int enqueue_step(gemma_engine *e);
+// the token of position *pos + 1 and the advance: the sampler on `row` when sampling is on, else
+// the greedy argmax keys (n_parts of them) exactly as before
+int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *keys, int n_parts);
 int tok_prepare(gemma_engine *e);
 int persist_report(gemma_engine *e, const int *w);
 int persist_check(gemma_engine *e);

@@ -156,10 +156,12 @@ static int enqueue_prefill(gemma_engine *e, int T, int p0, bool exact, float *ta
     }
     // greedy token from the last row; position p0+T-1 -> p0+T, token appended at hist[p0+T] unless
     // that is still a given token (k_advance's p >= n_fixed guard: a pass that ends mid-prompt)
-    if (launch_row_argmax(p.LG + (size_t)(T - 1) * c.n_vocab, c.n_vocab, (unsigned long long *)p.keys, 256, s)) return -1;
+    // (with the sampler on: its draw at position p0+T from the same row, after *pos is in place)
+    const float *last_row = p.LG + (size_t)(T - 1) * c.n_vocab;
+    if (!e->sampling && launch_row_argmax(last_row, c.n_vocab, (unsigned long long *)p.keys, 256, s)) return -1;
     const int last = p0 + T - 1;
     GHIP_CHECK(hipMemcpyAsync(e->pos, &last, 4, hipMemcpyHostToDevice, s));
-    return launch_advance((const unsigned long long *)p.keys, 256, e->token, e->pos, e->hist, c.n_ctx, e->nfix, rope_of(e), s);
+    return enqueue_pick(e, last_row, (const unsigned long long *)p.keys, 256);
 }
 
 // Batched prefill for K-quant layers (the reference's shipped Q4_K_M model, src/app.cpp:36): the

@@ -421,6 +421,31 @@ int launch_advance(const unsigned long long *keys, int n_parts, int *token, int 
                    const int *n_fixed, const rope_row &r, hipStream_t s);
 int launch_set_position(int token, int p, int *pos, int *hist, int *n_fixed, int fixed, const rope_row &r, hipStream_t s);
 
+// ---- on-device sampling (sample.hip; the rule: include/gemma_hpc.h, DESIGN.md §5b″) ------------
+constexpr int SAMPLE_MAX_K = 1024;  // candidates at most (top_k == 0 means this many)
+struct sampler_params {             // lives in device memory: a change is a stream-ordered copy
+    float temperature = 0.0f;
+    int top_k = 0;
+    float top_p = 1.0f;
+    int pad = 0;
+    unsigned long long seed = 0;
+};
+struct sample_ws {  // scratch of one sampler (sample_ws_alloc); the tail launch leaves hist and cur zero
+    unsigned *hist = nullptr, *cur = nullptr;  // key histogram [4096]; list cursors [2]
+    unsigned long long *list_a = nullptr, *list_b = nullptr;  // [SAMPLE_MAX_K], [cap_b] (key << 32 | ~index)
+    int64_t cap_b = 0;                                        // = n_vocab
+    unsigned long long *key = nullptr;  // the drawn token as one argmax key (launch_advance(key, 1, ...))
+};
+struct sample_dbg {  // optional outputs (tests): the token, cand[SAMPLE_MAX_K] (-1 past K), K, m
+    int *token = nullptr, *cand = nullptr, *n_cand = nullptr, *n_kept = nullptr;
+};
+int sample_ws_alloc(sample_ws *w, int64_t n_vocab, hipStream_t s);
+void sample_ws_free(sample_ws *w);
+// three launches: the token for sequence index *pos + 1 from row[0 .. n) into *w.key; prm and pos are
+// device pointers read by the kernels; the geometry depends on n only
+int launch_sample(const float *row, int64_t n, const sampler_params *prm, const int *pos, const sample_ws &w,
+                  const sample_dbg &dbg, hipStream_t s);
+
 // ---- generic ggml-op kernels used by the C-ABI and the ggml-compatible executor ----------------
 int launch_mul_mat_f16(const uint16_t *src0, int64_t nb01_elems, int64_t ne01, const uint16_t *src1,
                        int64_t row_size_elems, int64_t ncols, int64_t K, float *dst, hipStream_t s);

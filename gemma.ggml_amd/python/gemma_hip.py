@@ -36,7 +36,8 @@ EXPORTS = ["mul_mat", "hpc_init", "hpc_shutdown", "hpc_register_weight", "hpc_la
            "gguf_get_val_data", "gguf_get_n_tensors", "gguf_get_tensor_name", "gguf_get_tensor_type",
            "gguf_get_tensor_offset", "gguf_get_version", "gguf_get_alignment", "gguf_get_data_offset",
            "gguf_find_key", "gguf_find_tensor", "ggml_get_tensor", "ggml_nbytes",
-           "gemma_engine_create_from_gguf", "gemma_engine_config"]
+           "gemma_engine_create_from_gguf", "gemma_engine_config",
+           "gemma_engine_set_sampler", "gemma_engine_sampler", "gemma_test_sample"]
 
 
 def build():
@@ -52,6 +53,14 @@ class GemmaConfig(C.Structure):
                 ("head_dim", C.c_int), ("n_ff", C.c_int), ("n_vocab", C.c_int), ("n_ctx", C.c_int),
                 ("wtype", C.c_int), ("eps", C.c_float), ("rope_base", C.c_float), ("seed", C.c_uint64),
                 ("gelu_clamp", C.c_int), ("out_type", C.c_int), ("out_gain", C.c_float)]
+
+
+class GemmaSampler(C.Structure):
+    """struct gemma_sampler (include/gemma_hpc.h): temperature <= 0 is greedy."""
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("seed", C.c_uint64)]
+
+
+SAMPLE_MAX_K = 1024  # candidates at most (top_k == 0 means this many)
 
 
 class GgmlTensor(C.Structure):
@@ -159,6 +168,12 @@ def lib():
     L.gemma_engine_create_from_gguf.argtypes = [C.c_char_p, C.c_int, C.c_int]
     L.gemma_engine_config.restype = C.c_int
     L.gemma_engine_config.argtypes = [vp, C.POINTER(GemmaConfig)]
+    L.gemma_engine_set_sampler.restype = C.c_int
+    L.gemma_engine_set_sampler.argtypes = [vp, C.POINTER(GemmaSampler)]
+    L.gemma_engine_sampler.restype = C.c_int
+    L.gemma_engine_sampler.argtypes = [vp, C.POINTER(GemmaSampler)]
+    L.gemma_test_sample.restype = C.c_int
+    L.gemma_test_sample.argtypes = [vp, C.c_int, C.c_int, C.POINTER(GemmaSampler), vp, vp, vp, vp, vp]
     # GGUF reader (include/ggml.h)
     L.gguf_init_from_file.restype = vp
     L.gguf_init_from_file.argtypes = [C.c_char_p, GGUFInitParams]
@@ -379,6 +394,23 @@ class Engine:
         """a selectable variant (include/gemma_hpc.h gemma_engine_set_option); drops the decode graph"""
         self._chk(self.L.gemma_engine_set_option(self.h, name.encode(), int(value)), f"set_option({name})")
 
+    def set_sampler(self, temperature=0.0, top_k=0, top_p=1.0, seed=0):
+        """Seeded temperature / top-k / top-p sampling inside the decode step (include/gemma_hpc.h
+        has the rule).  temperature <= 0 or None: greedy, the default.  top_k 0 = 1024 candidates
+        (the most there are).  A change of parameters keeps the captured graph; on / off drops it."""
+        if temperature is None:
+            r = self.L.gemma_engine_set_sampler(self.h, None)
+        else:
+            s = GemmaSampler(float(temperature), int(top_k), float(top_p), int(seed) & (2 ** 64 - 1))
+            r = self.L.gemma_engine_set_sampler(self.h, C.byref(s))
+        self._chk(r, "set_sampler")
+
+    def sampler(self):
+        """(sampling on, {temperature, top_k, top_p, seed} as last set)"""
+        s = GemmaSampler()
+        on = self.L.gemma_engine_sampler(self.h, C.byref(s))
+        return on == 1, dict(temperature=s.temperature, top_k=s.top_k, top_p=s.top_p, seed=s.seed)
+
     def set_att_o(self, on=-1):
         """decode attention + attn-out in one launch per layer: on 1 / off 0 / keep -1; returns the setting"""
         return self.L.gemma_engine_set_att_o(self.h, on) == 1
@@ -439,6 +471,33 @@ class Engine:
         if us < 0:
             raise RuntimeError("time failed: " + last_error())
         return us, b.value
+
+
+def test_sample(rows, sampler, positions):
+    """The sampler's kernels on host logits rows [R][V] (gemma_test_sample): row r is drawn at sequence
+    index positions[r].  sampler: dict(temperature, top_k, top_p, seed).  Returns (tokens [R],
+    cand [R][1024] candidate ids in order with -1 past K, n_cand [R] = K, n_kept [R] = m);
+    raises RuntimeError with the library's message on a refused argument."""
+    x = np.ascontiguousarray(rows, dtype=np.float32)
+    if x.ndim == 1:
+        x = x[None, :]
+    R, V = x.shape
+    pos = np.ascontiguousarray(positions, dtype=np.int32)
+    if pos.shape != (R,):
+        raise ValueError("positions: one per row")
+    s = GemmaSampler(float(sampler.get("temperature", 1.0)), int(sampler.get("top_k", 0)),
+                     float(sampler.get("top_p", 1.0)), int(sampler.get("seed", 0)) & (2 ** 64 - 1))
+    tokens = np.zeros(R, dtype=np.int32)
+    cand = np.zeros((R, SAMPLE_MAX_K), dtype=np.int32)
+    n_cand = np.zeros(R, dtype=np.int32)
+    n_kept = np.zeros(R, dtype=np.int32)
+    r = lib().gemma_test_sample(_p(x), R, V, C.byref(s), _p(pos), _p(tokens), _p(cand), _p(n_cand), _p(n_kept))
+    if r != 0:
+        raise RuntimeError("gemma_test_sample failed: " + last_error())
+    return tokens, cand, n_cand, n_kept
+
+
+test_sample.__test__ = False  # a library wrapper, not a pytest test
 
 
 def tp_unique_id():

@@ -140,6 +140,28 @@ int gemma_engine_extend(gemma_engine *e, int keep, const int32_t *tokens, int n)
  * next call continues the prompt.  Scratch is sized by the largest n seen, not by n_seq.
  * Single-GPU engines only; K-quant layers have the exact form only. */
 int gemma_engine_prefill_next(gemma_engine *e, int n, int exact, float *logits_last, float *logits_all);
+/* Seeded temperature / top-k / top-p sampling inside the decode step (no host round trip; DESIGN.md
+ * §5b″ has the rule in full).  With the sampler on, the token at sequence index p comes from its logits
+ * row l[0..V): K = min(top_k, V) (top_k == 0: min(1024, V); more than 1024 candidates are not sampled:
+ * the distribution is truncated there); candidates c_0..c_{K-1} = the first K entries under "larger
+ * logit, then smaller index" (-0 == +0); f64 weights w_i = exp((l[c_i] - l[c_0]) / temperature) with
+ * prefix sums C_i, W = C_{K-1}; m = K when top_p == 1, else the smallest i + 1 with C_i >= top_p * W;
+ * u = (splitmix64_mix(seed + (p + 1) * 0x9E3779B97F4A7C15) >> 11) * 2^-53, r = u * C_{m-1}; the token
+ * is c_j for the smallest j < m with C_j > r (else j = m - 1).  The draw depends on (seed, p) only:
+ * not on call count, graph or eager, batching, or a rewind.  Steps, prefill and prefill_next all pick
+ * through it; given (prompt) positions are never overwritten.
+ * Changing the parameters of a running sampler is a stream-ordered copy and keeps the captured decode
+ * graph (the launch geometry does not depend on top_k); turning sampling on or off drops it. */
+typedef struct gemma_sampler { float temperature; int top_k; float top_p; uint64_t seed; } gemma_sampler;
+/* NULL or temperature <= 0: greedy (the default).  -1 + hpc_last_error, state untouched, on
+ * top_k outside [0, 1024], top_p outside (0, 1], a non-finite field, or a row-split engine. */
+int gemma_engine_set_sampler(gemma_engine *e, const gemma_sampler *s);
+int gemma_engine_sampler(const gemma_engine *e, gemma_sampler *out);   /* 1 = sampling on, 0 = greedy */
+/* per-op test entry: the sampler on host rows.  positions[r] = the p of row r.  Outputs (any may be
+ * NULL): tokens[rows]; cand[rows][1024] candidate ids in order, -1 past K; n_cand[rows] = K;
+ * n_kept[rows] = m */
+int gemma_test_sample(const float *logits, int rows, int n_vocab, const gemma_sampler *s,
+                      const int32_t *positions, int32_t *tokens, int32_t *cand, int32_t *n_cand, int32_t *n_kept);
 /* weights back in ggml row-major layout (tests); tid as in DESIGN.md §Synthetic weights */
 int64_t gemma_engine_tensor(gemma_engine *e, int tid, void *dst, int64_t cap);
 /* time `iters` launches of one hot kernel with hipEvents on the engine stream; returns avg µs and
