@@ -428,6 +428,50 @@ extern "C" int gemma_test_gemm_exact(int type, int64_t rows, int64_t K, int64_t 
     return test_gemm(true, type, rows, K, T, W, X, Y, xq_out, da_out);
 }
 
+// the skinny exact GEMM of the verify pass (tests/test_gpu_gemm_skinny.py): the same quantizer, then
+// launch_gemm_skinny with EPI_ADD when resid [T][rows] is given, else EPI_STORE
+extern "C" int gemma_test_gemm_skinny(int type, int64_t rows, int64_t K, int64_t T, const void *W, const float *X,
+                                      const float *resid, float *Y) {
+    set_error("");
+    if ((type != T_Q4_0 && type != T_Q8_0) || K <= 0 || K % 32 || rows <= 0 || !W || !X || !Y) {
+        set_error("gemma_test_gemm_skinny: bad arguments");
+        return -1;
+    }
+    if (T < 1 || T > GEMM_SKINNY_MAX_T) {
+        set_error("gemma_test_gemm_skinny: T = " + std::to_string(T) + " outside [1, " + std::to_string(GEMM_SKINNY_MAX_T) + "]");
+        return -1;
+    }
+    const int bb = type == T_Q4_0 ? 18 : 34;
+    const int64_t row_bytes = K / 32 * bb, ldq = (K + 255) / 256 * 256, ldd = ldq / 32;
+    uint8_t *d_rows = nullptr;
+    float *d_x = nullptr, *d_y = nullptr, *d_da = nullptr, *d_r = nullptr;
+    int8_t *d_q = nullptr;
+    GHIP_CHECK(hipMalloc(&d_rows, (size_t)(row_bytes * rows)));
+    GHIP_CHECK(hipMalloc(&d_x, (size_t)(T * K * 4)));
+    GHIP_CHECK(hipMalloc(&d_y, (size_t)(T * rows * 4)));
+    GHIP_CHECK(hipMalloc(&d_r, (size_t)(T * rows * 4)));
+    GHIP_CHECK(hipMalloc(&d_q, (size_t)(T * ldq)));
+    GHIP_CHECK(hipMalloc(&d_da, (size_t)(T * ldd * 4)));
+    GHIP_CHECK(hipMemcpy(d_rows, W, (size_t)(row_bytes * rows), hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_x, X, (size_t)(T * K * 4), hipMemcpyHostToDevice));
+    if (resid) GHIP_CHECK(hipMemcpy(d_r, resid, (size_t)(T * rows * 4), hipMemcpyHostToDevice));
+    tiled_mat m = alloc_tiled(type, rows, K, nullptr);
+    int r = launch_repack(m, d_rows, row_bytes, nullptr);
+    qrow_args qa;
+    qa.x = d_x; qa.ldx = K; qa.K = K; qa.q = d_q; qa.ldq = ldq; qa.da = d_da; qa.ldd = ldd;
+    if (r == 0) r = launch_quant_rows(QR_F32, qa, (int)T, nullptr);
+    gemm_args g;
+    set_mat(g, m);
+    g.xq = d_q; g.ldq = ldq; g.da = d_da; g.ldd = ldd; g.T = T; g.y = d_y; g.ldy = rows; g.resid = resid ? d_r : nullptr;
+    if (r == 0) r = launch_gemm_skinny(type, resid ? EPI_ADD : EPI_STORE, g, nullptr);
+    if (r == 0) GHIP_CHECK(hipDeviceSynchronize());
+    if (r == 0) GHIP_CHECK(hipMemcpy(Y, d_y, (size_t)(T * rows * 4), hipMemcpyDeviceToHost));
+    free_tiled(m);
+    void *bufs[] = {d_rows, d_x, d_y, d_r, d_q, d_da};
+    for (void *p : bufs) (void)hipFree(p);
+    return r;
+}
+
 // ---- K-quant matvec timing (bench.py): random bytes of the right shape, `iters` launches timed
 // with hipEvents on one stream; returns avg µs and the algorithmic bytes per launch
 extern "C" double gemma_kq_time(int type, int64_t rows, int64_t K, int iters, double *algo_bytes) {

@@ -788,6 +788,9 @@ extern "C" void gemma_engine_free(gemma_engine *e) {
         if (ev) (void)hipEventDestroy(ev);
     if (e->xq8k) (void)hipFree(e->xq8k);
     if (e->smp_dev) (void)hipFree(e->smp_dev);
+    if (e->vf.keys) (void)hipFree(e->vf.keys);
+    if (e->vf.ints) (void)hipFree(e->vf.ints);
+    if (e->vf.host) (void)hipHostFree(e->vf.host);
     sample_ws_free(&e->smp_ws);
     (void)hipStreamDestroy(e->stream);
     delete e;

@@ -163,15 +163,22 @@ int enqueue_logits_q6k(gemma_engine *e, const uint8_t *x, int ncols, float *y) {
 // The one place a token is picked.  Sampling off: k_advance reduces the greedy argmax keys, launch
 // for launch as before.  Sampling on: the sampler's three launches on the logits row, then the
 // unchanged k_advance on its one key (the p >= n_fixed guard, the RoPE row and the epoch bump stay).
+// enqueue_pick_keys is the pick without the advance (the verify pass picks every row, then advances
+// once over the accepted prefix).
+int enqueue_pick_keys(gemma_engine *e, const float *row, const int *pos, unsigned long long *skey,
+                      const unsigned long long **keys, int *n_parts) {
+    if (!e->sampling) return 0;
+    sample_ws w = e->smp_ws;
+    if (skey) w.key = skey;
+    if (launch_sample(row, e->cfg.n_vocab, e->smp_dev, pos, w, sample_dbg{}, e->stream)) return -1;
+    *keys = w.key;
+    *n_parts = 1;
+    return 0;
+}
+
 int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *keys, int n_parts) {
-    const gemma_hip_config &c = e->cfg;
-    hipStream_t s = e->stream;
-    if (e->sampling) {
-        if (launch_sample(row, c.n_vocab, e->smp_dev, e->pos, e->smp_ws, sample_dbg{}, s)) return -1;
-        keys = e->smp_ws.key;
-        n_parts = 1;
-    }
-    return launch_advance(keys, n_parts, e->token, e->pos, e->hist, c.n_ctx, e->nfix, rope_of(e), s);
+    if (enqueue_pick_keys(e, row, e->pos, nullptr, &keys, &n_parts)) return -1;
+    return launch_advance(keys, n_parts, e->token, e->pos, e->hist, e->cfg.n_ctx, e->nfix, rope_of(e), e->stream);
 }
 
 // the decode tail of a Q6_K tied output: rms_norm*out_norm -> Q8_K (have_img: the last down handed

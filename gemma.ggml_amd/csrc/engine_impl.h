@@ -1,9 +1,11 @@
 // engine_impl.h — the device-resident engine's state and what its translation units share
-// (internal: included only by engine.cpp, engine_decode.cpp, engine_prefill.cpp, engine_diag.cpp).
+// (internal: included only by engine.cpp, engine_decode.cpp, engine_prefill.cpp, engine_spec.cpp,
+// engine_diag.cpp).
 //   engine.cpp          lifecycle: create / free / begin / extend / step / tensor, TP and p2p set-up
 //   engine_decode.cpp   one decode token: enqueue_step (+ K-quant), the persistent launch's
 //                       arguments, the all-gathers
 //   engine_prefill.cpp  batched prefill and the ggml executor's entry points
+//   engine_spec.cpp     speculative decoding: the verify pass, lookup drafts, the generate loop
 //   engine_diag.cpp     timing, tuning, plan and option setters, stamps, taps, per-op test hooks
 #pragma once
 
@@ -184,6 +186,12 @@ struct gemma_engine {
         uint16_t *XM = nullptr;  // K-quant prefill: the Q4_K mins operand of the Q8_K image (k_q8k_expand)
         void *keys = nullptr;
     } pf;
+    // ---- verify pass (gemma_engine_verify; allocated at its first call) ----
+    struct {
+        unsigned long long *keys = nullptr;  // device: [8][256] greedy partial keys, then [8] sampler key slots
+        int *ints = nullptr;                 // device: [8] row positions (sampler), [9] result {a, g_0 .. g_7}
+        int *host = nullptr;                 // pinned: [8] drafts, [8] row positions, [9] result
+    } vf;
     // ---- diagnostics ----
     int time_hot = 0, ablate = 0;  // gemma_engine_time diagnostics: one layer's matrix repeated; ablations
     float *dbg = nullptr;  // per-layer taps [L][qkv_rows + qw + E] (debug steps only)
@@ -290,6 +298,11 @@ int enqueue_step(gemma_engine *e);
 // the token of position *pos + 1 and the advance: the sampler on `row` when sampling is on, else
 // the greedy argmax keys (n_parts of them) exactly as before
 int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *keys, int n_parts);
+// the pick alone, no advance: with sampling on, the sampler's draw for sequence index *pos + 1 from
+// `row` into the key slot skey (nullptr: the sampler's own), *keys / *n_parts set to that one key;
+// sampling off: nothing is launched and the caller's greedy keys stand
+int enqueue_pick_keys(gemma_engine *e, const float *row, const int *pos, unsigned long long *skey,
+                      const unsigned long long **keys, int *n_parts);
 int tok_prepare(gemma_engine *e);
 int persist_report(gemma_engine *e, const int *w);
 int persist_check(gemma_engine *e);
@@ -297,4 +310,7 @@ int att_o_check(gemma_engine *e);
 int tp_gather(gemma_engine *e, float *full, int64_t cnt);
 // ncols Q8_K columns x ((n_embd / 256) * 292 bytes apart) through the Q6_K tied output -> y [ncols][n_vocab]
 int enqueue_logits_q6k(gemma_engine *e, const uint8_t *x, int ncols, float *y);
+// engine_prefill.cpp: the exact batched pass over hist[p0 .. p0+T), T <= 8, with the Q4_0 / Q8_0
+// GEMMs on launch_gemm_skinny and no pick: the logits rows are left in pf.LG [T][n_vocab]
+int enqueue_verify_pass(gemma_engine *e, int T, int p0);
 #pragma GCC visibility pop

@@ -83,7 +83,9 @@ static int prefill_attention(gemma_engine *e, int il, int T, int p0, bool exact,
 // One batched pass over hist[p0 .. p0+T): the rows are sequence positions p0 .. p0+T-1, the caches
 // hold the positions before p0 (p0 = 0: the whole-prompt prefill).  Every scratch buffer is indexed
 // by the row t of the pass; only the token reads, RoPE, the cache stores and the attention know p0.
-static int enqueue_prefill(gemma_engine *e, int T, int p0, bool exact, float *taps = nullptr) {
+// verify (gemma_engine_verify only, T <= 8, exact): the Q4_0 / Q8_0 GEMMs go through
+// launch_gemm_skinny and the pass ends with the logits rows: the caller picks from every row.
+static int enqueue_prefill(gemma_engine *e, int T, int p0, bool exact, float *taps = nullptr, bool verify = false) {
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
     int mx_form = -1;  // the exact attention's form, resolved at the first layer
@@ -94,12 +96,13 @@ static int enqueue_prefill(gemma_engine *e, int T, int p0, bool exact, float *ta
         gemm_args g;
         set_mat(g, m);
         g.xq = p.XQ; g.xh = p.XH; g.ldq = p.ldq; g.da = p.DA; g.ldd = p.ldd; g.T = T; g.y = y; g.resid = resid; g.ldy = ldy;
+        if (verify) return launch_gemm_skinny(wt, epi, g, s);
         return exact ? launch_gemm_exact(wt, epi, g, s) : launch_gemm_q(wt, epi, g, s);
     };
     auto quant = [&](int mode, const float *x, const float *x2, int64_t K, const float *norm_w) {
         qrow_args a;
         a.x = x; a.x2 = x2; a.ldx = K; a.K = K; a.norm_w = norm_w; a.eps = c.eps;
-        const bool i8img = exact && gemm_x4_i8();  // the int8-staged exact GEMM reads the int8 image
+        const bool i8img = exact && (verify || gemm_x4_i8());  // the int8-staged exact GEMM and the skinny GEMM read the int8 image
         a.q = (!exact || i8img) ? p.XQ : nullptr; a.qh = (exact && !i8img) ? p.XH : nullptr; a.ldq = p.ldq; a.da = p.DA; a.ldd = p.ldd;
         a.gelu_tab = e->gelu_tab; a.gelu_clamp = c.gelu_clamp;
         if (mode == QR_EMBED_NORM) {
@@ -154,6 +157,7 @@ static int enqueue_prefill(gemma_engine *e, int T, int p0, bool exact, float *ta
         if (quant(QR_NORM, p.X, nullptr, E, e->out_norm)) return -1;
         if (gemm(e->embd, EPI_STORE, nullptr, p.LG, c.n_vocab)) return -1;
     }
+    if (verify) return 0;
     // greedy token from the last row; position p0+T-1 -> p0+T, token appended at hist[p0+T] unless
     // that is still a given token (k_advance's p >= n_fixed guard: a pass that ends mid-prompt)
     // (with the sampler on: its draw at position p0+T from the same row, after *pos is in place)
@@ -229,6 +233,15 @@ static int enqueue_prefill_kq(gemma_engine *e, int T, int p0) {
         if (mv(K.down, p.X, E, p.SA, nullptr, nullptr)) return -1;  // + sa
     }
     return 0;
+}
+
+int enqueue_verify_pass(gemma_engine *e, int T, int p0) {
+    if (T < 1 || T > GEMM_SKINNY_MAX_T) {
+        set_error("gemma_engine_verify: a pass of " + std::to_string(T) + " rows");
+        return -1;
+    }
+    if (prefill_alloc(e, GEMM_SKINNY_MAX_T)) return -1;  // sized once: no reallocation between passes
+    return enqueue_prefill(e, T, p0, true, nullptr, true);
 }
 
 // one pass over rows [p0, p0+T) and its results: the last row's logits, all rows' [T][n_vocab], the

@@ -1,0 +1,187 @@
+// engine_spec.cpp — speculative decoding on the device-resident engine (DESIGN.md §5b‴): the exact
+// multi-token verify pass, the cache read-back its tests use, prompt-lookup drafts and the generate
+// loop that alternates verify passes and plain graph steps.
+#include "engine_impl.h"
+
+static int verify_alloc(gemma_engine *e) {
+    if (e->vf.keys) return 0;
+    GHIP_CHECK(hipMalloc(&e->vf.keys, (size_t)(GEMM_SKINNY_MAX_T * 256 + GEMM_SKINNY_MAX_T) * 8));
+    GHIP_CHECK(hipMalloc(&e->vf.ints, (size_t)(GEMM_SKINNY_MAX_T + GEMM_SKINNY_MAX_T + 1) * 4));
+    GHIP_CHECK(hipHostMalloc((void **)&e->vf.host, (size_t)(3 * GEMM_SKINNY_MAX_T + 1) * 4, hipHostMallocDefault));
+    return 0;
+}
+
+// One batched exact pass over [pending token, k drafts] at p0 = pos, a pick from every row, the
+// accept rule and the advance over the accepted prefix on the device, the rejected rows' K / V
+// cleared: afterwards the device state is what a + 1 calls of gemma_engine_step leave.
+extern "C" int gemma_engine_verify(gemma_engine *e, const int32_t *draft, int k, int32_t *out_tokens, float *logits_all) {
+    set_error("");
+    const gemma_hip_config &c = e->cfg;
+    const int p0 = e->host_pos;
+    if (e->tp_n > 1 || e->comm || e->n_virtual > 1) {
+        set_error("gemma_engine_verify: single-GPU engines only (row-split engines decode token by token)");
+        return -1;
+    }
+    if (p0 < e->n_prompt || p0 < 1) {
+        set_error("gemma_engine_verify: " + std::to_string(std::max(e->n_prompt - p0, 0)) +
+                  " given tokens are still pending (the drafts follow the pending picked token)");
+        return -1;
+    }
+    if (k < 1 || k > GEMMA_VERIFY_MAX_DRAFT || !draft || !out_tokens) {
+        set_error("gemma_engine_verify: k = " + std::to_string(k) + " outside [1, " + std::to_string(GEMMA_VERIFY_MAX_DRAFT) +
+                  "], or a null draft / out_tokens");
+        return -1;
+    }
+    for (int i = 0; i < k; ++i)  // the embedding kernels index token_embd rows unchecked
+        if (draft[i] < 0 || draft[i] >= c.n_vocab) {
+            set_error("gemma_engine_verify: token id " + std::to_string(draft[i]) + " out of range [0, n_vocab)");
+            return -1;
+        }
+    if ((int64_t)p0 + k + 1 >= c.n_ctx) {
+        set_error("gemma_engine_verify: pos + k + 1 = " + std::to_string((int64_t)p0 + k + 1) + " does not fit n_ctx = " +
+                  std::to_string(c.n_ctx));
+        return -1;
+    }
+    (void)hipSetDevice(e->device);
+    hipStream_t s = e->stream;
+    if (verify_alloc(e)) return -1;
+    const int T = k + 1;
+    int *h_draft = e->vf.host, *h_pos = e->vf.host + GEMM_SKINNY_MAX_T, *h_out = e->vf.host + 2 * GEMM_SKINNY_MAX_T;
+    int *d_pos = e->vf.ints, *d_out = e->vf.ints + GEMM_SKINNY_MAX_T;
+    unsigned long long *d_skey = e->vf.keys + GEMM_SKINNY_MAX_T * 256;
+    for (int i = 0; i < k; ++i) h_draft[i] = draft[i];
+    for (int i = 0; i < T; ++i) h_pos[i] = p0 + i;
+    // 1. stage: the drafts become hist[pos+1 .. pos+k], the tokens of the pass's rows 1 .. k
+    GHIP_CHECK(hipMemcpyAsync(e->hist + p0 + 1, h_draft, (size_t)k * 4, hipMemcpyHostToDevice, s));
+    // 2. the pass
+    if (enqueue_verify_pass(e, T, p0)) return -1;
+    // 3. a pick from every row, none advances: row i gives the token of sequence index pos + i + 1
+    verify_args v;
+    if (e->sampling) {
+        GHIP_CHECK(hipMemcpyAsync(d_pos, h_pos, (size_t)T * 4, hipMemcpyHostToDevice, s));
+        for (int i = 0; i < T; ++i) {
+            const unsigned long long *key = nullptr;
+            int parts = 0;
+            if (enqueue_pick_keys(e, e->pf.LG + (size_t)i * c.n_vocab, d_pos + i, d_skey + i, &key, &parts)) return -1;
+        }
+        v.keys = d_skey; v.n_parts = 1; v.key_stride = 1;
+    } else {
+        for (int i = 0; i < T; ++i)
+            if (launch_row_argmax(e->pf.LG + (size_t)i * c.n_vocab, c.n_vocab, e->vf.keys + (size_t)i * 256, 256, s)) return -1;
+        v.keys = e->vf.keys; v.n_parts = 256; v.key_stride = 256;
+    }
+    // 4. accept + advance
+    v.k = k; v.p0 = p0; v.token = e->token; v.pos = e->pos; v.hist = e->hist; v.r = rope_of(e);
+    v.zero_keys = e->key; v.n_zero = e->grid_big; v.out = d_out;
+    if (launch_verify_accept(v, s)) return -1;
+    // 5. the rejected rows leave the caches
+    if (e->kc_ext.empty()) {
+        if (launch_verify_clean(e->kc, e->vc, c.n_layer, (int64_t)c.n_ctx * e->kvw, c.n_ctx, e->kvw, p0, k, d_out, s)) return -1;
+    } else {
+        for (int il = 0; il < c.n_layer; ++il)
+            if (launch_verify_clean(kc_of(e, il), vc_of(e, il), 1, 0, c.n_ctx, e->kvw, p0, k, d_out, s)) return -1;
+    }
+    // 6. results: one synchronise
+    GHIP_CHECK(hipMemcpyAsync(h_out, d_out, (size_t)(T + 1) * 4, hipMemcpyDeviceToHost, s));
+    if (logits_all) GHIP_CHECK(hipMemcpyAsync(logits_all, e->pf.LG, (size_t)T * c.n_vocab * 4, hipMemcpyDeviceToHost, s));
+    GHIP_CHECK(hipStreamSynchronize(s));
+    const int a = h_out[0];
+    if (a < 0 || a > k) {
+        set_error("gemma_engine_verify: the accept kernel reported " + std::to_string(a) + " accepted drafts");
+        return -1;
+    }
+    for (int i = 0; i <= a; ++i) out_tokens[i] = h_out[1 + i];
+    e->host_pos = p0 + a + 1;
+    return a + 1;
+}
+
+extern "C" int gemma_engine_kv_read(gemma_engine *e, int layer, int p0, int n, uint16_t *k_rows, uint16_t *v_rows) {
+    set_error("");
+    const gemma_hip_config &c = e->cfg;
+    if (layer < 0 || layer >= c.n_layer || p0 < 0 || n < 1 || (int64_t)p0 + n > c.n_ctx || !k_rows || !v_rows) {
+        set_error("gemma_engine_kv_read: layer or positions out of range");
+        return -1;
+    }
+    (void)hipSetDevice(e->device);
+    GHIP_CHECK(hipStreamSynchronize(e->stream));
+    const size_t kvw = (size_t)e->kvw, ctx = (size_t)c.n_ctx;
+    GHIP_CHECK(hipMemcpy(k_rows, kc_of(e, layer) + (size_t)p0 * kvw, (size_t)n * kvw * 2, hipMemcpyDeviceToHost));
+    std::vector<uint16_t> vt(kvw * (size_t)n);  // V is [kvw][ctx]: columns p0 .. p0+n, then transposed
+    GHIP_CHECK(hipMemcpy2D(vt.data(), (size_t)n * 2, vc_of(e, layer) + p0, ctx * 2, (size_t)n * 2, kvw, hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < kvw; ++j)
+        for (size_t r = 0; r < (size_t)n; ++r) v_rows[r * kvw + j] = vt[j * (size_t)n + r];
+    return 0;
+}
+
+// Prompt-lookup draft: for g = min(ngram_max, n - 1) .. 1, the most recent earlier occurrence of the
+// sequence's last g tokens (largest s < n - g with seq[s .. s+g) == seq[n-g .. n)); the first g with a
+// match wins and the draft is what followed it, seq[s+g .. min(s+g+k, n)).  No GPU.
+extern "C" int gemma_lookup_draft(const int32_t *seq, int n, int ngram_max, int k, int32_t *out) {
+    if (!seq || !out || n < 1 || ngram_max < 1 || k < 1 || k > GEMMA_VERIFY_MAX_DRAFT) {
+        set_error("gemma_lookup_draft: needs n >= 1, ngram_max >= 1 and 1 <= k <= " + std::to_string(GEMMA_VERIFY_MAX_DRAFT));
+        return -1;
+    }
+    for (int g = std::min(ngram_max, n - 1); g >= 1; --g)
+        for (int s = n - g - 1; s >= 0; --s)
+            if (memcmp(seq + s, seq + n - g, (size_t)g * 4) == 0) {
+                const int len = std::min(s + g + k, n) - (s + g);
+                for (int i = 0; i < len; ++i) out[i] = seq[s + g + i];
+                return len;
+            }
+    return 0;
+}
+
+extern "C" int gemma_engine_generate_lookup(gemma_engine *e, int n_new, int k, int ngram_max, int32_t *out,
+                                            gemma_spec_stats *stats) {
+    set_error("");
+    const gemma_hip_config &c = e->cfg;
+    gemma_spec_stats st{0, 0, 0, 0};
+    if (n_new < 0 || (n_new > 0 && !out) || k < 1 || k > GEMMA_VERIFY_MAX_DRAFT || ngram_max < 1) {
+        set_error("gemma_engine_generate_lookup: needs n_new >= 0, 1 <= k <= " + std::to_string(GEMMA_VERIFY_MAX_DRAFT) +
+                  " and ngram_max >= 1");
+        return -1;
+    }
+    if (e->host_pos < e->n_prompt || e->host_pos < 1) {
+        set_error("gemma_engine_generate_lookup: given tokens are still pending (consume the prompt first)");
+        return -1;
+    }
+    if ((int64_t)e->host_pos + n_new >= c.n_ctx) {
+        set_error("gemma_engine_generate_lookup: context full");
+        return -1;
+    }
+    std::vector<int32_t> seq((size_t)c.n_ctx + 1);
+    int n = gemma_engine_tokens(e, seq.data(), c.n_ctx + 1);  // the sequence so far, the pending token included
+    if (n != e->host_pos + 1) return -1;
+    int done = 0;
+    int32_t draft[GEMMA_VERIFY_MAX_DRAFT], got[GEMMA_VERIFY_MAX_DRAFT + 1];
+    while (done < n_new) {
+        // a pass over kd drafts appends up to kd + 1 tokens: never more than remain
+        const int kd_max = std::min(k, n_new - done - 1);
+        // The draft is grown by repeated lookups: one lookup stops at the sequence end (in a repeating
+        // run the most recent match sits right before it and yields a single token), so what it drafted
+        // is appended to the mirror as a guess and the rule applied again, until kd_max tokens or no
+        // match.  The guesses past n are overwritten below by what the pass accepts.
+        int kd = 0;
+        while (kd < kd_max) {
+            const int m = gemma_lookup_draft(seq.data(), n + kd, ngram_max, kd_max - kd, draft + kd);
+            if (m <= 0) break;
+            for (int i = 0; i < m; ++i) seq[n + kd + i] = draft[kd + i];
+            kd += m;
+        }
+        if (kd > 0 && (int64_t)e->host_pos + kd + 1 >= c.n_ctx) kd = 0;
+        if (kd > 0) {
+            const int m = gemma_engine_verify(e, draft, kd, got, nullptr);
+            if (m < 0) return -1;
+            st.passes += 1; st.drafted += kd; st.accepted += m - 1;
+            for (int i = 0; i < m; ++i) seq[n++] = out[done++] = got[i];
+        } else {
+            if (gemma_engine_step(e, 1, nullptr, 1)) return -1;
+            int32_t tok = 0;
+            GHIP_CHECK(hipMemcpy(&tok, e->token, 4, hipMemcpyDeviceToHost));
+            st.plain_steps += 1;
+            seq[n++] = out[done++] = tok;
+        }
+    }
+    if (stats) *stats = st;
+    return 0;
+}

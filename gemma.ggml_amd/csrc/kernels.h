@@ -233,6 +233,11 @@ struct gemm_args {  // Y[t][r] (stride ldy) = W (tiled) x Xq[t] (+ resid), t < T
 int launch_gemm_q(int wtype, int epi, const gemm_args &g, hipStream_t s);
 // the same product in ggml's AVX2 lane order (bit-identical to mul_mat)
 int launch_gemm_exact(int wtype, int epi, const gemm_args &g, hipStream_t s);
+// the same product for 1 <= T <= 8 rows (gemm_skinny.hip): every weight tile loaded once and applied
+// to all T columns, one thread per (row, AVX2 lane) as the decode matvec; reads the int8 image
+// (xq, da); EPI_STORE / EPI_ADD.  T outside [1, 8]: -1 with set_error
+constexpr int GEMM_SKINNY_MAX_T = 8;
+int launch_gemm_skinny(int wtype, int epi, const gemm_args &g, hipStream_t s);
 bool gemm_x4_i8();        // mode 3: k_gemm_x4 stages the activation from the int8 image (xq)
 bool gemm_x4_on();        // the exact GEMM's form: the K = 4 multi-block MFMA kernel (k_gemm_x4) or W32
 void set_gemm_x4(int v);
@@ -420,6 +425,22 @@ struct rope_row {  // k_advance also publishes the new position's RoPE row: cur 
 int launch_advance(const unsigned long long *keys, int n_parts, int *token, int *pos, int *hist, int hist_cap,
                    const int *n_fixed, const rope_row &r, hipStream_t s);
 int launch_set_position(int token, int p, int *pos, int *hist, int *n_fixed, int fixed, const rope_row &r, hipStream_t s);
+
+// ---- speculative verify pass (verify.hip; gemma_engine_verify, DESIGN.md §5b‴) --------------------
+struct verify_args {
+    const unsigned long long *keys = nullptr;  // row i's pick: n_parts partial argmax keys at keys + i * key_stride
+    int n_parts = 0, key_stride = 0;
+    int k = 0, p0 = 0;                         // drafts at hist[p0 + 1 .. p0 + k], the pass's rows p0 .. p0 + k
+    int *token = nullptr, *pos = nullptr, *hist = nullptr;
+    rope_row r;                                // the accepted position's RoPE row, the epoch bump
+    unsigned long long *zero_keys = nullptr;   // the decode step's argmax keys, zeroed as gemma_engine_extend does
+    int n_zero = 0;
+    int *out = nullptr;                        // [0] = a (accepted drafts), [1 + i] = g_i for i <= k
+};
+int launch_verify_accept(const verify_args &v, hipStream_t s);
+// K rows / V columns p0 + *accepted + 1 .. p0 + k of n_layer caches (layer_stride elements apart) zeroed
+int launch_verify_clean(uint16_t *kc, uint16_t *vc, int n_layer, int64_t layer_stride, int ctx, int kvw, int p0, int k,
+                        const int *accepted, hipStream_t s);
 
 // ---- on-device sampling (sample.hip; the rule: include/gemma_hpc.h, DESIGN.md §5b″) ------------
 constexpr int SAMPLE_MAX_K = 1024;  // candidates at most (top_k == 0 means this many)

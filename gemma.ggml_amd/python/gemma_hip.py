@@ -37,7 +37,9 @@ EXPORTS = ["mul_mat", "hpc_init", "hpc_shutdown", "hpc_register_weight", "hpc_la
            "gguf_get_tensor_offset", "gguf_get_version", "gguf_get_alignment", "gguf_get_data_offset",
            "gguf_find_key", "gguf_find_tensor", "ggml_get_tensor", "ggml_nbytes",
            "gemma_engine_create_from_gguf", "gemma_engine_config",
-           "gemma_engine_set_sampler", "gemma_engine_sampler", "gemma_test_sample"]
+           "gemma_engine_set_sampler", "gemma_engine_sampler", "gemma_test_sample",
+           "gemma_engine_verify", "gemma_engine_kv_read", "gemma_lookup_draft", "gemma_engine_generate_lookup",
+           "gemma_test_gemm_skinny"]
 
 
 def build():
@@ -61,6 +63,12 @@ class GemmaSampler(C.Structure):
 
 
 SAMPLE_MAX_K = 1024  # candidates at most (top_k == 0 means this many)
+VERIFY_MAX_DRAFT = 7  # include/gemma_hpc.h GEMMA_VERIFY_MAX_DRAFT
+
+
+class SpecStats(C.Structure):
+    """struct gemma_spec_stats (include/gemma_hpc.h)."""
+    _fields_ = [("passes", C.c_int), ("drafted", C.c_int), ("accepted", C.c_int), ("plain_steps", C.c_int)]
 
 
 class GgmlTensor(C.Structure):
@@ -174,6 +182,16 @@ def lib():
     L.gemma_engine_sampler.argtypes = [vp, C.POINTER(GemmaSampler)]
     L.gemma_test_sample.restype = C.c_int
     L.gemma_test_sample.argtypes = [vp, C.c_int, C.c_int, C.POINTER(GemmaSampler), vp, vp, vp, vp, vp]
+    L.gemma_engine_verify.restype = C.c_int
+    L.gemma_engine_verify.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.gemma_engine_kv_read.restype = C.c_int
+    L.gemma_engine_kv_read.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.gemma_lookup_draft.restype = C.c_int
+    L.gemma_lookup_draft.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    L.gemma_engine_generate_lookup.restype = C.c_int
+    L.gemma_engine_generate_lookup.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(SpecStats)]
+    L.gemma_test_gemm_skinny.restype = C.c_int
+    L.gemma_test_gemm_skinny.argtypes = [C.c_int, i64, i64, i64, vp, vp, vp, vp]
     # GGUF reader (include/ggml.h)
     L.gguf_init_from_file.restype = vp
     L.gguf_init_from_file.argtypes = [C.c_char_p, GGUFInitParams]
@@ -323,6 +341,38 @@ class Engine:
         lg = np.zeros((n, self.cfg.n_vocab), dtype=np.float32) if want_logits else None
         self._chk(self.L.gemma_engine_step(self.h, n, _p(lg) if want_logits else None, 1 if use_graph else 0), "step")
         return lg
+
+    def verify(self, draft, want_all=False):
+        """One exact pass over [pending token, drafts] (gemma_engine_verify): draft[i] is a guess for
+        sequence index pos + 1 + i.  Returns the tokens appended (the accepted drafts plus the token
+        that follows them: 1 .. len(draft) + 1 of them), with want_all also the pass's logits rows
+        [len(draft) + 1][n_vocab] (rows past the accepted ones were computed under rejected drafts)."""
+        d = np.ascontiguousarray([int(x) for x in draft], dtype=np.int32)
+        out = np.zeros(len(d) + 1, dtype=np.int32)
+        allv = np.zeros((len(d) + 1, self.cfg.n_vocab), dtype=np.float32) if want_all else None
+        n = self.L.gemma_engine_verify(self.h, _p(d), len(d), _p(out), _p(allv) if want_all else None)
+        if n < 0:
+            raise RuntimeError("verify failed: " + last_error())
+        toks = [int(t) for t in out[:n]]
+        return (toks, allv) if want_all else toks
+
+    def generate_lookup(self, n_new, k=4, ngram_max=3):
+        """n_new tokens by prompt-lookup drafts and verify passes (gemma_engine_generate_lookup): the
+        tokens step(n_new) appends, and dict(passes, drafted, accepted, plain_steps)."""
+        out = np.zeros(max(int(n_new), 1), dtype=np.int32)
+        st = SpecStats()
+        r = self.L.gemma_engine_generate_lookup(self.h, int(n_new), int(k), int(ngram_max), _p(out), C.byref(st))
+        self._chk(r, "generate_lookup")
+        return [int(t) for t in out[:n_new]], dict(passes=st.passes, drafted=st.drafted, accepted=st.accepted,
+                                                   plain_steps=st.plain_steps)
+
+    def kv_read(self, layer, p0, n):
+        """K rows and V columns p0 .. p0+n of one layer's cache as f16 bits: (k [n][kvw], v [n][kvw])"""
+        kvw = self.cfg.n_head_kv * self.cfg.head_dim
+        k = np.zeros((n, kvw), dtype=np.uint16)
+        v = np.zeros((n, kvw), dtype=np.uint16)
+        self._chk(self.L.gemma_engine_kv_read(self.h, int(layer), int(p0), int(n), _p(k), _p(v)), "kv_read")
+        return k, v
 
     def sync(self):
         """wait for the engine's stream"""
@@ -498,6 +548,31 @@ def test_sample(rows, sampler, positions):
 
 
 test_sample.__test__ = False  # a library wrapper, not a pytest test
+
+
+def lookup_draft(seq, ngram_max, k):
+    """Prompt-lookup draft for `seq` (gemma_lookup_draft, a host function: no GPU): the tokens that
+    followed the most recent earlier occurrence of the longest matching suffix n-gram, at most k."""
+    a = np.ascontiguousarray([int(x) for x in seq], dtype=np.int32)
+    out = np.zeros(VERIFY_MAX_DRAFT, dtype=np.int32)
+    n = lib().gemma_lookup_draft(_p(a), len(a), int(ngram_max), int(k), _p(out))
+    if n < 0:
+        raise ValueError("gemma_lookup_draft: " + last_error())
+    return [int(t) for t in out[:n]]
+
+
+def gemm_skinny(wtype, W, rows, X, resid=None):
+    """The skinny exact GEMM on host buffers (gemma_test_gemm_skinny): W ggml row-major blocks,
+    X [T][K] f32, resid [T][rows] or None; returns Y [T][rows]."""
+    x = np.ascontiguousarray(X, dtype=np.float32)
+    T, K = x.shape
+    y = np.zeros((T, rows), dtype=np.float32)
+    r = None if resid is None else np.ascontiguousarray(resid, dtype=np.float32)
+    w = np.ascontiguousarray(W)
+    rc = lib().gemma_test_gemm_skinny(int(wtype), rows, K, T, _p(w), _p(x), None if r is None else _p(r), _p(y))
+    if rc != 0:
+        raise RuntimeError("gemma_test_gemm_skinny failed: " + last_error())
+    return y
 
 
 def tp_unique_id():

@@ -162,6 +162,44 @@ int gemma_engine_sampler(const gemma_engine *e, gemma_sampler *out);   /* 1 = sa
  * n_kept[rows] = m */
 int gemma_test_sample(const float *logits, int rows, int n_vocab, const gemma_sampler *s,
                       const int32_t *positions, int32_t *tokens, int32_t *cand, int32_t *n_cand, int32_t *n_kept);
+/* Speculative decoding without a quality trade-off (DESIGN.md §5b‴).  A batched exact pass over
+ * [pending token, k drafted tokens] computes the logits rows k + 1 single steps would compute, bit for
+ * bit, and a pick depends on its row and position alone (greedy, or the sampler's (seed, p) rule), so
+ * accepting the longest correct prefix yields exactly the sequence gemma_engine_step yields.
+ * Precondition: the prompt is consumed (pos == n_seq, so hist[pos] is the pending picked token).
+ * draft[0..k) are guesses for sequence indices pos+1 .. pos+k (1 <= k <= GEMMA_VERIFY_MAX_DRAFT, ids in
+ * [0, n_vocab), pos + k + 1 < n_ctx).  One pass of k + 1 rows at p0 = pos (the Q4_0 / Q8_0 GEMMs on the
+ * skinny exact GEMM, weights streamed once), a pick g_i from every row i for index pos + i + 1, then on
+ * the device: a = the number of leading i < k with draft[i] == g_i (it stops at the first mismatch,
+ * whatever later drafts say); hist[pos+1 .. pos+a+1] = g_0 .. g_a; pos += a + 1; the K / V rows the
+ * pass stored for rejected drafts are cleared.  The device state afterwards is byte for byte what
+ * a + 1 calls of gemma_engine_step leave, and the captured decode graph is kept.
+ * Returns a + 1 (>= 1) with out_tokens[0..a] = g_0 .. g_a (room for k + 1).  logits_all (may be NULL):
+ * [k + 1][n_vocab]; rows 0..a are the sequence's own rows, rows past a are returned as computed under
+ * the rejected drafts (they belong to no sequence position).  One host synchronise, at the end.
+ * -1 with hpc_last_error naming gemma_engine_verify and the state untouched: given tokens still
+ * pending, bad k, a bad token id, pos + k + 1 >= n_ctx, a row-split engine (tp_n > 1, a communicator,
+ * virtual ranks). */
+#define GEMMA_VERIFY_MAX_DRAFT 7
+int gemma_engine_verify(gemma_engine *e, const int32_t *draft, int k, int32_t *out_tokens, float *logits_all);
+/* test entry: K rows and V columns p0 .. p0+n of one layer's cache, f16 bits; k_rows [n][kvw], v_rows
+ * [n][kvw] (V transposed), kvw = n_head_kv * head_dim */
+int gemma_engine_kv_read(gemma_engine *e, int layer, int p0, int n, uint16_t *k_rows, uint16_t *v_rows);
+/* Prompt-lookup draft for the sequence seq[0..n) (pure host function, no GPU): for g = min(ngram_max,
+ * n - 1) down to 1, the largest s < n - g with seq[s..s+g) == seq[n-g..n); the first g with a match
+ * wins and the draft is seq[s+g .. min(s+g+k, n)).  Returns its length (0: no g matches), -1 on
+ * ngram_max < 1 or k outside [1, GEMMA_VERIFY_MAX_DRAFT]. */
+int gemma_lookup_draft(const int32_t *seq, int n, int ngram_max, int k, int32_t *out);
+/* passes: verify calls; drafted / accepted: draft tokens sent / accepted; plain_steps: graph steps taken
+ * when no draft existed.  Tokens appended = passes + accepted + plain_steps. */
+typedef struct gemma_spec_stats { int passes, drafted, accepted, plain_steps; } gemma_spec_stats;
+/* n_new tokens by lookup drafts: the sequence (the pending token included) is mirrored on the host,
+ * drafted from with gemma_lookup_draft, and a draft is verified (else one graph step runs).  A draft is
+ * grown to k tokens by repeated lookups (what a lookup drafted is appended as a guess and the rule
+ * applied again: one lookup stops at the sequence end) and shortened so that never more than n_new
+ * tokens are appended.  out[0..n_new) and the final pos equal
+ * gemma_engine_step(n_new) token for token, sampler on or off.  0, or -1 with hpc_last_error. */
+int gemma_engine_generate_lookup(gemma_engine *e, int n_new, int k, int ngram_max, int32_t *out, gemma_spec_stats *stats);
 /* weights back in ggml row-major layout (tests); tid as in DESIGN.md §Synthetic weights */
 int64_t gemma_engine_tensor(gemma_engine *e, int tid, void *dst, int64_t cap);
 /* time `iters` launches of one hot kernel with hipEvents on the engine stream; returns avg µs and
@@ -224,6 +262,11 @@ int gemma_test_gemm(int type, int64_t rows, int64_t K, int64_t T, const void *W,
 /* the same with the exact (ggml AVX2 lane order) GEMM of the exact prefill */
 int gemma_test_gemm_exact(int type, int64_t rows, int64_t K, int64_t T, const void *W, const float *X, float *Y,
                           int8_t *xq_out, float *da_out);
+/* the same product for 1 <= T <= 8 rows through the skinny exact GEMM of the verify pass (each weight
+ * tile loaded once for all T columns): Y[T][rows] = W x Q8_0(X) (+ resid [T][rows], may be NULL);
+ * bit-identical to gemma_test_gemm_exact and mul_mat.  T outside [1, 8]: -1 with hpc_last_error */
+int gemma_test_gemm_skinny(int type, int64_t rows, int64_t K, int64_t T, const void *W, const float *X,
+                           const float *resid, float *Y);
 /* K-quant matvec (Q4_K / Q6_K x Q8_K) timed alone: avg µs per launch over
  * `iters` launches rotating over cold weight copies; *algo_bytes = weights + Q8_K column + y */
 double gemma_kq_time(int type, int64_t rows, int64_t K, int iters, double *algo_bytes);
