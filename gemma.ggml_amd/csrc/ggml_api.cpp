@@ -29,6 +29,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <tuple>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
@@ -194,7 +195,9 @@ struct executor {
     bool inited = false;
     hipStream_t stream = nullptr;
     std::unordered_map<const void *, leaf_mirror> leaves;  // keyed by root host data pointer
-    std::map<std::pair<const void *, int>, tiled_mat> tiled;  // quantized src0 re-tiled for the hot path
+    // quantized src0 re-tiled for the hot path, keyed by (data, type, ne0, ne1): two views of one
+    // weight (a row range from its first row, a reshape) share a pointer but not a tiling
+    std::map<std::tuple<const void *, int, int64_t, int64_t>, tiled_mat> tiled;
     std::unordered_set<const ggml_backend_buffer *> buffers;
     char *scratch = nullptr;
     size_t scratch_bytes = 0;
@@ -316,8 +319,7 @@ int sync_leaf(ggml_tensor *r, bool graph_written) {
 
 const tiled_mat *tiled_weight(run_state &rs, ggml_tensor *w) {
     executor &e = ex();
-    ggml_tensor *r = root_of(w);
-    const auto key = std::make_pair((const void *)w->data, (int)w->type);
+    const auto key = std::make_tuple((const void *)w->data, (int)w->type, w->ne[0], w->ne[1]);
     auto it = e.tiled.find(key);
     if (it != e.tiled.end()) return &it->second;
     if (!is_contiguous(w)) {
@@ -331,8 +333,22 @@ const tiled_mat *tiled_weight(run_state &rs, ggml_tensor *w) {
         if (!src) set_error("ggml mul_mat: src0 has no device data");
         return nullptr;
     }
-    (void)r;
     return &(e.tiled[key] = m);
+}
+
+// the tiled copies of every src0 whose data starts inside [p, p + bytes): that host memory is
+// being freed or rewritten (caller holds the executor's lock)
+void drop_tiled_in(const void *p, size_t bytes) {
+    executor &e = ex();
+    for (auto it = e.tiled.begin(); it != e.tiled.end();) {
+        const char *k = (const char *)std::get<0>(it->first);
+        if (k >= (const char *)p && k < (const char *)p + bytes) {
+            free_tiled(it->second);
+            it = e.tiled.erase(it);
+        } else {
+            ++it;
+        }
+    }
 }
 
 int run_mul_mat(run_state &rs, ggml_tensor *node) {
@@ -954,14 +970,14 @@ void ggml_free(struct ggml_context *ctx) {
     for (const ggml_tensor *t : ctx->tensors)
         if (!t->view_src && t->data) {
             lo = std::min(lo, (uintptr_t)t->data);
-            hi = std::max(hi, (uintptr_t)t->data + 1);
+            hi = std::max(hi, (uintptr_t)t->data + std::max<size_t>(ggml_nbytes(t), 1));
         }
     auto inside = [&](const void *p) { return (uintptr_t)p >= lo && (uintptr_t)p < hi; };
     {
         std::lock_guard<std::recursive_mutex> lk(ex().mu);
         bool any = false;
         for (const auto &kv : ex().leaves) any = any || inside(kv.first);
-        for (const auto &kv : ex().tiled) any = any || inside(kv.first.first);
+        for (const auto &kv : ex().tiled) any = any || inside(std::get<0>(kv.first));
         // a freed compute context's tensors leave the executor's caches keyed by their data
         if (any)
         for (ggml_tensor *t : ctx->tensors) {
@@ -971,12 +987,11 @@ void ggml_free(struct ggml_context *ctx) {
                 (void)hipFree(it->second.dev);
                 ex().leaves.erase(it);
             }
-            auto tt = ex().tiled.find(std::make_pair((const void *)t->data, (int)t->type));
-            if (tt != ex().tiled.end()) {
-                free_tiled(tt->second);
-                ex().tiled.erase(tt);
-            }
         }
+        // tiled copies are keyed by the src0 pointer, which for a view lies inside its root's data
+        if (any && !ex().tiled.empty())
+            for (const ggml_tensor *t : ctx->tensors)
+                if (!t->view_src && t->data) drop_tiled_in(t->data, ggml_nbytes(t));
         // a freed weight context takes the fast path's device copy of its weights with it; under the
         // executor's lock, which try_fast holds while it runs that engine
         fast_engine &f = fast();
@@ -1384,6 +1399,7 @@ void ggml_backend_buffer_clear(ggml_backend_buffer_t b, uint8_t value) {
         auto it = ex().leaves.find(t->data);
         if (it != ex().leaves.end()) it->second.valid = false;
     }
+    drop_tiled_in(b->mem, b->size);  // quantized weights in the buffer were rewritten too
 }
 const char *ggml_backend_buffer_name(ggml_backend_buffer_t b) {
     (void)b;
@@ -1400,6 +1416,7 @@ void ggml_backend_buffer_free(ggml_backend_buffer_t b) {
             ex().leaves.erase(it);
         }
     }
+    drop_tiled_in(b->mem, b->size);
     ex().buffers.erase(b);
     free(b->mem);
     delete b;
@@ -1409,6 +1426,8 @@ void ggml_backend_tensor_set(struct ggml_tensor *t, const void *data, size_t off
     memcpy((char *)t->data + offset, data, size);
     std::lock_guard<std::recursive_mutex> lk(ex().mu);
     ggml_tensor *r = root_of(t);
+    // a rewritten quantized weight: its tiled copies (of the tensor and of views into it) are stale
+    if (!ex().tiled.empty() && blck_size(r->type) > 1) drop_tiled_in(r->data, ggml_nbytes(r));
     auto it = ex().leaves.find(r->data);
     if (it != ex().leaves.end() && it->second.valid) {  // keep a device-authoritative mirror current
         const size_t off = (size_t)((char *)t->data - (char *)r->data) + offset;

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import oracle_ctypes as O
+from ggml_ctypes import build_driver
 from gguf_writer import ARR, F32, STR, U32, GGUFWriter
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,6 +24,7 @@ gpu = pytest.mark.gpu
 
 
 def test_driver_built():
+    build_driver()  # links it again if only the binary is missing
     assert os.path.exists(DRIVER), "make -C gemma.ggml_amd builds the ggml graph driver"
 
 

@@ -1,55 +1,13 @@
 """ggml graph executor, K-quant ops one node at a time through the ggml API (include/ggml.h, via
 ctypes): get_rows of Q4_0 / Q8_0 / Q4_K / Q6_K rows (ggml dequantize_row_*) and mul_mat with Q4_K /
 Q6_K src0 (device Q8_K INIT + the AVX2-lane-order K-quant dot), bit-identical to the oracle."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
-import gemma_hip as G
 import oracle_ctypes as O
+from ggml_ctypes import InitParams, _api, _compute, _get, _put
 
 gpu = pytest.mark.gpu
-
-
-class InitParams(C.Structure):
-    _fields_ = [("mem_size", C.c_size_t), ("mem_buffer", C.c_void_p), ("no_alloc", C.c_bool)]
-
-
-def _api():
-    L = G.lib()
-    T = C.POINTER(G.GgmlTensor)
-    L.ggml_init.restype = C.c_void_p
-    L.ggml_init.argtypes = [InitParams]
-    L.ggml_new_tensor_1d.restype = T
-    L.ggml_new_tensor_1d.argtypes = [C.c_void_p, C.c_int, C.c_int64]
-    L.ggml_new_tensor_2d.restype = T
-    L.ggml_new_tensor_2d.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64]
-    L.ggml_get_rows.restype = T
-    L.ggml_get_rows.argtypes = [C.c_void_p, T, T]
-    L.ggml_mul_mat.restype = T
-    L.ggml_mul_mat.argtypes = [C.c_void_p, T, T]
-    L.ggml_new_graph.restype = C.c_void_p
-    L.ggml_new_graph.argtypes = [C.c_void_p]
-    L.ggml_build_forward_expand.argtypes = [C.c_void_p, T]
-    L.ggml_graph_compute_with_ctx.restype = C.c_int
-    L.ggml_graph_compute_with_ctx.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    return L
-
-
-def _put(t, arr):
-    b = np.ascontiguousarray(arr).view(np.uint8).ravel()
-    C.memmove(t.contents.data, b.ctypes.data, b.size)
-
-
-def _get(t, n):
-    return np.ctypeslib.as_array((C.c_float * n).from_address(t.contents.data)).copy()
-
-
-def _compute(L, ctx, out):
-    g = L.ggml_new_graph(ctx)
-    L.ggml_build_forward_expand(g, out)
-    assert L.ggml_graph_compute_with_ctx(ctx, g, 1) == 0, G.last_error()
 
 
 @gpu

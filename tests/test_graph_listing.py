@@ -19,6 +19,8 @@ import subprocess
 
 import pytest
 
+from ggml_ctypes import build_driver
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER = os.path.join(ROOT, "tests", "ggml_driver", "gemma_graph_driver")
 FIXTURE = os.path.join(ROOT, "tests", "golden", "tensor_in_target_cgraph.txt")
@@ -44,6 +46,7 @@ def _target():
 
 
 def _ours(T, decode):
+    build_driver()  # links it again if only the binary is missing
     if not os.path.exists(DRIVER):
         pytest.skip("driver not built (make -C gemma.ggml_amd)")
     out = subprocess.run([DRIVER, "--graph-listing", *GEMMA_2B, str(T), "1" if decode else "0"], capture_output=True,
