@@ -20,11 +20,6 @@
 #include "ggml_impl.h"
 #include "kernels.h"
 
-namespace ghip {
-tiled_mat alloc_tiled(int type, int64_t rows, int64_t K, hipStream_t s);
-void free_tiled(tiled_mat &m);
-}  // namespace ghip
-
 using namespace ghip;
 
 namespace {
@@ -43,6 +38,7 @@ struct hpc_state {
     bool inited = false;
     int device = 0;
     hipStream_t stream = nullptr;
+    dev_pool mem;  // owns every cached weight copy, the scratch and the host stage
     std::map<weight_key, tiled_mat> weights;
     std::map<weight_key, uint8_t *> raw_weights;  // K-quants: ggml row-major super-blocks, packed rows
     void *scratch = nullptr;
@@ -55,8 +51,10 @@ struct hpc_state {
 };
 
 hpc_state &st() {
-    static hpc_state s;
-    return s;
+    // never destroyed: what hpc_shutdown has not freed is left to the process's end, not to a static
+    // destructor that would call into a runtime already shut down
+    static hpc_state *s = new hpc_state;
+    return *s;
 }
 
 void fail(const std::string &msg) {
@@ -70,9 +68,9 @@ void fail(const std::string &msg) {
 int ensure_scratch(size_t bytes) {
     hpc_state &s = st();
     if (s.scratch_bytes >= bytes) return 0;
-    if (s.scratch) GHIP_CHECK(hipFree(s.scratch));
-    s.scratch = nullptr;
-    GHIP_CHECK(hipMalloc(&s.scratch, bytes));
+    s.mem.put(s.scratch);
+    s.scratch_bytes = 0;
+    if (s.mem.get(&s.scratch, bytes)) return -1;
     s.scratch_bytes = bytes;
     return 0;
 }
@@ -83,24 +81,20 @@ const tiled_mat *get_weight(const weight_key &k) {
     if (it != s.weights.end()) return &it->second;
     const int bb = k.type == T_Q4_0 ? 18 : 34;
     const int64_t row_bytes = k.ne00 / 32 * bb;
+    dev_pool tmp;
     uint8_t *dev_rows = nullptr;
-    if (hipMalloc(&dev_rows, (size_t)(row_bytes * k.ne01)) != hipSuccess) {
-        set_error("mul_mat: weight upload alloc failed");
-        return nullptr;
-    }
+    if (tmp.get(&dev_rows, (size_t)(row_bytes * k.ne01))) return nullptr;
     // rows are row_bytes long at stride nb01 on the host
     if (hipMemcpy2D(dev_rows, row_bytes, k.host, k.nb01, row_bytes, k.ne01, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(dev_rows);
         set_error("mul_mat: weight upload failed");
         return nullptr;
     }
-    tiled_mat m = alloc_tiled(k.type, k.ne01, k.ne00, s.stream);
+    tiled_mat m;
+    if (alloc_tiled(s.mem, &m, k.type, k.ne01, k.ne00, s.stream)) return nullptr;
     if (launch_repack(m, dev_rows, row_bytes, s.stream) != 0 || hipStreamSynchronize(s.stream) != hipSuccess) {
-        (void)hipFree(dev_rows);
-        free_tiled(m);
+        free_tiled(s.mem, m);
         return nullptr;
     }
-    (void)hipFree(dev_rows);
     return &(s.weights[k] = m);
 }
 
@@ -113,12 +107,9 @@ const uint8_t *get_raw_weight(const weight_key &k) {
     if (it != s.raw_weights.end()) return it->second;
     const int64_t row_bytes = kq_row_bytes(k.type, k.ne00);
     uint8_t *dev = nullptr;
-    if (hipMalloc(&dev, (size_t)(row_bytes * k.ne01)) != hipSuccess) {
-        set_error("mul_mat: weight upload alloc failed");
-        return nullptr;
-    }
+    if (s.mem.get(&dev, (size_t)(row_bytes * k.ne01))) return nullptr;
     if (hipMemcpy2D(dev, row_bytes, k.host, k.nb01, row_bytes, k.ne01, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(dev);
+        s.mem.put(dev);
         set_error("mul_mat: weight upload failed");
         return nullptr;
     }
@@ -143,12 +134,9 @@ extern "C" void hpc_shutdown(void) {
     hpc_state &s = st();
     std::lock_guard<std::recursive_mutex> lk(s.mu);
     if (!s.inited) return;
-    for (auto &kv : s.weights) free_tiled(kv.second);
     s.weights.clear();
-    for (auto &kv : s.raw_weights) (void)hipFree(kv.second);
     s.raw_weights.clear();
-    if (s.scratch) (void)hipFree(s.scratch);
-    if (s.host_stage) (void)hipHostFree(s.host_stage);
+    s.mem.clear();
     s.scratch = s.host_stage = nullptr;
     s.scratch_bytes = s.host_stage_bytes = 0;
     (void)hipStreamDestroy(s.stream);
@@ -181,7 +169,7 @@ extern "C" int hpc_unregister_weight(const void *host) {
     int n = 0;
     for (auto it = s.weights.begin(); it != s.weights.end();) {
         if (it->first.host == host) {
-            free_tiled(it->second);
+            free_tiled(s.mem, it->second);
             it = s.weights.erase(it);
             ++n;
         } else {
@@ -190,7 +178,7 @@ extern "C" int hpc_unregister_weight(const void *host) {
     }
     for (auto it = s.raw_weights.begin(); it != s.raw_weights.end();) {
         if (it->first.host == host) {
-            (void)hipFree(it->second);
+            s.mem.put(it->second);
             it = s.raw_weights.erase(it);
             ++n;
         } else {
@@ -205,9 +193,9 @@ extern "C" void hpc_flush_weights(void) {
     hpc_state &s = st();
     std::lock_guard<std::recursive_mutex> lk(s.mu);
     if (s.inited) (void)hipStreamSynchronize(s.stream);
-    for (auto &kv : s.weights) free_tiled(kv.second);
+    for (auto &kv : s.weights) free_tiled(s.mem, kv.second);
     s.weights.clear();
-    for (auto &kv : s.raw_weights) (void)hipFree(kv.second);
+    for (auto &kv : s.raw_weights) s.mem.put(kv.second);
     s.raw_weights.clear();
 }
 
@@ -356,8 +344,9 @@ extern "C" void mul_mat(int64_t ne01, int64_t ne11, int64_t ne12, int64_t nb01, 
     }
     // copy back with the reference's dst addressing
     if (s.host_stage_bytes < dst_bytes) {
-        if (s.host_stage) (void)hipHostFree(s.host_stage);
-        if (hipHostMalloc(&s.host_stage, dst_bytes, 0) != hipSuccess) return fail("mul_mat: host stage alloc failed");
+        s.mem.put(s.host_stage);
+        s.host_stage_bytes = 0;
+        if (s.mem.get(&s.host_stage, dst_bytes, MEM_PINNED)) return fail("mul_mat: host stage alloc failed");
         s.host_stage_bytes = dst_bytes;
     }
     if (hipMemcpyAsync(s.host_stage, dev_dst, dst_bytes, hipMemcpyDeviceToHost, s.stream) != hipSuccess ||
@@ -386,15 +375,15 @@ static int test_gemm(bool exact, int type, int64_t rows, int64_t K, int64_t T, c
     float *d_x = nullptr, *d_y = nullptr, *d_da = nullptr;
     int8_t *d_q = nullptr;
     uint16_t *d_h = nullptr;
-    GHIP_CHECK(hipMalloc(&d_rows, (size_t)(row_bytes * rows)));
-    GHIP_CHECK(hipMalloc(&d_x, (size_t)(T * K * 4)));
-    GHIP_CHECK(hipMalloc(&d_y, (size_t)(T * rows * 4)));
-    GHIP_CHECK(hipMalloc(&d_q, (size_t)(T * ldq)));
-    GHIP_CHECK(hipMalloc(&d_da, (size_t)(T * ldd * 4)));
-    GHIP_CHECK(hipMalloc(&d_h, (size_t)(T * ldq * 2)));
+    dev_pool tmp;
+    if (tmp.get(&d_rows, (size_t)(row_bytes * rows)) || tmp.get(&d_x, (size_t)(T * K * 4)) ||
+        tmp.get(&d_y, (size_t)(T * rows * 4)) || tmp.get(&d_q, (size_t)(T * ldq)) || tmp.get(&d_da, (size_t)(T * ldd * 4)) ||
+        tmp.get(&d_h, (size_t)(T * ldq * 2)))
+        return -1;
     GHIP_CHECK(hipMemcpy(d_rows, W, (size_t)(row_bytes * rows), hipMemcpyHostToDevice));
     GHIP_CHECK(hipMemcpy(d_x, X, (size_t)(T * K * 4), hipMemcpyHostToDevice));
-    tiled_mat m = alloc_tiled(type, rows, K, nullptr);
+    tiled_mat m;
+    if (alloc_tiled(tmp, &m, type, rows, K, nullptr)) return -1;
     int r = launch_repack(m, d_rows, row_bytes, nullptr);
     qrow_args qa;
     qa.x = d_x; qa.ldx = K; qa.K = K; qa.q = d_q; qa.qh = exact ? d_h : nullptr; qa.ldq = ldq; qa.da = d_da; qa.ldd = ldd;
@@ -412,9 +401,6 @@ static int test_gemm(bool exact, int type, int64_t rows, int64_t K, int64_t T, c
             GHIP_CHECK(hipMemcpy2D(da_out, (size_t)(K / 32 * 4), d_da, (size_t)(ldd * 4), (size_t)(K / 32 * 4), (size_t)T,
                                    hipMemcpyDeviceToHost));
     }
-    free_tiled(m);
-    void *bufs[] = {d_rows, d_x, d_y, d_q, d_da, d_h};
-    for (void *p : bufs) (void)hipFree(p);
     return r;
 }
 
@@ -446,16 +432,16 @@ extern "C" int gemma_test_gemm_skinny(int type, int64_t rows, int64_t K, int64_t
     uint8_t *d_rows = nullptr;
     float *d_x = nullptr, *d_y = nullptr, *d_da = nullptr, *d_r = nullptr;
     int8_t *d_q = nullptr;
-    GHIP_CHECK(hipMalloc(&d_rows, (size_t)(row_bytes * rows)));
-    GHIP_CHECK(hipMalloc(&d_x, (size_t)(T * K * 4)));
-    GHIP_CHECK(hipMalloc(&d_y, (size_t)(T * rows * 4)));
-    GHIP_CHECK(hipMalloc(&d_r, (size_t)(T * rows * 4)));
-    GHIP_CHECK(hipMalloc(&d_q, (size_t)(T * ldq)));
-    GHIP_CHECK(hipMalloc(&d_da, (size_t)(T * ldd * 4)));
+    dev_pool tmp;
+    if (tmp.get(&d_rows, (size_t)(row_bytes * rows)) || tmp.get(&d_x, (size_t)(T * K * 4)) ||
+        tmp.get(&d_y, (size_t)(T * rows * 4)) || tmp.get(&d_r, (size_t)(T * rows * 4)) || tmp.get(&d_q, (size_t)(T * ldq)) ||
+        tmp.get(&d_da, (size_t)(T * ldd * 4)))
+        return -1;
     GHIP_CHECK(hipMemcpy(d_rows, W, (size_t)(row_bytes * rows), hipMemcpyHostToDevice));
     GHIP_CHECK(hipMemcpy(d_x, X, (size_t)(T * K * 4), hipMemcpyHostToDevice));
     if (resid) GHIP_CHECK(hipMemcpy(d_r, resid, (size_t)(T * rows * 4), hipMemcpyHostToDevice));
-    tiled_mat m = alloc_tiled(type, rows, K, nullptr);
+    tiled_mat m;
+    if (alloc_tiled(tmp, &m, type, rows, K, nullptr)) return -1;
     int r = launch_repack(m, d_rows, row_bytes, nullptr);
     qrow_args qa;
     qa.x = d_x; qa.ldx = K; qa.K = K; qa.q = d_q; qa.ldq = ldq; qa.da = d_da; qa.ldd = ldd;
@@ -466,9 +452,6 @@ extern "C" int gemma_test_gemm_skinny(int type, int64_t rows, int64_t K, int64_t
     if (r == 0) r = launch_gemm_skinny(type, resid ? EPI_ADD : EPI_STORE, g, nullptr);
     if (r == 0) GHIP_CHECK(hipDeviceSynchronize());
     if (r == 0) GHIP_CHECK(hipMemcpy(Y, d_y, (size_t)(T * rows * 4), hipMemcpyDeviceToHost));
-    free_tiled(m);
-    void *bufs[] = {d_rows, d_x, d_y, d_r, d_q, d_da};
-    for (void *p : bufs) (void)hipFree(p);
     return r;
 }
 
@@ -486,11 +469,8 @@ extern "C" double gemma_kq_time(int type, int64_t rows, int64_t K, int iters, do
     const int copies = (int)std::max<int64_t>(1, std::min<int64_t>(16, (int64_t)(768ull << 20) / (int64_t)wbytes));
     uint8_t *w = nullptr, *x = nullptr;
     float *y = nullptr;
-    if (hipMalloc(&w, wbytes * copies) != hipSuccess || hipMalloc(&x, (size_t)nsb * 292) != hipSuccess ||
-        hipMalloc(&y, (size_t)rows * 4) != hipSuccess) {
-        set_error("gemma_kq_time: alloc failed");
-        return -1.0;
-    }
+    dev_pool tmp;
+    if (tmp.get(&w, wbytes * copies) || tmp.get(&x, (size_t)nsb * 292) || tmp.get(&y, (size_t)rows * 4)) return -1.0;
     // valid-looking data: bytes 0x11 with small fp16 scales (value does not change the timing)
     (void)hipMemset(w, 0x11, wbytes * copies);
     (void)hipMemset(x, 0x01, (size_t)nsb * 292);
@@ -517,9 +497,6 @@ extern "C" double gemma_kq_time(int type, int64_t rows, int64_t K, int iters, do
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     (void)hipStreamDestroy(s);
-    (void)hipFree(w);
-    (void)hipFree(x);
-    (void)hipFree(y);
     if (r) return -1.0;
     if (algo_bytes) *algo_bytes = (double)wbytes + (double)nsb * 292 + (double)rows * 4;
     return (double)ms * 1e3 / iters;

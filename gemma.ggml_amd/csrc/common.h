@@ -12,6 +12,8 @@
 
 #include <string>
 
+#include "dev_mem.h"
+
 namespace ghip {
 
 // ggml type ids (GGUF numbering)
@@ -70,16 +72,6 @@ const std::string &last_error();
             ::ghip::set_error(std::string(#expr) + ": " + hipGetErrorString(_e) + " @" +          \
                               __FILE__ + ":" + std::to_string(__LINE__));                       \
             return -1;                                                                          \
-        }                                                                                       \
-    } while (0)
-
-#define GHIP_FATAL(expr)                                                                        \
-    do {                                                                                        \
-        hipError_t _e = (expr);                                                                 \
-        if (_e != hipSuccess) {                                                                 \
-            fprintf(stderr, "[gemma_hip] fatal HIP error %s at %s:%d: %s\n", #expr, __FILE__,     \
-                    __LINE__, hipGetErrorString(_e));                                           \
-            abort();                                                                            \
         }                                                                                       \
     } while (0)
 

@@ -96,7 +96,7 @@ enum { TID_EMBD = 0, TID_OUT_NORM = 1 };
 static inline int tid_layer(int il, int k) { return 16 + il * 16 + k; }
 enum { L_ATTN_NORM = 0, L_Q = 1, L_K = 2, L_V = 3, L_O = 4, L_FFN_NORM = 5, L_GATE = 6, L_UP = 7, L_DOWN = 8 };
 
-tiled_mat alloc_tiled(int type, int64_t rows, int64_t K, hipStream_t s) {
+int alloc_tiled(dev_pool &mem, tiled_mat *out, int type, int64_t rows, int64_t K, hipStream_t s) {
     tiled_mat m;
     m.type = type;
     m.rows = rows;
@@ -105,18 +105,17 @@ tiled_mat alloc_tiled(int type, int64_t rows, int64_t K, hipStream_t s) {
     m.n_rt = (rows + 7) / 8;
     const int bt = type == T_Q4_0 ? 8 : 4;
     m.n_bt = (m.nb + bt - 1) / bt;
-    GHIP_FATAL(hipMalloc(&m.qs, m.qs_bytes()));
-    GHIP_FATAL(hipMalloc(&m.sc, m.sc_bytes()));
-    // zero on the SAME stream as the generator / repack that fills it (non-blocking streams do
-    // not order against the null stream)
-    GHIP_FATAL(hipMemsetAsync(m.qs, 0, m.qs_bytes(), s));
-    GHIP_FATAL(hipMemsetAsync(m.sc, 0, m.sc_bytes(), s));
-    return m;
+    // zeroed on the SAME stream as the generator / repack that fills it
+    if (mem.get_zeroed(&m.qs, m.qs_bytes(), s) || mem.get_zeroed(&m.sc, m.sc_bytes(), s)) {
+        mem.put(m.qs);
+        return -1;
+    }
+    *out = m;
+    return 0;
 }
-void free_tiled(tiled_mat &m) {
-    if (m.qs) (void)hipFree(m.qs);
-    if (m.sc) (void)hipFree(m.sc);
-    m.qs = m.sc = nullptr;
+void free_tiled(dev_pool &mem, tiled_mat &m) {
+    mem.put(m.qs);
+    mem.put(m.sc);
 }
 
 }  // namespace ghip
@@ -127,12 +126,12 @@ static int kq_retile_inplace(uint8_t *w, int type, int64_t rows, int64_t K, hipS
     *tiled = false;
     if (type == T_Q6_K && K % 2048) return 0;
     const size_t bytes = (size_t)(K / 256 * (type == T_Q4_K ? 144 : 210) * rows);
+    dev_pool tmp_mem;
     uint8_t *tmp = nullptr;
-    GHIP_CHECK(hipMalloc(&tmp, bytes));
+    if (tmp_mem.get(&tmp, bytes)) return -1;
     if (launch_kq_retile(type, w, tmp, rows, K, true, s)) return -1;
     GHIP_CHECK(hipMemcpyAsync(w, tmp, bytes, hipMemcpyDeviceToDevice, s));
     GHIP_CHECK(hipStreamSynchronize(s));
-    GHIP_CHECK(hipFree(tmp));
     *tiled = true;
     return 0;
 }
@@ -150,12 +149,12 @@ static int upload_rows(const tiled_mat &dst, const void *host, int64_t r0, hipSt
         return 0;  // stream-ordered; engine_create synchronises before the first use
     }
     const int64_t rb = dst.nb * (dst.type == T_Q4_0 ? 18 : 34);
+    dev_pool tmp_mem;
     uint8_t *tmp = nullptr;
-    GHIP_CHECK(hipMalloc(&tmp, (size_t)(rb * dst.rows)));
+    if (tmp_mem.get(&tmp, (size_t)(rb * dst.rows))) return -1;
     GHIP_CHECK(hipMemcpyAsync(tmp, (const uint8_t *)host + r0 * rb, (size_t)(rb * dst.rows), hipMemcpyHostToDevice, s));
     const int rc = launch_repack(dst, tmp, rb, s);
     GHIP_CHECK(hipStreamSynchronize(s));
-    GHIP_CHECK(hipFree(tmp));
     return rc;
 }
 
@@ -206,56 +205,55 @@ static bool set_shards(gemma_engine *e, int tp_n, int tp_rank, const void *nccl_
 }
 
 // token_embd / tied output and the output norm: uploaded, or the synthetic generator straight into
-// the device layout (matches oracle/gemma_cpu.cpp); returns true when an upload failed
-static bool create_embeddings(gemma_engine *e, const host_weights *hw) {
+// the device layout (matches oracle/gemma_cpu.cpp); -1 when an allocation or upload failed
+static int create_embeddings(gemma_engine *e, const host_weights *hw) {
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
-    bool fail = false;
     const double emb_std = (c.out_gain > 0.0f ? (double)c.out_gain : 1.0) / sqrt((double)c.n_embd);
     if (e->out_type == T_Q6_K) {  // oracle make_kmat(TID_EMBD, Q6_K, out_gain/sqrt(E)) on the device
         e->embd_row_bytes = (int64_t)c.n_embd / 256 * 210;
-        GHIP_FATAL(hipMalloc(&e->embd_q6k, (size_t)(e->embd_row_bytes * c.n_vocab)));
-        GHIP_FATAL(hipMalloc(&e->xq8k, (size_t)c.n_embd / 256 * 292));
-        e->xq8k_rows = 1;
+        if (e->mem.get(&e->embd_q6k, (size_t)(e->embd_row_bytes * c.n_vocab)) ||
+            e->mem.get(&e->xq8k, (size_t)c.n_embd / 256 * 292))
+            return -1;
         if (!hw)
             launch_synth_kquant(T_Q6_K, e->embd_q6k, c.n_vocab, c.n_embd, tensor_key(c.seed, TID_EMBD),
                                 (float)(emb_std / 0.68), s);
     } else {
-        e->embd = alloc_tiled(c.wtype, c.n_vocab, c.n_embd, s);
+        if (alloc_tiled(e->mem, &e->embd, c.wtype, c.n_vocab, c.n_embd, s)) return -1;
         if (!hw) launch_synth_tiled(e->embd, tensor_key(c.seed, TID_EMBD), synth_scale(emb_std), 0, s);
     }
-    GHIP_FATAL(hipMalloc(&e->out_norm, (size_t)c.n_embd * 4));
+    if (e->mem.get(&e->out_norm, (size_t)c.n_embd * 4)) return -1;
     if (hw) {
         if (e->out_type == T_Q6_K)
-            GHIP_FATAL(hipMemcpy(e->embd_q6k, hw->embd, (size_t)(e->embd_row_bytes * c.n_vocab), hipMemcpyHostToDevice));
-        else
-            fail |= upload_rows(e->embd, hw->embd, 0, s) != 0;
-        GHIP_FATAL(hipMemcpy(e->out_norm, hw->out_norm, (size_t)c.n_embd * 4, hipMemcpyHostToDevice));
+            GHIP_CHECK(hipMemcpy(e->embd_q6k, hw->embd, (size_t)(e->embd_row_bytes * c.n_vocab), hipMemcpyHostToDevice));
+        else if (upload_rows(e->embd, hw->embd, 0, s))
+            return -1;
+        GHIP_CHECK(hipMemcpy(e->out_norm, hw->out_norm, (size_t)c.n_embd * 4, hipMemcpyHostToDevice));
     } else {
         launch_synth_norm(e->out_norm, c.n_embd, tensor_key(c.seed, TID_OUT_NORM), synth_scale(0.05), s);
     }
-    if (e->out_type == T_Q6_K && kq_retile_inplace(e->embd_q6k, T_Q6_K, c.n_vocab, c.n_embd, s, &e->embd_tiled)) fail = true;
-    return fail;
+    if (e->out_type == T_Q6_K) return kq_retile_inplace(e->embd_q6k, T_Q6_K, c.n_vocab, c.n_embd, s, &e->embd_tiled);
+    return 0;
 }
 
 // a layer's norms: replicated, the slot-0 copy serves every virtual rank
-static void create_layer_norms(gemma_engine *e, int il, int vr, const host_weights *hw) {
+static int create_layer_norms(gemma_engine *e, int il, int vr, const host_weights *hw) {
     const gemma_hip_config &c = e->cfg;
     layer_dev &L = layer_of(e, il, vr);
     if (vr > 0) {
         L.attn_norm = layer_of(e, il, 0).attn_norm;
         L.ffn_norm = layer_of(e, il, 0).ffn_norm;
-        return;
+        return 0;
     }
-    GHIP_FATAL(hipMalloc(&L.attn_norm, (size_t)c.n_embd * 4));
-    GHIP_FATAL(hipMalloc(&L.ffn_norm, (size_t)c.n_embd * 4));
+    if (e->mem.get(&L.attn_norm, (size_t)c.n_embd * 4) || e->mem.get(&L.ffn_norm, (size_t)c.n_embd * 4)) return -1;
     if (hw) {
-        GHIP_FATAL(hipMemcpy(L.attn_norm, hw->layers[il].attn_norm, (size_t)c.n_embd * 4, hipMemcpyHostToDevice));
-        GHIP_FATAL(hipMemcpy(L.ffn_norm, hw->layers[il].ffn_norm, (size_t)c.n_embd * 4, hipMemcpyHostToDevice));
+        GHIP_CHECK(hipMemcpy(L.attn_norm, hw->layers[il].attn_norm, (size_t)c.n_embd * 4, hipMemcpyHostToDevice));
+        GHIP_CHECK(hipMemcpy(L.ffn_norm, hw->layers[il].ffn_norm, (size_t)c.n_embd * 4, hipMemcpyHostToDevice));
     } else {
         launch_synth_norm(L.attn_norm, c.n_embd, tensor_key(c.seed, tid_layer(il, L_ATTN_NORM)), synth_scale(0.05), e->stream);
         launch_synth_norm(L.ffn_norm, c.n_embd, tensor_key(c.seed, tid_layer(il, L_FFN_NORM)), synth_scale(0.05), e->stream);
     }
+    return 0;
 }
 
 // layer il's K-quant matrices, raw rows: uploaded, or the oracle's make_kmat on the device; returns
@@ -272,20 +270,17 @@ static bool create_layer_kq(gemma_engine *e, int il, const host_weights *hw) {
     uint8_t *qk_buf = nullptr;
     if (tq == tk) {
         const int64_t rb = c.n_embd / 256 * (tq == T_Q4_K ? 144 : 210);
-        if (hipMalloc(&qk_buf, (size_t)(rb * (e->qw + e->kvw))) != hipSuccess) {
-            set_error("gemma_engine_create: weight alloc failed");
-            fail = true;
-        }
+        if (e->mem.get(&qk_buf, (size_t)(rb * (e->qw + e->kvw)))) return true;
     }
     auto make = [&](kq_mat &m, int type, int64_t rows, int64_t k, int tid, double stdv, const void *host) {
         m.type = type;
         m.rows = rows;
         m.K = k;
         m.rb = k / 256 * (type == T_Q4_K ? 144 : 210);
+        if (fail) return;
         if (qk_buf && (&m == &K.q || &m == &K.k)) {
             m.w = qk_buf + (&m == &K.k ? m.rb * e->qw : 0);
-        } else if (hipMalloc(&m.w, (size_t)(m.rb * rows)) != hipSuccess) {
-            set_error("gemma_engine_create: weight alloc failed");
+        } else if (e->mem.get(&m.w, (size_t)(m.rb * rows))) {
             fail = true;
             return;
         }
@@ -310,7 +305,7 @@ static bool create_layer_kq(gemma_engine *e, int il, const host_weights *hw) {
 }
 
 // layer il's tiled matrices for (virtual) rank slot vr: this rank's rows of each, uploaded or from
-// the synthetic generator straight into the tiled layout; returns true when an upload failed
+// the synthetic generator straight into the tiled layout; returns true when an allocation or upload failed
 static bool create_layer_tiled(gemma_engine *e, int il, int vr, const host_weights *hw) {
     const gemma_hip_config &c = e->cfg;
     const int wt = c.wtype;
@@ -324,7 +319,7 @@ static bool create_layer_tiled(gemma_engine *e, int il, int vr, const host_weigh
     const bool att_here = !e->rep_attn || vr == 0;
     // this rank's rows [r0, r0 + n) of the fused [Wq | Wk | Wv]: the pieces of each source tensor
     const int64_t q0 = e->rep_attn ? 0 : (int64_t)tp_rank * e->sh_qkv, qn = att_here ? e->sh_qkv : 0;
-    if (att_here) L.qkv = alloc_tiled(wt, qn, c.n_embd, s);
+    if (att_here && alloc_tiled(e->mem, &L.qkv, wt, qn, c.n_embd, s)) return true;
     const int64_t src_start[3] = {0, e->qw, e->qw + e->kvw}, src_rows[3] = {e->qw, e->kvw, e->kvw};
     const int src_tid[3] = {L_Q, L_K, L_V};
     const void *src_host[3] = {H ? H->q : nullptr, H ? H->k : nullptr, H ? H->v : nullptr};
@@ -339,7 +334,10 @@ static bool create_layer_tiled(gemma_engine *e, int il, int vr, const host_weigh
     }
     // rows [r0, r0 + rows) of one source tensor as its own matrix
     auto make = [&](tiled_mat &m, int64_t rows, int64_t K, const void *host, int tid, double stdv, int64_t r0) {
-        m = alloc_tiled(wt, rows, K, s);
+        if (fail || alloc_tiled(e->mem, &m, wt, rows, K, s)) {
+            fail = true;
+            return;
+        }
         if (hw) fail |= upload_rows(m, host, r0, s) != 0;
         else launch_synth_tiled(m, tensor_key(c.seed, tid_layer(il, tid)), synth_scale(stdv), r0, s);
     };
@@ -350,25 +348,21 @@ static bool create_layer_tiled(gemma_engine *e, int il, int vr, const host_weigh
     return fail;
 }
 
-template <typename T> static void alloc_zeroed(T **p, size_t bytes) {
-    GHIP_FATAL(hipMalloc(p, bytes));
-    GHIP_FATAL(hipMemset(*p, 0, bytes));
-}
-
 // caches, tables, activations, hand-off counters and the decode state; -1 (last_error set) when
 // the attention geometry is unsupported
 static int create_buffers(gemma_engine *e, const std::vector<uint16_t *> *kc_ext, const std::vector<uint16_t *> *vc_ext) {
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
+    dev_pool &M = e->mem;
     const size_t kv_elems = (size_t)c.n_layer * c.n_ctx * e->kvw;
     if (kc_ext && vc_ext) {
         e->kc_ext = *kc_ext;
         e->vc_ext = *vc_ext;
     } else {
-        GHIP_FATAL(hipMalloc(&e->kc, kv_elems * 2));
-        GHIP_FATAL(hipMalloc(&e->vc, kv_elems * 2));
-        GHIP_FATAL(hipMemsetAsync(e->kc, 0, kv_elems * 2, s));
-        GHIP_FATAL(hipMemsetAsync(e->vc, 0, kv_elems * 2, s));
+        if (M.get(&e->kc, kv_elems * 2)) return -1;
+        if (M.get(&e->vc, kv_elems * 2)) return -1;
+        GHIP_CHECK(hipMemsetAsync(e->kc, 0, kv_elems * 2, s));
+        GHIP_CHECK(hipMemsetAsync(e->vc, 0, kv_elems * 2, s));
     }
     std::vector<uint16_t> et, gt;
     build_f16_tables(et, gt);
@@ -381,78 +375,80 @@ static int create_buffers(gemma_engine *e, const std::vector<uint16_t *> *kc_ext
         set_error("gemma_engine_create: unsupported attention geometry");
         return -1;
     }
-    GHIP_FATAL(hipMalloc(&e->att_sbuf, std::max<size_t>(e->ag.sbuf_floats, 1) * 4));
-    GHIP_FATAL(hipMalloc(&e->att_sync, (e->ag.sync_ints + 1) * 4));
-    GHIP_FATAL(hipMemsetAsync(e->att_sync, 0, (e->ag.sync_ints + 1) * 4, s));
-    GHIP_FATAL(hipMalloc(&e->exp_tab, 65536 * 2));
-    GHIP_FATAL(hipMalloc(&e->gelu_tab, 65536 * 2));
-    GHIP_FATAL(hipMalloc(&e->rope_cos, rc.size() * 4));
-    GHIP_FATAL(hipMalloc(&e->rope_sin, rs.size() * 4));
-    GHIP_FATAL(hipMalloc(&e->rope_cur, (size_t)(c.head_dim + 4) * 4));  // [cos | sin | (int)pos]
-    GHIP_FATAL(hipMemcpy(e->exp_tab, et.data(), 65536 * 2, hipMemcpyHostToDevice));
-    GHIP_FATAL(hipMemcpy(e->gelu_tab, gt.data(), 65536 * 2, hipMemcpyHostToDevice));
-    GHIP_FATAL(hipMemcpy(e->rope_cos, rc.data(), rc.size() * 4, hipMemcpyHostToDevice));
-    GHIP_FATAL(hipMemcpy(e->rope_sin, rs.data(), rs.size() * 4, hipMemcpyHostToDevice));
-    GHIP_FATAL(hipMalloc(&e->x, (size_t)c.n_embd * 4));
-    GHIP_FATAL(hipMalloc(&e->qkv, (size_t)e->qkv_rows * 4));
-    GHIP_FATAL(hipMalloc(&e->attn, (size_t)e->qw * 4));
-    GHIP_FATAL(hipMalloc(&e->sa, (size_t)c.n_embd * 4));
-    GHIP_FATAL(hipMalloc(&e->h, (size_t)c.n_ff * 4));
+    if (M.get(&e->att_sbuf, std::max<size_t>(e->ag.sbuf_floats, 1) * 4)) return -1;
+    if (M.get(&e->att_sync, (e->ag.sync_ints + 1) * 4)) return -1;
+    GHIP_CHECK(hipMemsetAsync(e->att_sync, 0, (e->ag.sync_ints + 1) * 4, s));
+    if (M.get(&e->exp_tab, 65536 * 2)) return -1;
+    if (M.get(&e->gelu_tab, 65536 * 2)) return -1;
+    if (M.get(&e->rope_cos, rc.size() * 4)) return -1;
+    if (M.get(&e->rope_sin, rs.size() * 4)) return -1;
+    if (M.get(&e->rope_cur, (size_t)(c.head_dim + 4) * 4)) return -1;  // [cos | sin | (int)pos]
+    GHIP_CHECK(hipMemcpy(e->exp_tab, et.data(), 65536 * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(e->gelu_tab, gt.data(), 65536 * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(e->rope_cos, rc.data(), rc.size() * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(e->rope_sin, rs.data(), rs.size() * 4, hipMemcpyHostToDevice));
+    if (M.get(&e->x, (size_t)c.n_embd * 4)) return -1;
+    if (M.get(&e->qkv, (size_t)e->qkv_rows * 4)) return -1;
+    if (M.get(&e->attn, (size_t)e->qw * 4)) return -1;
+    if (M.get(&e->sa, (size_t)c.n_embd * 4)) return -1;
+    if (M.get(&e->h, (size_t)c.n_ff * 4)) return -1;
     // launch_attn_decode needs head_dim % (32 * dsplit) == 0: the largest of 4 / 2 / 1 that divides
     // (head_dim 32 / 64 / 96 / 160 / ... take fewer workgroups per head, never a failing step)
     if (e->att_dsplit < 1) e->att_dsplit = 1;
     while (e->att_dsplit > 1 && (c.head_dim % (32 * e->att_dsplit) || (e->att_dsplit & (e->att_dsplit - 1)))) --e->att_dsplit;
     if (e->qw % 128 == 0) {  // whole 4-block groups
-        GHIP_FATAL(hipMalloc(&e->att_act, (size_t)e->qw));
-        GHIP_FATAL(hipMalloc(&e->att_da, (size_t)e->qw / 32 * 4));
-        alloc_zeroed(&e->front_cnt, (size_t)c.n_layer * 16 * 32 * 4);
-        alloc_zeroed(&e->front_err, 64);
-        alloc_zeroed(&e->ao_cnt, (size_t)c.n_layer * 16 * 32 * 4);
-        alloc_zeroed(&e->ao_err, 64);
+        if (M.get(&e->att_act, (size_t)e->qw)) return -1;
+        if (M.get(&e->att_da, (size_t)e->qw / 32 * 4)) return -1;
+        if (M.get_zeroed(&e->front_cnt, (size_t)c.n_layer * 16 * 32 * 4, s)) return -1;
+        if (M.get_zeroed(&e->front_err, 64, s)) return -1;
+        if (M.get_zeroed(&e->ao_cnt, (size_t)c.n_layer * 16 * 32 * 4, s)) return -1;
+        if (M.get_zeroed(&e->ao_err, 64, s)) return -1;
     }
     if (e->sh_ff % 128 == 0) {  // every rank's shard is whole 4-block groups
-        GHIP_FATAL(hipMalloc(&e->h_act, (size_t)c.n_ff));
-        GHIP_FATAL(hipMalloc(&e->h_da, (size_t)c.n_ff / 32 * 4));
+        if (M.get(&e->h_act, (size_t)c.n_ff)) return -1;
+        if (M.get(&e->h_da, (size_t)c.n_ff / 32 * 4)) return -1;
     }
-    GHIP_FATAL(hipMalloc(&e->logits, (size_t)c.n_vocab * 4));
+    if (M.get(&e->logits, (size_t)c.n_vocab * 4)) return -1;
     if (e->kq) {
         const int64_t kmax = std::max<int64_t>(std::max<int64_t>(c.n_embd, e->qw), c.n_ff);
         const size_t img = (size_t)(kmax / 256 * 292 + 255) & ~(size_t)255;
-        GHIP_FATAL(hipMalloc(&e->kq_x, 4 * img));
+        if (M.get(&e->kq_x, 4 * img)) return -1;
         e->kq_xa = e->kq_x + img;
         e->kq_xf = e->kq_x + 2 * img;
         e->kq_xh = e->kq_x + 3 * img;
         // counters: a quantize hand-off takes rows/256 (gate/up: n_ff/256), a norm hand-off rows/256 + 1
         // (down, attn-out: n_embd/256 + 1 — more than n_ff/256 when n_ff <= n_embd)
         e->kq_cnt_cap = (int)std::max<int64_t>(std::max<int64_t>(c.n_ff / 256, c.n_embd / 256 + 1), 1);
-        alloc_zeroed(&e->kq_cnt, (size_t)e->kq_cnt_cap * 128);
-        GHIP_FATAL(hipMalloc(&e->kq_g, (size_t)c.n_ff * 4));
+        if (M.get_zeroed(&e->kq_cnt, (size_t)e->kq_cnt_cap * 128, s)) return -1;
+        if (M.get(&e->kq_g, (size_t)c.n_ff * 4)) return -1;
     }
     {  // the persistent token launch: granules, epoch, error word, argument copies
         const tok_gran_sizes g = token_gran_sizes(c.n_embd, c.n_ff, e->qkv_rows);
         const size_t n = g.gx + g.gqkv + g.gatt + g.gatt_da + g.gsa + g.gh + g.gh_da;
-        alloc_zeroed(&e->tok_gran, n * 8);
-        alloc_zeroed(&e->epoch, 64);
-        const unsigned one = 1;
-        GHIP_FATAL(hipMemcpy(e->epoch, &one, 4, hipMemcpyHostToDevice));
-        alloc_zeroed(&e->tok_err, 64);
-        GHIP_FATAL(hipMalloc(&e->tok_dev, sizeof(tok_args)));
-        GHIP_FATAL(hipMalloc(&e->tok_tab, (size_t)c.n_layer * sizeof(tok_layer)));
+        if (M.get_zeroed(&e->tok_gran, n * 8, s)) return -1;
+        if (M.get_zeroed(&e->epoch, 64, s)) return -1;
+        static const unsigned one = 1;  // after the zeroing, on its stream
+        GHIP_CHECK(hipMemcpyAsync(e->epoch, &one, 4, hipMemcpyHostToDevice, s));
+        if (M.get_zeroed(&e->tok_err, 64, s)) return -1;
+        if (M.get(&e->tok_dev, sizeof(tok_args))) return -1;
+        if (M.get(&e->tok_tab, (size_t)c.n_layer * sizeof(tok_layer))) return -1;
     }
-    GHIP_FATAL(hipMalloc(&e->key, (size_t)e->grid_big * 8));  // per-workgroup argmax keys
-    GHIP_FATAL(hipMalloc(&e->pos, 4));
-    GHIP_FATAL(hipMalloc(&e->token, 4));
-    GHIP_FATAL(hipMalloc(&e->nfix, 4));
-    GHIP_FATAL(hipMalloc(&e->hist, (size_t)(c.n_ctx + 1) * 4));
-    GHIP_FATAL(hipMemsetAsync(e->key, 0, (size_t)e->grid_big * 8, s));
-    GHIP_FATAL(hipMemsetAsync(e->hist, 0, (size_t)(c.n_ctx + 1) * 4, s));
-    GHIP_FATAL(hipMalloc(&e->rank_keys, (size_t)e->tp_n * 8));
+    if (M.get(&e->key, (size_t)e->grid_big * 8)) return -1;  // per-workgroup argmax keys
+    if (M.get(&e->pos, 4)) return -1;
+    if (M.get(&e->token, 4)) return -1;
+    if (M.get(&e->nfix, 4)) return -1;
+    if (M.get(&e->hist, (size_t)(c.n_ctx + 1) * 4)) return -1;
+    GHIP_CHECK(hipMemsetAsync(e->key, 0, (size_t)e->grid_big * 8, s));
+    GHIP_CHECK(hipMemsetAsync(e->hist, 0, (size_t)(c.n_ctx + 1) * 4, s));
+    if (M.get(&e->rank_keys, (size_t)e->tp_n * 8)) return -1;
     return 0;
 }
 
 // GEMMA_TP_P2P: inboxes mirroring every gathered vector, then one flag word per source rank
-static void create_p2p_arena(gemma_engine *e) {
+static int create_p2p_arena(gemma_engine *e) {
     const gemma_hip_config &c = e->cfg;
+    hipStream_t s = e->stream;
+    dev_pool &M = e->mem;
     size_t off = 0;
     auto take = [&](int64_t &ib, size_t bytes) { ib = (int64_t)off; off += (bytes + 255) & ~(size_t)255; };
     take(e->ib_qkv, (size_t)e->qkv_rows * 4);
@@ -464,11 +460,11 @@ static void create_p2p_arena(gemma_engine *e) {
     take(e->ib_logits, (size_t)c.n_vocab * 4);
     take(e->ib_keys, (size_t)e->tp_n * 8);
     take(e->ib_flags, (size_t)P2P_MAX_RANKS * 4);
-    GHIP_FATAL(hipExtMallocWithFlags((void **)&e->p2p_arena, off, hipDeviceMallocUncached));
-    GHIP_FATAL(hipMemset(e->p2p_arena, 0, off));
-    alloc_zeroed(&e->p2p_seq, 64);
-    alloc_zeroed(&e->p2p_err, 64);
+    if (M.get_zeroed(&e->p2p_arena, off, s, MEM_UNCACHED)) return -1;
+    if (M.get_zeroed(&e->p2p_seq, 64, s)) return -1;
+    if (M.get_zeroed(&e->p2p_err, 64, s)) return -1;
     e->p2p_peer[e->tp_rank] = e->p2p_arena;
+    return 0;
 }
 
 static gemma_engine *engine_create(const gemma_hip_config *cfg, int device, int tp_n, int tp_rank, const void *nccl_id,
@@ -487,20 +483,24 @@ static gemma_engine *engine_create(const gemma_hip_config *cfg, int device, int 
     auto *e = new gemma_engine();
     e->cfg = c;
     e->device = device;
-    GHIP_FATAL(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    if (!set_shards(e, tp_n, tp_rank, nccl_id, tp_flags)) {
+    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
+        set_error("gemma_engine_create: hipStreamCreateWithFlags failed");
+        delete e;
+        return nullptr;
+    }
+    if (!set_shards(e, tp_n, tp_rank, nccl_id, tp_flags)) {  // nothing allocated yet, tp_n not validated
+        (void)hipStreamDestroy(e->stream);
         delete e;
         return nullptr;
     }
     e->kq = c.wtype == T_Q4_K;
     e->out_type = (c.out_type == T_Q6_K || e->kq) ? T_Q6_K : c.wtype;
-    bool up_fail = create_embeddings(e, hw);  // a host-weight upload failed (last_error says which)
+    // an allocation or a host-weight upload failed (last_error says which)
+    bool up_fail = create_embeddings(e, hw) != 0;
     e->layers.resize((size_t)c.n_layer * e->n_virtual);
-    for (int il = 0; il < c.n_layer; ++il)
-        for (int vr = 0; vr < e->n_virtual; ++vr) {
-            create_layer_norms(e, il, vr, hw);
-            up_fail |= e->kq ? create_layer_kq(e, il, hw) : create_layer_tiled(e, il, vr, hw);
-        }
+    for (int il = 0; il < c.n_layer && !up_fail; ++il)
+        for (int vr = 0; vr < e->n_virtual && !up_fail; ++vr)
+            up_fail = create_layer_norms(e, il, vr, hw) || (e->kq ? create_layer_kq(e, il, hw) : create_layer_tiled(e, il, vr, hw));
     if (up_fail) {
         gemma_engine_free(e);
         return nullptr;
@@ -509,12 +509,12 @@ static gemma_engine *engine_create(const gemma_hip_config *cfg, int device, int 
         (void)hipStreamSynchronize(e->stream);
         fprintf(stderr, "[gemma_hip] engine create: weights %.2f ms\n", cnow() - ct0);
     }
-    if (create_buffers(e, kc_ext, vc_ext)) {
+    if (create_buffers(e, kc_ext, vc_ext) || (e->p2p && create_p2p_arena(e)) ||
+        hipStreamSynchronize(e->stream) != hipSuccess) {
+        if (last_error().empty()) set_error("gemma_engine_create: hipStreamSynchronize failed");
         gemma_engine_free(e);
         return nullptr;
     }
-    if (e->p2p) create_p2p_arena(e);
-    GHIP_FATAL(hipStreamSynchronize(e->stream));
     // a communicator whenever an id is given, also for ONE rank: every gather, the key gather and
     // RCCL inside the captured hipGraph then run exactly as on N GPUs (a 1-rank all-gather in place)
     if (nccl_id) {
@@ -752,46 +752,14 @@ extern "C" void gemma_engine_free(gemma_engine *e) {
     (void)hipSetDevice(e->device);
     (void)hipStreamSynchronize(e->stream);
     if (e->comm) (void)ncclCommDestroy(e->comm);
-    if (e->rank_keys) (void)hipFree(e->rank_keys);
-    if (e->p2p) {
+    if (e->p2p)
         for (int r = 0; r < e->tp_n; ++r)
             if (r != e->tp_rank && e->p2p_peer[r]) (void)hipIpcCloseMemHandle(e->p2p_peer[r]);
-        if (e->p2p_arena) (void)hipFree(e->p2p_arena);
-        if (e->p2p_seq) (void)hipFree(e->p2p_seq);
-        if (e->p2p_err) (void)hipFree(e->p2p_err);
-    }
-    if (e->ext_stage) (void)hipHostFree(e->ext_stage);
-    if (e->ext_err) (void)hipHostFree(e->ext_err);
     drop_graph(e);
-    free_tiled(e->embd);
-    for (size_t i = 0; i < e->layers.size(); ++i) {
-        layer_dev &L = e->layers[i];
-        free_tiled(L.qkv); free_tiled(L.o); free_tiled(L.gate); free_tiled(L.up); free_tiled(L.down);
-        if (i % e->n_virtual == 0) {  // norms are shared by a layer's virtual-rank slots
-            (void)hipFree(L.attn_norm);
-            (void)hipFree(L.ffn_norm);
-        }
-    }
-    void *bufs[] = {e->tok_gran, e->epoch, e->tok_err, e->tok_dev, e->tok_tab, e->front_cnt, e->front_err, e->ao_cnt, e->ao_err, e->att_act, e->att_da, e->h_act, e->h_da, e->rope_cur, e->att_sbuf, e->att_sync, e->out_norm, e->kc, e->vc, e->exp_tab, e->gelu_tab, e->rope_cos, e->rope_sin, e->x, e->qkv,
-                    e->attn, e->sa, e->h, e->logits, e->key, e->pos, e->token, e->hist, e->nfix, e->pf.X, e->pf.SA, e->pf.QKV, e->pf.ATT, e->pf.G, e->pf.U,
-                    e->pf.LG, e->pf.DA, e->pf.Q16, e->pf.XQ, e->pf.XH, e->pf.XM, e->pf.keys};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    if (e->embd_q6k) (void)hipFree(e->embd_q6k);
-    for (kq_layer &K : e->kql)
-        for (kq_mat *m : {&K.q, &K.k, &K.v, &K.o, &K.gate, &K.up, &K.down})
-            if (m->w && !(m == &K.k && K.qk_fused)) (void)hipFree(m->w);  // k lives inside q's q|k buffer
-    if (e->kq_x) (void)hipFree(e->kq_x);
-    if (e->kq_g) (void)hipFree(e->kq_g);
-    if (e->kq_cnt) (void)hipFree(e->kq_cnt);
     for (hipEvent_t &ev : e->fc_ev)
         if (ev) (void)hipEventDestroy(ev);
-    if (e->xq8k) (void)hipFree(e->xq8k);
-    if (e->smp_dev) (void)hipFree(e->smp_dev);
-    if (e->vf.keys) (void)hipFree(e->vf.keys);
-    if (e->vf.ints) (void)hipFree(e->vf.ints);
-    if (e->vf.host) (void)hipHostFree(e->vf.host);
-    sample_ws_free(&e->smp_ws);
+    e->pf_mem.clear();
+    e->mem.clear();
     (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -965,12 +933,12 @@ extern "C" int64_t gemma_engine_tensor(gemma_engine *e, int tid, void *dst, int6
     auto copy_mat = [&](const tiled_mat &m) -> int64_t {
         const int64_t bytes = m.rows * m.nb * (m.type == T_Q4_0 ? 18 : 34);
         if (cap < bytes) return -1;
+        dev_pool tmp_mem;
         uint8_t *tmp = nullptr;
-        GHIP_CHECK(hipMalloc(&tmp, (size_t)bytes));
+        if (tmp_mem.get(&tmp, (size_t)bytes)) return -1;
         if (launch_untile(m, tmp, e->stream)) return -1;
         GHIP_CHECK(hipStreamSynchronize(e->stream));
         GHIP_CHECK(hipMemcpy(dst, tmp, (size_t)bytes, hipMemcpyDeviceToHost));
-        GHIP_CHECK(hipFree(tmp));
         return bytes;
     };
     // K-quant rows back in ggml layout
@@ -981,12 +949,12 @@ extern "C" int64_t gemma_engine_tensor(gemma_engine *e, int tid, void *dst, int6
             GHIP_CHECK(hipMemcpy(dst, w, (size_t)bytes, hipMemcpyDeviceToHost));
             return bytes;
         }
+        dev_pool tmp_mem;
         uint8_t *tmp = nullptr;
-        GHIP_CHECK(hipMalloc(&tmp, (size_t)bytes));
+        if (tmp_mem.get(&tmp, (size_t)bytes)) return -1;
         if (launch_kq_retile(type, w, tmp, rows, K, false, e->stream)) return -1;
         GHIP_CHECK(hipStreamSynchronize(e->stream));
         GHIP_CHECK(hipMemcpy(dst, tmp, (size_t)bytes, hipMemcpyDeviceToHost));
-        GHIP_CHECK(hipFree(tmp));
         return bytes;
     };
     if (tid == TID_EMBD && e->out_type == T_Q6_K) return copy_kq(e->embd_q6k, T_Q6_K, c.n_vocab, c.n_embd, e->embd_tiled);

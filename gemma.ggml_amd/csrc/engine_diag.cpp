@@ -71,9 +71,6 @@ extern "C" double gemma_engine_time(gemma_engine *e, int which, int iters, doubl
     setup(e->layers[0]);
     const bool hot = e->time_hot != 0;
     a.ablate = e->ablate;
-    hipEvent_t t0, t1;
-    GHIP_FATAL(hipEventCreate(&t0));
-    GHIP_FATAL(hipEventCreate(&t1));
     auto run = [&]() -> int {
         if (which == 5) {
             if (ensure_graph(e)) return -1;
@@ -93,18 +90,26 @@ extern "C" double gemma_engine_time(gemma_engine *e, int which, int iters, doubl
             return -1.0;
         }
     }
-    for (int i = 0; i < 3; ++i)
-        if (run()) return -1.0;
-    GHIP_FATAL(hipEventRecord(t0, e->stream));
-    for (int i = 0; i < iters; ++i)
-        if (run()) return -1.0;
-    GHIP_FATAL(hipEventRecord(t1, e->stream));
-    GHIP_FATAL(hipEventSynchronize(t1));
-    if (which == 5) e->host_pos += iters + 3;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
     float ms = 0;
-    GHIP_FATAL(hipEventElapsedTime(&ms, t0, t1));
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
+    auto timed = [&]() -> int {
+        GHIP_CHECK(hipEventCreate(&t0));
+        GHIP_CHECK(hipEventCreate(&t1));
+        for (int i = 0; i < 3; ++i)
+            if (run()) return -1;
+        GHIP_CHECK(hipEventRecord(t0, e->stream));
+        for (int i = 0; i < iters; ++i)
+            if (run()) return -1;
+        GHIP_CHECK(hipEventRecord(t1, e->stream));
+        GHIP_CHECK(hipEventSynchronize(t1));
+        GHIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
+        return 0;
+    };
+    const int tr = timed();
+    if (t0) (void)hipEventDestroy(t0);
+    if (t1) (void)hipEventDestroy(t1);
+    if (tr) return -1.0;
+    if (which == 5) e->host_pos += iters + 3;
     if (algo_bytes) *algo_bytes = bytes;
     return (double)ms * 1000.0 / iters;
 }
@@ -351,18 +356,12 @@ extern "C" int gemma_engine_set_sampler(gemma_engine *e, const gemma_sampler *sp
     (void)hipSetDevice(e->device);
     if (on) {
         if (!e->smp_dev) {
-            sample_ws ws;
-            if (sample_ws_alloc(&ws, e->cfg.n_vocab, e->stream)) {
-                sample_ws_free(&ws);
+            // made once and kept for the engine's lifetime (the captured graph holds both)
+            if (sample_ws_alloc(e->mem, &e->smp_ws, e->cfg.n_vocab, e->stream)) return -1;
+            if (e->mem.get(&e->smp_dev, sizeof(sampler_params))) {
+                sample_ws_free(e->mem, &e->smp_ws);
                 return -1;
             }
-            if (hipMalloc(&e->smp_dev, sizeof(sampler_params)) != hipSuccess) {
-                sample_ws_free(&ws);
-                e->smp_dev = nullptr;
-                set_error("gemma_engine_set_sampler: allocation failed");
-                return -1;
-            }
-            e->smp_ws = ws;
         }
         // the copy's source must outlive the call: wait for an earlier copy before rewriting it
         GHIP_CHECK(hipStreamSynchronize(e->stream));
@@ -405,6 +404,7 @@ extern "C" int gemma_test_sample(const float *logits, int rows, int n_vocab, con
         set_error("gemma_test_sample: " + why);
         return -1;
     }
+    dev_pool tmp;
     sample_ws ws;
     sampler_params hp, *dp = nullptr;
     hp.temperature = sp->temperature; hp.top_k = sp->top_k; hp.top_p = sp->top_p; hp.seed = sp->seed;
@@ -413,35 +413,25 @@ extern "C" int gemma_test_sample(const float *logits, int rows, int n_vocab, con
     std::vector<int> pm1(positions, positions + rows);
     for (int &v : pm1) v -= 1;  // the kernels read *pos + 1, as k_advance does
     const size_t row_b = (size_t)n_vocab * 4;
-    auto run = [&]() -> int {
-        if (sample_ws_alloc(&ws, n_vocab, nullptr)) return -1;
-        GHIP_CHECK(hipMalloc(&dp, sizeof(hp)));
-        GHIP_CHECK(hipMalloc(&dl, row_b * rows));
-        GHIP_CHECK(hipMalloc(&dpos, (size_t)rows * 4));
-        GHIP_CHECK(hipMalloc(&dtok, (size_t)rows * 4));
-        GHIP_CHECK(hipMalloc(&dnc, (size_t)rows * 4));
-        GHIP_CHECK(hipMalloc(&dnk, (size_t)rows * 4));
-        GHIP_CHECK(hipMalloc(&dcand, (size_t)rows * SAMPLE_MAX_K * 4));
-        GHIP_CHECK(hipMemcpy(dp, &hp, sizeof(hp), hipMemcpyHostToDevice));
-        GHIP_CHECK(hipMemcpy(dl, logits, row_b * rows, hipMemcpyHostToDevice));
-        GHIP_CHECK(hipMemcpy(dpos, pm1.data(), (size_t)rows * 4, hipMemcpyHostToDevice));
-        for (int r = 0; r < rows; ++r) {
-            sample_dbg d;
-            d.token = dtok + r; d.cand = dcand + (size_t)r * SAMPLE_MAX_K; d.n_cand = dnc + r; d.n_kept = dnk + r;
-            if (launch_sample(dl + (size_t)r * n_vocab, n_vocab, dp, dpos + r, ws, d, nullptr)) return -1;
-        }
-        GHIP_CHECK(hipDeviceSynchronize());
-        if (tokens) GHIP_CHECK(hipMemcpy(tokens, dtok, (size_t)rows * 4, hipMemcpyDeviceToHost));
-        if (n_cand) GHIP_CHECK(hipMemcpy(n_cand, dnc, (size_t)rows * 4, hipMemcpyDeviceToHost));
-        if (n_kept) GHIP_CHECK(hipMemcpy(n_kept, dnk, (size_t)rows * 4, hipMemcpyDeviceToHost));
-        if (cand) GHIP_CHECK(hipMemcpy(cand, dcand, (size_t)rows * SAMPLE_MAX_K * 4, hipMemcpyDeviceToHost));
-        return 0;
-    };
-    const int r = run();
-    sample_ws_free(&ws);
-    for (void *p : {(void *)dp, (void *)dl, (void *)dpos, (void *)dtok, (void *)dnc, (void *)dnk, (void *)dcand})
-        if (p) (void)hipFree(p);
-    return r;
+    if (sample_ws_alloc(tmp, &ws, n_vocab, nullptr)) return -1;
+    if (tmp.get(&dp, sizeof(hp)) || tmp.get(&dl, row_b * rows) || tmp.get(&dpos, (size_t)rows * 4) ||
+        tmp.get(&dtok, (size_t)rows * 4) || tmp.get(&dnc, (size_t)rows * 4) || tmp.get(&dnk, (size_t)rows * 4) ||
+        tmp.get(&dcand, (size_t)rows * SAMPLE_MAX_K * 4))
+        return -1;
+    GHIP_CHECK(hipMemcpy(dp, &hp, sizeof(hp), hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(dl, logits, row_b * rows, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(dpos, pm1.data(), (size_t)rows * 4, hipMemcpyHostToDevice));
+    for (int r = 0; r < rows; ++r) {
+        sample_dbg d;
+        d.token = dtok + r; d.cand = dcand + (size_t)r * SAMPLE_MAX_K; d.n_cand = dnc + r; d.n_kept = dnk + r;
+        if (launch_sample(dl + (size_t)r * n_vocab, n_vocab, dp, dpos + r, ws, d, nullptr)) return -1;
+    }
+    GHIP_CHECK(hipDeviceSynchronize());
+    if (tokens) GHIP_CHECK(hipMemcpy(tokens, dtok, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    if (n_cand) GHIP_CHECK(hipMemcpy(n_cand, dnc, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    if (n_kept) GHIP_CHECK(hipMemcpy(n_kept, dnk, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    if (cand) GHIP_CHECK(hipMemcpy(cand, dcand, (size_t)rows * SAMPLE_MAX_K * 4, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // attention + attn-out in one launch on (1) / off (0) / unchanged (-1); returns the setting
@@ -502,17 +492,18 @@ extern "C" int gemma_engine_stamp_step(gemma_engine *e, int layer, unsigned long
     }
     (void)hipSetDevice(e->device);
     const size_t n = 6 * kStampRegion;
-    GHIP_CHECK(hipMalloc(&e->stamp, n * 8));
-    GHIP_CHECK(hipMemsetAsync(e->stamp, 0, n * 8, e->stream));
+    dev_pool tmp;
+    if (tmp.get_zeroed(&e->stamp, n * 8, e->stream)) return -1;
     e->stamp_layer = layer;
-    const int r = enqueue_step(e);
-    if (r == 0) {
+    auto run = [&]() -> int {
+        if (enqueue_step(e)) return -1;
         GHIP_CHECK(hipStreamSynchronize(e->stream));
         GHIP_CHECK(hipMemcpy(out, e->stamp, n * 8, hipMemcpyDeviceToHost));
         e->host_pos += 1;
-    }
-    (void)hipFree(e->stamp);
-    e->stamp = nullptr;
+        return 0;
+    };
+    const int r = run();
+    e->stamp = nullptr;  // on every exit: the buffer goes with tmp
     e->stamp_layer = -1;
     return r;
 }
@@ -534,19 +525,21 @@ extern "C" int gemma_engine_token_stamps(gemma_engine *e, unsigned long long *ou
     const size_t n = (size_t)(e->cfg.n_embd / 8) * e->cfg.n_layer * 16 + 256;  // + per-pop probes
     unsigned long long *buf = nullptr;
     GHIP_CHECK(hipStreamSynchronize(e->stream));
-    GHIP_CHECK(hipMalloc(&buf, n * 8));
+    dev_pool tmp;
+    if (tmp.get(&buf, n * 8)) return -1;
     GHIP_CHECK(hipMemset(buf, 0, n * 8));
     tok_args a = e->tok;
     a.dbg_t = buf;
     GHIP_CHECK(hipMemcpy(e->tok_dev, &a, sizeof(a), hipMemcpyHostToDevice));
     const int r = enqueue_step(e);
-    GHIP_CHECK(hipStreamSynchronize(e->stream));
+    const hipError_t se = hipStreamSynchronize(e->stream);
+    // back to the plain arguments before anything can return: buf goes with tmp
     GHIP_CHECK(hipMemcpy(e->tok_dev, &e->tok, sizeof(e->tok), hipMemcpyHostToDevice));
+    GHIP_CHECK(se);
     if (r == 0) {
         GHIP_CHECK(hipMemcpy(out, buf, n * 8, hipMemcpyDeviceToHost));
         e->host_pos += 1;
     }
-    (void)hipFree(buf);
     return r;
 }
 
@@ -556,16 +549,19 @@ extern "C" int gemma_engine_debug_step(gemma_engine *e, float *host_taps, float 
     (void)hipSetDevice(e->device);
     const gemma_hip_config &c = e->cfg;
     const size_t per = (size_t)e->qkv_rows + e->qw + c.n_embd;
-    GHIP_CHECK(hipMalloc(&e->dbg, per * c.n_layer * 4));
-    const int r = enqueue_step(e);
-    GHIP_CHECK(hipStreamSynchronize(e->stream));
-    if (r == 0) {
+    dev_pool tmp;
+    if (tmp.get(&e->dbg, per * c.n_layer * 4)) return -1;
+    auto run = [&]() -> int {
+        const int r = enqueue_step(e);
+        GHIP_CHECK(hipStreamSynchronize(e->stream));
+        if (r) return r;
         GHIP_CHECK(hipMemcpy(host_taps, e->dbg, per * c.n_layer * 4, hipMemcpyDeviceToHost));
         if (logits) GHIP_CHECK(hipMemcpy(logits, e->logits, (size_t)c.n_vocab * 4, hipMemcpyDeviceToHost));
         e->host_pos += 1;
-    }
-    GHIP_CHECK(hipFree(e->dbg));
-    e->dbg = nullptr;
+        return 0;
+    };
+    const int r = run();
+    e->dbg = nullptr;  // on every exit (persist_on() is false while it is set); the buffer goes with tmp
     return r;
 }
 
@@ -580,26 +576,27 @@ extern "C" int gemma_test_attn_decode(const float *qkv, uint16_t *kc, uint16_t *
     build_f16_tables(et, gt);
     std::vector<float> rc, rs;
     build_rope(ctx, hd, rope_base, rc, rs);
+    dev_pool tmp;
     float *d_qkv, *d_out, *d_c, *d_s;
     uint16_t *d_k, *d_v, *d_e;
     int *d_pos;
     float *d_dw = nullptr, *d_di = nullptr;
     unsigned long long *d_dt = nullptr;
     const size_t n_stamps = (size_t)H * 8 * 8;  // >= workgroups x 8 stamps for any hd <= 512
-    if (dbg_t) GHIP_CHECK(hipMalloc(&d_dt, n_stamps * 8));
+    if (dbg_t && tmp.get(&d_dt, n_stamps * 8)) return -1;
     if (dbg_t) GHIP_CHECK(hipMemset(d_dt, 0, n_stamps * 8));
     uint16_t *d_dp = nullptr;
-    if (dbg_w) GHIP_CHECK(hipMalloc(&d_dw, (size_t)H * ctx * 4));
-    if (dbg_p) GHIP_CHECK(hipMalloc(&d_dp, (size_t)H * ctx * 2));
-    if (dbg_inv) GHIP_CHECK(hipMalloc(&d_di, (size_t)H * 4));
-    GHIP_CHECK(hipMalloc(&d_qkv, qkv_n * 4));
-    GHIP_CHECK(hipMalloc(&d_out, (size_t)H * hd * 4));
-    GHIP_CHECK(hipMalloc(&d_c, rc.size() * 4));
-    GHIP_CHECK(hipMalloc(&d_s, rs.size() * 4));
-    GHIP_CHECK(hipMalloc(&d_k, cache_n * 2));
-    GHIP_CHECK(hipMalloc(&d_v, cache_n * 2));
-    GHIP_CHECK(hipMalloc(&d_e, 65536 * 2));
-    GHIP_CHECK(hipMalloc(&d_pos, 4));
+    if (dbg_w && tmp.get(&d_dw, (size_t)H * ctx * 4)) return -1;
+    if (dbg_p && tmp.get(&d_dp, (size_t)H * ctx * 2)) return -1;
+    if (dbg_inv && tmp.get(&d_di, (size_t)H * 4)) return -1;
+    if (tmp.get(&d_qkv, qkv_n * 4)) return -1;
+    if (tmp.get(&d_out, (size_t)H * hd * 4)) return -1;
+    if (tmp.get(&d_c, rc.size() * 4)) return -1;
+    if (tmp.get(&d_s, rs.size() * 4)) return -1;
+    if (tmp.get(&d_k, cache_n * 2)) return -1;
+    if (tmp.get(&d_v, cache_n * 2)) return -1;
+    if (tmp.get(&d_e, 65536 * 2)) return -1;
+    if (tmp.get(&d_pos, 4)) return -1;
     GHIP_CHECK(hipMemcpy(d_qkv, qkv, qkv_n * 4, hipMemcpyHostToDevice));
     GHIP_CHECK(hipMemcpy(d_c, rc.data(), rc.size() * 4, hipMemcpyHostToDevice));
     GHIP_CHECK(hipMemcpy(d_s, rs.data(), rs.size() * 4, hipMemcpyHostToDevice));
@@ -611,15 +608,15 @@ extern "C" int gemma_test_attn_decode(const float *qkv, uint16_t *kc, uint16_t *
     float *d_sb = nullptr;
     int *d_sy = nullptr;
     if (g.nwg) {
-        GHIP_CHECK(hipMalloc(&d_sb, g.sbuf_floats * 4));
-        GHIP_CHECK(hipMalloc(&d_sy, (g.sync_ints + 1) * 4));
+        if (tmp.get(&d_sb, g.sbuf_floats * 4)) return -1;
+        if (tmp.get(&d_sy, (g.sync_ints + 1) * 4)) return -1;
         GHIP_CHECK(hipMemset(d_sy, 0, (g.sync_ints + 1) * 4));
     }
     attn_args a;
     a.qkv = d_qkv; a.kc = d_k; a.vc = d_v; a.rope_cos = d_c; a.rope_sin = d_s; a.exp_tab = d_e; a.pos = d_pos;
     a.nwg = g.nwg; a.sbuf = d_sb; a.sync = d_sy; a.err = d_sy ? d_sy + g.sync_ints : nullptr;
     float *d_rc = nullptr;
-    GHIP_CHECK(hipMalloc(&d_rc, (size_t)(hd + 4) * 4));
+    if (tmp.get(&d_rc, (size_t)(hd + 4) * 4)) return -1;
     GHIP_CHECK(hipMemcpy(d_rc, rc.data() + (size_t)pos * (hd / 2), (size_t)(hd / 2) * 4, hipMemcpyHostToDevice));
     GHIP_CHECK(hipMemcpy(d_rc + hd / 2, rs.data() + (size_t)pos * (hd / 2), (size_t)(hd / 2) * 4, hipMemcpyHostToDevice));
     GHIP_CHECK(hipMemcpy(d_rc + hd, &pos, 4, hipMemcpyHostToDevice));
@@ -649,19 +646,16 @@ extern "C" int gemma_test_attn_decode(const float *qkv, uint16_t *kc, uint16_t *
             r = -1;
         }
     }
-    void *bufs[] = {d_qkv, d_out, d_c, d_s, d_k, d_v, d_e, d_pos, d_dw, d_dp, d_di, d_dt, d_sb, d_sy, d_rc};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
     return r;
 }
 
 extern "C" int gemma_test_exp_f16(uint16_t *out) {
     set_error("");
+    dev_pool tmp;
     uint16_t *d = nullptr;
-    GHIP_CHECK(hipMalloc(&d, 65536 * 2));
+    if (tmp.get(&d, 65536 * 2)) return -1;
     int r = launch_exp_f16_all(d, nullptr);
     if (r == 0) GHIP_CHECK(hipMemcpy(out, d, 65536 * 2, hipMemcpyDeviceToHost));
-    (void)hipFree(d);
     return r;
 }
 
@@ -677,9 +671,8 @@ extern "C" int gemma_test_rms_norm(int kind, const float *x, const float *w, int
     const size_t in_b = (size_t)rows * n * 4, out_b = kind == 0 ? in_b : (size_t)rows * (n / 256) * 292;
     float *dx = nullptr, *dw = nullptr;
     uint8_t *dy = nullptr;
-    GHIP_CHECK(hipMalloc(&dx, in_b));
-    GHIP_CHECK(hipMalloc(&dw, (size_t)n * 4));
-    GHIP_CHECK(hipMalloc(&dy, out_b));
+    dev_pool tmp;
+    if (tmp.get(&dx, in_b) || tmp.get(&dw, (size_t)n * 4) || tmp.get(&dy, out_b)) return -1;
     GHIP_CHECK(hipMemcpy(dx, x, in_b, hipMemcpyHostToDevice));
     if (w) GHIP_CHECK(hipMemcpy(dw, w, (size_t)n * 4, hipMemcpyHostToDevice));
     int r;
@@ -697,9 +690,6 @@ extern "C" int gemma_test_rms_norm(int kind, const float *x, const float *w, int
         r = launch_norm_q8K(dx, n, dw, n, eps, rows, dy, (n / 256) * 292, nullptr);
     }
     if (r == 0) GHIP_CHECK(hipMemcpy(out, dy, out_b, hipMemcpyDeviceToHost));
-    (void)hipFree(dx);
-    (void)hipFree(dw);
-    (void)hipFree(dy);
     return r;
 }
 
@@ -713,10 +703,8 @@ extern "C" double gemma_hbm_read_probe(int device, size_t bytes, int iters, int 
     if (hipSetDevice(device) != hipSuccess) return -1.0;
     void *buf = nullptr;
     unsigned *sink = nullptr;
-    if (hipMalloc(&buf, bytes) != hipSuccess || hipMalloc(&sink, 4) != hipSuccess) {
-        set_error("gemma_hbm_read_gbs: allocation failed");
-        return -1.0;
-    }
+    dev_pool tmp;
+    if (tmp.get(&buf, bytes) || tmp.get(&sink, 4)) return -1.0;
     (void)hipMemset(buf, 1, bytes);
     hipStream_t s;
     (void)hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
@@ -736,8 +724,6 @@ extern "C" double gemma_hbm_read_probe(int device, size_t bytes, int iters, int 
     (void)hipEventDestroy(t0);
     (void)hipEventDestroy(t1);
     (void)hipStreamDestroy(s);
-    (void)hipFree(buf);
-    (void)hipFree(sink);
     return gbs;
 }
 

@@ -56,6 +56,14 @@ struct gemma_engine {
     gemma_hip_config cfg{};
     int device = 0;
     hipStream_t stream = nullptr;
+    // ---- memory (DESIGN.md §Memory ownership) ----
+    // Every allocation belongs to one of two pools; gemma_engine_free clears them, nothing else frees.
+    //   mem     the engine's lifetime: weights, caches, tables, activations, decode state, and what is
+    //           created on first use and then kept (sampler workspace, verify buffers, pinned stages)
+    //   pf_mem  the batched prefill's scratch, dropped and re-made whole when a pass needs more rows
+    // The rule: anything a captured graph can hold lives in `mem` and is never reallocated; anything
+    // that is reallocated calls drop_graph.  (The decode graph holds no pf_mem address.)
+    dev_pool mem, pf_mem;
     int qw = 0, kvw = 0, qkv_rows = 0;
     // ---- weights ----
     tiled_mat embd;
@@ -67,8 +75,7 @@ struct gemma_engine {
     uint8_t *embd_q6k = nullptr;
     bool embd_tiled = false;  // embd_q6k in the lane-contiguous layout (launch_kq_retile)
     int64_t embd_row_bytes = 0;
-    uint8_t *xq8k = nullptr;  // Q8_K rows of rms_norm(x)*out_norm (decode: 1 row; prefill: T rows)
-    int64_t xq8k_rows = 0;
+    uint8_t *xq8k = nullptr;  // the decode step's Q8_K row of rms_norm(x)*out_norm (in the captured graph)
     // ---- K-quant layers ----
     bool kq = false;              // K-quant layers (kql) instead of the tiled Q4_0 / Q8_0 ones
     std::vector<kq_layer> kql;
@@ -184,6 +191,7 @@ struct gemma_engine {
         int8_t *XQ = nullptr;
         uint16_t *XH = nullptr;  // f16 image of the quantized activations (exact GEMM operand)
         uint16_t *XM = nullptr;  // K-quant prefill: the Q4_K mins operand of the Q8_K image (k_q8k_expand)
+        uint8_t *XQ8K = nullptr;  // Q6_K head: the T Q8_K rows of rms_norm(x)*out_norm
         void *keys = nullptr;
     } pf;
     // ---- verify pass (gemma_engine_verify; allocated at its first call) ----

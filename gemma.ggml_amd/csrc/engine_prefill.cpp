@@ -5,31 +5,31 @@
 
 #include "engine_impl.h"
 
-// prefill buffers (lazily sized for the largest pass seen: the prompt, or a gemma_engine_prefill_next chunk)
+// prefill buffers (lazily sized for the largest pass seen: the prompt, or a gemma_engine_prefill_next
+// chunk).  A regrow drops the whole scratch and makes it anew; pf.T is set last, so a failed regrow
+// leaves T = 0 and no pointer to freed memory.
 static int prefill_alloc(gemma_engine *e, int T) {
     auto &p = e->pf;
     if (p.T >= T) return 0;
-    void *bufs[] = {p.X, p.SA, p.QKV, p.ATT, p.G, p.U, p.LG, p.DA, p.Q16, p.XQ, p.XH, p.XM, p.keys};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
+    dev_pool &M = e->pf_mem;
+    M.clear();
+    p = {};
     const gemma_hip_config &c = e->cfg;
     const int64_t E = c.n_embd, F = c.n_ff;
     p.ldq = (std::max(std::max(E, F), (int64_t)e->qw) + 255) / 256 * 256;
     p.ldd = p.ldq / 32;
-    GHIP_CHECK(hipMalloc(&p.X, (size_t)T * E * 4));
-    GHIP_CHECK(hipMalloc(&p.SA, (size_t)T * E * 4));
-    GHIP_CHECK(hipMalloc(&p.QKV, (size_t)T * e->qkv_rows * 4));
-    GHIP_CHECK(hipMalloc(&p.ATT, (size_t)T * e->qw * 4));
-    GHIP_CHECK(hipMalloc(&p.G, (size_t)T * F * 4));
-    GHIP_CHECK(hipMalloc(&p.U, (size_t)T * F * 4));
-    GHIP_CHECK(hipMalloc(&p.LG, (size_t)T * c.n_vocab * 4));  // all rows, as the reference computes them
-    GHIP_CHECK(hipMalloc(&p.DA, (size_t)T * p.ldd * 4));
-    GHIP_CHECK(hipMalloc(&p.Q16, (size_t)T * e->qw * 2));
-    // K-quant layers: XQ holds T Q8_K columns (292 B per 256 values) instead of the int8 image
-    GHIP_CHECK(hipMalloc(&p.XQ, (size_t)T * (e->kq ? p.ldq / 256 * 292 : p.ldq)));
-    GHIP_CHECK(hipMalloc(&p.XH, (size_t)T * p.ldq * 2));
-    GHIP_CHECK(hipMalloc(&p.XM, (size_t)T * (p.ldq / 256) * 32));
-    GHIP_CHECK(hipMalloc(&p.keys, 256 * 8));
+    if (M.get(&p.X, (size_t)T * E * 4) || M.get(&p.SA, (size_t)T * E * 4) || M.get(&p.QKV, (size_t)T * e->qkv_rows * 4) ||
+        M.get(&p.ATT, (size_t)T * e->qw * 4) || M.get(&p.G, (size_t)T * F * 4) || M.get(&p.U, (size_t)T * F * 4) ||
+        M.get(&p.LG, (size_t)T * c.n_vocab * 4) ||  // all rows, as the reference computes them
+        M.get(&p.DA, (size_t)T * p.ldd * 4) || M.get(&p.Q16, (size_t)T * e->qw * 2) ||
+        // K-quant layers: XQ holds T Q8_K columns (292 B per 256 values) instead of the int8 image
+        M.get(&p.XQ, (size_t)T * (e->kq ? p.ldq / 256 * 292 : p.ldq)) || M.get(&p.XH, (size_t)T * p.ldq * 2) ||
+        M.get(&p.XM, (size_t)T * (p.ldq / 256) * 32) || M.get(&p.keys, 256 * 8) ||
+        (e->out_type == T_Q6_K && M.get(&p.XQ8K, (size_t)T * (E / 256) * 292))) {
+        M.clear();
+        p = {};
+        return -1;
+    }
     p.T = T;
     return 0;
 }
@@ -137,20 +137,15 @@ static int enqueue_prefill(gemma_engine *e, int T, int p0, bool exact, float *ta
     }
     if (q6) {  // Q6_K tied output: Q8_K INIT of every row, then the K-quant dot per (vocab row, position)
         const int64_t ld = E / 256 * 292;
-        if (e->xq8k_rows < T) {
-            GHIP_CHECK(hipFree(e->xq8k));
-            GHIP_CHECK(hipMalloc(&e->xq8k, (size_t)(ld * T)));
-            e->xq8k_rows = T;
-        }
-        if (launch_norm_q8K(p.X, E, e->out_norm, (int)E, c.eps, T, e->xq8k, ld, s)) return -1;
+        if (launch_norm_q8K(p.X, E, e->out_norm, (int)E, c.eps, T, p.XQ8K, ld, s)) return -1;
         if (exact && kq_prefill_mfma(T) && e->embd_tiled && E % 2048 == 0) {  // the MFMA GEMM (prefill_kq.hip)
-            if (kq_expand(e, e->xq8k, ld, E, T)) return -1;
+            if (kq_expand(e, p.XQ8K, ld, E, T)) return -1;
             kqg_args g;
             g.w = e->embd_q6k; g.row_bytes = e->embd_row_bytes; g.rows = c.n_vocab; g.nsb = (int)(E / 256); g.T = T;
             g.xh = p.XH; g.ldh = p.ldq; g.xd = p.DA; g.ldd = p.ldd; g.xm = p.XM; g.ldm = p.ldq / 256;
             g.y = p.LG; g.ldy = c.n_vocab;
             if (launch_gemm_kq(T_Q6_K, g, s)) return -1;
-        } else if (enqueue_logits_q6k(e, e->xq8k, T, p.LG)) {
+        } else if (enqueue_logits_q6k(e, p.XQ8K, T, p.LG)) {
             return -1;
         }
     } else {
@@ -329,13 +324,13 @@ extern "C" int gemma_engine_prefill_taps(gemma_engine *e, float *host_taps, int 
         return -1;
     }
     if (prefill_alloc(e, T)) return -1;
+    dev_pool tmp;
     float *d = nullptr;
     const size_t n = (size_t)c.n_layer * T * c.n_embd;
-    GHIP_CHECK(hipMalloc(&d, n * 4));
+    if (tmp.get(&d, n * 4)) return -1;
     int r = enqueue_prefill(e, T, 0, exact != 0, d);
     if (r == 0) GHIP_CHECK(hipStreamSynchronize(e->stream));
     if (r == 0) GHIP_CHECK(hipMemcpy(host_taps, d, n * 4, hipMemcpyDeviceToHost));
-    (void)hipFree(d);
     if (r == 0) e->host_pos = T;
     return r;
 }
@@ -374,10 +369,10 @@ int gemma_engine_ext_decode(gemma_engine *e, int token, int pos, float *logits) 
     const bool pchk = persist_on(e) && e->tok_err;
     auto copy_out = [&]() -> int {
         if (pchk) {
-            if (!e->ext_err) GHIP_CHECK(hipHostMalloc((void **)&e->ext_err, 16, hipHostMallocDefault));
+            if (!e->ext_err && e->mem.get(&e->ext_err, 16, MEM_PINNED)) return -1;
             GHIP_CHECK(hipMemcpyAsync(e->ext_err, e->tok_err, 12, hipMemcpyDeviceToHost, e->stream));
         }
-        if (!e->ext_stage) GHIP_CHECK(hipHostMalloc((void **)&e->ext_stage, lb, hipHostMallocDefault));
+        if (!e->ext_stage && e->mem.get(&e->ext_stage, lb, MEM_PINNED)) return -1;
         GHIP_CHECK(hipMemcpyAsync(e->ext_stage, e->logits, lb, hipMemcpyDeviceToHost, e->stream));
         GHIP_CHECK(hipStreamSynchronize(e->stream));
         return 0;
@@ -413,7 +408,7 @@ int gemma_engine_ext_prefill(gemma_engine *e, const int32_t *tokens, int T, floa
         (void)hipSetDevice(e->device);
         if (ext_set_position(e, tokens[0], 0) || enqueue_step(e) || ensure_graph(e)) return -1;
         GHIP_CHECK(hipGraphLaunch(e->graph_exec, e->stream));  // the graph's first launch uploads it
-        if (!e->ext_stage) GHIP_CHECK(hipHostMalloc((void **)&e->ext_stage, (size_t)e->cfg.n_vocab * 4, hipHostMallocDefault));
+        if (!e->ext_stage && e->mem.get(&e->ext_stage, (size_t)e->cfg.n_vocab * 4, MEM_PINNED)) return -1;
         GHIP_CHECK(hipMemcpyAsync(e->ext_stage, e->logits, (size_t)e->cfg.n_vocab * 4, hipMemcpyDeviceToHost, e->stream));
         GHIP_CHECK(hipStreamSynchronize(e->stream));
     }

@@ -3,11 +3,14 @@
 // loop that alternates verify passes and plain graph steps.
 #include "engine_impl.h"
 
+// the verify buffers: made at the first call and kept for the engine's lifetime (never regrown)
 static int verify_alloc(gemma_engine *e) {
-    if (e->vf.keys) return 0;
-    GHIP_CHECK(hipMalloc(&e->vf.keys, (size_t)(GEMM_SKINNY_MAX_T * 256 + GEMM_SKINNY_MAX_T) * 8));
-    GHIP_CHECK(hipMalloc(&e->vf.ints, (size_t)(GEMM_SKINNY_MAX_T + GEMM_SKINNY_MAX_T + 1) * 4));
-    GHIP_CHECK(hipHostMalloc((void **)&e->vf.host, (size_t)(3 * GEMM_SKINNY_MAX_T + 1) * 4, hipHostMallocDefault));
+    auto &v = e->vf;
+    dev_pool &M = e->mem;
+    if ((!v.keys && M.get(&v.keys, (size_t)(GEMM_SKINNY_MAX_T * 256 + GEMM_SKINNY_MAX_T) * 8)) ||
+        (!v.ints && M.get(&v.ints, (size_t)(GEMM_SKINNY_MAX_T + GEMM_SKINNY_MAX_T + 1) * 4)) ||
+        (!v.host && M.get(&v.host, (size_t)(3 * GEMM_SKINNY_MAX_T + 1) * 4, MEM_PINNED)))
+        return -1;
     return 0;
 }
 

@@ -194,6 +194,7 @@ struct executor {
     std::recursive_mutex mu;
     bool inited = false;
     hipStream_t stream = nullptr;
+    dev_pool mem;  // owns the mirrors, the tiled copies, the scratch and the process-lifetime tables
     std::unordered_map<const void *, leaf_mirror> leaves;  // keyed by root host data pointer
     // quantized src0 re-tiled for the hot path, keyed by (data, type, ne0, ne1): two views of one
     // weight (a row range from its first row, a reshape) share a pointer but not a tiling
@@ -208,8 +209,10 @@ struct executor {
 };
 
 executor &ex() {
-    static executor e;
-    return e;
+    // never destroyed: the tables and scratch live to the process's end, and no static destructor
+    // calls into a runtime already shut down
+    static executor *e = new executor;
+    return *e;
 }
 
 bool in_backend_buffer(const void *p) {
@@ -222,10 +225,10 @@ int ensure_init() {
     executor &e = ex();
     if (e.inited) return 0;
     if (hpc_init(0)) return -1;
-    GHIP_CHECK(hipStreamCreateWithFlags(&e.stream, hipStreamNonBlocking));
+    if (!e.stream) GHIP_CHECK(hipStreamCreateWithFlags(&e.stream, hipStreamNonBlocking));  // once: a failed init is retried
     std::vector<uint16_t> et, gt;
     build_f16_tables(et, gt);
-    GHIP_CHECK(hipMalloc(&e.gelu_tab, 65536 * 2));
+    if (!e.gelu_tab && e.mem.get(&e.gelu_tab, 65536 * 2)) return -1;
     GHIP_CHECK(hipMemcpy(e.gelu_tab, gt.data(), 65536 * 2, hipMemcpyHostToDevice));
     e.inited = true;
     return 0;
@@ -234,13 +237,16 @@ int ensure_init() {
 int ensure_rope(int npos, int n_dims, float base) {
     executor &e = ex();
     if (e.rope_c && e.rope_npos >= npos && e.rope_dims == n_dims && e.rope_base == base) return 0;
-    if (e.rope_c) (void)hipFree(e.rope_c);
-    if (e.rope_s) (void)hipFree(e.rope_s);
+    e.mem.put(e.rope_c);
+    e.mem.put(e.rope_s);
+    e.rope_npos = 0;  // no table is valid until the new ones are filled
     const int n = std::max(npos, 512);
     std::vector<float> c, s;
     build_rope(n, n_dims, base, c, s);
-    GHIP_CHECK(hipMalloc(&e.rope_c, c.size() * 4));
-    GHIP_CHECK(hipMalloc(&e.rope_s, s.size() * 4));
+    if (e.mem.get(&e.rope_c, c.size() * 4) || e.mem.get(&e.rope_s, s.size() * 4)) {
+        e.mem.put(e.rope_c);
+        return -1;
+    }
     GHIP_CHECK(hipMemcpy(e.rope_c, c.data(), c.size() * 4, hipMemcpyHostToDevice));
     GHIP_CHECK(hipMemcpy(e.rope_s, s.data(), s.size() * 4, hipMemcpyHostToDevice));
     e.rope_npos = n;
@@ -263,9 +269,9 @@ struct run_state {
 int scratch_reserve(size_t bytes) {
     executor &e = ex();
     if (e.scratch_bytes >= bytes) return 0;
-    if (e.scratch) GHIP_CHECK(hipFree(e.scratch));
-    e.scratch = nullptr;
-    GHIP_CHECK(hipMalloc(&e.scratch, bytes));
+    e.mem.put(e.scratch);
+    e.scratch_bytes = 0;
+    if (e.mem.get(&e.scratch, bytes)) return -1;
     e.scratch_bytes = bytes;
     return 0;
 }
@@ -304,10 +310,11 @@ int sync_leaf(ggml_tensor *r, bool graph_written) {
     const size_t bytes = ggml_nbytes(r);
     leaf_mirror &m = e.leaves[r->data];
     if (m.bytes < bytes) {
-        if (m.dev) GHIP_CHECK(hipFree(m.dev));
-        GHIP_CHECK(hipMalloc(&m.dev, bytes));
-        m.bytes = bytes;
+        e.mem.put(m.dev);
+        m.bytes = 0;
         m.valid = false;
+        if (e.mem.get(&m.dev, bytes)) return -1;
+        m.bytes = bytes;
     }
     const bool host_written_input = in_backend_buffer(r->data) && !graph_written;
     if (!m.valid || host_written_input) {
@@ -326,10 +333,11 @@ const tiled_mat *tiled_weight(run_state &rs, ggml_tensor *w) {
         set_error("ggml mul_mat: quantized src0 must be contiguous");
         return nullptr;
     }
-    tiled_mat m = alloc_tiled(w->type, w->ne[1], w->ne[0], e.stream);
+    tiled_mat m;
+    if (alloc_tiled(e.mem, &m, w->type, w->ne[1], w->ne[0], e.stream)) return nullptr;
     const char *src = dev_addr(rs, w);
     if (!src || launch_repack(m, (const uint8_t *)src, (int64_t)w->nb[1], e.stream)) {
-        free_tiled(m);
+        free_tiled(e.mem, m);
         if (!src) set_error("ggml mul_mat: src0 has no device data");
         return nullptr;
     }
@@ -343,7 +351,7 @@ void drop_tiled_in(const void *p, size_t bytes) {
     for (auto it = e.tiled.begin(); it != e.tiled.end();) {
         const char *k = (const char *)std::get<0>(it->first);
         if (k >= (const char *)p && k < (const char *)p + bytes) {
-            free_tiled(it->second);
+            free_tiled(e.mem, it->second);
             it = e.tiled.erase(it);
         } else {
             ++it;
@@ -984,7 +992,7 @@ void ggml_free(struct ggml_context *ctx) {
             if (t->view_src || !t->data) continue;
             auto it = ex().leaves.find(t->data);
             if (it != ex().leaves.end() && !in_backend_buffer(t->data)) {
-                (void)hipFree(it->second.dev);
+                ex().mem.put(it->second.dev);
                 ex().leaves.erase(it);
             }
         }
@@ -1412,7 +1420,7 @@ void ggml_backend_buffer_free(ggml_backend_buffer_t b) {
     for (ggml_tensor *t : b->tensors) {
         auto it = ex().leaves.find(t->data);
         if (it != ex().leaves.end()) {
-            (void)hipFree(it->second.dev);
+            ex().mem.put(it->second.dev);
             ex().leaves.erase(it);
         }
     }

@@ -90,10 +90,12 @@ int launch_g_mul_mat_f16(const gt_desc &a, const uint16_t *b16, int64_t ne10, co
 // host tables and tiled weights shared with the engine (engine.cpp)
 void build_f16_tables(std::vector<uint16_t> &exp_t, std::vector<uint16_t> &gelu_t);
 void build_rope(int ctx, int hd, float base, std::vector<float> &c, std::vector<float> &s);
-tiled_mat alloc_tiled(int type, int64_t rows, int64_t K, hipStream_t s);
+// both planes from `mem`, zeroed on s; -1 (error set, nothing kept) when an allocation fails
+int alloc_tiled(dev_pool &mem, tiled_mat *out, int type, int64_t rows, int64_t K, hipStream_t s);
+// for the cache owners that drop single entries (an engine's matrices go with its pool)
+void free_tiled(dev_pool &mem, tiled_mat &m);
 // capi.cpp: the C-ABI weight cache's tiled copy of a host weight (hpc_register_weight / mul_mat)
 bool registered_tiled(const void *host, int type, int64_t K, tiled_mat *out);
-void free_tiled(tiled_mat &m);
 
 // ---- K-quant matvec (kquant.hip) -----------------------------------------------------------------
 struct kq_args {  // y[c][r] = vec_dot_{q4_K,q6_K}_q8_K(row r of w, column c of x), ggml AVX2 lane order
@@ -460,8 +462,8 @@ struct sample_ws {  // scratch of one sampler (sample_ws_alloc); the tail launch
 struct sample_dbg {  // optional outputs (tests): the token, cand[SAMPLE_MAX_K] (-1 past K), K, m
     int *token = nullptr, *cand = nullptr, *n_cand = nullptr, *n_kept = nullptr;
 };
-int sample_ws_alloc(sample_ws *w, int64_t n_vocab, hipStream_t s);
-void sample_ws_free(sample_ws *w);
+int sample_ws_alloc(dev_pool &mem, sample_ws *w, int64_t n_vocab, hipStream_t s);  // all four buffers, or none
+void sample_ws_free(dev_pool &mem, sample_ws *w);
 // three launches: the token for sequence index *pos + 1 from row[0 .. n) into *w.key; prm and pos are
 // device pointers read by the kernels; the geometry depends on n only
 int launch_sample(const float *row, int64_t n, const sampler_params *prm, const int *pos, const sample_ws &w,

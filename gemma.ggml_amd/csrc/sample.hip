@@ -294,28 +294,27 @@ __global__ void __launch_bounds__(SM_TAIL) k_sample_tail(const sampler_params *p
 
 }  // namespace
 
-int sample_ws_alloc(sample_ws *w, int64_t n_vocab, hipStream_t s) {
+int sample_ws_alloc(dev_pool &mem, sample_ws *w, int64_t n_vocab, hipStream_t s) {
     if (n_vocab <= 0 || n_vocab > 0x7FFFFFFFll) {
         set_error("sampler: n_vocab out of range");
         return -1;
     }
     *w = sample_ws{};
     w->cap_b = n_vocab;
-    GHIP_CHECK(hipMalloc(&w->hist, (size_t)(SM_BINS + 16) * 4));
+    if (mem.get_zeroed(&w->hist, (size_t)(SM_BINS + 16) * 4, s) || mem.get(&w->list_a, (size_t)SAMPLE_MAX_K * 8) ||
+        mem.get(&w->list_b, (size_t)n_vocab * 8) || mem.get_zeroed(&w->key, 8, s)) {
+        sample_ws_free(mem, w);
+        return -1;
+    }
     w->cur = w->hist + SM_BINS;
-    GHIP_CHECK(hipMalloc(&w->list_a, (size_t)SAMPLE_MAX_K * 8));
-    GHIP_CHECK(hipMalloc(&w->list_b, (size_t)n_vocab * 8));
-    GHIP_CHECK(hipMalloc(&w->key, 8));
-    GHIP_CHECK(hipMemsetAsync(w->hist, 0, (size_t)(SM_BINS + 16) * 4, s));
-    GHIP_CHECK(hipMemsetAsync(w->key, 0, 8, s));
     return 0;
 }
 
-void sample_ws_free(sample_ws *w) {
-    if (w->hist) (void)hipFree(w->hist);
-    if (w->list_a) (void)hipFree(w->list_a);
-    if (w->list_b) (void)hipFree(w->list_b);
-    if (w->key) (void)hipFree(w->key);
+void sample_ws_free(dev_pool &mem, sample_ws *w) {
+    mem.put(w->hist);
+    mem.put(w->list_a);
+    mem.put(w->list_b);
+    mem.put(w->key);
     *w = sample_ws{};
 }
 

@@ -39,7 +39,7 @@ EXPORTS = ["mul_mat", "hpc_init", "hpc_shutdown", "hpc_register_weight", "hpc_la
            "gemma_engine_create_from_gguf", "gemma_engine_config",
            "gemma_engine_set_sampler", "gemma_engine_sampler", "gemma_test_sample",
            "gemma_engine_verify", "gemma_engine_kv_read", "gemma_lookup_draft", "gemma_engine_generate_lookup",
-           "gemma_test_gemm_skinny"]
+           "gemma_test_gemm_skinny", "gemma_hip_mem_live"]
 
 
 def build():
@@ -106,6 +106,7 @@ def lib():
     L.hpc_last_error.argtypes = [C.c_char_p, C.c_size_t]
     L.hpc_set_error_mode.argtypes = [C.c_int]
     L.hpc_weight_cache_entries.restype = C.c_int
+    L.gemma_hip_mem_live.argtypes = [C.POINTER(i64), C.POINTER(i64)]
     L.hpc_set_matvec_ks.argtypes = [C.c_int]
     L.hpc_set_gemm_x4.argtypes = [C.c_int]
     L.hpc_set_gemm_x4.restype = None
@@ -228,6 +229,13 @@ def last_error():
     buf = C.create_string_buffer(1024)
     lib().hpc_last_error(buf, 1024)
     return buf.value.decode()
+
+
+def mem_live():
+    """(live allocations, live bytes) of the whole library: gemma_hip_mem_live."""
+    n, b = C.c_int64(), C.c_int64()
+    lib().gemma_hip_mem_live(C.byref(n), C.byref(b))
+    return n.value, b.value
 
 
 def _p(a):

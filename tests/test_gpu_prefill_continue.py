@@ -165,6 +165,27 @@ def test_steps_then_batch():
     e.close()
 
 
+@pytest.mark.parametrize("shape,kmix,engine_kw", [(dict(O.TINY), 2, dict(out_type=G.GGML_TYPE_Q6_K)),
+                                                  (KSHAPE, 1, dict(wtype=G.GGML_TYPE_Q4_K))],
+                         ids=["q6K_output", "kquant_layers"])
+def test_steps_then_larger_batch_then_steps(shape, kmix, engine_kw):
+    """The captured decode graph holds the address of the 1-row Q8_K image of the output norm (Q6_K
+    head, K-quant `down` hand-off).  A 47-row pass after the capture must leave that address alone:
+    graph steps, the batch, then graph steps again, every row and step against the oracle."""
+    n_ctx = 128
+    prompt = tuple(int(t) for t in O.make_prompt(60, shape["n_vocab"]))
+    truth = _truth(_key(shape), n_ctx, O.Q4_0, kmix, prompt)
+    e = G.Engine(shape, n_ctx=n_ctx, device=0, **engine_kw)
+    e.begin(prompt)
+    lg = e.step(13, want_logits=True, use_graph=True)
+    _bits_equal(lg, truth[1][:13], "13 graph steps over the prompt")
+    n_graph = e.graph_kernels()
+    assert _chunks(e, truth[1], [0]) == truth[0] and e.pos() == 60  # 47 rows in one pass
+    _decode(e, truth)
+    assert e.graph_kernels() == n_graph  # the same captured graph ran before and after the pass
+    e.close()
+
+
 def test_batch_steps_batch():
     shape, prompt, truth, e = _tiny(60)
     e.begin(prompt)
