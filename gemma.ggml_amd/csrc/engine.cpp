@@ -758,6 +758,7 @@ extern "C" void gemma_engine_free(gemma_engine *e) {
     drop_graph(e);
     for (hipEvent_t &ev : e->fc_ev)
         if (ev) (void)hipEventDestroy(ev);
+    e->bt_mem.clear();
     e->pf_mem.clear();
     e->mem.clear();
     (void)hipStreamDestroy(e->stream);

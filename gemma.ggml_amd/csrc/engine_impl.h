@@ -1,11 +1,12 @@
 // engine_impl.h — the device-resident engine's state and what its translation units share
 // (internal: included only by engine.cpp, engine_decode.cpp, engine_prefill.cpp, engine_spec.cpp,
-// engine_diag.cpp).
+// engine_batch.cpp, engine_diag.cpp).
 //   engine.cpp          lifecycle: create / free / begin / extend / step / tensor, TP and p2p set-up
 //   engine_decode.cpp   one decode token: enqueue_step (+ K-quant), the persistent launch's
 //                       arguments, the all-gathers
 //   engine_prefill.cpp  batched prefill and the ggml executor's entry points
 //   engine_spec.cpp     speculative decoding: the verify pass, lookup drafts, the generate loop
+//   engine_batch.cpp    batched decode: up to 8 sequences (slots), one row each per weight pass
 //   engine_diag.cpp     timing, tuning, plan and option setters, stamps, taps, per-op test hooks
 #pragma once
 
@@ -52,18 +53,62 @@ struct launch_plan {
     int img = 0;  // attn-out / down: read the producer-written Q8_0 image (PRO_IMG) instead of f32
 };
 
+// scratch of a batched pass, every buffer indexed by the row t of the pass (lazily sized for the
+// largest pass seen: prefill_alloc)
+struct pf_scratch {
+    int T = 0;
+    int64_t ldq = 0, ldd = 0;
+    float *X = nullptr, *SA = nullptr, *QKV = nullptr, *ATT = nullptr, *G = nullptr, *U = nullptr, *LG = nullptr;
+    float *DA = nullptr;
+    uint16_t *Q16 = nullptr;
+    int8_t *XQ = nullptr;
+    uint16_t *XH = nullptr;  // f16 image of the quantized activations (exact GEMM operand)
+    uint16_t *XM = nullptr;  // K-quant prefill: the Q4_K mins operand of the Q8_K image (k_q8k_expand)
+    uint8_t *XQ8K = nullptr;  // Q6_K head: the T Q8_K rows of rms_norm(x)*out_norm
+    void *keys = nullptr;
+};
+
+// ---- batched decode (engine_batch.cpp, DESIGN.md §5b⁗) ------------------------------------------
+// One slot = one sequence: its own caches, history, position and RoPE row, all on the device and
+// advanced there (k_batch_advance).  host_pos / n_given mirror *pos / *nfix (passes are deterministic).
+struct batch_slot {
+    uint16_t *kc = nullptr, *vc = nullptr;  // [L][ctx][kvw], [L][kvw][ctx]
+    int *hist = nullptr;                    // [ctx + 1]
+    bool active = false;
+    int host_pos = 0, n_given = 0;
+};
+struct batch_state {
+    bool open = false;
+    int n_slots = 0;
+    batch_slot slot[GEMMA_BATCH_MAX_SLOTS];
+    int *ints = nullptr;       // device: pos[8] | nfix[8] | last[8] (the pending token, -1 inactive) by slot
+    float *rope = nullptr;     // device: [8][head_dim + 4], each slot's [cos | sin | (int)pos]
+    slot_row *rows = nullptr;  // device: the pass's row -> slot table, rewritten when the active set changes
+    int *row_tok = nullptr;    // device: [8] the token each row of the next pass processes
+    unsigned long long *keys = nullptr;  // device: [8][256] greedy partial keys, then [8] sampler key slots
+    void *stage = nullptr;     // pinned: the row table's source, batch_last's result
+    pf_scratch pf;             // the pass's scratch (8 rows), never reallocated while the batch is open
+    bool dirty = true;         // the active set changed since the table was written
+    int n_rows = 0, row_slot[GEMMA_BATCH_MAX_SLOTS] = {};
+    int *pos_of(int s) const { return ints + s; }
+    int *nfix_of(int s) const { return ints + GEMMA_BATCH_MAX_SLOTS + s; }
+    int *last_of(int s) const { return ints + 2 * GEMMA_BATCH_MAX_SLOTS + s; }
+};
+
 struct gemma_engine {
     gemma_hip_config cfg{};
     int device = 0;
     hipStream_t stream = nullptr;
     // ---- memory (DESIGN.md §Memory ownership) ----
-    // Every allocation belongs to one of two pools; gemma_engine_free clears them, nothing else frees.
+    // Every allocation belongs to one of three pools; gemma_engine_free clears them, nothing else frees.
     //   mem     the engine's lifetime: weights, caches, tables, activations, decode state, and what is
     //           created on first use and then kept (sampler workspace, verify buffers, pinned stages)
     //   pf_mem  the batched prefill's scratch, dropped and re-made whole when a pass needs more rows
+    //   bt_mem  the batched decode's slots, tables and pass scratch: made whole by batch_open, cleared by
+    //           batch_close; nothing in it is reallocated while the batch is open
     // The rule: anything a captured graph can hold lives in `mem` and is never reallocated; anything
     // that is reallocated calls drop_graph.  (The decode graph holds no pf_mem address.)
-    dev_pool mem, pf_mem;
+    dev_pool mem, pf_mem, bt_mem;
     int qw = 0, kvw = 0, qkv_rows = 0;
     // ---- weights ----
     tiled_mat embd;
@@ -181,19 +226,8 @@ struct gemma_engine {
     int grid_big_cap = 2048;  // workgroups the argmax key buffer holds
     launch_plan plan[MC_N];
     // ---- prefill ----
-    // prefill buffers (lazily sized for the prompt length)
-    struct {
-        int T = 0;
-        int64_t ldq = 0, ldd = 0;
-        float *X = nullptr, *SA = nullptr, *QKV = nullptr, *ATT = nullptr, *G = nullptr, *U = nullptr, *LG = nullptr;
-        float *DA = nullptr;
-        uint16_t *Q16 = nullptr;
-        int8_t *XQ = nullptr;
-        uint16_t *XH = nullptr;  // f16 image of the quantized activations (exact GEMM operand)
-        uint16_t *XM = nullptr;  // K-quant prefill: the Q4_K mins operand of the Q8_K image (k_q8k_expand)
-        uint8_t *XQ8K = nullptr;  // Q6_K head: the T Q8_K rows of rms_norm(x)*out_norm
-        void *keys = nullptr;
-    } pf;
+    pf_scratch pf;  // prefill buffers (lazily sized for the prompt length)
+    batch_state bt;
     // ---- verify pass (gemma_engine_verify; allocated at its first call) ----
     struct {
         unsigned long long *keys = nullptr;  // device: [8][256] greedy partial keys, then [8] sampler key slots
@@ -321,4 +355,10 @@ int enqueue_logits_q6k(gemma_engine *e, const uint8_t *x, int ncols, float *y);
 // engine_prefill.cpp: the exact batched pass over hist[p0 .. p0+T), T <= 8, with the Q4_0 / Q8_0
 // GEMMs on launch_gemm_skinny and no pick: the logits rows are left in pf.LG [T][n_vocab]
 int enqueue_verify_pass(gemma_engine *e, int T, int p0);
+// the batch's scratch (bt.pf, 8 rows, from bt_mem), and one batched-decode pass: the verify pass over
+// the batch's T rows (tokens bt.row_tok, attention by enqueue_batch_attention), logits left in bt.pf.LG
+int batch_scratch_alloc(gemma_engine *e);
+int enqueue_batch_pass(gemma_engine *e, int T);
+// engine_batch.cpp: layer il's attention step of a batch pass (k_attn_slots over the row table)
+int enqueue_batch_attention(gemma_engine *e, int il, int T);
 #pragma GCC visibility pop

@@ -8,10 +8,8 @@
 // prefill buffers (lazily sized for the largest pass seen: the prompt, or a gemma_engine_prefill_next
 // chunk).  A regrow drops the whole scratch and makes it anew; pf.T is set last, so a failed regrow
 // leaves T = 0 and no pointer to freed memory.
-static int prefill_alloc(gemma_engine *e, int T) {
-    auto &p = e->pf;
+static int scratch_alloc(gemma_engine *e, dev_pool &M, pf_scratch &p, int T) {
     if (p.T >= T) return 0;
-    dev_pool &M = e->pf_mem;
     M.clear();
     p = {};
     const gemma_hip_config &c = e->cfg;
@@ -33,14 +31,28 @@ static int prefill_alloc(gemma_engine *e, int T) {
     p.T = T;
     return 0;
 }
+static int prefill_alloc(gemma_engine *e, int T) { return scratch_alloc(e, e->pf_mem, e->pf, T); }
 
-static int enqueue_prefill_kq(gemma_engine *e, int T, int p0);
+// What the T rows of a pass are.  Every scratch buffer is indexed by the row t; the rows description
+// says where the T token ids come from and what runs at a layer's attention step:
+//   slots == false  rows are positions p0 .. p0+T-1 of the engine's own sequence: RoPE + K / V store
+//                   into the engine's caches, then the causal attention (prefill_attention)
+//   slots == true   rows are the batch's (engine_batch.cpp): row t is the next token of its own slot,
+//                   the attention is enqueue_batch_attention and the scratch is the batch's (bt.pf)
+struct pass_rows {
+    const int *tokens = nullptr;  // device array of the T token ids
+    int p0 = 0;
+    bool slots = false;
+};
+static pass_rows own_rows(const gemma_engine *e, int p0) { return pass_rows{e->hist + p0, p0, false}; }
+static pf_scratch &scratch_of(gemma_engine *e, const pass_rows &rows) { return rows.slots ? e->bt.pf : e->pf; }
+
+static int enqueue_prefill_kq(gemma_engine *e, int T, const pass_rows &rows);
 
 // the K-quant prefill's MFMA GEMM (prefill_kq.hip) for T prompt rows (kq_gemm_min: default 8)
 static bool kq_prefill_mfma(int T) { return T >= kq_gemm_min(); }
 // T Q8_K columns of K values (ld bytes apart) -> the GEMM's f16 image in the prefill scratch
-static int kq_expand(gemma_engine *e, const uint8_t *x, int64_t ld, int64_t K, int T) {
-    auto &p = e->pf;
+static int kq_expand(gemma_engine *e, pf_scratch &p, const uint8_t *x, int64_t ld, int64_t K, int T) {
     q8kx_args a;
     a.x = x; a.x_col_stride = ld; a.nsb = (int)(K / 256); a.T = T;
     a.xh = p.XH; a.ldh = p.ldq; a.xd = p.DA; a.ldd = p.ldd; a.xm = p.XM; a.ldm = p.ldq / 256;
@@ -62,10 +74,12 @@ static int launch_attn_exact(const attnp_args &at, bool mx, hipStream_t s) {
 // layer il of a T-row prefill of positions p0 .. p0+T-1, from pf.QKV: RoPE + K/V store into the
 // layer caches (which hold the positions before p0), then the causal attention into pf.ATT (exact:
 // the form *mx_form, resolved at the first layer; else f16 MFMA)
-static int prefill_attention(gemma_engine *e, int il, int T, int p0, bool exact, int *mx_form) {
+static int prefill_attention(gemma_engine *e, int il, int T, const pass_rows &rows, bool exact, int *mx_form) {
+    if (rows.slots) return enqueue_batch_attention(e, il, T);
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
     auto &p = e->pf;
+    const int p0 = rows.p0;
     ropekv_args r;
     r.qkv = p.QKV; r.ldqkv = e->qkv_rows; r.rope_cos = e->rope_cos; r.rope_sin = e->rope_sin; r.q16 = p.Q16;
     r.kc = kc_of(e, il); r.vc = vc_of(e, il);
@@ -80,16 +94,17 @@ static int prefill_attention(gemma_engine *e, int il, int T, int p0, bool exact,
     return exact ? launch_attn_exact(at, *mx_form == 1, s) : launch_attn_prefill(at, s);
 }
 
-// One batched pass over hist[p0 .. p0+T): the rows are sequence positions p0 .. p0+T-1, the caches
-// hold the positions before p0 (p0 = 0: the whole-prompt prefill).  Every scratch buffer is indexed
-// by the row t of the pass; only the token reads, RoPE, the cache stores and the attention know p0.
+// One batched pass over T rows.  Own rows (own_rows(e, p0)): hist[p0 .. p0+T), sequence positions
+// p0 .. p0+T-1, the caches hold the positions before p0 (p0 = 0: the whole-prompt prefill).  Every
+// scratch buffer is indexed by the row t of the pass; only the token reads, RoPE, the cache stores and
+// the attention know what a row is (pass_rows).
 // verify (gemma_engine_verify only, T <= 8, exact): the Q4_0 / Q8_0 GEMMs go through
 // launch_gemm_skinny and the pass ends with the logits rows: the caller picks from every row.
-static int enqueue_prefill(gemma_engine *e, int T, int p0, bool exact, float *taps = nullptr, bool verify = false) {
+static int enqueue_prefill(gemma_engine *e, int T, const pass_rows &rows, bool exact, float *taps = nullptr, bool verify = false) {
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
     int mx_form = -1;  // the exact attention's form, resolved at the first layer
-    auto &p = e->pf;
+    auto &p = scratch_of(e, rows);
     const int wt = c.wtype;
     const int64_t E = c.n_embd, F = c.n_ff;
     auto gemm = [&](const tiled_mat &m, int epi, const float *resid, float *y, int64_t ldy) {
@@ -106,7 +121,7 @@ static int enqueue_prefill(gemma_engine *e, int T, int p0, bool exact, float *ta
         a.q = (!exact || i8img) ? p.XQ : nullptr; a.qh = (exact && !i8img) ? p.XH : nullptr; a.ldq = p.ldq; a.da = p.DA; a.ldd = p.ldd;
         a.gelu_tab = e->gelu_tab; a.gelu_clamp = c.gelu_clamp;
         if (mode == QR_EMBED_NORM) {
-            a.tokens = e->hist + p0; a.emb_qs = e->embd.qs; a.emb_sc = e->embd.sc; a.emb_type = wt;
+            a.tokens = rows.tokens; a.emb_qs = e->embd.qs; a.emb_sc = e->embd.sc; a.emb_type = wt;
             a.emb_n_bt = e->embd.n_bt; a.emb_scale = sqrtf((float)E); a.emb_out = p.X; a.ldx = E;
         }
         return launch_quant_rows(mode, a, T, s);
@@ -117,15 +132,15 @@ static int enqueue_prefill(gemma_engine *e, int T, int p0, bool exact, float *ta
             set_error("gemma_engine_prefill_fast: K-quant layer engines have the exact batched prefill only");
             return -1;
         }
-        if (enqueue_prefill_kq(e, T, p0)) return -1;
-    } else if (q6 && launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, e->hist + p0, nullptr, T, (int)E, sqrtf((float)E), p.X, s, e->embd_tiled)) {
+        if (enqueue_prefill_kq(e, T, rows)) return -1;
+    } else if (q6 && launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, rows.tokens, nullptr, T, (int)E, sqrtf((float)E), p.X, s, e->embd_tiled)) {
         return -1;
     }
     for (int il = 0; il < (e->kq ? 0 : c.n_layer); ++il) {
         layer_dev &L = e->layers[il];
         if (quant(il == 0 && !q6 ? QR_EMBED_NORM : QR_NORM, p.X, nullptr, E, L.attn_norm)) return -1;
         if (gemm(L.qkv, EPI_STORE, nullptr, p.QKV, e->qkv_rows)) return -1;
-        if (prefill_attention(e, il, T, p0, exact, &mx_form)) return -1;
+        if (prefill_attention(e, il, T, rows, exact, &mx_form)) return -1;
         if (quant(QR_F32, p.ATT, nullptr, e->qw, nullptr)) return -1;
         if (gemm(L.o, EPI_ADD, p.X, p.SA, E)) return -1;
         if (quant(QR_NORM, p.SA, nullptr, E, L.ffn_norm)) return -1;
@@ -139,7 +154,7 @@ static int enqueue_prefill(gemma_engine *e, int T, int p0, bool exact, float *ta
         const int64_t ld = E / 256 * 292;
         if (launch_norm_q8K(p.X, E, e->out_norm, (int)E, c.eps, T, p.XQ8K, ld, s)) return -1;
         if (exact && kq_prefill_mfma(T) && e->embd_tiled && E % 2048 == 0) {  // the MFMA GEMM (prefill_kq.hip)
-            if (kq_expand(e, p.XQ8K, ld, E, T)) return -1;
+            if (kq_expand(e, p, p.XQ8K, ld, E, T)) return -1;
             kqg_args g;
             g.w = e->embd_q6k; g.row_bytes = e->embd_row_bytes; g.rows = c.n_vocab; g.nsb = (int)(E / 256); g.T = T;
             g.xh = p.XH; g.ldh = p.ldq; g.xd = p.DA; g.ldd = p.ldd; g.xm = p.XM; g.ldm = p.ldq / 256;
@@ -153,6 +168,7 @@ static int enqueue_prefill(gemma_engine *e, int T, int p0, bool exact, float *ta
         if (gemm(e->embd, EPI_STORE, nullptr, p.LG, c.n_vocab)) return -1;
     }
     if (verify) return 0;
+    const int p0 = rows.p0;
     // greedy token from the last row; position p0+T-1 -> p0+T, token appended at hist[p0+T] unless
     // that is still a given token (k_advance's p >= n_fixed guard: a pass that ends mid-prompt)
     // (with the sampler on: its draw at position p0+T from the same row, after *pos is in place)
@@ -169,11 +185,11 @@ static int enqueue_prefill(gemma_engine *e, int T, int p0, bool exact, float *ta
 // column's Q8_K INIT — every K-quant launch covers all T columns (grid.y) — and the exact per-row
 // attention of the Q4_0 prefill (k_rope_kv_prefill + k_attn_rows).  Bit-identical to the token
 // loop and to the CPU path: no operation depends on the batching.
-static int enqueue_prefill_kq(gemma_engine *e, int T, int p0) {
+static int enqueue_prefill_kq(gemma_engine *e, int T, const pass_rows &rows) {
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
     int mx_form = -1;  // the exact attention's form, resolved at the first layer
-    auto &p = e->pf;
+    auto &p = scratch_of(e, rows);
     const int64_t E = c.n_embd, F = c.n_ff;
     const int64_t ldk = p.ldq / 256 * 292;  // Q8_K column stride in XQ
     uint8_t *img = (uint8_t *)p.XQ;
@@ -182,7 +198,7 @@ static int enqueue_prefill_kq(gemma_engine *e, int T, int p0) {
     // GHIP_KQ_MFMA=0, the dot4 T-column kernel.  Same bytes either way (tests/test_gpu_engine_gguf.py).
     const bool mfma = kq_prefill_mfma(T);
     auto mfma_ok = [&](const kq_mat &W) { return mfma && W.tiled && (W.type == T_Q4_K || W.K % 2048 == 0); };
-    auto expand = [&](int64_t K) { return mfma ? kq_expand(e, img, ldk, K, T) : 0; };
+    auto expand = [&](int64_t K) { return mfma ? kq_expand(e, p, img, ldk, K, T) : 0; };
     auto mv = [&](const kq_mat &W, float *y, int64_t ldy, const float *resid, const float *gate_in, const kq_mat *up) {
         if (!up && mfma_ok(W)) {
             kqg_args g;
@@ -199,7 +215,7 @@ static int enqueue_prefill_kq(gemma_engine *e, int T, int p0) {
         if (up) k.w2 = up->w;
         return launch_matvec_kq(W.type, k, s);
     };
-    if (launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, e->hist + p0, nullptr, T, (int)E, sqrtf((float)E), p.X, s, e->embd_tiled)) return -1;
+    if (launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, rows.tokens, nullptr, T, (int)E, sqrtf((float)E), p.X, s, e->embd_tiled)) return -1;
     for (int il = 0; il < c.n_layer; ++il) {
         const layer_dev &L = e->layers[il];
         const kq_layer &K = e->kql[il];
@@ -214,7 +230,7 @@ static int enqueue_prefill_kq(gemma_engine *e, int T, int p0) {
             return -1;
         }
         if (mv(K.v, p.QKV + e->qw + e->kvw, ldqkv, nullptr, nullptr, nullptr)) return -1;
-        if (prefill_attention(e, il, T, p0, true, &mx_form)) return -1;
+        if (prefill_attention(e, il, T, rows, true, &mx_form)) return -1;
         if (launch_quant_q8_K(p.ATT, e->qw, e->qw, T, img, ldk, s) || expand(e->qw)) return -1;
         if (mv(K.o, p.SA, E, p.X, nullptr, nullptr)) return -1;  // + inpL
         if (launch_norm_q8K(p.SA, E, L.ffn_norm, (int)E, c.eps, T, img, ldk, s) || expand(E)) return -1;
@@ -236,7 +252,22 @@ int enqueue_verify_pass(gemma_engine *e, int T, int p0) {
         return -1;
     }
     if (prefill_alloc(e, GEMM_SKINNY_MAX_T)) return -1;  // sized once: no reallocation between passes
-    return enqueue_prefill(e, T, p0, true, nullptr, true);
+    return enqueue_prefill(e, T, own_rows(e, p0), true, nullptr, true);
+}
+
+int batch_scratch_alloc(gemma_engine *e) {
+    e->bt.pf = {};
+    return scratch_alloc(e, e->bt_mem, e->bt.pf, GEMM_SKINNY_MAX_T);
+}
+
+// the verify pass over the batch's rows: tokens from the row-token array, the attention step by
+// k_attn_slots; the caller picks from every row and advances the slots
+int enqueue_batch_pass(gemma_engine *e, int T) {
+    if (T < 1 || T > GEMM_SKINNY_MAX_T || e->bt.pf.T < GEMM_SKINNY_MAX_T) {
+        set_error("gemma_engine_batch_step: a pass of " + std::to_string(T) + " rows, or no batch scratch");
+        return -1;
+    }
+    return enqueue_prefill(e, T, pass_rows{e->bt.row_tok, 0, true}, true, nullptr, true);
 }
 
 // one pass over rows [p0, p0+T) and its results: the last row's logits, all rows' [T][n_vocab], the
@@ -244,7 +275,7 @@ int enqueue_verify_pass(gemma_engine *e, int T, int p0) {
 static int prefill_pass(gemma_engine *e, int T, int p0, bool exact, float *logits_last, float *logits_all) {
     const gemma_hip_config &c = e->cfg;
     if (prefill_alloc(e, T)) return -1;
-    if (enqueue_prefill(e, T, p0, exact)) return -1;
+    if (enqueue_prefill(e, T, own_rows(e, p0), exact)) return -1;
     GHIP_CHECK(hipStreamSynchronize(e->stream));
     if (logits_last)
         GHIP_CHECK(hipMemcpy(logits_last, e->pf.LG + (size_t)(T - 1) * c.n_vocab, (size_t)c.n_vocab * 4,
@@ -328,7 +359,7 @@ extern "C" int gemma_engine_prefill_taps(gemma_engine *e, float *host_taps, int 
     float *d = nullptr;
     const size_t n = (size_t)c.n_layer * T * c.n_embd;
     if (tmp.get(&d, n * 4)) return -1;
-    int r = enqueue_prefill(e, T, 0, exact != 0, d);
+    int r = enqueue_prefill(e, T, own_rows(e, 0), exact != 0, d);
     if (r == 0) GHIP_CHECK(hipStreamSynchronize(e->stream));
     if (r == 0) GHIP_CHECK(hipMemcpy(host_taps, d, n * 4, hipMemcpyDeviceToHost));
     if (r == 0) e->host_pos = T;

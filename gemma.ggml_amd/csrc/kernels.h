@@ -444,6 +444,27 @@ int launch_verify_accept(const verify_args &v, hipStream_t s);
 int launch_verify_clean(uint16_t *kc, uint16_t *vc, int n_layer, int64_t layer_stride, int ctx, int kvw, int p0, int k,
                         const int *accepted, hipStream_t s);
 
+// ---- batched decode (batch.hip; gemma_engine_batch_*, DESIGN.md §5b⁗) ---------------------------
+// One row of a batch pass: the next token of its own sequence (slot).  The table lives in device
+// memory and is rewritten when the set of active slots changes; no entry depends on a position.
+struct slot_row {
+    const float *qkv = nullptr;  // the row's q | k | v in the pass's scratch
+    float *out = nullptr;        // the row's attention output [H*hd]
+    uint16_t *kc = nullptr, *vc = nullptr;  // the slot's caches, layer 0 (layers a fixed stride apart)
+    float *rope = nullptr;       // the slot's [cos | sin | (int)pos]: the position is read on the device
+    int *hist = nullptr, *pos = nullptr, *last = nullptr;
+    const int *nfix = nullptr;
+};
+// k_attn_slots: the decode attention (attn_head_dev, per-head form) for R rows, each against its own
+// slot's caches at its own position.  a: the shared fields (geometry, tables, dsplit); qkv, kc, vc,
+// rope_cur and out come from rows[r], the caches offset by layer_off elements.
+int launch_attn_slots(const attn_args &a, const slot_row *rows, int R, int64_t layer_off, hipStream_t s);
+// k_batch_advance: per row, reduce the n_parts pick keys at keys + r * key_stride, then k_advance for
+// the row's slot: p = pos + 1, hist[p] = pick if p >= nfix, pos = p, the RoPE row of p, and the next
+// pass's token hist[p] into row_tok[r] and the slot's `last`
+int launch_batch_advance(const slot_row *rows, int R, const unsigned long long *keys, int n_parts, int key_stride,
+                         int *row_tok, int hist_cap, const rope_row &r, hipStream_t s);
+
 // ---- on-device sampling (sample.hip; the rule: include/gemma_hpc.h, DESIGN.md §5b″) ------------
 constexpr int SAMPLE_MAX_K = 1024;  // candidates at most (top_k == 0 means this many)
 struct sampler_params {             // lives in device memory: a change is a stream-ordered copy

@@ -39,7 +39,10 @@ EXPORTS = ["mul_mat", "hpc_init", "hpc_shutdown", "hpc_register_weight", "hpc_la
            "gemma_engine_create_from_gguf", "gemma_engine_config",
            "gemma_engine_set_sampler", "gemma_engine_sampler", "gemma_test_sample",
            "gemma_engine_verify", "gemma_engine_kv_read", "gemma_lookup_draft", "gemma_engine_generate_lookup",
-           "gemma_test_gemm_skinny", "gemma_hip_mem_live"]
+           "gemma_test_gemm_skinny", "gemma_hip_mem_live",
+           "gemma_engine_batch_open", "gemma_engine_batch_close", "gemma_engine_batch_begin", "gemma_engine_batch_adopt",
+           "gemma_engine_batch_release", "gemma_engine_batch_step", "gemma_engine_batch_pos", "gemma_engine_batch_tokens",
+           "gemma_engine_batch_last", "gemma_engine_batch_kv_read"]
 
 
 def build():
@@ -64,6 +67,7 @@ class GemmaSampler(C.Structure):
 
 SAMPLE_MAX_K = 1024  # candidates at most (top_k == 0 means this many)
 VERIFY_MAX_DRAFT = 7  # include/gemma_hpc.h GEMMA_VERIFY_MAX_DRAFT
+BATCH_MAX_SLOTS = 8   # include/gemma_hpc.h GEMMA_BATCH_MAX_SLOTS
 
 
 class SpecStats(C.Structure):
@@ -193,6 +197,11 @@ def lib():
     L.gemma_engine_generate_lookup.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(SpecStats)]
     L.gemma_test_gemm_skinny.restype = C.c_int
     L.gemma_test_gemm_skinny.argtypes = [C.c_int, i64, i64, i64, vp, vp, vp, vp]
+    for fn, at in (("open", [C.c_int]), ("close", []), ("begin", [C.c_int, vp, C.c_int]), ("adopt", [C.c_int]),
+                   ("release", [C.c_int]), ("step", [C.c_int, vp]), ("pos", [C.c_int]), ("tokens", [C.c_int, vp, C.c_int]),
+                   ("last", [vp]), ("kv_read", [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp])):
+        getattr(L, "gemma_engine_batch_" + fn).restype = C.c_int
+        getattr(L, "gemma_engine_batch_" + fn).argtypes = [vp] + at
     # GGUF reader (include/ggml.h)
     L.gguf_init_from_file.restype = vp
     L.gguf_init_from_file.argtypes = [C.c_char_p, GGUFInitParams]
@@ -380,6 +389,63 @@ class Engine:
         k = np.zeros((n, kvw), dtype=np.uint16)
         v = np.zeros((n, kvw), dtype=np.uint16)
         self._chk(self.L.gemma_engine_kv_read(self.h, int(layer), int(p0), int(n), _p(k), _p(v)), "kv_read")
+        return k, v
+
+    # ---- batched decode (gemma_engine_batch_*): up to BATCH_MAX_SLOTS sequences per weight pass ----
+    def batch_open(self, n_slots):
+        """Open the engine's batch with n_slots (1 .. BATCH_MAX_SLOTS) sequence slots."""
+        self._chk(self.L.gemma_engine_batch_open(self.h, int(n_slots)), "batch_open")
+
+    def batch_close(self):
+        self._chk(self.L.gemma_engine_batch_close(self.h), "batch_close")
+
+    def batch_begin(self, slot, tokens):
+        """begin() for a slot: caches cleared, `tokens` given, position 0, the slot active."""
+        p = np.ascontiguousarray(tokens, dtype=np.int32)
+        self._chk(self.L.gemma_engine_batch_begin(self.h, int(slot), _p(p), len(p)), "batch_begin")
+
+    def batch_adopt(self, slot):
+        """Copy the engine's own sequence (caches, history, position, pending token) into a slot."""
+        self._chk(self.L.gemma_engine_batch_adopt(self.h, int(slot)), "batch_adopt")
+
+    def batch_release(self, slot):
+        self._chk(self.L.gemma_engine_batch_release(self.h, int(slot)), "batch_release")
+
+    def batch_step(self, n, want_logits=False):
+        """n passes, one row per active slot in ascending slot order; with want_logits the rows
+        [n][R][n_vocab]."""
+        lg = None
+        if want_logits:
+            R = sum(1 for t in self.batch_last() if t >= 0)
+            lg = np.zeros((max(int(n), 0), R, self.cfg.n_vocab), dtype=np.float32)
+        self._chk(self.L.gemma_engine_batch_step(self.h, int(n), _p(lg) if want_logits else None), "batch_step")
+        return lg
+
+    def batch_pos(self, slot):
+        """processed positions of a slot; -1 for an inactive (or invalid) slot"""
+        return self.L.gemma_engine_batch_pos(self.h, int(slot))
+
+    def batch_tokens(self, slot):
+        """the slot's sequence so far, the pending token included"""
+        out = np.zeros(self.cfg.n_ctx + 1, dtype=np.int32)
+        n = self.L.gemma_engine_batch_tokens(self.h, int(slot), _p(out), len(out))
+        if n < 0:
+            raise RuntimeError("batch_tokens failed: " + last_error())
+        return out[:n]
+
+    def batch_last(self):
+        """the BATCH_MAX_SLOTS pending tokens in one transfer, -1 for inactive slots"""
+        out = np.zeros(BATCH_MAX_SLOTS, dtype=np.int32)
+        self._chk(self.L.gemma_engine_batch_last(self.h, _p(out)), "batch_last")
+        return out
+
+    def batch_kv_read(self, slot, layer, p0, n):
+        """kv_read of a slot's caches: (k [n][kvw], v [n][kvw]) f16 bits"""
+        kvw = self.cfg.n_head_kv * self.cfg.head_dim
+        k = np.zeros((n, kvw), dtype=np.uint16)
+        v = np.zeros((n, kvw), dtype=np.uint16)
+        self._chk(self.L.gemma_engine_batch_kv_read(self.h, int(slot), int(layer), int(p0), int(n), _p(k), _p(v)),
+                  "batch_kv_read")
         return k, v
 
     def sync(self):

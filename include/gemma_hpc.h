@@ -188,6 +188,45 @@ int gemma_engine_verify(gemma_engine *e, const int32_t *draft, int k, int32_t *o
 /* test entry: K rows and V columns p0 .. p0+n of one layer's cache, f16 bits; k_rows [n][kvw], v_rows
  * [n][kvw] (V transposed), kvw = n_head_kv * head_dim */
 int gemma_engine_kv_read(gemma_engine *e, int layer, int p0, int n, uint16_t *k_rows, uint16_t *v_rows);
+/* Batched decode (DESIGN.md §5b⁗): one batch per engine, owned by the engine, of up to
+ * GEMMA_BATCH_MAX_SLOTS independent sequences (slots).  Each slot has its own KV caches, history and
+ * position; one weight pass (the verify pass's skinny GEMMs, weights streamed once) advances every
+ * active slot by one token.  Every slot's logits and tokens are bit for bit what gemma_engine_step gives
+ * that sequence alone, and a pick needs its row and position only (greedy, or the engine's sampler with
+ * (seed, p)).  The engine's own sequence, its captured decode graph and its buffers are not touched.
+ * Every call returns 0 or a count; -1 with hpc_last_error naming the function and the state untouched
+ * on a bad argument.
+ *   open     n_slots in [1, 8]: allocates the slots, the pass's tables and its scratch.  Refused: a
+ *            batch already open, row-split engines (tp_n > 1, a communicator, virtual ranks), engines
+ *            whose decode attention is the position-split form (n_ctx > 2048 or head_dim > 256).
+ *   close    frees everything open allocated (gemma_engine_free does so too).
+ *   begin    what gemma_engine_begin does, for the slot: caches and history cleared, tokens given,
+ *            pos = 0, the slot active (an active slot is restarted).  Same argument checks.
+ *   adopt    copies the engine's own sequence into the slot, device to device: caches, history,
+ *            position, given-token count, RoPE row — the pending picked token and any
+ *            given-but-unprocessed tokens included.  The engine's sequence stays as it is.  (A long
+ *            prompt enters a slot at prefill speed: begin, prefill, batch_adopt.)
+ *   release  the slot becomes inactive; its memory stays for the next begin / adopt.
+ *   step     n passes, each one row per active slot in ascending slot order (R rows, constant within
+ *            the call).  Row r processes hist_s[pos_s] of its slot s against that slot's caches and
+ *            stores that position's K / V there; if pos_s + 1 >= the slot's given-token count the
+ *            row's pick becomes hist_s[pos_s + 1]; pos_s += 1.  All on the device, one host synchronise
+ *            at the end.  logits: NULL or [n][R][n_vocab].  Refused: no batch, no active slot, any
+ *            active slot with pos + n >= n_ctx (then no slot advances).
+ *   pos      processed positions of the slot (-1: inactive).   tokens: the slot's sequence so far, the
+ *            pending token included (returns the count).   last: the 8 slots' pending tokens in one
+ *            transfer, -1 for inactive slots.   kv_read: gemma_engine_kv_read of the slot's caches. */
+#define GEMMA_BATCH_MAX_SLOTS 8
+int gemma_engine_batch_open(gemma_engine *e, int n_slots);
+int gemma_engine_batch_close(gemma_engine *e);
+int gemma_engine_batch_begin(gemma_engine *e, int slot, const int32_t *tokens, int n);
+int gemma_engine_batch_adopt(gemma_engine *e, int slot);
+int gemma_engine_batch_release(gemma_engine *e, int slot);
+int gemma_engine_batch_step(gemma_engine *e, int n, float *logits);
+int gemma_engine_batch_pos(gemma_engine *e, int slot);
+int gemma_engine_batch_tokens(gemma_engine *e, int slot, int32_t *out, int cap);
+int gemma_engine_batch_last(gemma_engine *e, int32_t *out8);
+int gemma_engine_batch_kv_read(gemma_engine *e, int slot, int layer, int p0, int n, uint16_t *k_rows, uint16_t *v_rows);
 /* Prompt-lookup draft for the sequence seq[0..n) (pure host function, no GPU): for g = min(ngram_max,
  * n - 1) down to 1, the largest s < n - g with seq[s..s+g) == seq[n-g..n); the first g with a match
  * wins and the draft is seq[s+g .. min(s+g+k, n)).  Returns its length (0: no g matches), -1 on

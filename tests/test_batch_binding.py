@@ -1,0 +1,31 @@
+"""CPU: the batched-decode boundary (gemma_engine_batch_*) is declared in include/gemma_hpc.h, listed in
+the Python binding's EXPORTS (tests/test_capi_symbols.py then checks the built library exports it) and
+wrapped by Engine; the binding's slot bound equals the header's."""
+import os
+import re
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "gemma.ggml_amd", "python"))
+
+import gemma_hip  # noqa: E402
+
+CALLS = ("open", "close", "begin", "adopt", "release", "step", "pos", "tokens", "last", "kv_read")
+
+
+def _header():
+    return open(os.path.join(ROOT, "include", "gemma_hpc.h")).read()
+
+
+def test_every_batch_function_is_declared_and_exported():
+    text = _header()
+    for c in CALLS:
+        name = "gemma_engine_batch_" + c
+        assert re.search(r"^int " + name + r"\(gemma_engine \*e", text, flags=re.M), name
+        assert name in gemma_hip.EXPORTS, name
+        assert callable(getattr(gemma_hip.Engine, "batch_" + c)), c
+
+
+def test_slot_bound_equals_the_headers():
+    m = re.search(r"^#define GEMMA_BATCH_MAX_SLOTS (\d+)", _header(), flags=re.M)
+    assert m and gemma_hip.BATCH_MAX_SLOTS == int(m.group(1)) == 8
