@@ -9,6 +9,7 @@
 //    another.
 //  * k_batch_advance: k_advance per row — the pick-key reduction and the slot's token feedback.
 #include "attn_impl.h"
+#include "pick.h"
 
 namespace ghip {
 namespace {
@@ -37,26 +38,10 @@ __global__ void __launch_bounds__(256) k_batch_advance(const slot_row *rows, con
     // every thread reads the position before the barrier; thread 0 writes it after (as k_advance)
     const int p = *sr.pos + 1;
     const int fixed = *sr.nfix;
-    if (p < r.ctx) {  // the RoPE row of the next position with its position word
-        for (int i = threadIdx.x; i < r.half; i += 256) {
-            sr.rope[i] = r.cos[(int64_t)p * r.half + i];
-            sr.rope[r.half + i] = r.sin[(int64_t)p * r.half + i];
-        }
-        if (threadIdx.x == 0) ((int *)sr.rope)[2 * r.half] = p;
-    }
-    unsigned long long best = 0;
-    for (int i = threadIdx.x; i < n_parts; i += 256) best = keys[i] > best ? keys[i] : best;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off);
-        best = o > best ? o : best;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
-    __syncthreads();
+    if (p < r.ctx) publish_rope_row(sr.rope, r.cos, r.sin, r.half, p);  // the next position's, with its position word
+    const unsigned long long best = block_max_key(keys, n_parts, red);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) best = red[w] > best ? red[w] : best;
-        // strict '>' argmax, first max wins: the key's low word is ~index
-        int tok = (int)(0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull));
+        int tok = key_index(best);
         if (p < hist_cap) {
             if (p >= fixed) sr.hist[p] = tok;  // never overwrite a given token
             else tok = sr.hist[p];

@@ -354,16 +354,12 @@ static int create_buffers(gemma_engine *e, const std::vector<uint16_t *> *kc_ext
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
     dev_pool &M = e->mem;
-    const size_t kv_elems = (size_t)c.n_layer * c.n_ctx * e->kvw;
     if (kc_ext && vc_ext) {
         e->kc_ext = *kc_ext;
         e->vc_ext = *vc_ext;
-    } else {
-        if (M.get(&e->kc, kv_elems * 2)) return -1;
-        if (M.get(&e->vc, kv_elems * 2)) return -1;
-        GHIP_CHECK(hipMemsetAsync(e->kc, 0, kv_elems * 2, s));
-        GHIP_CHECK(hipMemsetAsync(e->vc, 0, kv_elems * 2, s));
     }
+    // the own sequence: made once, here (the captured decode graph holds its addresses)
+    if (seq_alloc(e, M, e->seq, e->kc_ext.empty(), nullptr)) return -1;
     std::vector<uint16_t> et, gt;
     build_f16_tables(et, gt);
     std::vector<float> rc, rs;
@@ -382,7 +378,6 @@ static int create_buffers(gemma_engine *e, const std::vector<uint16_t *> *kc_ext
     if (M.get(&e->gelu_tab, 65536 * 2)) return -1;
     if (M.get(&e->rope_cos, rc.size() * 4)) return -1;
     if (M.get(&e->rope_sin, rs.size() * 4)) return -1;
-    if (M.get(&e->rope_cur, (size_t)(c.head_dim + 4) * 4)) return -1;  // [cos | sin | (int)pos]
     GHIP_CHECK(hipMemcpy(e->exp_tab, et.data(), 65536 * 2, hipMemcpyHostToDevice));
     GHIP_CHECK(hipMemcpy(e->gelu_tab, gt.data(), 65536 * 2, hipMemcpyHostToDevice));
     GHIP_CHECK(hipMemcpy(e->rope_cos, rc.data(), rc.size() * 4, hipMemcpyHostToDevice));
@@ -434,12 +429,7 @@ static int create_buffers(gemma_engine *e, const std::vector<uint16_t *> *kc_ext
         if (M.get(&e->tok_tab, (size_t)c.n_layer * sizeof(tok_layer))) return -1;
     }
     if (M.get(&e->key, (size_t)e->grid_big * 8)) return -1;  // per-workgroup argmax keys
-    if (M.get(&e->pos, 4)) return -1;
-    if (M.get(&e->token, 4)) return -1;
-    if (M.get(&e->nfix, 4)) return -1;
-    if (M.get(&e->hist, (size_t)(c.n_ctx + 1) * 4)) return -1;
     GHIP_CHECK(hipMemsetAsync(e->key, 0, (size_t)e->grid_big * 8, s));
-    GHIP_CHECK(hipMemsetAsync(e->hist, 0, (size_t)(c.n_ctx + 1) * 4, s));
     if (M.get(&e->rank_keys, (size_t)e->tp_n * 8)) return -1;
     return 0;
 }
@@ -765,6 +755,101 @@ extern "C" void gemma_engine_free(gemma_engine *e) {
     delete e;
 }
 
+// ---- a sequence (seq_state, engine_impl.h) --------------------------------------------------------
+// What is done to a sequence, once for the engine's own and for a batch slot: its buffers, the reset
+// to a prompt, the copy, the cache and token read-backs, and the token-id check of everything the
+// host hands in.
+bool token_ids_ok(const gemma_engine *e, const int32_t *tokens, int n, const char *fn, bool name_id) {
+    for (int i = 0; i < n; ++i)  // the embedding kernels index token_embd rows unchecked
+        if (tokens[i] < 0 || tokens[i] >= e->cfg.n_vocab) {
+            set_error(name_id ? std::string(fn) + ": token id " + std::to_string(tokens[i]) + " out of range [0, n_vocab)"
+                              : std::string(fn) + ": token id out of range");
+            return false;
+        }
+    return true;
+}
+
+int seq_alloc(gemma_engine *e, dev_pool &M, seq_state &S, bool caches, int *token_word) {
+    const gemma_hip_config &c = e->cfg;
+    hipStream_t s = e->stream;
+    const size_t kv_bytes = (size_t)c.n_layer * c.n_ctx * e->kvw * 2;
+    S = seq_state{};
+    if (caches && (M.get_zeroed(&S.kc, kv_bytes, s) || M.get_zeroed(&S.vc, kv_bytes, s))) return -1;
+    if (M.get_zeroed(&S.hist, (size_t)(c.n_ctx + 1) * 4, s) || M.get_zeroed(&S.pos, 4, s) || M.get_zeroed(&S.nfix, 4, s) ||
+        M.get_zeroed(&S.rope, (size_t)(c.head_dim + 4) * 4, s))
+        return -1;
+    S.token = token_word;
+    return token_word ? 0 : M.get_zeroed(&S.token, 4, s);
+}
+
+int seq_begin(gemma_engine *e, seq_state &S, const int32_t *tokens, int n) {
+    const gemma_hip_config &c = e->cfg;
+    hipStream_t s = e->stream;
+    const size_t layer_bytes = (size_t)c.n_ctx * e->kvw * 2;
+    if (S.kc) {  // the sequence's own allocation: all layers at once
+        GHIP_CHECK(hipMemsetAsync(S.kc, 0, c.n_layer * layer_bytes, s));
+        GHIP_CHECK(hipMemsetAsync(S.vc, 0, c.n_layer * layer_bytes, s));
+    }
+    for (int il = 0; il < (S.kc ? 0 : c.n_layer); ++il) {  // external caches: one allocation per layer
+        GHIP_CHECK(hipMemsetAsync(kc_of(e, S, il), 0, layer_bytes, s));
+        GHIP_CHECK(hipMemsetAsync(vc_of(e, S, il), 0, layer_bytes, s));
+    }
+    GHIP_CHECK(hipMemsetAsync(S.hist, 0, (size_t)(c.n_ctx + 1) * 4, s));
+    GHIP_CHECK(hipMemcpyAsync(S.hist, tokens, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    GHIP_CHECK(hipMemsetAsync(S.pos, 0, 4, s));
+    const size_t half = (size_t)c.head_dim / 2;  // RoPE row of position 0
+    GHIP_CHECK(hipMemcpyAsync(S.rope, e->rope_cos, half * 4, hipMemcpyDeviceToDevice, s));
+    GHIP_CHECK(hipMemcpyAsync(S.rope + half, e->rope_sin, half * 4, hipMemcpyDeviceToDevice, s));
+    GHIP_CHECK(hipMemsetAsync(S.rope + 2 * half, 0, 4, s));
+    GHIP_CHECK(hipMemcpyAsync(S.nfix, &n, 4, hipMemcpyHostToDevice, s));
+    GHIP_CHECK(hipStreamSynchronize(s));
+    S.n_given = n;
+    S.host_pos = 0;
+    return 0;
+}
+
+int seq_copy(gemma_engine *e, seq_state &dst, const seq_state &src) {
+    const gemma_hip_config &c = e->cfg;
+    hipStream_t s = e->stream;
+    const size_t layer = (size_t)c.n_ctx * e->kvw;  // elements
+    for (int il = 0; il < c.n_layer; ++il) {  // (an engine on external caches has one allocation per layer)
+        GHIP_CHECK(hipMemcpyAsync(kc_of(e, dst, il), kc_of(e, src, il), layer * 2, hipMemcpyDeviceToDevice, s));
+        GHIP_CHECK(hipMemcpyAsync(vc_of(e, dst, il), vc_of(e, src, il), layer * 2, hipMemcpyDeviceToDevice, s));
+    }
+    GHIP_CHECK(hipMemcpyAsync(dst.hist, src.hist, (size_t)(c.n_ctx + 1) * 4, hipMemcpyDeviceToDevice, s));
+    GHIP_CHECK(hipMemcpyAsync(dst.pos, src.pos, 4, hipMemcpyDeviceToDevice, s));
+    GHIP_CHECK(hipMemcpyAsync(dst.nfix, src.nfix, 4, hipMemcpyDeviceToDevice, s));
+    GHIP_CHECK(hipMemcpyAsync(dst.token, src.hist + src.host_pos, 4, hipMemcpyDeviceToDevice, s));
+    GHIP_CHECK(hipMemcpyAsync(dst.rope, src.rope, ((size_t)c.head_dim + 1) * 4, hipMemcpyDeviceToDevice, s));
+    GHIP_CHECK(hipStreamSynchronize(s));
+    dst.host_pos = src.host_pos;
+    dst.n_given = src.n_given;
+    return 0;
+}
+
+int seq_kv_read(gemma_engine *e, const seq_state &S, int layer, int p0, int n, uint16_t *k_rows, uint16_t *v_rows, const char *fn) {
+    const gemma_hip_config &c = e->cfg;
+    if (layer < 0 || layer >= c.n_layer || p0 < 0 || n < 1 || (int64_t)p0 + n > c.n_ctx || !k_rows || !v_rows) {
+        set_error(std::string(fn) + ": layer or positions out of range");
+        return -1;
+    }
+    (void)hipSetDevice(e->device);
+    GHIP_CHECK(hipStreamSynchronize(e->stream));
+    const size_t kvw = (size_t)e->kvw, ctx = (size_t)c.n_ctx;
+    GHIP_CHECK(hipMemcpy(k_rows, kc_of(e, S, layer) + (size_t)p0 * kvw, (size_t)n * kvw * 2, hipMemcpyDeviceToHost));
+    std::vector<uint16_t> vt(kvw * (size_t)n);  // V is [kvw][ctx]: columns p0 .. p0+n, then transposed
+    GHIP_CHECK(hipMemcpy2D(vt.data(), (size_t)n * 2, vc_of(e, S, layer) + p0, ctx * 2, (size_t)n * 2, kvw, hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < kvw; ++j)
+        for (size_t r = 0; r < (size_t)n; ++r) v_rows[r * kvw + j] = vt[j * (size_t)n + r];
+    return 0;
+}
+
+int seq_tokens(const seq_state &S, int32_t *out, int cap) {
+    const int n = std::min(cap, S.host_pos + 1);  // the pending token included
+    if (n) GHIP_CHECK(hipMemcpy(out, S.hist, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return n;
+}
+
 extern "C" int gemma_engine_begin(gemma_engine *e, const int32_t *prompt, int n_prompt) {
     set_error("");
     const gemma_hip_config &c = e->cfg;
@@ -772,30 +857,12 @@ extern "C" int gemma_engine_begin(gemma_engine *e, const int32_t *prompt, int n_
         set_error("gemma_engine_begin: prompt length out of range");
         return -1;
     }
-    for (int i = 0; i < n_prompt; ++i)  // the embedding kernels index token_embd rows unchecked
-        if (prompt[i] < 0 || prompt[i] >= c.n_vocab) {
-            set_error("gemma_engine_begin: token id " + std::to_string(prompt[i]) + " out of range [0, n_vocab)");
-            return -1;
-        }
+    if (!token_ids_ok(e, prompt, n_prompt, "gemma_engine_begin")) return -1;
     (void)hipSetDevice(e->device);
-    hipStream_t s = e->stream;
-    for (int il = 0; il < c.n_layer; ++il) {
-        GHIP_CHECK(hipMemsetAsync(kc_of(e, il), 0, (size_t)c.n_ctx * e->kvw * 2, s));
-        GHIP_CHECK(hipMemsetAsync(vc_of(e, il), 0, (size_t)c.n_ctx * e->kvw * 2, s));
-    }
-    GHIP_CHECK(hipMemsetAsync(e->hist, 0, (size_t)(c.n_ctx + 1) * 4, s));
-    GHIP_CHECK(hipMemcpyAsync(e->hist, prompt, (size_t)n_prompt * 4, hipMemcpyHostToDevice, s));
-    GHIP_CHECK(hipMemsetAsync(e->pos, 0, 4, s));
-    const size_t half = (size_t)c.head_dim / 2;  // RoPE row of position 0
-    GHIP_CHECK(hipMemcpyAsync(e->rope_cur, e->rope_cos, half * 4, hipMemcpyDeviceToDevice, s));
-    GHIP_CHECK(hipMemcpyAsync(e->rope_cur + half, e->rope_sin, half * 4, hipMemcpyDeviceToDevice, s));
-    GHIP_CHECK(hipMemsetAsync(e->rope_cur + 2 * half, 0, 4, s));
-    GHIP_CHECK(hipMemsetAsync(e->key, 0, (size_t)e->grid_big * 8, s));
-    GHIP_CHECK(hipMemcpyAsync(e->nfix, &n_prompt, 4, hipMemcpyHostToDevice, s));
-    GHIP_CHECK(hipStreamSynchronize(s));
-    e->n_prompt = n_prompt;
-    e->host_pos = 0;
-    return 0;
+    // the decode step's argmax keys start from zero; the epoch is not bumped (gemma_engine_extend's
+    // k_set_position bumps it)
+    GHIP_CHECK(hipMemsetAsync(e->key, 0, (size_t)e->grid_big * 8, e->stream));
+    return seq_begin(e, e->seq, prompt, n_prompt);
 }
 
 // Continue or rewind: positions [0, keep) stay, everything from `keep` on is dropped and `tokens`
@@ -807,34 +874,30 @@ extern "C" int gemma_engine_begin(gemma_engine *e, const int32_t *prompt, int n_
 extern "C" int gemma_engine_extend(gemma_engine *e, int keep, const int32_t *tokens, int n) {
     set_error("");
     const gemma_hip_config &c = e->cfg;
-    if (keep < 0 || keep > e->host_pos) {
-        set_error("gemma_engine_extend: keep = " + std::to_string(keep) + " outside [0, pos = " + std::to_string(e->host_pos) + "]");
+    if (keep < 0 || keep > e->seq.host_pos) {
+        set_error("gemma_engine_extend: keep = " + std::to_string(keep) + " outside [0, pos = " + std::to_string(e->seq.host_pos) + "]");
         return -1;
     }
     if (n <= 0 || !tokens || (int64_t)keep + n >= c.n_ctx) {
         set_error("gemma_engine_extend: needs n >= 1 tokens with keep + n < n_ctx");
         return -1;
     }
-    for (int i = 0; i < n; ++i)  // the embedding kernels index token_embd rows unchecked
-        if (tokens[i] < 0 || tokens[i] >= c.n_vocab) {
-            set_error("gemma_engine_extend: token id " + std::to_string(tokens[i]) + " out of range [0, n_vocab)");
-            return -1;
-        }
+    if (!token_ids_ok(e, tokens, n, "gemma_engine_extend")) return -1;
     (void)hipSetDevice(e->device);
     hipStream_t s = e->stream;
     const size_t ctx = (size_t)c.n_ctx, drop = ctx - (size_t)keep;
     for (int il = 0; il < c.n_layer; ++il) {  // K [ctx][kvw]: rows >= keep; V [kvw][ctx]: columns >= keep
-        GHIP_CHECK(hipMemsetAsync(kc_of(e, il) + (size_t)keep * e->kvw, 0, drop * e->kvw * 2, s));
-        GHIP_CHECK(hipMemset2DAsync(vc_of(e, il) + keep, ctx * 2, 0, drop * 2, (size_t)e->kvw, s));
+        GHIP_CHECK(hipMemsetAsync(kc_of(e, e->seq, il) + (size_t)keep * e->kvw, 0, drop * e->kvw * 2, s));
+        GHIP_CHECK(hipMemset2DAsync(vc_of(e, e->seq, il) + keep, ctx * 2, 0, drop * 2, (size_t)e->kvw, s));
     }
-    GHIP_CHECK(hipMemsetAsync(e->hist + keep, 0, (ctx + 1 - (size_t)keep) * 4, s));
-    GHIP_CHECK(hipMemcpyAsync(e->hist + keep, tokens, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    GHIP_CHECK(hipMemsetAsync(e->seq.hist + keep, 0, (ctx + 1 - (size_t)keep) * 4, s));
+    GHIP_CHECK(hipMemcpyAsync(e->seq.hist + keep, tokens, (size_t)n * 4, hipMemcpyHostToDevice, s));
     GHIP_CHECK(hipMemsetAsync(e->key, 0, (size_t)e->grid_big * 8, s));
     // *pos = keep, its RoPE row with the position word, *n_fixed = keep + n, the epoch bump
-    if (launch_set_position(tokens[0], keep, e->pos, e->hist, e->nfix, keep + n, rope_of(e), s)) return -1;
+    if (launch_set_position(tokens[0], keep, e->seq.pos, e->seq.hist, e->seq.nfix, keep + n, rope_of(e), s)) return -1;
     GHIP_CHECK(hipStreamSynchronize(s));
-    e->n_prompt = keep + n;
-    e->host_pos = keep;
+    e->seq.n_given = keep + n;
+    e->seq.host_pos = keep;
     return 0;
 }
 
@@ -863,7 +926,7 @@ extern "C" int gemma_engine_step(gemma_engine *e, int n, float *logits, int use_
         return -1;
     }
     const gemma_hip_config &c = e->cfg;
-    if (e->host_pos + n >= c.n_ctx) {
+    if (e->seq.host_pos + n >= c.n_ctx) {
         set_error("gemma_engine_step: context full");
         return -1;
     }
@@ -874,7 +937,7 @@ extern "C" int gemma_engine_step(gemma_engine *e, int n, float *logits, int use_
         if (logits && tp_gather(e, e->logits, e->sh_v)) return -1;
         GHIP_CHECK(hipStreamSynchronize(e->stream));
         if (logits) GHIP_CHECK(hipMemcpy(logits, e->logits, (size_t)c.n_vocab * 4, hipMemcpyDeviceToHost));
-        e->host_pos += 1;
+        e->seq.host_pos += 1;
         if (logits) logits += c.n_vocab;
         n -= 1;
         if (ensure_graph(e)) return -1;
@@ -901,7 +964,7 @@ extern "C" int gemma_engine_step(gemma_engine *e, int n, float *logits, int use_
                                       hipMemcpyDeviceToHost, e->stream));
             GHIP_CHECK(hipStreamSynchronize(e->stream));
         }
-        e->host_pos += 1;
+        e->seq.host_pos += 1;
     }
     GHIP_CHECK(hipStreamSynchronize(e->stream));
     if (persist_check(e)) return -1;  // the sequence must be restarted (gemma_engine_begin)
@@ -915,12 +978,10 @@ extern "C" int gemma_engine_sync(gemma_engine *e) {
 }
 
 extern "C" int gemma_engine_tokens(gemma_engine *e, int32_t *out, int cap) {
-    const int n = std::min(cap, e->host_pos + 1);
-    GHIP_CHECK(hipMemcpy(out, e->hist, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return n;
+    return seq_tokens(e->seq, out, cap);
 }
 
-extern "C" int gemma_engine_pos(gemma_engine *e) { return e->host_pos; }
+extern "C" int gemma_engine_pos(gemma_engine *e) { return e->seq.host_pos; }
 
 extern "C" int64_t gemma_engine_tensor(gemma_engine *e, int tid, void *dst, int64_t cap) {
     set_error("");

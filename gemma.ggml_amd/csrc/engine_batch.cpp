@@ -10,10 +10,6 @@
 static constexpr int NS = GEMMA_BATCH_MAX_SLOTS;
 static_assert(GEMMA_BATCH_MAX_SLOTS == GEMM_SKINNY_MAX_T, "a pass has one skinny-GEMM column per slot");
 
-static size_t kv_bytes(const gemma_engine *e) { return (size_t)e->cfg.n_layer * e->cfg.n_ctx * e->kvw * 2; }
-static size_t rope_words(const gemma_engine *e) { return (size_t)e->cfg.head_dim + 4; }  // [cos | sin | (int)pos]
-static float *rope_of_slot(const gemma_engine *e, int s) { return e->bt.rope + (size_t)s * rope_words(e); }
-
 // the batch is open and `slot` one of its slots, else the error (naming fn) is set
 static bool slot_ok(const gemma_engine *e, int slot, const char *fn) {
     if (!e->bt.open) {
@@ -34,7 +30,6 @@ static void batch_drop(gemma_engine *e) {
 
 extern "C" int gemma_engine_batch_open(gemma_engine *e, int n_slots) {
     set_error("");
-    const gemma_hip_config &c = e->cfg;
     if (e->bt.open) {
         set_error("gemma_engine_batch_open: a batch is already open (gemma_engine_batch_close)");
         return -1;
@@ -43,7 +38,7 @@ extern "C" int gemma_engine_batch_open(gemma_engine *e, int n_slots) {
         set_error("gemma_engine_batch_open: n_slots = " + std::to_string(n_slots) + " outside [1, " + std::to_string(NS) + "]");
         return -1;
     }
-    if (e->tp_n > 1 || e->comm || e->n_virtual > 1) {
+    if (row_split(e)) {
         set_error("gemma_engine_batch_open: single-GPU engines only (row-split engines decode one sequence)");
         return -1;
     }
@@ -56,17 +51,14 @@ extern "C" int gemma_engine_batch_open(gemma_engine *e, int n_slots) {
     dev_pool &M = e->bt_mem;
     batch_state &b = e->bt;
     b = batch_state{};
-    bool bad = batch_scratch_alloc(e) != 0;
-    for (int i = 0; i < n_slots && !bad; ++i)
-        bad = M.get_zeroed(&b.slot[i].kc, kv_bytes(e), s) || M.get_zeroed(&b.slot[i].vc, kv_bytes(e), s) ||
-              M.get_zeroed(&b.slot[i].hist, (size_t)(c.n_ctx + 1) * 4, s);
-    bad = bad || M.get_zeroed(&b.ints, 3 * NS * 4, s) || M.get_zeroed(&b.rope, NS * rope_words(e) * 4, s) ||
-          M.get_zeroed(&b.rows, NS * sizeof(slot_row), s) || M.get_zeroed(&b.row_tok, NS * 4, s) ||
-          M.get_zeroed(&b.keys, (size_t)(NS * 256 + NS) * 8, s) || M.get(&b.stage, NS * sizeof(slot_row), MEM_PINNED);
+    bool bad = batch_scratch_alloc(e) != 0 || M.get_zeroed(&b.last, NS * 4, s);
+    for (int i = 0; i < n_slots && !bad; ++i) bad = seq_alloc(e, M, b.slot[i], true, b.last + i) != 0;
+    bad = bad || M.get_zeroed(&b.rows, NS * sizeof(slot_row), s) || M.get_zeroed(&b.row_tok, NS * 4, s) ||
+          pick_buf_alloc(M, b.picks, s) || M.get(&b.stage, NS * sizeof(slot_row), MEM_PINNED);
     if (!bad) {  // no slot is active: every pending token reads -1
         int *h = (int *)b.stage;
         for (int i = 0; i < NS; ++i) h[i] = -1;
-        bad = hipMemcpyAsync(b.last_of(0), h, NS * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+        bad = hipMemcpyAsync(b.last, h, NS * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
               hipStreamSynchronize(s) != hipSuccess;
         if (bad) set_error("gemma_engine_batch_open: initialising the slot state failed");
     }
@@ -101,61 +93,30 @@ extern "C" int gemma_engine_batch_begin(gemma_engine *e, int slot, const int32_t
         set_error("gemma_engine_batch_begin: prompt length out of range");
         return -1;
     }
-    for (int i = 0; i < n; ++i)  // the embedding kernels index token_embd rows unchecked
-        if (tokens[i] < 0 || tokens[i] >= c.n_vocab) {
-            set_error("gemma_engine_batch_begin: token id " + std::to_string(tokens[i]) + " out of range [0, n_vocab)");
-            return -1;
-        }
+    if (!token_ids_ok(e, tokens, n, "gemma_engine_batch_begin")) return -1;
     (void)hipSetDevice(e->device);
-    hipStream_t s = e->stream;
     batch_state &b = e->bt;
-    batch_slot &S = b.slot[slot];
-    GHIP_CHECK(hipMemsetAsync(S.kc, 0, kv_bytes(e), s));
-    GHIP_CHECK(hipMemsetAsync(S.vc, 0, kv_bytes(e), s));
-    GHIP_CHECK(hipMemsetAsync(S.hist, 0, (size_t)(c.n_ctx + 1) * 4, s));
-    GHIP_CHECK(hipMemcpyAsync(S.hist, tokens, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    GHIP_CHECK(hipMemsetAsync(b.pos_of(slot), 0, 4, s));
-    GHIP_CHECK(hipMemcpyAsync(b.nfix_of(slot), &n, 4, hipMemcpyHostToDevice, s));
-    GHIP_CHECK(hipMemcpyAsync(b.last_of(slot), tokens, 4, hipMemcpyHostToDevice, s));
-    const size_t half = (size_t)c.head_dim / 2;  // RoPE row of position 0
-    float *rope = rope_of_slot(e, slot);
-    GHIP_CHECK(hipMemcpyAsync(rope, e->rope_cos, half * 4, hipMemcpyDeviceToDevice, s));
-    GHIP_CHECK(hipMemcpyAsync(rope + half, e->rope_sin, half * 4, hipMemcpyDeviceToDevice, s));
-    GHIP_CHECK(hipMemsetAsync(rope + 2 * half, 0, 4, s));
-    GHIP_CHECK(hipStreamSynchronize(s));
+    seq_state &S = b.slot[slot];
+    // the slot's token word is its pending token, hist[0]; neither the decode step's argmax keys nor
+    // the epoch belong to a slot
+    GHIP_CHECK(hipMemcpyAsync(S.token, tokens, 4, hipMemcpyHostToDevice, e->stream));
+    if (seq_begin(e, S, tokens, n)) return -1;
     S.active = true;
-    S.host_pos = 0;
-    S.n_given = n;
     b.dirty = true;
     return 0;
 }
 
 extern "C" int gemma_engine_batch_adopt(gemma_engine *e, int slot) {
     set_error("");
-    const gemma_hip_config &c = e->cfg;
     if (!slot_ok(e, slot, "gemma_engine_batch_adopt")) return -1;
-    if (e->n_prompt <= 0) {
+    if (e->seq.n_given <= 0) {
         set_error("gemma_engine_batch_adopt: the engine has no sequence (gemma_engine_begin)");
         return -1;
     }
     (void)hipSetDevice(e->device);
-    hipStream_t s = e->stream;
     batch_state &b = e->bt;
-    batch_slot &S = b.slot[slot];
-    const size_t layer = (size_t)c.n_ctx * e->kvw;  // elements
-    for (int il = 0; il < c.n_layer; ++il) {  // (an engine on external caches has one allocation per layer)
-        GHIP_CHECK(hipMemcpyAsync(S.kc + il * layer, kc_of(e, il), layer * 2, hipMemcpyDeviceToDevice, s));
-        GHIP_CHECK(hipMemcpyAsync(S.vc + il * layer, vc_of(e, il), layer * 2, hipMemcpyDeviceToDevice, s));
-    }
-    GHIP_CHECK(hipMemcpyAsync(S.hist, e->hist, (size_t)(c.n_ctx + 1) * 4, hipMemcpyDeviceToDevice, s));
-    GHIP_CHECK(hipMemcpyAsync(b.pos_of(slot), e->pos, 4, hipMemcpyDeviceToDevice, s));
-    GHIP_CHECK(hipMemcpyAsync(b.nfix_of(slot), e->nfix, 4, hipMemcpyDeviceToDevice, s));
-    GHIP_CHECK(hipMemcpyAsync(b.last_of(slot), e->hist + e->host_pos, 4, hipMemcpyDeviceToDevice, s));
-    GHIP_CHECK(hipMemcpyAsync(rope_of_slot(e, slot), e->rope_cur, ((size_t)c.head_dim + 1) * 4, hipMemcpyDeviceToDevice, s));
-    GHIP_CHECK(hipStreamSynchronize(s));
-    S.active = true;
-    S.host_pos = e->host_pos;
-    S.n_given = e->n_prompt;
+    if (seq_copy(e, b.slot[slot], e->seq)) return -1;
+    b.slot[slot].active = true;
     b.dirty = true;
     return 0;
 }
@@ -166,7 +127,7 @@ extern "C" int gemma_engine_batch_release(gemma_engine *e, int slot) {
     (void)hipSetDevice(e->device);
     batch_state &b = e->bt;
     static const int none = -1;
-    GHIP_CHECK(hipMemcpyAsync(b.last_of(slot), &none, 4, hipMemcpyHostToDevice, e->stream));
+    GHIP_CHECK(hipMemcpyAsync(b.slot[slot].token, &none, 4, hipMemcpyHostToDevice, e->stream));
     GHIP_CHECK(hipStreamSynchronize(e->stream));
     b.slot[slot].active = false;
     b.dirty = true;
@@ -184,12 +145,12 @@ static int batch_write_rows(gemma_engine *e) {
         slot_row r;
         r.qkv = b.pf.QKV + (size_t)R * e->qkv_rows;
         r.out = b.pf.ATT + (size_t)R * e->qw;
-        r.kc = b.slot[i].kc; r.vc = b.slot[i].vc;
-        r.rope = rope_of_slot(e, i);
-        r.hist = b.slot[i].hist; r.pos = b.pos_of(i); r.nfix = b.nfix_of(i); r.last = b.last_of(i);
+        const seq_state &S = b.slot[i];
+        r.kc = S.kc; r.vc = S.vc; r.rope = S.rope;
+        r.hist = S.hist; r.pos = S.pos; r.nfix = S.nfix; r.last = S.token;
         h[R] = r;
         b.row_slot[R] = i;
-        GHIP_CHECK(hipMemcpyAsync(b.row_tok + R, b.last_of(i), 4, hipMemcpyDeviceToDevice, s));  // = hist[pos]
+        GHIP_CHECK(hipMemcpyAsync(b.row_tok + R, S.token, 4, hipMemcpyDeviceToDevice, s));  // = hist[pos]
         ++R;
     }
     if (R) GHIP_CHECK(hipMemcpyAsync(b.rows, h, (size_t)R * sizeof(slot_row), hipMemcpyHostToDevice, s));
@@ -230,24 +191,16 @@ extern "C" int gemma_engine_batch_step(gemma_engine *e, int n, float *logits) {
     (void)hipSetDevice(e->device);
     hipStream_t s = e->stream;
     if (b.dirty && batch_write_rows(e)) return -1;
-    unsigned long long *skey = b.keys + NS * 256;
+    const int *row_pos[NS];
+    for (int r = 0; r < R; ++r) row_pos[r] = b.slot[b.row_slot[r]].pos;
     for (int i = 0; i < n; ++i) {
         if (enqueue_batch_pass(e, R)) return -1;
         // a pick from every row: row r gives the token of its slot's sequence index pos + 1
-        const unsigned long long *keys = b.keys;
-        int n_parts = 256, stride = 256;
-        for (int r = 0; r < R; ++r) {
-            const float *row = b.pf.LG + (size_t)r * c.n_vocab;
-            if (e->sampling) {
-                if (enqueue_pick_keys(e, row, b.pos_of(b.row_slot[r]), skey + r, &keys, &n_parts)) return -1;
-            } else if (launch_row_argmax(row, c.n_vocab, b.keys + (size_t)r * 256, 256, s)) {
-                return -1;
-            }
-        }
-        if (e->sampling) { keys = skey; n_parts = 1; stride = 1; }
+        row_picks pk;
+        if (enqueue_row_picks(e, b.pf.LG, R, row_pos, b.picks, &pk)) return -1;
         if (logits)
             GHIP_CHECK(hipMemcpyAsync(logits + (size_t)i * R * c.n_vocab, b.pf.LG, (size_t)R * c.n_vocab * 4, hipMemcpyDeviceToHost, s));
-        if (launch_batch_advance(b.rows, R, keys, n_parts, stride, b.row_tok, c.n_ctx, rope_of(e), s)) return -1;
+        if (launch_batch_advance(b.rows, R, pk.keys, pk.n_parts, pk.stride, b.row_tok, c.n_ctx, rope_of(e), s)) return -1;
     }
     GHIP_CHECK(hipStreamSynchronize(s));
     for (int i = 0; i < b.n_slots; ++i)
@@ -268,15 +221,13 @@ extern "C" int gemma_engine_batch_pos(gemma_engine *e, int slot) {
 extern "C" int gemma_engine_batch_tokens(gemma_engine *e, int slot, int32_t *out, int cap) {
     set_error("");
     if (!slot_ok(e, slot, "gemma_engine_batch_tokens")) return -1;
-    const batch_slot &S = e->bt.slot[slot];
+    const seq_state &S = e->bt.slot[slot];
     if (!S.active || !out || cap < 0) {
         set_error("gemma_engine_batch_tokens: slot " + std::to_string(slot) + " is not active, or a null / negative buffer");
         return -1;
     }
     (void)hipSetDevice(e->device);
-    const int n = std::min(cap, S.host_pos + 1);  // the pending token included
-    if (n > 0) GHIP_CHECK(hipMemcpy(out, S.hist, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return n;
+    return seq_tokens(S, out, cap);
 }
 
 extern "C" int gemma_engine_batch_last(gemma_engine *e, int32_t *out8) {
@@ -287,7 +238,7 @@ extern "C" int gemma_engine_batch_last(gemma_engine *e, int32_t *out8) {
     }
     (void)hipSetDevice(e->device);
     int *h = (int *)e->bt.stage;
-    GHIP_CHECK(hipMemcpyAsync(h, e->bt.last_of(0), NS * 4, hipMemcpyDeviceToHost, e->stream));
+    GHIP_CHECK(hipMemcpyAsync(h, e->bt.last, NS * 4, hipMemcpyDeviceToHost, e->stream));
     GHIP_CHECK(hipStreamSynchronize(e->stream));
     memcpy(out8, h, NS * 4);
     return 0;
@@ -296,20 +247,6 @@ extern "C" int gemma_engine_batch_last(gemma_engine *e, int32_t *out8) {
 extern "C" int gemma_engine_batch_kv_read(gemma_engine *e, int slot, int layer, int p0, int n, uint16_t *k_rows,
                                           uint16_t *v_rows) {
     set_error("");
-    const gemma_hip_config &c = e->cfg;
     if (!slot_ok(e, slot, "gemma_engine_batch_kv_read")) return -1;
-    if (layer < 0 || layer >= c.n_layer || p0 < 0 || n < 1 || (int64_t)p0 + n > c.n_ctx || !k_rows || !v_rows) {
-        set_error("gemma_engine_batch_kv_read: layer or positions out of range");
-        return -1;
-    }
-    (void)hipSetDevice(e->device);
-    GHIP_CHECK(hipStreamSynchronize(e->stream));
-    const size_t kvw = (size_t)e->kvw, ctx = (size_t)c.n_ctx;
-    const uint16_t *kc = e->bt.slot[slot].kc + (size_t)layer * ctx * kvw, *vc = e->bt.slot[slot].vc + (size_t)layer * ctx * kvw;
-    GHIP_CHECK(hipMemcpy(k_rows, kc + (size_t)p0 * kvw, (size_t)n * kvw * 2, hipMemcpyDeviceToHost));
-    std::vector<uint16_t> vt(kvw * (size_t)n);  // V is [kvw][ctx]: columns p0 .. p0+n, then transposed
-    GHIP_CHECK(hipMemcpy2D(vt.data(), (size_t)n * 2, vc + p0, ctx * 2, (size_t)n * 2, kvw, hipMemcpyDeviceToHost));
-    for (size_t j = 0; j < kvw; ++j)
-        for (size_t r = 0; r < (size_t)n; ++r) v_rows[r * kvw + j] = vt[j * (size_t)n + r];
-    return 0;
+    return seq_kv_read(e, e->bt.slot[slot], layer, p0, n, k_rows, v_rows, "gemma_engine_batch_kv_read");
 }

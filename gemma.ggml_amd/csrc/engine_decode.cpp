@@ -71,7 +71,7 @@ int tok_prepare(gemma_engine *e) {
     e->persist_why.clear();
     if (e->kq) e->persist_why = "K-quant layers";
     else if (e->out_type == T_Q6_K) e->persist_why = "Q6_K token_embd (the launch dequantizes the layer type)";
-    else if (e->tp_n != 1 || e->n_virtual != 1 || e->comm) e->persist_why = "row-split TP";
+    else if (row_split(e)) e->persist_why = "row-split TP";
     if (!e->persist_why.empty() || !e->tok_gran) {
         if (e->persist_why.empty()) e->persist_why = "no buffers";
         return 0;
@@ -83,7 +83,7 @@ int tok_prepare(gemma_engine *e) {
         T.qkv_qs = L.qkv.qs; T.qkv_sc = L.qkv.sc; T.o_qs = L.o.qs; T.o_sc = L.o.sc;
         T.g_qs = L.gate.qs; T.g_sc = L.gate.sc; T.u_qs = L.up.qs; T.u_sc = L.up.sc; T.d_qs = L.down.qs; T.d_sc = L.down.sc;
         T.attn_norm = L.attn_norm; T.ffn_norm = L.ffn_norm;
-        T.kc = kc_of(e, il); T.vc = vc_of(e, il);
+        T.kc = kc_of(e, e->seq, il); T.vc = vc_of(e, e->seq, il);
     }
     GHIP_CHECK(hipMemcpy(e->tok_tab, tab.data(), tab.size() * sizeof(tok_layer), hipMemcpyHostToDevice));
     tok_args &a = e->tok;
@@ -95,7 +95,7 @@ int tok_prepare(gemma_engine *e) {
     a.att_split = e->att_dsplit;
     a.eps = c.eps; a.emb_scale = sqrtf((float)c.n_embd); a.q_scale = 1.0f / sqrtf((float)c.head_dim);
     a.emb_qs = e->embd.qs; a.emb_sc = e->embd.sc; a.emb_n_bt = e->embd.n_bt;
-    a.hist = e->hist; a.pos = e->pos; a.rope_cur = e->rope_cur;
+    a.hist = e->seq.hist; a.pos = e->seq.pos; a.rope_cur = e->seq.rope;
     a.exp_tab = e->exp_tab; a.gelu_tab = e->gelu_tab; a.gelu_clamp = c.gelu_clamp;
     const tok_gran_sizes g = token_gran_sizes(c.n_embd, c.n_ff, e->qkv_rows);
     unsigned long long *p = e->tok_gran;
@@ -177,8 +177,29 @@ int enqueue_pick_keys(gemma_engine *e, const float *row, const int *pos, unsigne
 }
 
 int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *keys, int n_parts) {
-    if (enqueue_pick_keys(e, row, e->pos, nullptr, &keys, &n_parts)) return -1;
-    return launch_advance(keys, n_parts, e->token, e->pos, e->hist, e->cfg.n_ctx, e->nfix, rope_of(e), e->stream);
+    if (enqueue_pick_keys(e, row, e->seq.pos, nullptr, &keys, &n_parts)) return -1;
+    return launch_advance(keys, n_parts, e->seq.token, e->seq.pos, e->seq.hist, e->cfg.n_ctx, e->seq.nfix, rope_of(e), e->stream);
+}
+
+// The picks of a pass's T rows, none advancing: the verify pass then accepts a prefix, the batch pass
+// advances every row's slot.
+int pick_buf_alloc(dev_pool &M, pick_buf &b, hipStream_t s) {
+    return M.get_zeroed(&b.keys, (size_t)(GEMM_SKINNY_MAX_T * 256 + GEMM_SKINNY_MAX_T) * 8, s);
+}
+
+int enqueue_row_picks(gemma_engine *e, const float *LG, int T, const int *const *pos, const pick_buf &b, row_picks *out) {
+    const int64_t V = e->cfg.n_vocab;
+    unsigned long long *skey = b.keys + GEMM_SKINNY_MAX_T * 256;
+    for (int t = 0; t < T; ++t) {
+        const float *row = LG + (size_t)t * V;
+        const unsigned long long *key = nullptr;
+        int parts = 0;
+        if (e->sampling ? enqueue_pick_keys(e, row, pos[t], skey + t, &key, &parts)
+                        : launch_row_argmax(row, V, b.keys + (size_t)t * 256, 256, e->stream))
+            return -1;
+    }
+    *out = e->sampling ? row_picks{skey, 1, 1} : row_picks{b.keys, 256, 256};
+    return 0;
 }
 
 // the decode tail of a Q6_K tied output: rms_norm*out_norm -> Q8_K (have_img: the last down handed
@@ -264,7 +285,7 @@ static int enqueue_step_kq(gemma_engine *e) {
         if (in.norm_w) return launch_norm_q8K(in.xf, K, in.norm_w, K, c.eps, 1, in.x, (K / 256) * 292, s);
         return launch_quant_q8_K(in.xf, K, K, 1, in.x, (K / 256) * 292, s);
     };
-    if (launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, e->hist, e->pos, 1, E, sqrtf((float)E), e->x, s, e->embd_tiled)) return -1;
+    if (launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, e->seq.hist, e->seq.pos, 1, E, sqrtf((float)E), e->x, s, e->embd_tiled)) return -1;
     for (int il = 0; il < c.n_layer; ++il) {
         const layer_dev &L = e->layers[il];
         const kq_layer &K = e->kql[il];
@@ -357,8 +378,7 @@ static mv_args attn_out_of(gemma_engine *e, const layer_dev &L, size_t r0, bool 
 }
 static bool att_img_on(const gemma_engine *e) { return e->att_act && att_img_ok(e) && e->plan[MC_O].img; }
 static bool front_on(const gemma_engine *e) {
-    return e->front_cnt && e->fuse_front && e->tp_n == 1 && !e->comm && e->n_virtual == 1 &&
-           e->att_mode == ATTN_PER_HEAD && e->att_act && e->plan[MC_QKV].ks == KS_RR &&
+    return e->front_cnt && e->fuse_front && !row_split(e) && e->att_mode == ATTN_PER_HEAD && e->att_act && e->plan[MC_QKV].ks == KS_RR &&
            e->plan[MC_O].ks == KS_RR && e->plan[MC_O].img;
 }
 
@@ -394,7 +414,7 @@ static int step_qkv(gemma_engine *e, int il) {
         int pro = PRO_NORM;
         if (il == 0 && e->out_type != T_Q6_K) {
             pro = PRO_EMBED;
-            a.x = e->hist; a.tok_pos = e->pos;
+            a.x = e->seq.hist; a.tok_pos = e->seq.pos;
             a.emb_qs = e->embd.qs; a.emb_sc = e->embd.sc; a.emb_n_bt = e->embd.n_bt;
             a.emb_scale = sqrtf((float)c.n_embd);
             a.emb_out = e->x;
@@ -534,7 +554,7 @@ static int step_logits(gemma_engine *e) {
             return -1;
         }
     }
-    return launch_advance(e->rank_keys, e->tp_n, e->token, e->pos, e->hist, c.n_ctx, e->nfix, rr, s);
+    return launch_advance(e->rank_keys, e->tp_n, e->seq.token, e->seq.pos, e->seq.hist, c.n_ctx, e->seq.nfix, rr, s);
 }
 
 // One decode token: the embedding (a Q6_K token_embd; else layer 0's qkv prologue), the layers as
@@ -544,7 +564,7 @@ int enqueue_step(gemma_engine *e) {
     hipStream_t s = e->stream;
     if (e->kq) return enqueue_step_kq(e);
     if (e->out_type == T_Q6_K &&
-        launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, e->hist, e->pos, 1, c.n_embd, sqrtf((float)c.n_embd), e->x, s,
+        launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, e->seq.hist, e->seq.pos, 1, c.n_embd, sqrtf((float)c.n_embd), e->x, s,
                          e->embd_tiled))
         return -1;
     if (persist_on(e)) {

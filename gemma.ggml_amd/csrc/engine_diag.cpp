@@ -85,7 +85,7 @@ extern "C" double gemma_engine_time(gemma_engine *e, int which, int iters, doubl
     };
     if (which == 5) {
         // whole step replays advance the position: keep within the context
-        if (e->host_pos + 2 * iters + 4 >= c.n_ctx) {
+        if (e->seq.host_pos + 2 * iters + 4 >= c.n_ctx) {
             set_error("gemma_engine_time: context too small for step timing");
             return -1.0;
         }
@@ -109,7 +109,7 @@ extern "C" double gemma_engine_time(gemma_engine *e, int which, int iters, doubl
     if (t0) (void)hipEventDestroy(t0);
     if (t1) (void)hipEventDestroy(t1);
     if (tr) return -1.0;
-    if (which == 5) e->host_pos += iters + 3;
+    if (which == 5) e->seq.host_pos += iters + 3;
     if (algo_bytes) *algo_bytes = bytes;
     return (double)ms * 1000.0 / iters;
 }
@@ -228,7 +228,7 @@ extern "C" int gemma_engine_tune(gemma_engine *e, int iters) {
     drop_graph(e);
     (void)hipEventDestroy(t0);
     (void)hipEventDestroy(t1);
-    e->host_pos = 0;
+    e->seq.host_pos = 0;
     return rc;
 }
 
@@ -348,7 +348,7 @@ extern "C" int gemma_engine_set_sampler(gemma_engine *e, const gemma_sampler *sp
         }
     }
     const bool on = sp && sp->temperature > 0.0f;
-    if (on && (e->tp_n > 1 || e->comm || e->n_virtual > 1 || e->tp_n_keys)) {
+    if (on && (row_split(e) || e->tp_n_keys)) {
         set_error("gemma_engine_set_sampler: row-split engines hold a vocabulary shard per rank; sampling needs the whole row "
                   "(single-GPU engines only)");
         return -1;
@@ -499,7 +499,7 @@ extern "C" int gemma_engine_stamp_step(gemma_engine *e, int layer, unsigned long
         if (enqueue_step(e)) return -1;
         GHIP_CHECK(hipStreamSynchronize(e->stream));
         GHIP_CHECK(hipMemcpy(out, e->stamp, n * 8, hipMemcpyDeviceToHost));
-        e->host_pos += 1;
+        e->seq.host_pos += 1;
         return 0;
     };
     const int r = run();
@@ -538,7 +538,7 @@ extern "C" int gemma_engine_token_stamps(gemma_engine *e, unsigned long long *ou
     GHIP_CHECK(se);
     if (r == 0) {
         GHIP_CHECK(hipMemcpy(out, buf, n * 8, hipMemcpyDeviceToHost));
-        e->host_pos += 1;
+        e->seq.host_pos += 1;
     }
     return r;
 }
@@ -557,7 +557,7 @@ extern "C" int gemma_engine_debug_step(gemma_engine *e, float *host_taps, float 
         if (r) return r;
         GHIP_CHECK(hipMemcpy(host_taps, e->dbg, per * c.n_layer * 4, hipMemcpyDeviceToHost));
         if (logits) GHIP_CHECK(hipMemcpy(logits, e->logits, (size_t)c.n_vocab * 4, hipMemcpyDeviceToHost));
-        e->host_pos += 1;
+        e->seq.host_pos += 1;
         return 0;
     };
     const int r = run();

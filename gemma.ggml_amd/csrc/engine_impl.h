@@ -1,9 +1,10 @@
 // engine_impl.h — the device-resident engine's state and what its translation units share
 // (internal: included only by engine.cpp, engine_decode.cpp, engine_prefill.cpp, engine_spec.cpp,
 // engine_batch.cpp, engine_diag.cpp).
-//   engine.cpp          lifecycle: create / free / begin / extend / step / tensor, TP and p2p set-up
-//   engine_decode.cpp   one decode token: enqueue_step (+ K-quant), the persistent launch's
-//                       arguments, the all-gathers
+//   engine.cpp          lifecycle: create / free / begin / extend / step / tensor, TP and p2p set-up;
+//                       what is done to a sequence (seq_state), the engine's own or a batch slot
+//   engine_decode.cpp   one decode token: enqueue_step (+ K-quant), the pick, the persistent
+//                       launch's arguments, the all-gathers
 //   engine_prefill.cpp  batched prefill and the ggml executor's entry points
 //   engine_spec.cpp     speculative decoding: the verify pass, lookup drafts, the generate loop
 //   engine_batch.cpp    batched decode: up to 8 sequences (slots), one row each per weight pass
@@ -68,31 +69,41 @@ struct pf_scratch {
     void *keys = nullptr;
 };
 
-// ---- batched decode (engine_batch.cpp, DESIGN.md §5b⁗) ------------------------------------------
-// One slot = one sequence: its own caches, history, position and RoPE row, all on the device and
-// advanced there (k_batch_advance).  host_pos / n_given mirror *pos / *nfix (passes are deterministic).
-struct batch_slot {
-    uint16_t *kc = nullptr, *vc = nullptr;  // [L][ctx][kvw], [L][kvw][ctx]
-    int *hist = nullptr;                    // [ctx + 1]
-    bool active = false;
-    int host_pos = 0, n_given = 0;
+// ---- a sequence (engine.cpp) ---- ---------------------------------------------------
+// One sequence's state: everything on the device and advanced there (k_advance, k_batch_advance,
+// k_verify_accept), plus the host's mirrors (steps and passes are deterministic).  The engine holds
+// one as its own sequence (in `mem`, made once: the captured decode graph holds these addresses); a
+// batch slot is another (in `bt_mem`).
+struct seq_state {
+    uint16_t *kc = nullptr, *vc = nullptr;  // [L][ctx][kvw], [L][kvw][ctx] (null: the engine's own on external caches)
+    int *hist = nullptr;                    // [ctx + 1] the tokens by position
+    int *pos = nullptr, *nfix = nullptr;    // processed positions; given tokens (hist below *nfix is never overwritten)
+    // the token word.  The engine's own: always the last pick (also inside the given tokens).  A
+    // slot's: the pending token hist[*pos] (-1: inactive), a word of batch_state::last
+    int *token = nullptr;
+    float *rope = nullptr;                  // [cos | sin | (int)pos] of *pos, head_dim + 4 words
+    bool active = false;                    // slots: holds a sequence
+    int host_pos = 0, n_given = 0;          // mirrors of *pos / *nfix
 };
+
+// the pick keys of a pass of up to 8 rows (enqueue_row_picks)
+struct pick_buf {
+    unsigned long long *keys = nullptr;  // device: [8][256] greedy partial keys, then [8] sampler key slots
+};
+
+// ---- batched decode (engine_batch.cpp, DESIGN.md §5b⁗) ------------------------------------------
 struct batch_state {
     bool open = false;
     int n_slots = 0;
-    batch_slot slot[GEMMA_BATCH_MAX_SLOTS];
-    int *ints = nullptr;       // device: pos[8] | nfix[8] | last[8] (the pending token, -1 inactive) by slot
-    float *rope = nullptr;     // device: [8][head_dim + 4], each slot's [cos | sin | (int)pos]
+    seq_state slot[GEMMA_BATCH_MAX_SLOTS];
+    int *last = nullptr;       // device: [8] the slots' token words (one copy reads them: batch_last)
     slot_row *rows = nullptr;  // device: the pass's row -> slot table, rewritten when the active set changes
     int *row_tok = nullptr;    // device: [8] the token each row of the next pass processes
-    unsigned long long *keys = nullptr;  // device: [8][256] greedy partial keys, then [8] sampler key slots
+    pick_buf picks;
     void *stage = nullptr;     // pinned: the row table's source, batch_last's result
     pf_scratch pf;             // the pass's scratch (8 rows), never reallocated while the batch is open
     bool dirty = true;         // the active set changed since the table was written
     int n_rows = 0, row_slot[GEMMA_BATCH_MAX_SLOTS] = {};
-    int *pos_of(int s) const { return ints + s; }
-    int *nfix_of(int s) const { return ints + GEMMA_BATCH_MAX_SLOTS + s; }
-    int *last_of(int s) const { return ints + 2 * GEMMA_BATCH_MAX_SLOTS + s; }
 };
 
 struct gemma_engine {
@@ -158,14 +169,13 @@ struct gemma_engine {
     int64_t ib_qkv = 0, ib_sa = 0, ib_h = 0, ib_x = 0, ib_hact = 0, ib_hda = 0, ib_logits = 0, ib_keys = 0, ib_flags = 0;
     unsigned long long *rank_keys = nullptr;           // [tp_n] one argmax key per rank
     // ---- attention ----
-    uint16_t *kc = nullptr, *vc = nullptr;  // [L][ctx][kvw], [L][kvw][ctx]
-    std::vector<uint16_t *> kc_ext, vc_ext;  // external per-layer caches (ggml executor), else empty
+    std::vector<uint16_t *> kc_ext, vc_ext;  // external per-layer caches of the own sequence (ggml executor), else empty
     int att_mode = ATTN_PER_HEAD;
     attn_geom ag;                           // split-attention geometry and its scratch
     float *att_sbuf = nullptr;
     int *att_sync = nullptr;                // hand-off counters [Hkv][2] + sticky error word
     uint16_t *exp_tab = nullptr, *gelu_tab = nullptr;
-    float *rope_cos = nullptr, *rope_sin = nullptr, *rope_cur = nullptr;
+    float *rope_cos = nullptr, *rope_sin = nullptr;
     // per-head decode attention: workgroups per head (each the KQ/softmax, 1/att_dsplit of the KQV
     // dims; option "att_dsplit"). Same box, decode tok/s: 1 / 2 / 4 -> 1,443 / 1,458 / 1,458; after the
     // batched K/V step loads 2 / 4 / 8 -> 1,470-1,482 / 1,491 / 1,355-1,369 (scripts/env_ab.sh)
@@ -203,16 +213,14 @@ struct gemma_engine {
     unsigned *ao_cnt = nullptr;
     int *ao_err = nullptr;
     // ---- decode state ----
-    unsigned long long *key = nullptr;
-    int *pos = nullptr, *token = nullptr, *hist = nullptr, *nfix = nullptr;
+    seq_state seq;                      // the engine's own sequence (begin / extend / step / verify)
+    unsigned long long *key = nullptr;  // the decode step's per-workgroup argmax keys
     // on-device sampling (gemma_engine_set_sampler; sample.hip): off = greedy, nothing below is used
     bool sampling = false;
     gemma_sampler smp{0.0f, 0, 1.0f, 0};  // the parameters as given
     sampler_params smp_host;              // their device form (source of the stream-ordered copy)
     sampler_params *smp_dev = nullptr;
     sample_ws smp_ws;                     // allocated when sampling is first turned on
-    int n_prompt = 0;  // host-given tokens: positions [0, n_prompt) of hist (begin / extend; *nfix mirrors it)
-    int host_pos = 0;  // mirror of *pos (steps are deterministic): processed positions, K / V rows in the caches
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     // flow control of gemma_engine_step: an event every FC_EVERY graph launches, FC_SLOTS of them
@@ -230,7 +238,7 @@ struct gemma_engine {
     batch_state bt;
     // ---- verify pass (gemma_engine_verify; allocated at its first call) ----
     struct {
-        unsigned long long *keys = nullptr;  // device: [8][256] greedy partial keys, then [8] sampler key slots
+        pick_buf picks;
         int *ints = nullptr;                 // device: [8] row positions (sampler), [9] result {a, g_0 .. g_7}
         int *host = nullptr;                 // pinned: [8] drafts, [8] row positions, [9] result
     } vf;
@@ -250,13 +258,18 @@ static inline unsigned long long *stamp_region(gemma_engine *e, int il, int k) {
 // layer il's shards of (virtual) rank slot vr, and the rank that slot stands for
 static inline layer_dev &layer_of(gemma_engine *e, int il, int vr) { return e->layers[(size_t)il * e->n_virtual + vr]; }
 static inline int rank_of(const gemma_engine *e, int vr) { return e->n_virtual > 1 ? vr : e->tp_rank; }
-// layer il's caches: K [ctx][kvw], V [kvw][ctx]
-static inline uint16_t *kc_of(const gemma_engine *e, int il) {
-    return e->kc_ext.empty() ? e->kc + (size_t)il * e->cfg.n_ctx * e->kvw : e->kc_ext[il];
+// layer il's caches of a sequence: K [ctx][kvw], V [kvw][ctx] (only the engine's own can be external).
+// "The engine's own" is decided by address: S must be e->seq itself or a slot, never a copy of one
+// (a copy of e->seq on an external-cache engine has null caches).
+static inline uint16_t *kc_of(const gemma_engine *e, const seq_state &S, int il) {
+    return &S == &e->seq && !e->kc_ext.empty() ? e->kc_ext[il] : S.kc + (size_t)il * e->cfg.n_ctx * e->kvw;
 }
-static inline uint16_t *vc_of(const gemma_engine *e, int il) {
-    return e->vc_ext.empty() ? e->vc + (size_t)il * e->cfg.n_ctx * e->kvw : e->vc_ext[il];
+static inline uint16_t *vc_of(const gemma_engine *e, const seq_state &S, int il) {
+    return &S == &e->seq && !e->vc_ext.empty() ? e->vc_ext[il] : S.vc + (size_t)il * e->cfg.n_ctx * e->kvw;
 }
+// all ranks' rows are not in one matrix on one GPU: a row-split engine (RCCL, p2p or virtual ranks).
+// (prefill_run / prefill_next test tp_n > 1 || comm without n_virtual and are left exactly so.)
+static inline bool row_split(const gemma_engine *e) { return e->tp_n > 1 || e->comm || e->n_virtual > 1; }
 
 // attention can hand attn-out the Q8_0 image of its output (per-head form; split form with 32-dim slices)
 static inline bool att_img_ok(const gemma_engine *e) { return e->att_mode == ATTN_PER_HEAD || e->ag.img; }
@@ -303,10 +316,10 @@ static inline attn_args attn_of(gemma_engine *e, int il) {
     const gemma_hip_config &c = e->cfg;
     attn_args t;
     t.qkv = e->qkv;
-    t.kc = kc_of(e, il);
-    t.vc = vc_of(e, il);
-    t.rope_cos = e->rope_cos; t.rope_sin = e->rope_sin; t.rope_cur = e->rope_cur; t.exp_tab = e->exp_tab;
-    t.pos = e->pos; t.out = e->attn;
+    t.kc = kc_of(e, e->seq, il);
+    t.vc = vc_of(e, e->seq, il);
+    t.rope_cos = e->rope_cos; t.rope_sin = e->rope_sin; t.rope_cur = e->seq.rope; t.exp_tab = e->exp_tab;
+    t.pos = e->seq.pos; t.out = e->attn;
     t.H = c.n_head; t.Hkv = c.n_head_kv; t.hd = c.head_dim; t.ctx = c.n_ctx;
     t.q_scale = 1.0f / sqrtf((float)c.head_dim);
     t.mode = e->att_mode;
@@ -317,7 +330,7 @@ static inline attn_args attn_of(gemma_engine *e, int il) {
 // the RoPE tables and the current-position row k_advance / k_set_position publish
 static inline rope_row rope_of(const gemma_engine *e) {
     rope_row rr;
-    rr.cos = e->rope_cos; rr.sin = e->rope_sin; rr.cur = e->rope_cur; rr.half = e->cfg.head_dim / 2; rr.ctx = e->cfg.n_ctx;
+    rr.cos = e->rope_cos; rr.sin = e->rope_sin; rr.cur = e->seq.rope; rr.half = e->cfg.head_dim / 2; rr.ctx = e->cfg.n_ctx;
     rr.epoch = e->epoch;
     return rr;
 }
@@ -335,6 +348,24 @@ static inline std::string sampler_invalid(const gemma_sampler &s) {
 // engine.cpp
 int ensure_graph(gemma_engine *e);
 void drop_graph(gemma_engine *e);
+// engine.cpp: one function per thing done to a sequence, the engine's own or a slot
+// every id in [0, n_vocab), else the error "<fn>: token id <id> out of range [0, n_vocab)" (name_id
+// false: "<fn>: token id out of range")
+bool token_ids_ok(const gemma_engine *e, const int32_t *tokens, int n, const char *fn, bool name_id = true);
+// S's buffers from pool M, zeroed (caches false: none, the engine's own on external ones; token_word:
+// the word to use instead of one of its own)
+int seq_alloc(gemma_engine *e, dev_pool &M, seq_state &S, bool caches, int *token_word);
+// S = the n given tokens at position 0: caches and history cleared, *pos = 0 with its RoPE row,
+// *nfix = n; synchronises.  The token word is the caller's (its meaning differs, seq_state)
+int seq_begin(gemma_engine *e, seq_state &S, const int32_t *tokens, int n);
+// dst = src (caches, history, position, RoPE row with its position word), dst's token word the
+// pending token hist[host_pos]: what a slot's word means; synchronises
+int seq_copy(gemma_engine *e, seq_state &dst, const seq_state &src);
+// K rows / V columns p0 .. p0+n of one layer as [n][kvw] each; fn names the caller in the range error
+int seq_kv_read(gemma_engine *e, const seq_state &S, int layer, int p0, int n, uint16_t *k_rows, uint16_t *v_rows,
+                const char *fn);
+// hist[0 .. min(cap, host_pos + 1)): the pending token included; returns the count
+int seq_tokens(const seq_state &S, int32_t *out, int cap);
 // engine_decode.cpp
 int enqueue_step(gemma_engine *e);
 // the token of position *pos + 1 and the advance: the sampler on `row` when sampling is on, else
@@ -345,6 +376,15 @@ int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *ke
 // sampling off: nothing is launched and the caller's greedy keys stand
 int enqueue_pick_keys(gemma_engine *e, const float *row, const int *pos, unsigned long long *skey,
                       const unsigned long long **keys, int *n_parts);
+// The pick of every row of a pass: LG [T][n_vocab], pos[t] the device position word of row t (its
+// token is that sequence's index *pos[t] + 1).  Enqueues the sampler's draws (sampling on) or the row
+// argmaxes into b and returns what the advance kernel takes: row t's n_parts keys at keys + t * stride
+struct row_picks {
+    const unsigned long long *keys = nullptr;
+    int n_parts = 0, stride = 0;
+};
+int pick_buf_alloc(dev_pool &M, pick_buf &b, hipStream_t s);  // zeroed on s
+int enqueue_row_picks(gemma_engine *e, const float *LG, int T, const int *const *pos, const pick_buf &b, row_picks *out);
 int tok_prepare(gemma_engine *e);
 int persist_report(gemma_engine *e, const int *w);
 int persist_check(gemma_engine *e);

@@ -44,7 +44,7 @@ struct pass_rows {
     int p0 = 0;
     bool slots = false;
 };
-static pass_rows own_rows(const gemma_engine *e, int p0) { return pass_rows{e->hist + p0, p0, false}; }
+static pass_rows own_rows(const gemma_engine *e, int p0) { return pass_rows{e->seq.hist + p0, p0, false}; }
 static pf_scratch &scratch_of(gemma_engine *e, const pass_rows &rows) { return rows.slots ? e->bt.pf : e->pf; }
 
 static int enqueue_prefill_kq(gemma_engine *e, int T, const pass_rows &rows);
@@ -82,7 +82,7 @@ static int prefill_attention(gemma_engine *e, int il, int T, const pass_rows &ro
     const int p0 = rows.p0;
     ropekv_args r;
     r.qkv = p.QKV; r.ldqkv = e->qkv_rows; r.rope_cos = e->rope_cos; r.rope_sin = e->rope_sin; r.q16 = p.Q16;
-    r.kc = kc_of(e, il); r.vc = vc_of(e, il);
+    r.kc = kc_of(e, e->seq, il); r.vc = vc_of(e, e->seq, il);
     r.H = c.n_head; r.Hkv = c.n_head_kv; r.hd = c.head_dim; r.ctx = c.n_ctx; r.p0 = p0;
     r.q_scale = 1.0f / sqrtf((float)c.head_dim);
     if (launch_rope_kv_prefill(r, T, s)) return -1;
@@ -175,7 +175,7 @@ static int enqueue_prefill(gemma_engine *e, int T, const pass_rows &rows, bool e
     const float *last_row = p.LG + (size_t)(T - 1) * c.n_vocab;
     if (!e->sampling && launch_row_argmax(last_row, c.n_vocab, (unsigned long long *)p.keys, 256, s)) return -1;
     const int last = p0 + T - 1;
-    GHIP_CHECK(hipMemcpyAsync(e->pos, &last, 4, hipMemcpyHostToDevice, s));
+    GHIP_CHECK(hipMemcpyAsync(e->seq.pos, &last, 4, hipMemcpyHostToDevice, s));
     return enqueue_pick(e, last_row, (const unsigned long long *)p.keys, 256);
 }
 
@@ -282,8 +282,8 @@ static int prefill_pass(gemma_engine *e, int T, int p0, bool exact, float *logit
                              hipMemcpyDeviceToHost));
     if (logits_all) GHIP_CHECK(hipMemcpy(logits_all, e->pf.LG, (size_t)T * c.n_vocab * 4, hipMemcpyDeviceToHost));
     int tok = -1;
-    GHIP_CHECK(hipMemcpy(&tok, e->token, 4, hipMemcpyDeviceToHost));
-    e->host_pos = p0 + T;
+    GHIP_CHECK(hipMemcpy(&tok, e->seq.token, 4, hipMemcpyDeviceToHost));
+    e->seq.host_pos = p0 + T;
     return tok;
 }
 
@@ -295,8 +295,8 @@ static int prefill_pass(gemma_engine *e, int T, int p0, bool exact, float *logit
 // it in fp32 summation order.
 static int prefill_run(gemma_engine *e, bool exact, float *logits_last, float *logits_all) {
     (void)hipSetDevice(e->device);
-    const int T = e->n_prompt;
-    if (T <= 0 || e->host_pos != 0) {
+    const int T = e->seq.n_given;
+    if (T <= 0 || e->seq.host_pos != 0) {
         set_error("gemma_engine_prefill: call right after gemma_engine_begin");
         return -1;
     }
@@ -323,7 +323,7 @@ extern "C" int gemma_engine_prefill_fast(gemma_engine *e, float *logits_last, fl
 extern "C" int gemma_engine_prefill_next(gemma_engine *e, int n, int exact, float *logits_last, float *logits_all) {
     set_error("");
     (void)hipSetDevice(e->device);
-    const int p0 = e->host_pos, left = e->n_prompt - p0;
+    const int p0 = e->seq.host_pos, left = e->seq.n_given - p0;
     if (e->tp_n > 1 || e->comm) {
         set_error("gemma_engine_prefill_next: the batched prefill is single-GPU (row-split engines prefill token by token)");
         return -1;
@@ -349,8 +349,8 @@ extern "C" int gemma_engine_prefill_taps(gemma_engine *e, float *host_taps, int 
     set_error("");
     (void)hipSetDevice(e->device);
     const gemma_hip_config &c = e->cfg;
-    const int T = e->n_prompt;
-    if (T <= 0 || e->host_pos != 0) {
+    const int T = e->seq.n_given;
+    if (T <= 0 || e->seq.host_pos != 0) {
         set_error("gemma_engine_prefill_taps: call right after gemma_engine_begin");
         return -1;
     }
@@ -362,7 +362,7 @@ extern "C" int gemma_engine_prefill_taps(gemma_engine *e, float *host_taps, int 
     int r = enqueue_prefill(e, T, own_rows(e, 0), exact != 0, d);
     if (r == 0) GHIP_CHECK(hipStreamSynchronize(e->stream));
     if (r == 0) GHIP_CHECK(hipMemcpy(host_taps, d, n * 4, hipMemcpyDeviceToHost));
-    if (r == 0) e->host_pos = T;
+    if (r == 0) e->seq.host_pos = T;
     return r;
 }
 
@@ -371,7 +371,7 @@ extern "C" int gemma_engine_prefill_taps(gemma_engine *e, float *host_taps, int 
 // publishes it between steps of a device-fed sequence; here the host feeds every token)
 static int ext_set_position(gemma_engine *e, int token, int pos) {
     // n_fixed past the history: k_advance must not overwrite hist (the host supplies every token)
-    return launch_set_position(token, pos, e->pos, e->hist, e->nfix, e->cfg.n_ctx + 1, rope_of(e), e->stream);
+    return launch_set_position(token, pos, e->seq.pos, e->seq.hist, e->seq.nfix, e->cfg.n_ctx + 1, rope_of(e), e->stream);
 }
 
 int gemma_engine_ext_decode(gemma_engine *e, int token, int pos, float *logits) {
@@ -418,7 +418,7 @@ int gemma_engine_ext_decode(gemma_engine *e, int token, int pos, float *logits) 
     const double t2 = prof ? us() : 0.0;
     memcpy(logits, e->ext_stage, lb);
     if (prof) fprintf(stderr, "[gemma_hip] ext_decode: launch+run %.1f us, copy %.1f us, host copy %.1f us\n", t1 - t0, t2 - t1, us() - t2);
-    e->host_pos = pos + 1;
+    e->seq.host_pos = pos + 1;
     return 0;
 }
 
@@ -427,11 +427,7 @@ int gemma_engine_ext_prefill(gemma_engine *e, const int32_t *tokens, int T, floa
         set_error("gemma_engine_ext_prefill: prompt length out of range");
         return -1;
     }
-    for (int i = 0; i < T; ++i)
-        if (tokens[i] < 0 || tokens[i] >= e->cfg.n_vocab) {
-            set_error("gemma_engine_ext_prefill: token id out of range");
-            return -1;
-        }
+    if (!token_ids_ok(e, tokens, T, "gemma_engine_ext_prefill", false)) return -1;
     if (!e->graph_exec) {
         // the decode step's first launches (code-object loading, LDS attributes) and its graph
         // capture happen here, in the prompt's call, instead of in the first generated token: one

@@ -7,7 +7,7 @@
 static int verify_alloc(gemma_engine *e) {
     auto &v = e->vf;
     dev_pool &M = e->mem;
-    if ((!v.keys && M.get(&v.keys, (size_t)(GEMM_SKINNY_MAX_T * 256 + GEMM_SKINNY_MAX_T) * 8)) ||
+    if ((!v.picks.keys && pick_buf_alloc(M, v.picks, e->stream)) ||
         (!v.ints && M.get(&v.ints, (size_t)(GEMM_SKINNY_MAX_T + GEMM_SKINNY_MAX_T + 1) * 4)) ||
         (!v.host && M.get(&v.host, (size_t)(3 * GEMM_SKINNY_MAX_T + 1) * 4, MEM_PINNED)))
         return -1;
@@ -20,13 +20,13 @@ static int verify_alloc(gemma_engine *e) {
 extern "C" int gemma_engine_verify(gemma_engine *e, const int32_t *draft, int k, int32_t *out_tokens, float *logits_all) {
     set_error("");
     const gemma_hip_config &c = e->cfg;
-    const int p0 = e->host_pos;
-    if (e->tp_n > 1 || e->comm || e->n_virtual > 1) {
+    const int p0 = e->seq.host_pos;
+    if (row_split(e)) {
         set_error("gemma_engine_verify: single-GPU engines only (row-split engines decode token by token)");
         return -1;
     }
-    if (p0 < e->n_prompt || p0 < 1) {
-        set_error("gemma_engine_verify: " + std::to_string(std::max(e->n_prompt - p0, 0)) +
+    if (p0 < e->seq.n_given || p0 < 1) {
+        set_error("gemma_engine_verify: " + std::to_string(std::max(e->seq.n_given - p0, 0)) +
                   " given tokens are still pending (the drafts follow the pending picked token)");
         return -1;
     }
@@ -35,11 +35,7 @@ extern "C" int gemma_engine_verify(gemma_engine *e, const int32_t *draft, int k,
                   "], or a null draft / out_tokens");
         return -1;
     }
-    for (int i = 0; i < k; ++i)  // the embedding kernels index token_embd rows unchecked
-        if (draft[i] < 0 || draft[i] >= c.n_vocab) {
-            set_error("gemma_engine_verify: token id " + std::to_string(draft[i]) + " out of range [0, n_vocab)");
-            return -1;
-        }
+    if (!token_ids_ok(e, draft, k, "gemma_engine_verify")) return -1;
     if ((int64_t)p0 + k + 1 >= c.n_ctx) {
         set_error("gemma_engine_verify: pos + k + 1 = " + std::to_string((int64_t)p0 + k + 1) + " does not fit n_ctx = " +
                   std::to_string(c.n_ctx));
@@ -51,38 +47,31 @@ extern "C" int gemma_engine_verify(gemma_engine *e, const int32_t *draft, int k,
     const int T = k + 1;
     int *h_draft = e->vf.host, *h_pos = e->vf.host + GEMM_SKINNY_MAX_T, *h_out = e->vf.host + 2 * GEMM_SKINNY_MAX_T;
     int *d_pos = e->vf.ints, *d_out = e->vf.ints + GEMM_SKINNY_MAX_T;
-    unsigned long long *d_skey = e->vf.keys + GEMM_SKINNY_MAX_T * 256;
     for (int i = 0; i < k; ++i) h_draft[i] = draft[i];
     for (int i = 0; i < T; ++i) h_pos[i] = p0 + i;
     // 1. stage: the drafts become hist[pos+1 .. pos+k], the tokens of the pass's rows 1 .. k
-    GHIP_CHECK(hipMemcpyAsync(e->hist + p0 + 1, h_draft, (size_t)k * 4, hipMemcpyHostToDevice, s));
+    GHIP_CHECK(hipMemcpyAsync(e->seq.hist + p0 + 1, h_draft, (size_t)k * 4, hipMemcpyHostToDevice, s));
     // 2. the pass
     if (enqueue_verify_pass(e, T, p0)) return -1;
     // 3. a pick from every row, none advances: row i gives the token of sequence index pos + i + 1
-    verify_args v;
-    if (e->sampling) {
-        GHIP_CHECK(hipMemcpyAsync(d_pos, h_pos, (size_t)T * 4, hipMemcpyHostToDevice, s));
-        for (int i = 0; i < T; ++i) {
-            const unsigned long long *key = nullptr;
-            int parts = 0;
-            if (enqueue_pick_keys(e, e->pf.LG + (size_t)i * c.n_vocab, d_pos + i, d_skey + i, &key, &parts)) return -1;
-        }
-        v.keys = d_skey; v.n_parts = 1; v.key_stride = 1;
-    } else {
-        for (int i = 0; i < T; ++i)
-            if (launch_row_argmax(e->pf.LG + (size_t)i * c.n_vocab, c.n_vocab, e->vf.keys + (size_t)i * 256, 256, s)) return -1;
-        v.keys = e->vf.keys; v.n_parts = 256; v.key_stride = 256;
-    }
+    // (the sampler reads each row's position from the device: p0 + i)
+    if (e->sampling) GHIP_CHECK(hipMemcpyAsync(d_pos, h_pos, (size_t)T * 4, hipMemcpyHostToDevice, s));
+    const int *row_pos[GEMM_SKINNY_MAX_T];
+    for (int i = 0; i < T; ++i) row_pos[i] = d_pos + i;
+    row_picks pk;
+    if (enqueue_row_picks(e, e->pf.LG, T, row_pos, e->vf.picks, &pk)) return -1;
     // 4. accept + advance
-    v.k = k; v.p0 = p0; v.token = e->token; v.pos = e->pos; v.hist = e->hist; v.r = rope_of(e);
+    verify_args v;
+    v.keys = pk.keys; v.n_parts = pk.n_parts; v.key_stride = pk.stride;
+    v.k = k; v.p0 = p0; v.token = e->seq.token; v.pos = e->seq.pos; v.hist = e->seq.hist; v.r = rope_of(e);
     v.zero_keys = e->key; v.n_zero = e->grid_big; v.out = d_out;
     if (launch_verify_accept(v, s)) return -1;
     // 5. the rejected rows leave the caches
     if (e->kc_ext.empty()) {
-        if (launch_verify_clean(e->kc, e->vc, c.n_layer, (int64_t)c.n_ctx * e->kvw, c.n_ctx, e->kvw, p0, k, d_out, s)) return -1;
+        if (launch_verify_clean(e->seq.kc, e->seq.vc, c.n_layer, (int64_t)c.n_ctx * e->kvw, c.n_ctx, e->kvw, p0, k, d_out, s)) return -1;
     } else {
         for (int il = 0; il < c.n_layer; ++il)
-            if (launch_verify_clean(kc_of(e, il), vc_of(e, il), 1, 0, c.n_ctx, e->kvw, p0, k, d_out, s)) return -1;
+            if (launch_verify_clean(kc_of(e, e->seq, il), vc_of(e, e->seq, il), 1, 0, c.n_ctx, e->kvw, p0, k, d_out, s)) return -1;
     }
     // 6. results: one synchronise
     GHIP_CHECK(hipMemcpyAsync(h_out, d_out, (size_t)(T + 1) * 4, hipMemcpyDeviceToHost, s));
@@ -94,26 +83,13 @@ extern "C" int gemma_engine_verify(gemma_engine *e, const int32_t *draft, int k,
         return -1;
     }
     for (int i = 0; i <= a; ++i) out_tokens[i] = h_out[1 + i];
-    e->host_pos = p0 + a + 1;
+    e->seq.host_pos = p0 + a + 1;
     return a + 1;
 }
 
 extern "C" int gemma_engine_kv_read(gemma_engine *e, int layer, int p0, int n, uint16_t *k_rows, uint16_t *v_rows) {
     set_error("");
-    const gemma_hip_config &c = e->cfg;
-    if (layer < 0 || layer >= c.n_layer || p0 < 0 || n < 1 || (int64_t)p0 + n > c.n_ctx || !k_rows || !v_rows) {
-        set_error("gemma_engine_kv_read: layer or positions out of range");
-        return -1;
-    }
-    (void)hipSetDevice(e->device);
-    GHIP_CHECK(hipStreamSynchronize(e->stream));
-    const size_t kvw = (size_t)e->kvw, ctx = (size_t)c.n_ctx;
-    GHIP_CHECK(hipMemcpy(k_rows, kc_of(e, layer) + (size_t)p0 * kvw, (size_t)n * kvw * 2, hipMemcpyDeviceToHost));
-    std::vector<uint16_t> vt(kvw * (size_t)n);  // V is [kvw][ctx]: columns p0 .. p0+n, then transposed
-    GHIP_CHECK(hipMemcpy2D(vt.data(), (size_t)n * 2, vc_of(e, layer) + p0, ctx * 2, (size_t)n * 2, kvw, hipMemcpyDeviceToHost));
-    for (size_t j = 0; j < kvw; ++j)
-        for (size_t r = 0; r < (size_t)n; ++r) v_rows[r * kvw + j] = vt[j * (size_t)n + r];
-    return 0;
+    return seq_kv_read(e, e->seq, layer, p0, n, k_rows, v_rows, "gemma_engine_kv_read");
 }
 
 // Prompt-lookup draft: for g = min(ngram_max, n - 1) .. 1, the most recent earlier occurrence of the
@@ -144,17 +120,17 @@ extern "C" int gemma_engine_generate_lookup(gemma_engine *e, int n_new, int k, i
                   " and ngram_max >= 1");
         return -1;
     }
-    if (e->host_pos < e->n_prompt || e->host_pos < 1) {
+    if (e->seq.host_pos < e->seq.n_given || e->seq.host_pos < 1) {
         set_error("gemma_engine_generate_lookup: given tokens are still pending (consume the prompt first)");
         return -1;
     }
-    if ((int64_t)e->host_pos + n_new >= c.n_ctx) {
+    if ((int64_t)e->seq.host_pos + n_new >= c.n_ctx) {
         set_error("gemma_engine_generate_lookup: context full");
         return -1;
     }
     std::vector<int32_t> seq((size_t)c.n_ctx + 1);
     int n = gemma_engine_tokens(e, seq.data(), c.n_ctx + 1);  // the sequence so far, the pending token included
-    if (n != e->host_pos + 1) return -1;
+    if (n != e->seq.host_pos + 1) return -1;
     int done = 0;
     int32_t draft[GEMMA_VERIFY_MAX_DRAFT], got[GEMMA_VERIFY_MAX_DRAFT + 1];
     while (done < n_new) {
@@ -171,7 +147,7 @@ extern "C" int gemma_engine_generate_lookup(gemma_engine *e, int n_new, int k, i
             for (int i = 0; i < m; ++i) seq[n + kd + i] = draft[kd + i];
             kd += m;
         }
-        if (kd > 0 && (int64_t)e->host_pos + kd + 1 >= c.n_ctx) kd = 0;
+        if (kd > 0 && (int64_t)e->seq.host_pos + kd + 1 >= c.n_ctx) kd = 0;
         if (kd > 0) {
             const int m = gemma_engine_verify(e, draft, kd, got, nullptr);
             if (m < 0) return -1;
@@ -180,7 +156,7 @@ extern "C" int gemma_engine_generate_lookup(gemma_engine *e, int n_new, int k, i
         } else {
             if (gemma_engine_step(e, 1, nullptr, 1)) return -1;
             int32_t tok = 0;
-            GHIP_CHECK(hipMemcpy(&tok, e->token, 4, hipMemcpyDeviceToHost));
+            GHIP_CHECK(hipMemcpy(&tok, e->seq.token, 4, hipMemcpyDeviceToHost));
             st.plain_steps += 1;
             seq[n++] = out[done++] = tok;
         }

@@ -22,6 +22,7 @@
 
 #include "device_util.h"
 #include "kernels.h"
+#include "pick.h"
 
 namespace ghip {
 namespace {
@@ -539,12 +540,6 @@ __device__ __forceinline__ float fold8(float v) {
     return fold8_dpp(v);
 }
 
-__device__ __forceinline__ unsigned long long argmax_key(float v, int64_t idx) {
-    uint32_t u = __builtin_bit_cast(uint32_t, v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)idx);
-}
-
 __device__ __forceinline__ float gelu_tab(const mv_args &a, float x) {
     if (a.gelu_clamp && x <= -10.0f) return 0.0f;
     if (a.gelu_clamp && x >= 10.0f) return x;
@@ -1054,11 +1049,7 @@ __global__ void __launch_bounds__(512) k_matvec(mv_args a) {
         }
     }
     if (EPI == EPI_ARGMAX) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const unsigned long long o = __shfl_xor(best, off);
-            best = o > best ? o : best;
-        }
+        best = wave_max_key(best);
         // one plain store per workgroup into its own slot (a single-word atomic from every wave
         // serialises at the memory side: MI355X_MICROARCH fan-in row); k_advance reduces the slots
         unsigned long long *red = (unsigned long long *)(smem + m.red);

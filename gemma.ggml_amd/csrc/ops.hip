@@ -13,6 +13,7 @@
 #include "attn_impl.h"
 #include "device_util.h"
 #include "kernels.h"
+#include "pick.h"
 
 namespace ghip {
 namespace {
@@ -698,19 +699,8 @@ __global__ void k_exp_f16_all(uint16_t *out) {
 __global__ void __launch_bounds__(256) k_reduce_keys(const unsigned long long *keys, int n, int64_t row_base,
                                                      unsigned long long *out) {
     __shared__ unsigned long long red[4];
-    unsigned long long best = 0;
-    for (int i = threadIdx.x; i < n; i += 256) best = keys[i] > best ? keys[i] : best;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off);
-        best = o > best ? o : best;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    for (int w = 1; w < 4; ++w) best = red[w] > best ? red[w] : best;
-    const uint32_t local = 0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull);
-    *out = (best & 0xFFFFFFFF00000000ull) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)(local + row_base));
+    const unsigned long long best = block_max_key(keys, n, red);
+    if (threadIdx.x == 0) *out = key_with_index(best, key_index(best) + row_base);
 }
 
 __global__ void __launch_bounds__(256) k_advance(const unsigned long long *keys, int n_parts, int *token, int *pos,
@@ -722,26 +712,11 @@ __global__ void __launch_bounds__(256) k_advance(const unsigned long long *keys,
     // only after the barrier below, which every read precedes)
     const int p = *pos + 1;
     const int fixed = hist ? *n_fixed : 0;
-    if (r.cur && p < r.ctx) {  // the RoPE row of the next position, at a fixed address (attention loads it without *pos)
-        for (int i = threadIdx.x; i < r.half; i += 256) {
-            r.cur[i] = r.cos[(int64_t)p * r.half + i];
-            r.cur[r.half + i] = r.sin[(int64_t)p * r.half + i];
-        }
-        if (threadIdx.x == 0) ((int *)r.cur)[2 * r.half] = p;
-    }
-    unsigned long long best = 0;
-    for (int i = threadIdx.x; i < n_parts; i += 256) best = keys[i] > best ? keys[i] : best;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off);
-        best = o > best ? o : best;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
-    __syncthreads();
+    // the RoPE row of the next position, at a fixed address (attention loads it without *pos)
+    if (r.cur && p < r.ctx) publish_rope_row(r.cur, r.cos, r.sin, r.half, p);
+    const unsigned long long best = block_max_key(keys, n_parts, red);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) best = red[w] > best ? red[w] : best;
-        // strict '>' argmax, first max wins (src/gemma_model.cpp:538-543): the key's low word is ~index
-        const int idx = (int)(0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull));
+        const int idx = key_index(best);
         *token = idx;
         if (hist && p < hist_cap && p >= fixed) hist[p] = idx;  // never overwrite the prompt
         *pos = p;
@@ -758,13 +733,9 @@ __global__ void __launch_bounds__(256) k_set_position(int token, int p, int *pos
         hist[p] = token;
         *pos = p;
         *n_fixed = fixed;
-        ((int *)r.cur)[2 * r.half] = p;
         if (r.epoch) ++*r.epoch;
     }
-    for (int i = threadIdx.x; i < r.half; i += 256) {
-        r.cur[i] = r.cos[(int64_t)p * r.half + i];
-        r.cur[r.half + i] = r.sin[(int64_t)p * r.half + i];
-    }
+    publish_rope_row(r.cur, r.cos, r.sin, r.half, p);  // (no p < ctx guard: the host checked p)
 }
 
 // C-ABI F16 mul_mat (KQ/KQV shapes): one thread per (row, col), vec_dot_f16 order

@@ -14,6 +14,7 @@
 
 #include "device_util.h"
 #include "kernels.h"
+#include "pick.h"
 
 namespace ghip {
 namespace {
@@ -1158,23 +1159,12 @@ __global__ void __launch_bounds__(256) k_attn_prefill(attnp_args a) {
 __global__ void __launch_bounds__(256) k_row_argmax(const float *row, int64_t n, unsigned long long *keys) {
     unsigned long long best = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        uint32_t u = __builtin_bit_cast(uint32_t, row[i]);
-        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-        const unsigned long long key = ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i);
+        const unsigned long long key = argmax_key(row[i], i);
         best = key > best ? key : best;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off);
-        best = o > best ? o : best;
-    }
     __shared__ unsigned long long red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) best = red[w] > best ? red[w] : best;
-        keys[blockIdx.x] = best;
-    }
+    best = block_max_key(best, red);
+    if (threadIdx.x == 0) keys[blockIdx.x] = best;
 }
 
 }  // namespace

@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "pick.h"
 
 namespace ghip {
 namespace {
@@ -34,14 +35,11 @@ constexpr int SM_TAIL = 1024;  // the tail workgroup: one thread per candidate
 constexpr int SM_CAP = 2048;   // entries the tail sorts (>= SAMPLE_MAX_K)
 static_assert(SM_TAIL == SAMPLE_MAX_K && SM_CAP >= SAMPLE_MAX_K && SM_BINS == 16 * SM_TH, "sampler geometry");
 
-// monotone key of a logit: the argmax key's high word (matvec_impl.h argmax_key) with -0 made +0
+// monotone key of a logit: the argmax key's high word (pick.h) with -0 made +0
 __device__ __forceinline__ uint32_t logit_key(float v) {
     uint32_t u = __builtin_bit_cast(uint32_t, v);
     if (u == 0x80000000u) u = 0;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_logit(uint32_t k) {
-    return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+    return ordered_bits(u);
 }
 __device__ __forceinline__ int sample_k(const sampler_params &p, int64_t n) {
     const int k = p.top_k > 0 ? p.top_k : SAMPLE_MAX_K;
@@ -117,7 +115,7 @@ __global__ void __launch_bounds__(SM_TH) k_sample_compact(const float *row, int6
             if (i < n) {
                 const uint32_t key = logit_key(row[i]);
                 const unsigned bin = key >> SM_SHIFT;
-                comp[k] = ((unsigned long long)key << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i);
+                comp[k] = pack_key(key, i);
                 if (bin > bsel) slot[k] = (int)atomicAdd(&s_cnt[0], 1u);
                 else if (bin == bsel) slot[k] = (int)atomicAdd(&s_cnt[1], 1u) | (1 << 30);
             }
@@ -248,10 +246,10 @@ __global__ void __launch_bounds__(SM_TAIL) k_sample_tail(const sampler_params *p
         }
     }
     // weights (f64) and their prefix sums: thread i = candidate i
-    const float l0 = key_logit((uint32_t)(ks[0] >> 32));
+    const float l0 = key_value(ks[0]);
     double w = 0.0;
     if (tid < Ke) {
-        const float li = key_logit((uint32_t)(ks[tid] >> 32));
+        const float li = key_value(ks[tid]);
         w = exp(((double)li - (double)l0) / (double)P.temperature);
     }
     double incl = w;
@@ -285,11 +283,11 @@ __global__ void __launch_bounds__(SM_TAIL) k_sample_tail(const sampler_params *p
     const unsigned long long pick = ks[s_j];
     if (tid == 0) {
         *key_out = pick;
-        if (dbg.token) *dbg.token = (int)(0xFFFFFFFFu - (uint32_t)(pick & 0xFFFFFFFFull));
+        if (dbg.token) *dbg.token = key_index(pick);
         if (dbg.n_cand) *dbg.n_cand = Ke;
         if (dbg.n_kept) *dbg.n_kept = m;
     }
-    if (dbg.cand) dbg.cand[tid] = tid < Ke ? (int)(0xFFFFFFFFu - (uint32_t)(ks[tid] & 0xFFFFFFFFull)) : -1;
+    if (dbg.cand) dbg.cand[tid] = tid < Ke ? key_index(ks[tid]) : -1;
 }
 
 }  // namespace

@@ -2,6 +2,7 @@
 // accept rule and the advance over the accepted prefix in one launch, then the rejected rows' K / V
 // cleared.  Both read the accepted count from device memory: no host round trip inside the pass.
 #include "kernels.h"
+#include "pick.h"
 
 namespace ghip {
 namespace {
@@ -15,23 +16,9 @@ __global__ void __launch_bounds__(256) k_verify_accept(verify_args v) {
     __shared__ int gs[GEMM_SKINNY_MAX_T], a_sh;
     const int tid = threadIdx.x;
     for (int i = 0; i <= v.k; ++i) {
-        unsigned long long best = 0;
-        for (int j = tid; j < v.n_parts; j += 256) {
-            const unsigned long long key = v.keys[(int64_t)i * v.key_stride + j];
-            best = key > best ? key : best;
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const unsigned long long o = __shfl_xor(best, off);
-            best = o > best ? o : best;
-        }
-        if ((tid & 63) == 0) red[tid >> 6] = best;
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < 4; ++w) best = red[w] > best ? red[w] : best;
-            gs[i] = (int)(0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull));  // the key's low word is ~index
-        }
-        __syncthreads();
+        const unsigned long long best = block_max_key(v.keys + (int64_t)i * v.key_stride, v.n_parts, red);
+        if (tid == 0) gs[i] = key_index(best);
+        __syncthreads();  // red[] is reused by the next row: thread 0 has read it
     }
     if (tid == 0) {
         int a = 0;
@@ -47,13 +34,7 @@ __global__ void __launch_bounds__(256) k_verify_accept(verify_args v) {
     }
     __syncthreads();
     const int p = v.p0 + a_sh + 1;
-    if (v.r.cur && p < v.r.ctx) {
-        for (int i = tid; i < v.r.half; i += 256) {
-            v.r.cur[i] = v.r.cos[(int64_t)p * v.r.half + i];
-            v.r.cur[v.r.half + i] = v.r.sin[(int64_t)p * v.r.half + i];
-        }
-        if (tid == 0) ((int *)v.r.cur)[2 * v.r.half] = p;
-    }
+    if (v.r.cur && p < v.r.ctx) publish_rope_row(v.r.cur, v.r.cos, v.r.sin, v.r.half, p);
     for (int j = tid; j < v.n_zero; j += 256) v.zero_keys[j] = 0;
 }
 
