@@ -455,6 +455,97 @@ extern "C" int gemma_test_gemm_skinny(int type, int64_t rows, int64_t K, int64_t
     return r;
 }
 
+// ---- per-op test entry for the decode matvec (tests/test_gpu_kernarg_args.py) ---------------------
+// One launch_matvec with every field of its mv_args supplied by the caller (include/gemma_hpc.h).
+extern "C" int gemma_test_matvec(const gemma_test_matvec_args *t) {
+    set_error("");
+    auto bad = [](const char *why) {
+        set_error(std::string("gemma_test_matvec: ") + why);
+        return -1;
+    };
+    if (!t || (t->type != T_Q4_0 && t->type != T_Q8_0) || t->K <= 0 || t->K % 32 || t->rows <= 0 || !t->W || !t->x || !t->y)
+        return bad("bad arguments");
+    if (t->ncols < 1 || t->ncols > 8 || t->grid < 1 || t->grid > 4096 || t->y_stride < t->rows) return bad("bad geometry");
+    const int pro = t->pro, epi = t->epi;
+    if (pro != PRO_F32 && pro != PRO_NORM && pro != PRO_EMBED && pro != PRO_IMG) return bad("prologue not covered");
+    if (epi < EPI_STORE || epi > EPI_ARGMAX) return bad("bad epilogue");
+    if ((pro == PRO_F32 || pro == PRO_NORM) && t->x_stride < t->K) return bad("x_stride < K");
+    if ((pro == PRO_NORM || pro == PRO_EMBED) && !t->norm_w) return bad("norm_w missing");
+    if (pro == PRO_IMG && (!t->x_da || t->K % 128)) return bad("the image needs x_da and K % 128 == 0");
+    if (epi == EPI_ADD && !t->resid) return bad("resid missing");
+    if (epi == EPI_GELU_MUL && !t->W2) return bad("W2 missing");
+    if (epi == EPI_ARGMAX && !t->keys) return bad("keys missing");
+    if (pro == PRO_EMBED) {
+        if (!t->emb || t->emb_rows <= 0 || t->n_tok <= 0 || t->tok_pos < 0 || t->tok_pos >= t->n_tok) return bad("bad embedding source");
+        const int32_t tok = ((const int32_t *)t->x)[t->tok_pos];
+        if (tok < 0 || tok >= t->emb_rows) return bad("token outside the embedding");
+    }
+    const int bb = t->type == T_Q4_0 ? 18 : 34;
+    const int64_t K = t->K, rows = t->rows, nb = K / 32, row_bytes = nb * bb;
+    const size_t y_floats = (size_t)((t->ncols - 1) * t->y_stride + rows);
+    const size_t x_bytes = pro == PRO_EMBED ? (size_t)t->n_tok * 4 : pro == PRO_IMG ? (size_t)K : (size_t)((t->ncols - 1) * t->x_stride + K) * 4;
+    dev_pool tmp;
+    uint8_t *d_rows = nullptr, *d_x = nullptr;
+    float *d_y = nullptr, *d_r = nullptr, *d_nw = nullptr, *d_da = nullptr, *d_eo = nullptr;
+    int *d_pos = nullptr;
+    uint16_t *d_gelu = nullptr;
+    unsigned long long *d_keys = nullptr;
+    const size_t n_keys = (size_t)t->grid * t->ncols;
+    const int64_t max_rows = std::max(rows, pro == PRO_EMBED ? t->emb_rows : (int64_t)0);
+    if (tmp.get(&d_rows, (size_t)(row_bytes * max_rows)) || tmp.get(&d_x, x_bytes) || tmp.get(&d_y, y_floats * 4) ||
+        tmp.get(&d_r, y_floats * 4) || tmp.get(&d_nw, (size_t)K * 4) || tmp.get(&d_da, (size_t)nb * 4) ||
+        tmp.get(&d_eo, (size_t)K * 4) || tmp.get(&d_pos, 4) || tmp.get(&d_gelu, 65536 * 2) || tmp.get(&d_keys, n_keys * 8))
+        return -1;
+    tiled_mat m, m2, me;
+    auto tiled = [&](tiled_mat *out, const void *src, int64_t n_rows) -> int {
+        GHIP_CHECK(hipMemcpy(d_rows, src, (size_t)(row_bytes * n_rows), hipMemcpyHostToDevice));
+        if (alloc_tiled(tmp, out, t->type, n_rows, K, nullptr)) return -1;
+        if (launch_repack(*out, d_rows, row_bytes, nullptr)) return -1;
+        GHIP_CHECK(hipDeviceSynchronize());  // d_rows is reused
+        return 0;
+    };
+    if (tiled(&m, t->W, rows)) return -1;
+    if (epi == EPI_GELU_MUL && tiled(&m2, t->W2, rows)) return -1;
+    if (pro == PRO_EMBED && tiled(&me, t->emb, t->emb_rows)) return -1;
+    GHIP_CHECK(hipMemcpy(d_x, t->x, x_bytes, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemset(d_y, 0, y_floats * 4));
+    GHIP_CHECK(hipMemset(d_keys, 0, n_keys * 8));
+    mv_args a;
+    set_mat(a, m);
+    a.x = d_x; a.x_col_stride = pro == PRO_F32 || pro == PRO_NORM ? t->x_stride * 4 : 0;
+    a.y = d_y; a.y_col_stride = t->y_stride; a.ncols = t->ncols; a.eps = t->eps;
+    if (t->norm_w) {
+        GHIP_CHECK(hipMemcpy(d_nw, t->norm_w, (size_t)K * 4, hipMemcpyHostToDevice));
+        a.norm_w = d_nw;
+    }
+    if (pro == PRO_IMG) {
+        GHIP_CHECK(hipMemcpy(d_da, t->x_da, (size_t)nb * 4, hipMemcpyHostToDevice));
+        a.x_da = d_da;
+    }
+    if (pro == PRO_EMBED) {
+        GHIP_CHECK(hipMemcpy(d_pos, &t->tok_pos, 4, hipMemcpyHostToDevice));
+        a.tok_pos = d_pos; a.emb_qs = me.qs; a.emb_sc = me.sc; a.emb_n_bt = me.n_bt; a.emb_scale = t->emb_scale;
+        if (t->emb_out) a.emb_out = d_eo;
+    }
+    if (epi == EPI_ADD) {
+        GHIP_CHECK(hipMemcpy(d_r, t->resid, y_floats * 4, hipMemcpyHostToDevice));
+        a.resid = d_r;
+    }
+    if (epi == EPI_GELU_MUL) {
+        std::vector<uint16_t> exp_t, gelu_t;
+        build_f16_tables(exp_t, gelu_t);
+        GHIP_CHECK(hipMemcpy(d_gelu, gelu_t.data(), 65536 * 2, hipMemcpyHostToDevice));
+        a.qs2 = m2.qs; a.sc2 = m2.sc; a.gelu_tab = d_gelu;
+    }
+    if (epi == EPI_ARGMAX) a.argmax_key = d_keys;
+    if (launch_matvec(t->type, t->ks, pro, epi, a, t->grid, nullptr)) return -1;
+    GHIP_CHECK(hipDeviceSynchronize());
+    GHIP_CHECK(hipMemcpy(t->y, d_y, y_floats * 4, hipMemcpyDeviceToHost));
+    if (epi == EPI_ARGMAX) GHIP_CHECK(hipMemcpy(t->keys, d_keys, n_keys * 8, hipMemcpyDeviceToHost));
+    if (pro == PRO_EMBED && t->emb_out) GHIP_CHECK(hipMemcpy(t->emb_out, d_eo, (size_t)K * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // ---- K-quant matvec timing (bench.py): random bytes of the right shape, `iters` launches timed
 // with hipEvents on one stream; returns avg µs and the algorithmic bytes per launch
 extern "C" double gemma_kq_time(int type, int64_t rows, int64_t K, int iters, double *algo_bytes) {

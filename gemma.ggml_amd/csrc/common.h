@@ -23,6 +23,13 @@ namespace ghip {
 #ifndef GHIP_STAMPS
 #define GHIP_STAMPS 0
 #endif
+// timing-only ablations of the decode matvecs (mv_args::ablate, option "ablate"): compiled out of
+// the product build too.  A run-time flag is a kernel argument the prologue must load and wait for
+// before its first activation load; tests/ablate_kernels.py runs against a variant built with
+// -DGHIP_ABLATE=1 (scripts/build_variant.sh ablate matvec.hip,...,engine_diag.cpp -DGHIP_ABLATE=1)
+#ifndef GHIP_ABLATE
+#define GHIP_ABLATE 0
+#endif
 
 enum : int { T_F32 = 0, T_F16 = 1, T_Q4_0 = 2, T_Q8_0 = 8, T_Q4_K = 12, T_Q6_K = 14, T_Q8_K = 15 };
 

@@ -329,6 +329,12 @@ extern "C" int gemma_engine_set_option(gemma_engine *e, const char *name, int va
         set_error("gemma_engine_set_option: unknown option '" + n + "'");
         return -1;
     }
+    // the product kernels do not read the flag: a timing taken without the ablation must not pass
+    // for one taken with it
+    if (!GHIP_ABLATE && n == "ablate" && value != 0) {
+        set_error("gemma_engine_set_option: ablate: library built without -DGHIP_ABLATE=1 (scripts/build_variant.sh)");
+        return -1;
+    }
     *f = value;
     drop_graph(e);
     return 0;

@@ -761,6 +761,9 @@ __device__ __forceinline__ float carry_chain(const void *st_s, const float *st_d
     return carry_run<2, false>(ps, pd, total, acc);
 }
 
+// the timing ablations a kernel sees: a constant 0 unless the library is the GHIP_ABLATE variant,
+// so the product kernels never read (or wait for) mv_args::ablate
+#define MV_ABLATE(a) (GHIP_ABLATE ? (a).ablate : 0)
 #ifndef GHIP_NOSCALE
 #define GHIP_NOSCALE 0
 #endif
@@ -777,9 +780,17 @@ __device__ __forceinline__ float carry_chain(const void *st_s, const float *st_d
 #define GHIP_SCL 1  // gate/up scales as one 1 KiB run per row tile and matrix (k_matvec SCL)
 #endif
 // ONE_SHOT: every wave's items fit the register ring (n_items <= U): no refills in the stream loop
+// Launch front: the four weight planes and the tile counts that address the scale
+// runs and the first ring slots come as leading scalar parameters (14 dwords, the user-SGPR
+// preload's reach on gfx950) and replace the struct's copies; the body is written against one
+// mv_args.  (The activation loads in front of them still wait for x / nb / norm_w from the struct:
+// six pointers and five sizes do not fit, scripts/kernarg_front.py shows what is left.)
 template <int WT, int KS, int PRO, int EPI, int U, int R, bool NSA, bool ONE_SHOT>
-__global__ void __launch_bounds__(512) k_matvec(mv_args a) {
+__global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t *sc, const uint8_t *qs2, const uint8_t *sc2,
+                                                int64_t n_bt, int64_t rt_q, int64_t rt_r, mv_args a_rest) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    mv_args a = a_rest;
+    a.qs = qs; a.sc = sc; a.qs2 = qs2; a.sc2 = sc2; a.n_bt = n_bt; a.rt_q = rt_q; a.rt_r = rt_r;
     constexpr int BT = wfmt<WT>::BT, SB = wfmt<WT>::SCALE_BYTES;
     constexpr int NM = EPI == EPI_GELU_MUL ? 2 : 1;  // matrices per row tile (gate, up)
     // readfirstlane: makes the wave index (and every cursor derived from it) provably uniform, so
@@ -890,7 +901,7 @@ __global__ void __launch_bounds__(512) k_matvec(mv_args a) {
 
     // 2) activation image in LDS
     norm_state ns;
-    if (!(a.ablate & 1)) {  // timing ablations only
+    if (!(MV_ABLATE(a) & 1)) {  // timing ablations only (GHIP_ABLATE build)
         ns = build_activation<WT, PRO, R, NSA, NTH>(a, col, smem, m, ar);
         // the norm's check before the rest of the ring: the fallback's registers would otherwise sit
         // beside the whole ring's (measured: VGPRs 44 -> 74 on the rr kernel, spills on long K)
@@ -942,7 +953,7 @@ __global__ void __launch_bounds__(512) k_matvec(mv_args a) {
                 issue(qb[u], sb[u]);
                 issue(qb[u + 1], sb[u + 1]);
                 if (k + u < n_items) {
-                    if (a.ablate & 8) {  // timing only: the loads without the dot products
+                    if (MV_ABLATE(a) & 8) {  // timing only: the loads without the dot products
                         acc += __builtin_bit_cast(float, q0.x ^ s0.x ^ q1.y ^ s1.y);
                     } else {
                         const act_tile<WT> at = load_act<WT, NSA>(smem, m, cc.bt, l);
@@ -1011,7 +1022,7 @@ __global__ void __launch_bounds__(512) k_matvec(mv_args a) {
                             const int gl = wave * RPW * 8 + lane;
                             if (wave < NCAR && lane < RPW * 8) {
                                 float c = hand[gl];
-                                if (!(a.ablate & 4)) c = carry_chain<WT, KS>(st_s, st_d, m, seg_blocks, gl, c);
+                                if (!(MV_ABLATE(a) & 4)) c = carry_chain<WT, KS>(st_s, st_d, m, seg_blocks, gl, c);
                                 if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 8] = __builtin_amdgcn_s_memrealtime();
                                 const float v = fold8(c);
                                 if ((lane & 7) == 0) epilogue<EPI>(a, col, cc.rt * 8 + (gl >> 3), v, 0.0f, best);
@@ -1243,9 +1254,10 @@ int launch_t(const mv_args &a, int grid_x, hipStream_t s) {
     if (lds > 64 * 1024) GHIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (os)
         hipLaunchKernelGGL((k_matvec<WT, KS, PRO, EPI, U, R, NSA, KS != 1 || EPI == EPI_GELU_MUL>), dim3(grid_x, a.ncols),
-                           dim3(threads), lds, s, la);
+                           dim3(threads), lds, s, la.qs, la.sc, la.qs2, la.sc2, la.n_bt, la.rt_q, la.rt_r, la);
     else
-        hipLaunchKernelGGL((k_matvec<WT, KS, PRO, EPI, U, R, NSA, false>), dim3(grid_x, a.ncols), dim3(threads), lds, s, la);
+        hipLaunchKernelGGL((k_matvec<WT, KS, PRO, EPI, U, R, NSA, false>), dim3(grid_x, a.ncols), dim3(threads), lds, s, la.qs,
+                           la.sc, la.qs2, la.sc2, la.n_bt, la.rt_q, la.rt_r, la);
     GHIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -20,9 +20,18 @@
 namespace ghip {
 namespace {
 
+// Launch front: the fields the first activation and weight loads are addressed with
+// come as leading scalar parameters (14 dwords, the user-SGPR preload's reach on gfx950) and replace
+// the struct's copies, so the body below is written against one mv_args.  act2 is the activation's
+// second pointer: x_da for PRO_IMG, norm_w otherwise.
 template <int WT, int PRO, int EPI, int NR, int R, int DD>
-__global__ void __launch_bounds__(RR_NTH) k_matvec_rr(mv_args a) {
+__global__ void __launch_bounds__(RR_NTH) k_matvec_rr(const void *x, const float *act2, const uint8_t *qs, const uint8_t *sc,
+                                                      int64_t n_bt, int64_t nb, int64_t x_col_stride, mv_args a_rest) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    mv_args a = a_rest;
+    a.x = x; a.qs = qs; a.sc = sc; a.n_bt = n_bt; a.nb = nb; a.x_col_stride = x_col_stride;
+    if (PRO == PRO_IMG) a.x_da = act2;
+    else a.norm_w = act2;
     using G = rr_geom<WT>;
     constexpr int BT = G::BT, SB = wfmt<WT>::SCALE_BYTES;
     constexpr bool NSA = true;
@@ -56,7 +65,7 @@ __global__ void __launch_bounds__(RR_NTH) k_matvec_rr(mv_args a) {
     act_regs<R> ar;
     prefetch_activation<WT, PRO, R, RR_NTH>(a, col, ar);
     norm_state ns;
-    if (!(a.ablate & 1)) ns = build_activation<WT, PRO, R, NSA, RR_NTH>(a, col, smem, m, ar);  // timing ablations only
+    if (!(MV_ABLATE(a) & 1)) ns = build_activation<WT, PRO, R, NSA, RR_NTH>(a, col, smem, m, ar);  // timing ablations only
     if (GHIP_STAMPS && stp && tid == 0) stp[10] = __builtin_amdgcn_s_memrealtime();
     // 1) the rest of the ring (loader w, round r -> block tile w + 8r; D rounds in flight per wave),
     //    issued after the image is used, so these loads may sit in a loader-only branch
@@ -67,7 +76,7 @@ __global__ void __launch_bounds__(RR_NTH) k_matvec_rr(mv_args a) {
     // the norm's check (PRO_NORM / PRO_EMBED) with the weights already in flight: off the path to
     // the first weight load (measured: +0.35-0.45 us on qkv with the check in front of the issue);
     // the fallback reloads x and w, so only the ring's D rounds stay live beside it
-    if (!(a.ablate & 1)) finish_activation<WT, PRO, R, NSA, RR_NTH>(a, col, smem, m, ar, ns);
+    if (!(MV_ABLATE(a) & 1)) finish_activation<WT, PRO, R, NSA, RR_NTH>(a, col, smem, m, ar, ns);
     if (GHIP_STAMPS && stp && tid == 0) stp[11] = __builtin_amdgcn_s_memrealtime();
     lds_barrier();
     if (GHIP_STAMPS && stp && tid == 0) stp[1] = __builtin_amdgcn_s_memrealtime();
@@ -90,22 +99,22 @@ __global__ void __launch_bounds__(RR_NTH) k_matvec_rr(mv_args a) {
             float *st = slot_s(r) + (size_t)lane * G::SBP;
             float *sd = slot_d(r) + (size_t)rr * G::SBPD;
             const uint4 q = qb[r % D], sc = sb[r % D];
-            if (a.ablate & 8)  // timing only: consume the loads without the dot products
+            if (MV_ABLATE(a) & 8)  // timing only: consume the loads without the dot products
                 acc += __builtin_bit_cast(float, q.x ^ sc.y);
             else
                 tile_terms<WT>(q, sc, smem, m, wave + RR_NL * r, l, st, sd, wave * BT);
             if (r + D < NR) issue(r + D);
             if (GHIP_STAMPS && stp && lane == 0 && wave == 0 && r < 8) stp[2 + r] = __builtin_amdgcn_s_memrealtime();
             if (GHIP_STAMPS && stp && lane == 0 && wave == RR_NL - 1 && r == NR - 1) stp[15] = __builtin_amdgcn_s_memrealtime();
-        } else if (r > 0 && !(a.ablate & 4)) {
+        } else if (r > 0 && !(MV_ABLATE(a) & 4)) {
             chain(r - 1);
             if (GHIP_STAMPS && stp && lane == 0 && wave == RR_NL && r == 6) stp[12] = __builtin_amdgcn_s_memrealtime();
         }
         lds_barrier();
     }
-    if (loader && (a.ablate & 8) && acc == 1.2345f) a.y[0] = acc;  // keeps the ablated loads live
+    if (loader && (MV_ABLATE(a) & 8) && acc == 1.2345f) a.y[0] = acc;  // keeps the ablated loads live
     if (!loader) {
-        if (!(a.ablate & 4)) chain(NR - 1);
+        if (!(MV_ABLATE(a) & 4)) chain(NR - 1);
         if (GHIP_STAMPS && stp && lane == 0 && wave == RR_NL) stp[13] = __builtin_amdgcn_s_memrealtime();
         const float v = fold8(acc);
         unsigned long long best = 0;
@@ -142,7 +151,9 @@ int launch_rr_t(const mv_args &a, hipStream_t s) {
     const void *fn = deep ? (const void *)k_matvec_rr<WT, PRO, EPI, NR, R, DD> : (const void *)k_matvec_rr<WT, PRO, EPI, NR, R, 64>;
     if (lds > 64 * 1024) GHIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     mv_args la = a;
-    void *args[] = {(void *)&la};
+    const float *act2 = PRO == PRO_IMG ? la.x_da : la.norm_w;
+    void *args[] = {(void *)&la.x, (void *)&act2, (void *)&la.qs, (void *)&la.sc, (void *)&la.n_bt, (void *)&la.nb,
+                    (void *)&la.x_col_stride, (void *)&la};
     GHIP_CHECK(hipLaunchKernel(fn, dim3((unsigned)a.n_rt, a.ncols), dim3(RR_NTH), args, lds, s));
     GHIP_CHECK(hipGetLastError());
     return 0;

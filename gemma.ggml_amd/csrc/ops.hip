@@ -511,8 +511,15 @@ __global__ void __launch_bounds__(ATT_THREADS) k_attn_decode(attn_args a) {
 }
 
 // the per-head form (k_attn_head) lives in attn_impl.h: the fused layer-front kernel runs it too
-__global__ void __launch_bounds__(AH_THREADS) k_attn_head(attn_args a) {
+// Launch front: what the RoPE inputs, the position and the K / V prefetch are
+// addressed with comes as leading scalar parameters (13 dwords, within the user-SGPR preload's reach
+// on gfx950) and replaces the struct's copies; the body is written against one attn_args.
+__global__ void __launch_bounds__(AH_THREADS) k_attn_head(const float *qkv, uint16_t *kc, uint16_t *vc, const float *rope_cur,
+                                                          int H, int Hkv, int hd, int ctx, int dsplit, attn_args a_rest) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    attn_args a = a_rest;
+    a.qkv = qkv; a.kc = kc; a.vc = vc; a.rope_cur = rope_cur;
+    a.H = H; a.Hkv = Hkv; a.hd = hd; a.ctx = ctx; a.dsplit = dsplit;
     const int S = a.dsplit, G = a.H / a.Hkv;
     // one inlined copy of the body (a second call site doubled the kernel's code: measured slower,
     // DESIGN.md §10)
@@ -860,7 +867,8 @@ int launch_attn_decode(const attn_args &a, hipStream_t s) {
         // DESIGN.md §10)
         if (lds > 64 * 1024)
             GHIP_CHECK(hipFuncSetAttribute((const void *)k_attn_head, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_attn_head, dim3(8 * a.H * a.dsplit), dim3(AH_THREADS), lds, s, a);
+        hipLaunchKernelGGL(k_attn_head, dim3(8 * a.H * a.dsplit), dim3(AH_THREADS), lds, s, a.qkv, a.kc, a.vc, a.rope_cur, a.H,
+                           a.Hkv, a.hd, a.ctx, a.dsplit, a);
         GHIP_CHECK(hipGetLastError());
         return 0;
     }

@@ -39,7 +39,7 @@ EXPORTS = ["mul_mat", "hpc_init", "hpc_shutdown", "hpc_register_weight", "hpc_la
            "gemma_engine_create_from_gguf", "gemma_engine_config",
            "gemma_engine_set_sampler", "gemma_engine_sampler", "gemma_test_sample",
            "gemma_engine_verify", "gemma_engine_kv_read", "gemma_lookup_draft", "gemma_engine_generate_lookup",
-           "gemma_test_gemm_skinny", "gemma_hip_mem_live",
+           "gemma_test_gemm_skinny", "gemma_test_matvec", "gemma_hip_mem_live",
            "gemma_engine_batch_open", "gemma_engine_batch_close", "gemma_engine_batch_begin", "gemma_engine_batch_adopt",
            "gemma_engine_batch_release", "gemma_engine_batch_step", "gemma_engine_batch_pos", "gemma_engine_batch_tokens",
            "gemma_engine_batch_last", "gemma_engine_batch_kv_read"]

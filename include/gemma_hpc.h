@@ -267,7 +267,8 @@ int gemma_engine_set_att_o(gemma_engine *e, int on);
    (q|k and v one launch), "kq_abl" (timing ablation, wrong results), "att_mx" (exact prefill attention
    on the f32 matrix cores; 0 = the row form), "att_dsplit" (decode attention workgroups per head:
    1/2/4/8), "ks_small" / "ks_down" (launch-plan K split defaults), "grid_big", and the
-   gemma_engine_time diagnostics "time_hot" / "ablate".  Returns 0, -1 (unknown name or bad value). */
+   gemma_engine_time diagnostics "time_hot" / "ablate" (a non-zero "ablate" needs the -DGHIP_ABLATE=1
+   build of the library: the product kernels do not read it).  Returns 0, -1 (unknown name or bad value). */
 int gemma_engine_set_option(gemma_engine *e, const char *name, int value);
 int gemma_engine_graph_kernels(gemma_engine *e);            /* kernel launches per decode token (captured graph) */
 /* the decode step's layers as ONE persistent launch (opt-in: off by default, GHIP_PERSIST=1 or this
@@ -309,6 +310,31 @@ int gemma_test_gemm_exact(int type, int64_t rows, int64_t K, int64_t T, const vo
  * bit-identical to gemma_test_gemm_exact and mul_mat.  T outside [1, 8]: -1 with hpc_last_error */
 int gemma_test_gemm_skinny(int type, int64_t rows, int64_t K, int64_t T, const void *W, const float *X,
                            const float *resid, float *Y);
+/* per-op test entry: ONE decode matvec launch (either form) on host buffers, every argument of the
+ * launch set by the caller, so that a test can make each of them distinguishable.
+ * pro: 0 x = ncols columns of K floats (x_stride floats apart), 1 the same through rms_norm * norm_w,
+ *      3 x = int32 tokens[n_tok], the row tokens[tok_pos] of emb (ggml rows [emb_rows][K/32] of `type`)
+ *      * emb_scale through rms_norm * norm_w, 4 x = the Q8_0 activation image u32 [K/4] + x_da f32 [K/32]
+ * epi: 0 y = dot, 1 y = dot + resid, 2 y = gelu(W . x) * (W2 . x), 3 y = dot and keys[ncols][grid]
+ * ks:  1 / 2 / 4 / 8 waves per row tile over `grid` workgroups, 9 the round-pipelined form */
+typedef struct gemma_test_matvec_args {
+    int type, ks, pro, epi, ncols, grid;
+    int64_t rows, K;
+    const void *W, *W2;          /* ggml row-major blocks [rows][K/32] */
+    const void *x;
+    int64_t x_stride;
+    const float *x_da, *norm_w;
+    float eps, emb_scale;
+    int n_tok, tok_pos;
+    const void *emb;
+    int64_t emb_rows;
+    float *emb_out;              /* pro 3, optional: the scaled embedding row [K] */
+    const float *resid;          /* epi 1: ncols columns y_stride floats apart */
+    int64_t y_stride;
+    float *y;                    /* ncols columns y_stride floats apart ((ncols - 1) * y_stride + rows floats) */
+    unsigned long long *keys;    /* epi 3 */
+} gemma_test_matvec_args;
+int gemma_test_matvec(const gemma_test_matvec_args *a);
 /* K-quant matvec (Q4_K / Q6_K x Q8_K) timed alone: avg µs per launch over
  * `iters` launches rotating over cold weight copies; *algo_bytes = weights + Q8_K column + y */
 double gemma_kq_time(int type, int64_t rows, int64_t K, int iters, double *algo_bytes);

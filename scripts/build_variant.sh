@@ -7,7 +7,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 PKG=$ROOT/gemma.ggml_amd
 make -s -C $PKG
 mkdir -p $ROOT/ab_libs/$NAME
-FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form=1 -Wno-unused-result"
+FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form=1 -mllvm -amdgpu-kernarg-preload-count=16 -Wno-unused-result"
 OBJS=$(ls $PKG/build/*.o)
 VOBJS=""
 for FILE in ${FILES//,/ }; do

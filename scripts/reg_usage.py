@@ -7,6 +7,7 @@ import sys
 
 PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gemma.ggml_amd")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1",
+         "-mllvm", "-amdgpu-kernarg-preload-count=16",
          "-I../include", "-Icsrc", "-c", "-o", "/tmp/_ru.o", "-Rpass-analysis=kernel-resource-usage"]
 
 
