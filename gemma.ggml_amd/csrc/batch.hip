@@ -1,5 +1,5 @@
 // batch.hip — batched decode (gemma_engine_batch_*, DESIGN.md §5b⁗): the two kernels that let one
-// weight pass serve up to 8 independent sequences.
+// weight pass serve up to 64 independent sequences (8 on the skinny GEMM, more on the MFMA GEMMs).
 //
 //  * k_attn_slots: the decode attention for R rows, row r against the caches of its own slot at its
 //    own position.  It is k_attn_head's body (attn_head_dev, attn_impl.h) instantiated per row: RoPE
@@ -57,8 +57,8 @@ __global__ void __launch_bounds__(256) k_batch_advance(const slot_row *rows, con
 int launch_attn_slots(const attn_args &a, const slot_row *rows, int R, int64_t layer_off, hipStream_t s) {
     if (a.mode != ATTN_PER_HEAD || a.hd % 32 != 0 || a.hd > 256 || a.ctx % 32 != 0 || a.Hkv <= 0 || a.H % a.Hkv != 0 ||
         a.dsplit < 1 || a.hd % (32 * a.dsplit) || 4 * (a.hd / a.dsplit) > AH_THREADS || a.out_act || a.out_q8k ||
-        a.out_gran || !rows || R < 1 || R > GEMM_SKINNY_MAX_T) {
-        set_error("attn_slots: unsupported shape for the per-head form, or a pass outside [1, 8] rows");
+        a.out_gran || !rows || R < 1 || R > ATTN_SLOTS_MAX_R) {
+        set_error("attn_slots: unsupported shape for the per-head form, or a pass outside [1, 64] rows");
         return -1;
     }
     const size_t lds = ((2 * (size_t)a.hd * 2 + 15) & ~(size_t)15) + (size_t)a.ctx * 4 + (size_t)a.ctx * 2 + 16;

@@ -165,40 +165,44 @@ int enqueue_logits_q6k(gemma_engine *e, const uint8_t *x, int ncols, float *y) {
 // unchanged k_advance on its one key (the p >= n_fixed guard, the RoPE row and the epoch bump stay).
 // enqueue_pick_keys is the pick without the advance (the verify pass picks every row, then advances
 // once over the accepted prefix).
-int enqueue_pick_keys(gemma_engine *e, const float *row, const int *pos, unsigned long long *skey,
-                      const unsigned long long **keys, int *n_parts) {
+int enqueue_pick_keys(gemma_engine *e, const float *row, const int *pos, const unsigned long long **keys, int *n_parts) {
     if (!e->sampling) return 0;
-    sample_ws w = e->smp_ws;
-    if (skey) w.key = skey;
-    if (launch_sample(row, e->cfg.n_vocab, e->smp_dev, pos, w, sample_dbg{}, e->stream)) return -1;
+    const sample_ws &w = e->smp_ws;
+    if (launch_sample(row, 0, 1, e->cfg.n_vocab, e->smp_dev, pos, nullptr, w, sample_dbg{}, e->stream)) return -1;
     *keys = w.key;
     *n_parts = 1;
     return 0;
 }
 
 int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *keys, int n_parts) {
-    if (enqueue_pick_keys(e, row, e->seq.pos, nullptr, &keys, &n_parts)) return -1;
+    if (enqueue_pick_keys(e, row, e->seq.pos, &keys, &n_parts)) return -1;
     return launch_advance(keys, n_parts, e->seq.token, e->seq.pos, e->seq.hist, e->cfg.n_ctx, e->seq.nfix, rope_of(e), e->stream);
 }
 
 // The picks of a pass's T rows, none advancing: the verify pass then accepts a prefix, the batch pass
-// advances every row's slot.
+// advances every row's slot.  The launch count does not depend on T: one row-argmax launch (greedy)
+// or the sampler's three (sampling), each with the row in grid.y.
 int pick_buf_alloc(dev_pool &M, pick_buf &b, hipStream_t s) {
-    return M.get_zeroed(&b.keys, (size_t)(GEMM_SKINNY_MAX_T * 256 + GEMM_SKINNY_MAX_T) * 8, s);
+    return M.get_zeroed(&b.keys, (size_t)(PICK_MAX_ROWS * 256 + PICK_MAX_ROWS) * 8, s);
 }
 
-int enqueue_row_picks(gemma_engine *e, const float *LG, int T, const int *const *pos, const pick_buf &b, row_picks *out) {
+int enqueue_row_picks(gemma_engine *e, const float *LG, int T, const int *pos, const slot_row *tab, const pick_buf &b,
+                      row_picks *out) {
     const int64_t V = e->cfg.n_vocab;
-    unsigned long long *skey = b.keys + GEMM_SKINNY_MAX_T * 256;
-    for (int t = 0; t < T; ++t) {
-        const float *row = LG + (size_t)t * V;
-        const unsigned long long *key = nullptr;
-        int parts = 0;
-        if (e->sampling ? enqueue_pick_keys(e, row, pos[t], skey + t, &key, &parts)
-                        : launch_row_argmax(row, V, b.keys + (size_t)t * 256, 256, e->stream))
-            return -1;
+    if (T < 1 || T > PICK_MAX_ROWS) {
+        set_error("row picks: a pass of " + std::to_string(T) + " rows");
+        return -1;
     }
-    *out = e->sampling ? row_picks{skey, 1, 1} : row_picks{b.keys, 256, 256};
+    if (!e->sampling) {
+        if (launch_row_argmax(LG, V, b.keys, 256, e->stream, T, V)) return -1;
+        *out = row_picks{b.keys, 256, 256};
+        return 0;
+    }
+    // every row in its own workspace: the buffer's own (a wide batch's), else the engine's 8
+    sample_ws w = b.ws.hist ? b.ws : e->smp_ws;
+    w.key = b.keys + PICK_MAX_ROWS * 256;
+    if (launch_sample(LG, V, T, V, e->smp_dev, pos, tab, w, sample_dbg{}, e->stream)) return -1;
+    *out = row_picks{w.key, 1, 1};
     return 0;
 }
 

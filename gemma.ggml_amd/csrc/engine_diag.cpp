@@ -325,6 +325,14 @@ extern "C" int gemma_engine_set_option(gemma_engine *e, const char *name, int va
         }
         f = &e->grid_big;
     }
+    if (n == "bt_mfma_min") {
+        if (value <= GEMM_SKINNY_MAX_T || value > GEMMA_BATCH_WIDE_MAX_SLOTS + 1) {
+            set_error("gemma_engine_set_option: bt_mfma_min must be in [9, 65] (65: never the MFMA form)");
+            return -1;
+        }
+        e->bt_mfma_min = value;  // read at the next batch_step; no captured graph holds a batch pass
+        return 0;
+    }
     if (!f) {
         set_error("gemma_engine_set_option: unknown option '" + n + "'");
         return -1;
@@ -362,8 +370,9 @@ extern "C" int gemma_engine_set_sampler(gemma_engine *e, const gemma_sampler *sp
     (void)hipSetDevice(e->device);
     if (on) {
         if (!e->smp_dev) {
-            // made once and kept for the engine's lifetime (the captured graph holds both)
-            if (sample_ws_alloc(e->mem, &e->smp_ws, e->cfg.n_vocab, e->stream)) return -1;
+            // made once and kept for the engine's lifetime (the captured graph holds both): a workspace
+            // per row of a verify pass or a narrow batch pass, the decode step uses the first
+            if (sample_ws_alloc(e->mem, &e->smp_ws, e->cfg.n_vocab, e->stream, GEMM_SKINNY_MAX_T)) return -1;
             if (e->mem.get(&e->smp_dev, sizeof(sampler_params))) {
                 sample_ws_free(e->mem, &e->smp_ws);
                 return -1;
@@ -419,7 +428,9 @@ extern "C" int gemma_test_sample(const float *logits, int rows, int n_vocab, con
     std::vector<int> pm1(positions, positions + rows);
     for (int &v : pm1) v -= 1;  // the kernels read *pos + 1, as k_advance does
     const size_t row_b = (size_t)n_vocab * 4;
-    if (sample_ws_alloc(tmp, &ws, n_vocab, nullptr)) return -1;
+    // the batched launches: up to 64 rows a time, each row in its own workspace
+    const int chunk = std::min(rows, (int)PICK_MAX_ROWS);
+    if (sample_ws_alloc(tmp, &ws, n_vocab, nullptr, chunk)) return -1;
     if (tmp.get(&dp, sizeof(hp)) || tmp.get(&dl, row_b * rows) || tmp.get(&dpos, (size_t)rows * 4) ||
         tmp.get(&dtok, (size_t)rows * 4) || tmp.get(&dnc, (size_t)rows * 4) || tmp.get(&dnk, (size_t)rows * 4) ||
         tmp.get(&dcand, (size_t)rows * SAMPLE_MAX_K * 4))
@@ -427,10 +438,11 @@ extern "C" int gemma_test_sample(const float *logits, int rows, int n_vocab, con
     GHIP_CHECK(hipMemcpy(dp, &hp, sizeof(hp), hipMemcpyHostToDevice));
     GHIP_CHECK(hipMemcpy(dl, logits, row_b * rows, hipMemcpyHostToDevice));
     GHIP_CHECK(hipMemcpy(dpos, pm1.data(), (size_t)rows * 4, hipMemcpyHostToDevice));
-    for (int r = 0; r < rows; ++r) {
+    for (int r = 0; r < rows; r += chunk) {
         sample_dbg d;
         d.token = dtok + r; d.cand = dcand + (size_t)r * SAMPLE_MAX_K; d.n_cand = dnc + r; d.n_kept = dnk + r;
-        if (launch_sample(dl + (size_t)r * n_vocab, n_vocab, dp, dpos + r, ws, d, nullptr)) return -1;
+        if (launch_sample(dl + (size_t)r * n_vocab, n_vocab, std::min(chunk, rows - r), n_vocab, dp, dpos + r, nullptr, ws, d, nullptr))
+            return -1;
     }
     GHIP_CHECK(hipDeviceSynchronize());
     if (tokens) GHIP_CHECK(hipMemcpy(tokens, dtok, (size_t)rows * 4, hipMemcpyDeviceToHost));

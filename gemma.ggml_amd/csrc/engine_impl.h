@@ -7,7 +7,7 @@
 //                       launch's arguments, the all-gathers
 //   engine_prefill.cpp  batched prefill and the ggml executor's entry points
 //   engine_spec.cpp     speculative decoding: the verify pass, lookup drafts, the generate loop
-//   engine_batch.cpp    batched decode: up to 8 sequences (slots), one row each per weight pass
+//   engine_batch.cpp    batched decode: up to 64 sequences (slots), one row each per weight pass
 //   engine_diag.cpp     timing, tuning, plan and option setters, stamps, taps, per-op test hooks
 #pragma once
 
@@ -86,24 +86,33 @@ struct seq_state {
     int host_pos = 0, n_given = 0;          // mirrors of *pos / *nfix
 };
 
-// the pick keys of a pass of up to 8 rows (enqueue_row_picks)
+// the pick keys of a pass of up to 64 rows (enqueue_row_picks)
+static constexpr int PICK_MAX_ROWS = GEMMA_BATCH_WIDE_MAX_SLOTS;
 struct pick_buf {
-    unsigned long long *keys = nullptr;  // device: [8][256] greedy partial keys, then [8] sampler key slots
+    unsigned long long *keys = nullptr;  // device: [64][256] greedy partial keys, then [64] sampler key slots
+    sample_ws ws;                        // a wide batch's own sampler workspaces (else the engine's 8: smp_ws)
 };
 
 // ---- batched decode (engine_batch.cpp, DESIGN.md §5b⁗) ------------------------------------------
+// rows from which a pass of more than 8 rows runs as ONE pass on the exact MFMA GEMMs (option
+// "bt_mfma_min", [9, 65], 65 = never); below it the rows run as groups of up to 8 on the skinny GEMM.
+// The default is the smallest R from which the MFMA form is faster at every larger R: DESIGN.md §5b⁗
+// "Wide passes", table 1 (profiles/batch_wide/pass_time.json, pass_time_fine.json; Gemma-2B Q4_0,
+// µs per pass, groups / MFMA): R = 24 5,888 / 7,256, 28 7,293 / 7,398, 29 7,529 / 7,401,
+// 32 7,848 / 7,440, 48 11,887 / 7,866, 64 16,005 / 8,282.
+static constexpr int BT_MFMA_MIN_DEFAULT = 29;
 struct batch_state {
     bool open = false;
     int n_slots = 0;
-    seq_state slot[GEMMA_BATCH_MAX_SLOTS];
-    int *last = nullptr;       // device: [8] the slots' token words (one copy reads them: batch_last)
+    seq_state slot[GEMMA_BATCH_WIDE_MAX_SLOTS];
+    int *last = nullptr;       // device: [64] the slots' token words (one copy reads them: batch_last_n)
     slot_row *rows = nullptr;  // device: the pass's row -> slot table, rewritten when the active set changes
-    int *row_tok = nullptr;    // device: [8] the token each row of the next pass processes
+    int *row_tok = nullptr;    // device: [64] the token each row of the next pass processes
     pick_buf picks;
     void *stage = nullptr;     // pinned: the row table's source, batch_last's result
-    pf_scratch pf;             // the pass's scratch (8 rows), never reallocated while the batch is open
+    pf_scratch pf;             // the pass's scratch (max(8, n_slots) rows), never reallocated while the batch is open
     bool dirty = true;         // the active set changed since the table was written
-    int n_rows = 0, row_slot[GEMMA_BATCH_MAX_SLOTS] = {};
+    int n_rows = 0, row_slot[GEMMA_BATCH_WIDE_MAX_SLOTS] = {};
 };
 
 struct gemma_engine {
@@ -236,6 +245,7 @@ struct gemma_engine {
     // ---- prefill ----
     pf_scratch pf;  // prefill buffers (lazily sized for the prompt length)
     batch_state bt;
+    int bt_mfma_min = BT_MFMA_MIN_DEFAULT;  // option "bt_mfma_min"
     // ---- verify pass (gemma_engine_verify; allocated at its first call) ----
     struct {
         pick_buf picks;
@@ -372,19 +382,20 @@ int enqueue_step(gemma_engine *e);
 // the greedy argmax keys (n_parts of them) exactly as before
 int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *keys, int n_parts);
 // the pick alone, no advance: with sampling on, the sampler's draw for sequence index *pos + 1 from
-// `row` into the key slot skey (nullptr: the sampler's own), *keys / *n_parts set to that one key;
-// sampling off: nothing is launched and the caller's greedy keys stand
-int enqueue_pick_keys(gemma_engine *e, const float *row, const int *pos, unsigned long long *skey,
-                      const unsigned long long **keys, int *n_parts);
-// The pick of every row of a pass: LG [T][n_vocab], pos[t] the device position word of row t (its
-// token is that sequence's index *pos[t] + 1).  Enqueues the sampler's draws (sampling on) or the row
-// argmaxes into b and returns what the advance kernel takes: row t's n_parts keys at keys + t * stride
+// `row` into the sampler's own key slot, *keys / *n_parts set to that one key; sampling off: nothing
+// is launched and the caller's greedy keys stand
+int enqueue_pick_keys(gemma_engine *e, const float *row, const int *pos, const unsigned long long **keys, int *n_parts);
+// The pick of every row of a pass: LG [T][n_vocab], T <= 64; the device position word of row t is
+// tab[t].pos when the pass has a row table, else pos + t (its token is that sequence's index *pos_t + 1).
+// Enqueues the sampler's draws (sampling on: three launches) or the row argmaxes (one launch) into b
+// and returns what the advance kernel takes: row t's n_parts keys at keys + t * stride
 struct row_picks {
     const unsigned long long *keys = nullptr;
     int n_parts = 0, stride = 0;
 };
 int pick_buf_alloc(dev_pool &M, pick_buf &b, hipStream_t s);  // zeroed on s
-int enqueue_row_picks(gemma_engine *e, const float *LG, int T, const int *const *pos, const pick_buf &b, row_picks *out);
+int enqueue_row_picks(gemma_engine *e, const float *LG, int T, const int *pos, const slot_row *tab, const pick_buf &b,
+                      row_picks *out);
 int tok_prepare(gemma_engine *e);
 int persist_report(gemma_engine *e, const int *w);
 int persist_check(gemma_engine *e);
@@ -395,10 +406,12 @@ int enqueue_logits_q6k(gemma_engine *e, const uint8_t *x, int ncols, float *y);
 // engine_prefill.cpp: the exact batched pass over hist[p0 .. p0+T), T <= 8, with the Q4_0 / Q8_0
 // GEMMs on launch_gemm_skinny and no pick: the logits rows are left in pf.LG [T][n_vocab]
 int enqueue_verify_pass(gemma_engine *e, int T, int p0);
-// the batch's scratch (bt.pf, 8 rows, from bt_mem), and one batched-decode pass: the verify pass over
-// the batch's T rows (tokens bt.row_tok, attention by enqueue_batch_attention), logits left in bt.pf.LG
-int batch_scratch_alloc(gemma_engine *e);
-int enqueue_batch_pass(gemma_engine *e, int T);
-// engine_batch.cpp: layer il's attention step of a batch pass (k_attn_slots over the row table)
-int enqueue_batch_attention(gemma_engine *e, int il, int T);
+// the batch's scratch (bt.pf, `rows` >= 8 rows, from bt_mem), and one batched-decode pass over the
+// batch's rows [r0, r0 + T) (tokens bt.row_tok, attention by enqueue_batch_attention), their logits
+// left in bt.pf.LG.  skinny: T <= 8 on the skinny GEMM (the verify pass's form); else the exact MFMA GEMMs
+int batch_scratch_alloc(gemma_engine *e, int rows);
+int enqueue_batch_pass(gemma_engine *e, int r0, int T, bool skinny);
+// engine_batch.cpp: layer il's attention step for rows [r0, r0 + T) of a batch pass (k_attn_slots
+// over the row table)
+int enqueue_batch_attention(gemma_engine *e, int il, int r0, int T);
 #pragma GCC visibility pop

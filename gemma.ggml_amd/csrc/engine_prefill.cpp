@@ -39,13 +39,31 @@ static int prefill_alloc(gemma_engine *e, int T) { return scratch_alloc(e, e->pf
 //                   into the engine's caches, then the causal attention (prefill_attention)
 //   slots == true   rows are the batch's (engine_batch.cpp): row t is the next token of its own slot,
 //                   the attention is enqueue_batch_attention and the scratch is the batch's (bt.pf)
+//                   r0 > 0: the pass is rows [r0, r0 + T) of the batch (a group of a wide batch): its
+//                   tokens, its part of the row table and a view of the scratch shifted by r0 rows
 struct pass_rows {
     const int *tokens = nullptr;  // device array of the T token ids
     int p0 = 0;
     bool slots = false;
+    int r0 = 0;
 };
-static pass_rows own_rows(const gemma_engine *e, int p0) { return pass_rows{e->seq.hist + p0, p0, false}; }
-static pf_scratch &scratch_of(gemma_engine *e, const pass_rows &rows) { return rows.slots ? e->bt.pf : e->pf; }
+static pass_rows own_rows(const gemma_engine *e, int p0) { return pass_rows{e->seq.hist + p0, p0, false, 0}; }
+// the scratch of a pass, by value: the engine's or the batch's, every row-indexed buffer shifted by
+// the pass's first row (each by its own row stride: scratch_alloc)
+static pf_scratch scratch_of(gemma_engine *e, const pass_rows &rows) {
+    pf_scratch p = rows.slots ? e->bt.pf : e->pf;
+    if (!rows.r0) return p;
+    const gemma_hip_config &c = e->cfg;
+    const size_t r = (size_t)rows.r0;
+    p.T -= rows.r0;
+    p.X += r * c.n_embd; p.SA += r * c.n_embd; p.QKV += r * e->qkv_rows; p.ATT += r * e->qw;
+    p.G += r * c.n_ff; p.U += r * c.n_ff; p.LG += r * c.n_vocab;
+    p.DA += r * p.ldd; p.Q16 += r * e->qw;
+    p.XQ += r * (e->kq ? p.ldq / 256 * 292 : p.ldq); p.XH += r * p.ldq;
+    p.XM += r * (p.ldq / 256) * 16;  // 32 bytes per 256 values
+    if (p.XQ8K) p.XQ8K += r * (c.n_embd / 256) * 292;
+    return p;
+}
 
 static int enqueue_prefill_kq(gemma_engine *e, int T, const pass_rows &rows);
 
@@ -75,7 +93,7 @@ static int launch_attn_exact(const attnp_args &at, bool mx, hipStream_t s) {
 // layer caches (which hold the positions before p0), then the causal attention into pf.ATT (exact:
 // the form *mx_form, resolved at the first layer; else f16 MFMA)
 static int prefill_attention(gemma_engine *e, int il, int T, const pass_rows &rows, bool exact, int *mx_form) {
-    if (rows.slots) return enqueue_batch_attention(e, il, T);
+    if (rows.slots) return enqueue_batch_attention(e, il, rows.r0, T);
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
     auto &p = e->pf;
@@ -98,26 +116,32 @@ static int prefill_attention(gemma_engine *e, int il, int T, const pass_rows &ro
 // p0 .. p0+T-1, the caches hold the positions before p0 (p0 = 0: the whole-prompt prefill).  Every
 // scratch buffer is indexed by the row t of the pass; only the token reads, RoPE, the cache stores and
 // the attention know what a row is (pass_rows).
-// verify (gemma_engine_verify only, T <= 8, exact): the Q4_0 / Q8_0 GEMMs go through
-// launch_gemm_skinny and the pass ends with the logits rows: the caller picks from every row.
-static int enqueue_prefill(gemma_engine *e, int T, const pass_rows &rows, bool exact, float *taps = nullptr, bool verify = false) {
+// Two things a caller chooses apart from the rows (pass_end):
+//   logits_only  the pass ends with the logits rows and the caller picks from every row (the verify
+//                pass, a batch pass); else the last row's pick and the advance follow
+//   skinny       T <= 8, exact: the Q4_0 / Q8_0 GEMMs go through launch_gemm_skinny (the verify pass,
+//                a batch pass or group of up to 8 rows); else launch_gemm_exact / launch_gemm_q
+struct pass_end {
+    bool logits_only = false, skinny = false;
+};
+static int enqueue_prefill(gemma_engine *e, int T, const pass_rows &rows, bool exact, float *taps = nullptr, pass_end end = {}) {
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
     int mx_form = -1;  // the exact attention's form, resolved at the first layer
-    auto &p = scratch_of(e, rows);
+    pf_scratch p = scratch_of(e, rows);
     const int wt = c.wtype;
     const int64_t E = c.n_embd, F = c.n_ff;
     auto gemm = [&](const tiled_mat &m, int epi, const float *resid, float *y, int64_t ldy) {
         gemm_args g;
         set_mat(g, m);
         g.xq = p.XQ; g.xh = p.XH; g.ldq = p.ldq; g.da = p.DA; g.ldd = p.ldd; g.T = T; g.y = y; g.resid = resid; g.ldy = ldy;
-        if (verify) return launch_gemm_skinny(wt, epi, g, s);
+        if (end.skinny) return launch_gemm_skinny(wt, epi, g, s);
         return exact ? launch_gemm_exact(wt, epi, g, s) : launch_gemm_q(wt, epi, g, s);
     };
     auto quant = [&](int mode, const float *x, const float *x2, int64_t K, const float *norm_w) {
         qrow_args a;
         a.x = x; a.x2 = x2; a.ldx = K; a.K = K; a.norm_w = norm_w; a.eps = c.eps;
-        const bool i8img = exact && (verify || gemm_x4_i8());  // the int8-staged exact GEMM and the skinny GEMM read the int8 image
+        const bool i8img = exact && (end.skinny || gemm_x4_i8());  // the int8-staged exact GEMM and the skinny GEMM read the int8 image
         a.q = (!exact || i8img) ? p.XQ : nullptr; a.qh = (exact && !i8img) ? p.XH : nullptr; a.ldq = p.ldq; a.da = p.DA; a.ldd = p.ldd;
         a.gelu_tab = e->gelu_tab; a.gelu_clamp = c.gelu_clamp;
         if (mode == QR_EMBED_NORM) {
@@ -167,7 +191,7 @@ static int enqueue_prefill(gemma_engine *e, int T, const pass_rows &rows, bool e
         if (quant(QR_NORM, p.X, nullptr, E, e->out_norm)) return -1;
         if (gemm(e->embd, EPI_STORE, nullptr, p.LG, c.n_vocab)) return -1;
     }
-    if (verify) return 0;
+    if (end.logits_only) return 0;
     const int p0 = rows.p0;
     // greedy token from the last row; position p0+T-1 -> p0+T, token appended at hist[p0+T] unless
     // that is still a given token (k_advance's p >= n_fixed guard: a pass that ends mid-prompt)
@@ -189,7 +213,7 @@ static int enqueue_prefill_kq(gemma_engine *e, int T, const pass_rows &rows) {
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
     int mx_form = -1;  // the exact attention's form, resolved at the first layer
-    auto &p = scratch_of(e, rows);
+    pf_scratch p = scratch_of(e, rows);
     const int64_t E = c.n_embd, F = c.n_ff;
     const int64_t ldk = p.ldq / 256 * 292;  // Q8_K column stride in XQ
     uint8_t *img = (uint8_t *)p.XQ;
@@ -252,22 +276,24 @@ int enqueue_verify_pass(gemma_engine *e, int T, int p0) {
         return -1;
     }
     if (prefill_alloc(e, GEMM_SKINNY_MAX_T)) return -1;  // sized once: no reallocation between passes
-    return enqueue_prefill(e, T, own_rows(e, p0), true, nullptr, true);
+    return enqueue_prefill(e, T, own_rows(e, p0), true, nullptr, pass_end{true, true});
 }
 
-int batch_scratch_alloc(gemma_engine *e) {
+int batch_scratch_alloc(gemma_engine *e, int rows) {
     e->bt.pf = {};
-    return scratch_alloc(e, e->bt_mem, e->bt.pf, GEMM_SKINNY_MAX_T);
+    return scratch_alloc(e, e->bt_mem, e->bt.pf, std::max(rows, GEMM_SKINNY_MAX_T));
 }
 
-// the verify pass over the batch's rows: tokens from the row-token array, the attention step by
-// k_attn_slots; the caller picks from every row and advances the slots
-int enqueue_batch_pass(gemma_engine *e, int T) {
-    if (T < 1 || T > GEMM_SKINNY_MAX_T || e->bt.pf.T < GEMM_SKINNY_MAX_T) {
-        set_error("gemma_engine_batch_step: a pass of " + std::to_string(T) + " rows, or no batch scratch");
+// a pass over the batch's rows [r0, r0 + T): tokens from the row-token array, the attention step by
+// k_attn_slots, the logits rows left in the scratch; the caller picks from every row and advances
+// the slots.  skinny: the verify pass's GEMMs (T <= 8); else the exact MFMA GEMMs, any T
+int enqueue_batch_pass(gemma_engine *e, int r0, int T, bool skinny) {
+    if (T < 1 || r0 < 0 || r0 + T > e->bt.pf.T || (skinny && T > GEMM_SKINNY_MAX_T)) {
+        set_error("gemma_engine_batch_step: a pass of " + std::to_string(T) + " rows from row " + std::to_string(r0) +
+                  ", or no batch scratch");
         return -1;
     }
-    return enqueue_prefill(e, T, pass_rows{e->bt.row_tok, 0, true}, true, nullptr, true);
+    return enqueue_prefill(e, T, pass_rows{e->bt.row_tok + r0, 0, true, r0}, true, nullptr, pass_end{true, skinny});
 }
 
 // one pass over rows [p0, p0+T) and its results: the last row's logits, all rows' [T][n_vocab], the

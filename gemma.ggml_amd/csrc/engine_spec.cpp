@@ -56,10 +56,8 @@ extern "C" int gemma_engine_verify(gemma_engine *e, const int32_t *draft, int k,
     // 3. a pick from every row, none advances: row i gives the token of sequence index pos + i + 1
     // (the sampler reads each row's position from the device: p0 + i)
     if (e->sampling) GHIP_CHECK(hipMemcpyAsync(d_pos, h_pos, (size_t)T * 4, hipMemcpyHostToDevice, s));
-    const int *row_pos[GEMM_SKINNY_MAX_T];
-    for (int i = 0; i < T; ++i) row_pos[i] = d_pos + i;
     row_picks pk;
-    if (enqueue_row_picks(e, e->pf.LG, T, row_pos, e->vf.picks, &pk)) return -1;
+    if (enqueue_row_picks(e, e->pf.LG, T, d_pos, nullptr, e->vf.picks, &pk)) return -1;
     // 4. accept + advance
     verify_args v;
     v.keys = pk.keys; v.n_parts = pk.n_parts; v.key_stride = pk.stride;

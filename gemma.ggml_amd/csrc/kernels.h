@@ -275,7 +275,10 @@ int launch_attn_mx(const attnp_args &a, hipStream_t s);
 // (slot, device), thread-safe: slots LDS_SLOT_*
 enum { LDS_SLOT_ATTN_MX = 0, LDS_SLOT_GELU_LDS = 1, LDS_SLOTS = 2 };
 int allow_full_lds(const void *fn, int slot);
-int launch_row_argmax(const float *row, int64_t n, unsigned long long *keys, int parts, hipStream_t s);
+// the `parts` partial argmax keys of each of `rows` rows (ld floats apart) in ONE launch, grid (parts,
+// rows): row r's keys at keys + r * parts
+int launch_row_argmax(const float *row, int64_t n, unsigned long long *keys, int parts, hipStream_t s, int rows = 1,
+                      int64_t ld = 0);
 
 // ---- weights (ops.hip) ------------------------------------------------------------------------
 // ggml row-major blocks (host layout) already on device -> tiled layout
@@ -457,7 +460,8 @@ struct slot_row {
 };
 // k_attn_slots: the decode attention (attn_head_dev, per-head form) for R rows, each against its own
 // slot's caches at its own position.  a: the shared fields (geometry, tables, dsplit); qkv, kc, vc,
-// rope_cur and out come from rows[r], the caches offset by layer_off elements.
+// rope_cur and out come from rows[r], the caches offset by layer_off elements.  R <= 64.
+constexpr int ATTN_SLOTS_MAX_R = 64;
 int launch_attn_slots(const attn_args &a, const slot_row *rows, int R, int64_t layer_off, hipStream_t s);
 // k_batch_advance: per row, reduce the n_parts pick keys at keys + r * key_stride, then k_advance for
 // the row's slot: p = pos + 1, hist[p] = pick if p >= nfix, pos = p, the RoPE row of p, and the next
@@ -474,21 +478,26 @@ struct sampler_params {             // lives in device memory: a change is a str
     int pad = 0;
     unsigned long long seed = 0;
 };
-struct sample_ws {  // scratch of one sampler (sample_ws_alloc); the tail launch leaves hist and cur zero
-    unsigned *hist = nullptr, *cur = nullptr;  // key histogram [4096]; list cursors [2]
-    unsigned long long *list_a = nullptr, *list_b = nullptr;  // [SAMPLE_MAX_K], [cap_b] (key << 32 | ~index)
+constexpr int SAMPLE_WS_HIST = 4096 + 16;  // words of one row's histogram and list cursors
+struct sample_ws {  // scratch of `rows` samplers, one per row of a launch (sample_ws_alloc); the tail
+                    // launch leaves every row's hist and cur zero
+    int rows = 0;
+    unsigned *hist = nullptr, *cur = nullptr;  // [rows][SAMPLE_WS_HIST]: key histogram [4096], list cursors [2] (cur = hist + 4096)
+    unsigned long long *list_a = nullptr, *list_b = nullptr;  // [rows][SAMPLE_MAX_K], [rows][cap_b] (key << 32 | ~index)
     int64_t cap_b = 0;                                        // = n_vocab
-    unsigned long long *key = nullptr;  // the drawn token as one argmax key (launch_advance(key, 1, ...))
+    unsigned long long *key = nullptr;  // [rows] the drawn tokens, each one argmax key (launch_advance(key, 1, ...))
 };
-struct sample_dbg {  // optional outputs (tests): the token, cand[SAMPLE_MAX_K] (-1 past K), K, m
+struct sample_dbg {  // optional outputs (tests), per row: token [rows], cand [rows][SAMPLE_MAX_K] (-1 past K), K, m [rows]
     int *token = nullptr, *cand = nullptr, *n_cand = nullptr, *n_kept = nullptr;
 };
-int sample_ws_alloc(dev_pool &mem, sample_ws *w, int64_t n_vocab, hipStream_t s);  // all four buffers, or none
+int sample_ws_alloc(dev_pool &mem, sample_ws *w, int64_t n_vocab, hipStream_t s, int rows = 1);  // all four buffers, or none
 void sample_ws_free(dev_pool &mem, sample_ws *w);
-// three launches: the token for sequence index *pos + 1 from row[0 .. n) into *w.key; prm and pos are
-// device pointers read by the kernels; the geometry depends on n only
-int launch_sample(const float *row, int64_t n, const sampler_params *prm, const int *pos, const sample_ws &w,
-                  const sample_dbg &dbg, hipStream_t s);
+// The rows of a pass, three launches in all (grid.y = row): row r's token for sequence index
+// *pos_r + 1 from lg[r * ld .. + n) into w.key[r], in row r's own workspace.  pos_r is tab[r].pos when
+// a row table is given, else pos + r.  prm, pos and tab are device pointers read by the kernels; the
+// geometry depends on n and rows only
+int launch_sample(const float *lg, int64_t ld, int rows, int64_t n, const sampler_params *prm, const int *pos,
+                  const slot_row *tab, const sample_ws &w, const sample_dbg &dbg, hipStream_t s);
 
 // ---- generic ggml-op kernels used by the C-ABI and the ggml-compatible executor ----------------
 int launch_mul_mat_f16(const uint16_t *src0, int64_t nb01_elems, int64_t ne01, const uint16_t *src1,

@@ -1156,7 +1156,10 @@ __global__ void __launch_bounds__(256) k_attn_prefill(attnp_args a) {
 
 // argmax over one logits row -> per-workgroup partial keys (ordered float, ~index), reduced by
 // k_advance exactly as in the decode step (first max wins, src/gemma_model.cpp:538-543)
-__global__ void __launch_bounds__(256) k_row_argmax(const float *row, int64_t n, unsigned long long *keys) {
+// grid (parts, rows): row blockIdx.y of lg (ld floats apart) -> its `parts` partial keys at keys + row * parts
+__global__ void __launch_bounds__(256) k_row_argmax(const float *lg, int64_t ld, int64_t n, unsigned long long *keys) {
+    const float *row = lg + (int64_t)blockIdx.y * ld;
+    keys += (int64_t)blockIdx.y * gridDim.x;
     unsigned long long best = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const unsigned long long key = argmax_key(row[i], i);
@@ -1269,8 +1272,8 @@ int launch_gemm_exact(int wtype, int epi, const gemm_args &g, hipStream_t s) {
     return 0;
 }
 
-int launch_row_argmax(const float *row, int64_t n, unsigned long long *keys, int parts, hipStream_t s) {
-    hipLaunchKernelGGL(k_row_argmax, dim3(parts), dim3(256), 0, s, row, n, keys);
+int launch_row_argmax(const float *row, int64_t n, unsigned long long *keys, int parts, hipStream_t s, int rows, int64_t ld) {
+    hipLaunchKernelGGL(k_row_argmax, dim3(parts, rows), dim3(256), 0, s, row, ld, n, keys);
     GHIP_CHECK(hipGetLastError());
     return 0;
 }

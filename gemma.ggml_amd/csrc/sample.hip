@@ -46,9 +46,13 @@ __device__ __forceinline__ int sample_k(const sampler_params &p, int64_t n) {
     return (int)(n < (int64_t)k ? n : (int64_t)k);
 }
 
-__global__ void __launch_bounds__(SM_TH) k_sample_hist(const float *row, int64_t n, unsigned *ghist) {
+// All three kernels: grid.y = the row of the pass.  A row's logits are lg + row * ld and its
+// workspace the row-th of each sample_ws array; the offsets are wave-uniform (scalar registers).
+__global__ void __launch_bounds__(SM_TH) k_sample_hist(const float *lg, int64_t ld, int64_t n, unsigned *ghist) {
     __shared__ unsigned h[SM_BINS];
     const int tid = threadIdx.x;
+    const float *row = lg + (int64_t)blockIdx.y * ld;
+    ghist += (int64_t)blockIdx.y * SAMPLE_WS_HIST;
     for (int i = tid; i < SM_BINS; i += SM_TH) h[i] = 0;
     __syncthreads();
     for (int64_t base = (int64_t)blockIdx.x * SM_CHUNK; base < n; base += (int64_t)gridDim.x * SM_CHUNK) {
@@ -65,12 +69,18 @@ __global__ void __launch_bounds__(SM_TH) k_sample_hist(const float *row, int64_t
     }
 }
 
-__global__ void __launch_bounds__(SM_TH) k_sample_compact(const float *row, int64_t n, const sampler_params *prm,
+__global__ void __launch_bounds__(SM_TH) k_sample_compact(const float *lg, int64_t ld, int64_t n, const sampler_params *prm,
                                                           const unsigned *ghist, unsigned *cur, unsigned long long *list_a,
                                                           unsigned long long *list_b, int64_t cap_b) {
     __shared__ unsigned wtot[SM_TH / 64];
     __shared__ unsigned s_bin, s_cnt[2], s_base[2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t r = blockIdx.y;
+    const float *row = lg + r * ld;
+    ghist += r * SAMPLE_WS_HIST;
+    cur += r * SAMPLE_WS_HIST;
+    list_a += r * SAMPLE_MAX_K;
+    list_b += r * cap_b;
     const unsigned K = (unsigned)sample_k(*prm, n);
     // b*: the bin with (entries in bins above it) < K <= (those + its own); thread t owns bins 16t .. 16t+15
     unsigned loc[16], sum = 0;
@@ -144,10 +154,23 @@ __device__ __forceinline__ uint64_t splitmix64_mix(uint64_t z) {
     return z ^ (z >> 31);
 }
 
-__global__ void __launch_bounds__(SM_TAIL) k_sample_tail(const sampler_params *prm, const int *pos, int64_t n, unsigned *ghist,
-                                                         unsigned *cur, const unsigned long long *list_a,
+__global__ void __launch_bounds__(SM_TAIL) k_sample_tail(const sampler_params *prm, const int *pos, const slot_row *tab, int64_t n,
+                                                         unsigned *ghist, unsigned *cur, const unsigned long long *list_a,
                                                          const unsigned long long *list_b, int64_t cap_b,
                                                          unsigned long long *key_out, sample_dbg dbg) {
+    {  // this row's position word, workspace, key slot and debug outputs
+        const int64_t r = blockIdx.y;
+        pos = tab ? tab[r].pos : pos + r;
+        ghist += r * SAMPLE_WS_HIST;
+        cur += r * SAMPLE_WS_HIST;
+        list_a += r * SAMPLE_MAX_K;
+        list_b += r * cap_b;
+        key_out += r;
+        if (dbg.token) dbg.token += r;
+        if (dbg.n_cand) dbg.n_cand += r;
+        if (dbg.n_kept) dbg.n_kept += r;
+        if (dbg.cand) dbg.cand += r * SAMPLE_MAX_K;
+    }
     __shared__ unsigned long long ks[SM_CAP];
     __shared__ double cs[SM_TAIL];
     __shared__ double wtot[SM_TAIL / 64];
@@ -292,19 +315,21 @@ __global__ void __launch_bounds__(SM_TAIL) k_sample_tail(const sampler_params *p
 
 }  // namespace
 
-int sample_ws_alloc(dev_pool &mem, sample_ws *w, int64_t n_vocab, hipStream_t s) {
-    if (n_vocab <= 0 || n_vocab > 0x7FFFFFFFll) {
-        set_error("sampler: n_vocab out of range");
+int sample_ws_alloc(dev_pool &mem, sample_ws *w, int64_t n_vocab, hipStream_t s, int rows) {
+    if (n_vocab <= 0 || n_vocab > 0x7FFFFFFFll || rows < 1) {
+        set_error("sampler: n_vocab or rows out of range");
         return -1;
     }
     *w = sample_ws{};
     w->cap_b = n_vocab;
-    if (mem.get_zeroed(&w->hist, (size_t)(SM_BINS + 16) * 4, s) || mem.get(&w->list_a, (size_t)SAMPLE_MAX_K * 8) ||
-        mem.get(&w->list_b, (size_t)n_vocab * 8) || mem.get_zeroed(&w->key, 8, s)) {
+    const size_t R = (size_t)rows;
+    if (mem.get_zeroed(&w->hist, R * SAMPLE_WS_HIST * 4, s) || mem.get(&w->list_a, R * SAMPLE_MAX_K * 8) ||
+        mem.get(&w->list_b, R * (size_t)n_vocab * 8) || mem.get_zeroed(&w->key, R * 8, s)) {
         sample_ws_free(mem, w);
         return -1;
     }
     w->cur = w->hist + SM_BINS;
+    w->rows = rows;
     return 0;
 }
 
@@ -316,17 +341,17 @@ void sample_ws_free(dev_pool &mem, sample_ws *w) {
     *w = sample_ws{};
 }
 
-int launch_sample(const float *row, int64_t n, const sampler_params *prm, const int *pos, const sample_ws &w,
-                  const sample_dbg &dbg, hipStream_t s) {
-    if (!w.hist || n <= 0 || n > w.cap_b) {
-        set_error("sampler: scratch not sized for this row");
+int launch_sample(const float *lg, int64_t ld, int rows, int64_t n, const sampler_params *prm, const int *pos,
+                  const slot_row *tab, const sample_ws &w, const sample_dbg &dbg, hipStream_t s) {
+    if (!w.hist || n <= 0 || n > w.cap_b || rows < 1 || rows > w.rows || (!pos && !tab)) {
+        set_error("sampler: scratch not sized for these rows");
         return -1;
     }
     const int grid = (int)std::min<int64_t>((n + SM_CHUNK - 1) / SM_CHUNK, SM_GRID_MAX);
-    hipLaunchKernelGGL(k_sample_hist, dim3(grid), dim3(SM_TH), 0, s, row, n, w.hist);
-    hipLaunchKernelGGL(k_sample_compact, dim3(grid), dim3(SM_TH), 0, s, row, n, prm, (const unsigned *)w.hist, w.cur, w.list_a,
-                       w.list_b, w.cap_b);
-    hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(SM_TAIL), 0, s, prm, pos, n, w.hist, w.cur,
+    hipLaunchKernelGGL(k_sample_hist, dim3(grid, rows), dim3(SM_TH), 0, s, lg, ld, n, w.hist);
+    hipLaunchKernelGGL(k_sample_compact, dim3(grid, rows), dim3(SM_TH), 0, s, lg, ld, n, prm, (const unsigned *)w.hist, w.cur,
+                       w.list_a, w.list_b, w.cap_b);
+    hipLaunchKernelGGL(k_sample_tail, dim3(1, rows), dim3(SM_TAIL), 0, s, prm, pos, tab, n, w.hist, w.cur,
                        (const unsigned long long *)w.list_a, (const unsigned long long *)w.list_b, w.cap_b, w.key, dbg);
     GHIP_CHECK(hipGetLastError());
     return 0;

@@ -42,7 +42,8 @@ EXPORTS = ["mul_mat", "hpc_init", "hpc_shutdown", "hpc_register_weight", "hpc_la
            "gemma_test_gemm_skinny", "gemma_test_matvec", "gemma_hip_mem_live",
            "gemma_engine_batch_open", "gemma_engine_batch_close", "gemma_engine_batch_begin", "gemma_engine_batch_adopt",
            "gemma_engine_batch_release", "gemma_engine_batch_step", "gemma_engine_batch_pos", "gemma_engine_batch_tokens",
-           "gemma_engine_batch_last", "gemma_engine_batch_kv_read"]
+           "gemma_engine_batch_last", "gemma_engine_batch_kv_read", "gemma_engine_batch_open_wide",
+           "gemma_engine_batch_last_n"]
 
 
 def build():
@@ -68,6 +69,7 @@ class GemmaSampler(C.Structure):
 SAMPLE_MAX_K = 1024  # candidates at most (top_k == 0 means this many)
 VERIFY_MAX_DRAFT = 7  # include/gemma_hpc.h GEMMA_VERIFY_MAX_DRAFT
 BATCH_MAX_SLOTS = 8   # include/gemma_hpc.h GEMMA_BATCH_MAX_SLOTS
+BATCH_WIDE_MAX_SLOTS = 64  # include/gemma_hpc.h GEMMA_BATCH_WIDE_MAX_SLOTS
 
 
 class SpecStats(C.Structure):
@@ -199,7 +201,8 @@ def lib():
     L.gemma_test_gemm_skinny.argtypes = [C.c_int, i64, i64, i64, vp, vp, vp, vp]
     for fn, at in (("open", [C.c_int]), ("close", []), ("begin", [C.c_int, vp, C.c_int]), ("adopt", [C.c_int]),
                    ("release", [C.c_int]), ("step", [C.c_int, vp]), ("pos", [C.c_int]), ("tokens", [C.c_int, vp, C.c_int]),
-                   ("last", [vp]), ("kv_read", [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp])):
+                   ("last", [vp]), ("kv_read", [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+                   ("open_wide", [C.c_int]), ("last_n", [vp, C.c_int])):
         getattr(L, "gemma_engine_batch_" + fn).restype = C.c_int
         getattr(L, "gemma_engine_batch_" + fn).argtypes = [vp] + at
     # GGUF reader (include/ggml.h)
@@ -396,6 +399,11 @@ class Engine:
         """Open the engine's batch with n_slots (1 .. BATCH_MAX_SLOTS) sequence slots."""
         self._chk(self.L.gemma_engine_batch_open(self.h, int(n_slots)), "batch_open")
 
+    def batch_open_wide(self, n_slots):
+        """Open the engine's batch with n_slots (1 .. BATCH_WIDE_MAX_SLOTS) sequence slots: passes of
+        more than 8 rows run on the exact MFMA GEMMs (option "bt_mfma_min"), the same bits."""
+        self._chk(self.L.gemma_engine_batch_open_wide(self.h, int(n_slots)), "batch_open_wide")
+
     def batch_close(self):
         self._chk(self.L.gemma_engine_batch_close(self.h), "batch_close")
 
@@ -416,7 +424,7 @@ class Engine:
         [n][R][n_vocab]."""
         lg = None
         if want_logits:
-            R = sum(1 for t in self.batch_last() if t >= 0)
+            R = sum(1 for t in self.batch_last_n() if t >= 0)
             lg = np.zeros((max(int(n), 0), R, self.cfg.n_vocab), dtype=np.float32)
         self._chk(self.L.gemma_engine_batch_step(self.h, int(n), _p(lg) if want_logits else None), "batch_step")
         return lg
@@ -438,6 +446,15 @@ class Engine:
         out = np.zeros(BATCH_MAX_SLOTS, dtype=np.int32)
         self._chk(self.L.gemma_engine_batch_last(self.h, _p(out)), "batch_last")
         return out
+
+    def batch_last_n(self):
+        """the pending tokens of the batch's slots [0, n_slots) in one transfer, -1 for inactive slots
+        (any batch, up to BATCH_WIDE_MAX_SLOTS slots)"""
+        out = np.zeros(BATCH_WIDE_MAX_SLOTS, dtype=np.int32)
+        n = self.L.gemma_engine_batch_last_n(self.h, _p(out), len(out))
+        if n < 0:
+            raise RuntimeError("batch_last_n failed: " + last_error())
+        return out[:n]
 
     def batch_kv_read(self, slot, layer, p0, n):
         """kv_read of a slot's caches: (k [n][kvw], v [n][kvw]) f16 bits"""

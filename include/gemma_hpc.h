@@ -215,8 +215,18 @@ int gemma_engine_kv_read(gemma_engine *e, int layer, int p0, int n, uint16_t *k_
  *            active slot with pos + n >= n_ctx (then no slot advances).
  *   pos      processed positions of the slot (-1: inactive).   tokens: the slot's sequence so far, the
  *            pending token included (returns the count).   last: the 8 slots' pending tokens in one
- *            transfer, -1 for inactive slots.   kv_read: gemma_engine_kv_read of the slot's caches. */
+ *            transfer, -1 for inactive slots.   kv_read: gemma_engine_kv_read of the slot's caches.
+ * Wide batches: up to GEMMA_BATCH_WIDE_MAX_SLOTS slots.
+ *   open_wide  open with n_slots in [1, 64] and the same refusals; every other call works unchanged on
+ *            a wide batch (the slot range is [0, n_slots)).  A pass of R <= 8 rows is the pass above; a
+ *            pass of more rows runs as one pass on the exact MFMA GEMMs of the batched prefill when
+ *            R >= bt_mfma_min (gemma_engine_set_option(e, "bt_mfma_min", v), v in [9, 65], 65 = never),
+ *            else as consecutive groups of up to 8 rows.  The same bits in every form.
+ *   last_n   the pending tokens of slots [0, n_slots) into out[0 .. n_slots), -1 for inactive slots;
+ *            returns n_slots, -1 when cap < n_slots.  gemma_engine_batch_last serves batches of up to 8
+ *            slots only (it returns -1 on a wider one). */
 #define GEMMA_BATCH_MAX_SLOTS 8
+#define GEMMA_BATCH_WIDE_MAX_SLOTS 64
 int gemma_engine_batch_open(gemma_engine *e, int n_slots);
 int gemma_engine_batch_close(gemma_engine *e);
 int gemma_engine_batch_begin(gemma_engine *e, int slot, const int32_t *tokens, int n);
@@ -227,6 +237,8 @@ int gemma_engine_batch_pos(gemma_engine *e, int slot);
 int gemma_engine_batch_tokens(gemma_engine *e, int slot, int32_t *out, int cap);
 int gemma_engine_batch_last(gemma_engine *e, int32_t *out8);
 int gemma_engine_batch_kv_read(gemma_engine *e, int slot, int layer, int p0, int n, uint16_t *k_rows, uint16_t *v_rows);
+int gemma_engine_batch_open_wide(gemma_engine *e, int n_slots);
+int gemma_engine_batch_last_n(gemma_engine *e, int32_t *out, int cap);
 /* Prompt-lookup draft for the sequence seq[0..n) (pure host function, no GPU): for g = min(ngram_max,
  * n - 1) down to 1, the largest s < n - g with seq[s..s+g) == seq[n-g..n); the first g with a match
  * wins and the draft is seq[s+g .. min(s+g+k, n)).  Returns its length (0: no g matches), -1 on
@@ -266,7 +278,8 @@ int gemma_engine_set_att_o(gemma_engine *e, int on);
    environment: "kq_fuse" (K-quant Q8_K INIT plan 0..6), "kq_dual" (gate+up one launch), "kq_pair"
    (q|k and v one launch), "kq_abl" (timing ablation, wrong results), "att_mx" (exact prefill attention
    on the f32 matrix cores; 0 = the row form), "att_dsplit" (decode attention workgroups per head:
-   1/2/4/8), "ks_small" / "ks_down" (launch-plan K split defaults), "grid_big", and the
+   1/2/4/8), "ks_small" / "ks_down" (launch-plan K split defaults), "grid_big", "bt_mfma_min" (rows
+   from which a wide batch pass runs as one MFMA pass, [9, 65], 65 = never; default 29, measured), and the
    gemma_engine_time diagnostics "time_hot" / "ablate" (a non-zero "ablate" needs the -DGHIP_ABLATE=1
    build of the library: the product kernels do not read it).  Returns 0, -1 (unknown name or bad value). */
 int gemma_engine_set_option(gemma_engine *e, const char *name, int value);
