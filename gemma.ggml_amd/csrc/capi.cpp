@@ -457,7 +457,9 @@ extern "C" int gemma_test_gemm_skinny(int type, int64_t rows, int64_t K, int64_t
 
 // ---- per-op test entry for the decode matvec (tests/test_gpu_kernarg_args.py) ---------------------
 // One launch_matvec with every field of its mv_args supplied by the caller (include/gemma_hpc.h).
-extern "C" int gemma_test_matvec(const gemma_test_matvec_args *t) {
+// gelu_clamp, and img_act u32 [ceil(rows / 128) * 32] + img_da f32 [rows / 32] (the Q8_0 image of y that
+// epi 2 also writes, ncols 1; the image holds whole groups of 4 blocks), are gemma_test_matvec_tail's additions
+static int test_matvec(const gemma_test_matvec_args *t, int gelu_clamp, uint32_t *img_act, float *img_da) {
     set_error("");
     auto bad = [](const char *why) {
         set_error(std::string("gemma_test_matvec: ") + why);
@@ -475,6 +477,8 @@ extern "C" int gemma_test_matvec(const gemma_test_matvec_args *t) {
     if (epi == EPI_ADD && !t->resid) return bad("resid missing");
     if (epi == EPI_GELU_MUL && !t->W2) return bad("W2 missing");
     if (epi == EPI_ARGMAX && !t->keys) return bad("keys missing");
+    if ((img_act || img_da) && (!img_act || !img_da || epi != EPI_GELU_MUL || t->ks != 1 || t->ncols != 1 || t->rows % 32))
+        return bad("the image of y needs epi 2, ks 1, one column and whole 32-row blocks");
     if (pro == PRO_EMBED) {
         if (!t->emb || t->emb_rows <= 0 || t->n_tok <= 0 || t->tok_pos < 0 || t->tok_pos >= t->n_tok) return bad("bad embedding source");
         const int32_t tok = ((const int32_t *)t->x)[t->tok_pos];
@@ -489,6 +493,8 @@ extern "C" int gemma_test_matvec(const gemma_test_matvec_args *t) {
     float *d_y = nullptr, *d_r = nullptr, *d_nw = nullptr, *d_da = nullptr, *d_eo = nullptr;
     int *d_pos = nullptr;
     uint16_t *d_gelu = nullptr;
+    uint32_t *d_ia = nullptr;
+    float *d_ida = nullptr;
     unsigned long long *d_keys = nullptr;
     const size_t n_keys = (size_t)t->grid * t->ncols;
     const int64_t max_rows = std::max(rows, pro == PRO_EMBED ? t->emb_rows : (int64_t)0);
@@ -496,6 +502,11 @@ extern "C" int gemma_test_matvec(const gemma_test_matvec_args *t) {
         tmp.get(&d_r, y_floats * 4) || tmp.get(&d_nw, (size_t)K * 4) || tmp.get(&d_da, (size_t)nb * 4) ||
         tmp.get(&d_eo, (size_t)K * 4) || tmp.get(&d_pos, 4) || tmp.get(&d_gelu, 65536 * 2) || tmp.get(&d_keys, n_keys * 8))
         return -1;
+    const size_t ia_bytes = (size_t)((rows + 127) / 128) * 128;
+    if (img_act) {
+        if (tmp.get(&d_ia, ia_bytes) || tmp.get(&d_ida, (size_t)rows / 32 * 4)) return -1;
+        GHIP_CHECK(hipMemset(d_ia, 0, ia_bytes));
+    }
     tiled_mat m, m2, me;
     auto tiled = [&](tiled_mat *out, const void *src, int64_t n_rows) -> int {
         GHIP_CHECK(hipMemcpy(d_rows, src, (size_t)(row_bytes * n_rows), hipMemcpyHostToDevice));
@@ -535,7 +546,8 @@ extern "C" int gemma_test_matvec(const gemma_test_matvec_args *t) {
         std::vector<uint16_t> exp_t, gelu_t;
         build_f16_tables(exp_t, gelu_t);
         GHIP_CHECK(hipMemcpy(d_gelu, gelu_t.data(), 65536 * 2, hipMemcpyHostToDevice));
-        a.qs2 = m2.qs; a.sc2 = m2.sc; a.gelu_tab = d_gelu;
+        a.qs2 = m2.qs; a.sc2 = m2.sc; a.gelu_tab = d_gelu; a.gelu_clamp = gelu_clamp;
+        a.out_act = d_ia; a.out_da = d_ida;
     }
     if (epi == EPI_ARGMAX) a.argmax_key = d_keys;
     if (launch_matvec(t->type, t->ks, pro, epi, a, t->grid, nullptr)) return -1;
@@ -543,7 +555,19 @@ extern "C" int gemma_test_matvec(const gemma_test_matvec_args *t) {
     GHIP_CHECK(hipMemcpy(t->y, d_y, y_floats * 4, hipMemcpyDeviceToHost));
     if (epi == EPI_ARGMAX) GHIP_CHECK(hipMemcpy(t->keys, d_keys, n_keys * 8, hipMemcpyDeviceToHost));
     if (pro == PRO_EMBED && t->emb_out) GHIP_CHECK(hipMemcpy(t->emb_out, d_eo, (size_t)K * 4, hipMemcpyDeviceToHost));
+    if (img_act) {
+        GHIP_CHECK(hipMemcpy(img_act, d_ia, ia_bytes, hipMemcpyDeviceToHost));
+        GHIP_CHECK(hipMemcpy(img_da, d_ida, (size_t)rows / 32 * 4, hipMemcpyDeviceToHost));
+    }
     return 0;
+}
+
+extern "C" int gemma_test_matvec(const gemma_test_matvec_args *t) { return test_matvec(t, 0, nullptr, nullptr); }
+
+// the launch tails (tests/test_gpu_matvec_tails.py): the same launch with the GELU clamp selectable and
+// the Q8_0 image of y read back
+extern "C" int gemma_test_matvec_tail(const gemma_test_matvec_args *t, int gelu_clamp, uint32_t *img_act, float *img_da) {
+    return test_matvec(t, gelu_clamp, img_act, img_da);
 }
 
 // ---- K-quant matvec timing (bench.py): random bytes of the right shape, `iters` launches timed

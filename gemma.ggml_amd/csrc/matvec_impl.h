@@ -561,6 +561,21 @@ __device__ __forceinline__ void epilogue(const mv_args &a, int col, int64_t row,
     }
 }
 
+// EPI_ADD off the launch tail: the residual has existed since the kernel started, so
+// the lane that will store row `row` loads it right behind the activation loads (never in front of
+// them: the launch front) and keeps it in a register; the store at the end then waits for no memory.
+// `mine`: this lane stores the row.  Lanes that will not store read nothing.
+__device__ __forceinline__ float resid_early(const mv_args &a, int col, int64_t row, bool mine) {
+    float held = 0.0f;
+    if (mine && row < a.rows) held = a.resid[(int64_t)col * a.y_col_stride + row];
+    return held;
+}
+
+__device__ __forceinline__ void epilogue_held(const mv_args &a, int col, int64_t row, float v, float held) {
+    if (row >= a.rows) return;
+    a.y[(int64_t)col * a.y_col_stride + row] = v + held;  // ggml_add of the residual (EPI_ADD)
+}
+
 // ---- the tile stream: a wave's sequence of (matrix, row tile, block tile) items ----------------
 // item k -> row tile rt0 + (k / per_rt) * rstride; within it matrix (k % per_rt) / nbt and block
 // tile bt0 + (k % per_rt) % nbt.  Cursors advance incrementally (no divisions in the loop).
@@ -832,6 +847,11 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
     // 0) this thread's activation values (older than the weight loads -> waited for by count)
     act_regs<R> ar;
     prefetch_activation<WT, PRO, R, NTH>(a, col, ar);
+    // K-split EPI_ADD: the carrier's (wave 0) storing lanes take the first row tile's residual behind
+    // the activation loads and in front of the ring, so it lands before the weights and the ring's
+    // counted waits never stand behind it
+    float held = 0.0f;
+    if constexpr (KS > 1 && EPI == EPI_ADD) held = resid_early(a, col, rt0 * 8 + rr, wave == 0 && l == 0);
     uint4 scl_g = make_uint4(0, 0, 0, 0), scl_u = scl_g;
     if constexpr (SCL) {
         const int64_t rts = n_items ? rt0 : 0;
@@ -858,9 +878,6 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
         // weights are read once per token by one CU: non-temporal loads (MI355X_MICROARCH nt-weights:
         // issued -> landed -18 %, decode layer -5..10 %)
         qd = ld_nt16(qt + q_off);
-        if constexpr (SCL) {
-            (void)st; (void)sd;
-        } else {
 #if GHIP_NOSCALE  // timing only: no scale loads (wrong results)
         sd = make_uint4(0x3c003c00u, 0x3c003c00u, 0x3c003c00u, 0x3c003c00u);
         (void)st;
@@ -872,7 +889,6 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
             sd = make_uint4(v.x, v.y, 0, 0);
         }
 #endif
-        }
         ++issued;
         if (issued < n_items) {
             if (NM == 2) {  // gate and up of one block tile back to back (shared act operands)
@@ -895,8 +911,20 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
     // UPRE ring slots go out before the prologue, the rest after it: a full ring from every wave at
     // once oversubscribes the CU's load queue and would hold the prologue behind the issue
     constexpr int UP = GHIP_UPRE < U ? GHIP_UPRE : U;
+    // SCL runs its one row tile matrix-major at fixed positions: item i is block tile i % NB of gate
+    // (i < NB) or up (launch_t: n_bt == NB).  A wave without a row tile re-reads one tile (L2 hits).
+    constexpr int NB = 1024 / (8 * SB);
+    const int64_t mm_t0 = (n_items ? rt0 : 0) * NB;
+    const int mm_live = n_items ? 1 : 0;
+    auto issue_mm = [&](int i, uint4 &qd) {
+        const int64_t tile = mm_t0 + (i % NB) * mm_live;
+        qd = ld_nt16((i < NB ? a.qs : a.qs2) + tile * 1024 + q_off);
+    };
 #pragma unroll
-    for (int u = 0; u < UP; ++u) issue(qb[u], sb[u]);
+    for (int u = 0; u < UP; ++u) {
+        if constexpr (SCL) issue_mm(u, qb[u]);
+        else issue(qb[u], sb[u]);
+    }
     if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 1] = __builtin_amdgcn_s_memrealtime();
 
     // 2) activation image in LDS
@@ -908,7 +936,10 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
         finish_activation<WT, PRO, R, NSA, NTH>(a, col, smem, m, ar, ns);
     }
 #pragma unroll
-    for (int u = UP; u < U; ++u) issue(qb[u], sb[u]);
+    for (int u = UP; u < U; ++u) {
+        if constexpr (SCL) issue_mm(u, qb[u]);
+        else issue(qb[u], sb[u]);
+    }
     if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 2] = __builtin_amdgcn_s_memrealtime();
     uint8_t *scl_w = smem + m.total + (size_t)wave * 2048;  // SCL: this wave's [gate | up] scale runs
     if constexpr (SCL) {
@@ -928,9 +959,59 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
     unsigned long long best = 0;
     int y_it = 0;  // row tiles this wave has finished (EPI_GELU_MUL image buffer slot)
     cursor cc{rt0, 0, 0};
-    float acc = 0.0f, va = 0.0f;
-    const int64_t n_pad = ONE_SHOT && !SCL ? U : (n_items + U - 1) / U * U;
-    if constexpr (NM == 2) {
+    float acc = 0.0f;
+    const int64_t n_pad = ONE_SHOT ? U : (n_items + U - 1) / U * U;
+    if constexpr (SCL) {
+        // the gate chain first, then the up chain, as straight-line code: the GELU table lookup (a
+        // dependent global load addressed by the finished gate dot) goes out when the gate chain ends,
+        // in the middle of the stream, and is consumed when the up chain ends — by then it has long
+        // landed, where the pair order left it (and everything behind it) exposed at the end of every
+        // workgroup.  The positions are fixed, so the lookup and the ring refills sit in no branch
+        // and every wait is by count (the pair loop's per-item branches cost it vmcnt(0) drains); the
+        // clamp cases are selects.  The activation operands are read once per matrix (twice the LDS
+        // reads of the pair order): measured, the stream still ends ~1.4 us earlier.
+        constexpr int NI = 2 * NB;
+        static_assert(KS == 1 && NI % U == 0, "gate/up matrix-major ring");
+        float accu = 0.0f, vg = 0.0f;
+        uint32_t th = 0;
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int bt = i % NB;
+            const uint4 q = qb[i % U];
+            const uint8_t *sp = scl_w + (i / NB) * 1024 + (bt * 8 + rr) * SB;
+            uint4 s;
+            if constexpr (WT == T_Q4_0) {
+                s = *(const uint4 *)sp;
+            } else {
+                const uint2 s2 = *(const uint2 *)sp;
+                s = make_uint4(s2.x, s2.y, 0, 0);
+            }
+            if (i + U < NI) issue_mm(i + U, qb[i % U]);
+            if (MV_ABLATE(a) & 8) {  // timing only: the loads without the dot products
+                acc += __builtin_bit_cast(float, q.x ^ s.x);
+            } else {
+                const act_tile<WT> at = load_act<WT, NSA>(smem, m, bt, l);
+                if (i < NB) acc = tile_dot_a<WT>(q, s, at, acc);
+                else accu = tile_dot_a<WT>(q, s, at, accu);
+            }
+            if (i == NB - 1) {
+                vg = fold8(acc);
+                th = a.gelu_tab[f2h(vg)];  // every lane, any index is inside the table
+                asm volatile("" ::: "memory");  // the lookup stays here, not beside its use
+            }
+        }
+        float vu = fold8(accu);
+        if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 8] = __builtin_amdgcn_s_memrealtime();
+        asm volatile("" : "+v"(th), "+v"(vu));  // the lookup is waited for here, after the last up tile
+        float g = h2f(th);
+        if (a.gelu_clamp) g = vg <= -10.0f ? 0.0f : vg >= 10.0f ? vg : g;
+        const float yv = g * vu;  // gelu(gate) then ggml_mul by up
+        if (mm_live && (lane & 7) == 0) {
+            epilogue<EPI_STORE>(a, col, rt0 * 8 + rr, yv, 0.0f, best);
+            if (yimg) ((float *)(smem + m.ybuf))[wave * 8 + rr] = yv;
+        }
+        if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 9] = __builtin_amdgcn_s_memrealtime();
+    } else if constexpr (NM == 2) {
         // (gate, up) item pairs of the same block tile; two ordered chains (acc: gate, acc2: up)
         static_assert(KS == 1 && U % 2 == 0, "gate/up pairing");
         float acc2 = 0.0f;
@@ -938,18 +1019,7 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
 #pragma unroll
             for (int u = 0; u < U; u += 2) {
                 const uint4 q0 = qb[u], q1 = qb[u + 1];
-                uint4 s0 = sb[u], s1 = sb[u + 1];
-                if constexpr (SCL) {  // block tile cc.bt, row rr: bytes (bt*8 + rr)*SB of each run
-                    const uint8_t *sp = scl_w + (cc.bt * 8 + rr) * SB;
-                    if constexpr (WT == T_Q4_0) {
-                        s0 = *(const uint4 *)sp;
-                        s1 = *(const uint4 *)(sp + 1024);
-                    } else {
-                        const uint2 g2 = *(const uint2 *)sp, u2 = *(const uint2 *)(sp + 1024);
-                        s0 = make_uint4(g2.x, g2.y, 0, 0);
-                        s1 = make_uint4(u2.x, u2.y, 0, 0);
-                    }
-                }
+                const uint4 s0 = sb[u], s1 = sb[u + 1];
                 issue(qb[u], sb[u]);
                 issue(qb[u + 1], sb[u + 1]);
                 if (k + u < n_items) {
@@ -964,10 +1034,13 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
                         const float vg = fold8(acc), vu = fold8(acc2);
                         acc = 0.0f;
                         acc2 = 0.0f;
-                        if ((lane & 7) == 0) {
-                            epilogue<EPI>(a, col, cc.rt * 8 + rr, vg, vu, best);
-                            if (yimg) ((float *)(smem + m.ybuf))[y_it * 32 + wave * 8 + rr] = gelu_tab(a, vg) * vu;
+                        if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 8] = __builtin_amdgcn_s_memrealtime();
+                        if ((lane & 7) == 0) {  // one lookup: y and the image buffer take the same value
+                            const float yv = gelu_tab(a, vg) * vu;  // gelu(gate) then ggml_mul by up
+                            epilogue<EPI_STORE>(a, col, cc.rt * 8 + rr, yv, 0.0f, best);
+                            if (yimg) ((float *)(smem + m.ybuf))[y_it * 32 + wave * 8 + rr] = yv;
                         }
+                        if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 9] = __builtin_amdgcn_s_memrealtime();
                         ++y_it;
                         cc.bt = 0;
                         cc.rt += rstride;
@@ -981,6 +1054,7 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
     for (int64_t k = 0; k < n_pad; k += U) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
+            static_assert(NM == 1, "gate/up (NM == 2) takes one of the two branches above");
             const uint4 qc = qb[u], scc = sb[u];
             if (!ONE_SHOT) issue(qb[u], sb[u]);
             if (k + u < n_items) {
@@ -994,16 +1068,7 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
                     if (KS == 1) {
                         const float v = fold8(acc);
                         acc = 0.0f;
-                        if (NM == 2 && cc.m == 0) {
-                            va = v;
-                        } else {
-                            if ((lane & 7) == 0) {
-                                epilogue<EPI>(a, col, cc.rt * 8 + rr, NM == 2 ? va : v, v, best);
-                                if (EPI == EPI_GELU_MUL && yimg)
-                                    ((float *)(smem + m.ybuf))[y_it * 32 + wave * 8 + rr] = gelu_tab(a, va) * v;
-                            }
-                            ++y_it;
-                        }
+                        if ((lane & 7) == 0) epilogue<EPI>(a, col, cc.rt * 8 + rr, v, 0.0f, best);
                     } else {
                         // ordered carry: wave 0 hands its accumulators over through LDS, then after ONE
                         // barrier the carrier waves continue the chains of their rows through the
@@ -1025,7 +1090,16 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
                                 if (!(MV_ABLATE(a) & 4)) c = carry_chain<WT, KS>(st_s, st_d, m, seg_blocks, gl, c);
                                 if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 8] = __builtin_amdgcn_s_memrealtime();
                                 const float v = fold8(c);
-                                if ((lane & 7) == 0) epilogue<EPI>(a, col, cc.rt * 8 + (gl >> 3), v, 0.0f, best);
+                                if constexpr (EPI == EPI_ADD) {
+                                    if ((lane & 7) == 0) {
+                                        epilogue_held(a, col, cc.rt * 8 + (gl >> 3), v, held);
+                                        // a workgroup with further row tiles: the next one's residual, now
+                                        // (behind the ring loads already issued, consumed after them)
+                                        if (!ONE_SHOT) held = resid_early(a, col, (cc.rt + rstride) * 8 + (gl >> 3), true);
+                                    }
+                                } else if ((lane & 7) == 0) {
+                                    epilogue<EPI>(a, col, cc.rt * 8 + (gl >> 3), v, 0.0f, best);
+                                }
                                 if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 9] = __builtin_amdgcn_s_memrealtime();
                             }
                         }

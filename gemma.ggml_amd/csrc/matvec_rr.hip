@@ -64,8 +64,23 @@ __global__ void __launch_bounds__(RR_NTH) k_matvec_rr(const void *x, const float
     // (weight rounds issued before the activation, or right behind its loads, measured slower: DESIGN.md §10)
     act_regs<R> ar;
     prefetch_activation<WT, PRO, R, RR_NTH>(a, col, ar);
+    // EPI_ADD: every wave takes the residual of its lanes' rows (the carrier's storing lanes use it) right
+    // behind the activation loads, so the epilogue waits for no memory.  Every wave, because the load in
+    // the carrier's branch made the compiler copy the loaders' ring registers at the join, with a full
+    // wait behind the ring loads.  R > 1 (activation values held in registers over the image build): after
+    // the build, when those registers are free again, still microseconds before the last round.
+    float held = 0.0f;
+    auto take_resid = [&]() {
+        __builtin_amdgcn_sched_barrier(0);  // its address waits for struct fields: after the activation loads
+        // uniform base, 32-bit lane offset: the rows left from this tile's first, clamped into the matrix
+        const int64_t left = a.rows - 1 - rt * 8;
+        const uint32_t ro = (uint32_t)rr < (uint32_t)left ? (uint32_t)rr : (uint32_t)left;
+        held = (a.resid + (int64_t)col * a.y_col_stride + rt * 8)[ro];
+    };
+    if (EPI == EPI_ADD && R == 1) take_resid();
     norm_state ns;
     if (!(MV_ABLATE(a) & 1)) ns = build_activation<WT, PRO, R, NSA, RR_NTH>(a, col, smem, m, ar);  // timing ablations only
+    if (EPI == EPI_ADD && R > 1) take_resid();
     if (GHIP_STAMPS && stp && tid == 0) stp[10] = __builtin_amdgcn_s_memrealtime();
     // 1) the rest of the ring (loader w, round r -> block tile w + 8r; D rounds in flight per wave),
     //    issued after the image is used, so these loads may sit in a loader-only branch
@@ -118,7 +133,10 @@ __global__ void __launch_bounds__(RR_NTH) k_matvec_rr(const void *x, const float
         if (GHIP_STAMPS && stp && lane == 0 && wave == RR_NL) stp[13] = __builtin_amdgcn_s_memrealtime();
         const float v = fold8(acc);
         unsigned long long best = 0;
-        if (l == 0) epilogue<EPI>(a, col, rt * 8 + crow, v, 0.0f, best);
+        if (l == 0) {
+            if (EPI == EPI_ADD) epilogue_held(a, col, rt * 8 + crow, v, held);
+            else epilogue<EPI>(a, col, rt * 8 + crow, v, 0.0f, best);
+        }
         if (GHIP_STAMPS && stp && lane == 0 && wave == RR_NL) stp[14] = __builtin_amdgcn_s_memrealtime();
     }
 }

@@ -348,6 +348,10 @@ typedef struct gemma_test_matvec_args {
     unsigned long long *keys;    /* epi 3 */
 } gemma_test_matvec_args;
 int gemma_test_matvec(const gemma_test_matvec_args *a);
+/* the same launch with the GELU clamp (epi 2) selectable and, when img_act / img_da are given (epi 2, ks 1,
+ * ncols 1, rows % 32 == 0), the Q8_0 image of y the launch also writes: img_act u32 [ceil(rows / 128) * 32] in
+ * the activation image's layout (whole groups of 4 blocks), img_da f32 [rows / 32] */
+int gemma_test_matvec_tail(const gemma_test_matvec_args *a, int gelu_clamp, uint32_t *img_act, float *img_da);
 /* K-quant matvec (Q4_K / Q6_K x Q8_K) timed alone: avg µs per launch over
  * `iters` launches rotating over cold weight copies; *algo_bytes = weights + Q8_K column + y */
 double gemma_kq_time(int type, int64_t rows, int64_t K, int iters, double *algo_bytes);
