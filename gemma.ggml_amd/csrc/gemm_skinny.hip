@@ -71,12 +71,7 @@ __global__ void __launch_bounds__(256) k_gemm_skinny(gemm_args g) {
     auto wload = [&](int i, int bt) {
         bt = bt < n_bt ? bt : n_bt - 1;
         wq[i] = ld_nt16(qrow + (int64_t)bt * 1024);
-        if (WT == T_Q4_0) {
-            ws[i] = ld_sc16(srow + (int64_t)bt * 8 * SB);
-        } else {
-            const uint2 v = ld_sc8(srow + (int64_t)bt * 8 * SB);
-            ws[i] = make_uint4(v.x, v.y, 0, 0);
-        }
+        ws[i] = ld_scale<WT>(srow + (int64_t)bt * 8 * SB);
     };
 
     // ---- activation staging: chunk c -> registers -> LDS buffer (transposed) ---------------------

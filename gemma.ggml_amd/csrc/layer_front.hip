@@ -114,12 +114,7 @@ __device__ void rr_tiles(const mv_args &a, int64_t rt0, int64_t rt1, uint8_t *sm
         for (int r = 0; r < 2; ++r) {
             const int64_t tile = (r == 0 || rt1 < 0 ? rt0 : rt1) * a.n_bt + wave;
             qb[r] = ld_nt16(a.qs + tile * 1024 + q_off);
-            if (WT == T_Q4_0) {
-                sb[r] = ld_sc16(a.sc + tile * 8 * SB + s_off);
-            } else {
-                const uint2 v = ld_sc8(a.sc + tile * 8 * SB + s_off);
-                sb[r] = make_uint4(v.x, v.y, 0, 0);
-            }
+            sb[r] = ld_scale<WT>(a.sc + tile * 8 * SB + s_off);
         }
     }
     if (WAIT) {
@@ -162,12 +157,12 @@ __device__ void rr_tiles(const mv_args &a, int64_t rt0, int64_t rt1, uint8_t *sm
         }
     };
     if (loader) {
-        tile_terms<WT>(qb[0], sb[0], smem, m, wave, l, slot_s(0) + (size_t)lane * G::SBP, slot_d(0) + (size_t)rr * G::SBPD,
-                       wave * BT);
+        rr_stash<WT>(qb[0], sb[0], smem, m, wave, l, slot_s(0) + (size_t)lane * G::SBP, slot_d(0) + (size_t)rr * G::SBPD,
+                     wave * BT);
         if (nt == 2) {
             lds_barrier();
-            tile_terms<WT>(qb[1], sb[1], smem, m, wave, l, slot_s(1) + (size_t)lane * G::SBP,
-                           slot_d(1) + (size_t)rr * G::SBPD, wave * BT);
+            rr_stash<WT>(qb[1], sb[1], smem, m, wave, l, slot_s(1) + (size_t)lane * G::SBP,
+                         slot_d(1) + (size_t)rr * G::SBPD, wave * BT);
         }
         lds_barrier();
     } else {  // the carrier (wave RR_NL) chains; waves past it only keep the barrier count

@@ -18,6 +18,12 @@
 // K-split (KS > 1): the waves of a workgroup each take a contiguous K segment of the same 8 rows;
 // waves 1..KS-1 stash their exact (d, isum) terms in LDS and the fma chain is carried across the
 // segments in order (wave w continues wave w-1's accumulator), which keeps the AVX2 order.
+//
+// The arithmetic lives in two places.  tile_step (and tile_terms, the whole tile) turns a weight tile
+// and its activation operands (load_act) into the exact (d, isum) terms; tile_acc, stash_f32 and
+// stash_i16 only consume them (one measured exception: matvec_rr.h's rr_stash for Q8_0).
+// carry_load / carry_fma read and apply one stashed chunk; carry_ring and carry_chain only order them.
+// matvec_rr.hip, layer_front.hip and token.hip build on the same functions.
 #pragma once
 
 #include "device_util.h"
@@ -29,29 +35,21 @@ namespace {
 
 typedef uint32_t v4u_nt __attribute__((ext_vector_type(4)));
 typedef uint32_t v2u_nt __attribute__((ext_vector_type(2)));
-#ifndef GHIP_MV_NT
-#define GHIP_MV_NT 1  // weight loads non-temporal (0: plain loads, an A/B switch)
-#endif
+// weight and scale loads are non-temporal: both are read once per token by one CU
 __device__ __forceinline__ uint4 ld_nt16(const uint8_t *p) {
-    if constexpr (!GHIP_MV_NT) return *(const uint4 *)p;
     const v4u_nt v = __builtin_nontemporal_load((const v4u_nt *)p);
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ uint2 ld_nt8(const uint8_t *p) {
-    if constexpr (!GHIP_MV_NT) return *(const uint2 *)p;
     const v2u_nt v = __builtin_nontemporal_load((const v2u_nt *)p);
     return make_uint2(v.x, v.y);
 }
-#ifndef GHIP_MV_SCNT
-#define GHIP_MV_SCNT 1  // the scale loads' policy on its own (0: plain, an A/B switch)
-#endif
-__device__ __forceinline__ uint4 ld_sc16(const uint8_t *p) {
-    if constexpr (!GHIP_MV_SCNT) return *(const uint4 *)p;
-    return ld_nt16(p);
-}
-__device__ __forceinline__ uint2 ld_sc8(const uint8_t *p) {
-    if constexpr (!GHIP_MV_SCNT) return *(const uint2 *)p;
-    return ld_nt8(p);
+// one row's scales of a tile (Q4_0: 8 fp16 = 16 B, Q8_0: 4 fp16 = 8 B), as the uint4 the tile terms take
+template <int WT>
+__device__ __forceinline__ uint4 ld_scale(const uint8_t *p) {
+    if constexpr (WT == T_Q4_0) return ld_nt16(p);
+    const uint2 v = ld_nt8(p);
+    return make_uint4(v.x, v.y, 0, 0);
 }
 
 __device__ __forceinline__ int sdot4(uint32_t a, uint32_t b, int c) {
@@ -214,9 +212,6 @@ __device__ __forceinline__ void prefetch_activation(const mv_args &a, int col, a
     }
 }
 
-#ifndef GHIP_MV_NORM_DPP
-#define GHIP_MV_NORM_DPP 1
-#endif
 // The rms_norm's tree sum and mean (PRO_NORM / PRO_EMBED), kept for finish_activation's check.
 struct norm_state {
     double q = 0.0;  // T/n: float(q) is the mean
@@ -342,12 +337,7 @@ __device__ norm_state build_activation(const mv_args &a, int col, uint8_t *smem,
             }
         }
         double *red = (double *)(smem + m.red);
-#if GHIP_MV_NORM_DPP
         part = wave_sum_f64(part);  // DPP + v_readlane: no ds_bpermute round trips (any order: §3)
-#else
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off);  // (once per launch)
-#endif
         if ((tid & 63) == 0) red[tid >> 6] = part;
         __syncthreads();
         double sum = 0.0;
@@ -429,110 +419,84 @@ __device__ __forceinline__ act_tile<WT> load_act(const uint8_t *smem, const lds_
     return t;
 }
 
-// the same arithmetic as tile_dot<WT, false, NSA>, on preloaded operands
+// The tile terms — the one place the per-tile arithmetic lives.  For this thread's (row, lane) and
+// the tile's blocks j = 0..BT-1, in block order: d[j] = f32(dw_j) * da_j (mix_lo / mix_hi: a true
+// v_fma_mix_f32 product, addend +0) and s[j] = the lane's 4-element integer sum of block j, one
+// v_dot4_i32_i8 (exact).  Q4_0: sum((nib - 8) * a) = sum(nib * a) - 8 * sum(a), exact in int32; the
+// addend -8 * sum(a) is act_tile::nv.  tile_step forms them one weight dword at a time (step p of 4:
+// Q4_0 blocks 2p and 2p+1, the dword's two nibble planes; Q8_0 block p).  The fma chain, the f32
+// stash and the int16 stash below are all built from it, so they cannot drift apart.
 template <int WT>
-__device__ __forceinline__ float tile_dot_a(uint4 q, uint4 scv, const act_tile<WT> &t, float acc) {
-    const uint32_t qv[4] = {q.x, q.y, q.z, q.w};
+__device__ __forceinline__ void tile_step(int p, const uint32_t (&qv)[4], const uint32_t (&sv)[4], const act_tile<WT> &t,
+                                          float *d, int *s) {
     if constexpr (WT == T_Q4_0) {
-        const uint32_t sv[4] = {scv.x, scv.y, scv.z, scv.w};
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const uint32_t lo = qv[p] & 0x0F0F0F0Fu, hi = (qv[p] >> 4) & 0x0F0F0F0Fu;
-            const int s0 = sdot4(lo, t.av[2 * p], (int)t.nv[2 * p]);
-            const int s1 = sdot4(hi, t.av[2 * p + 1], (int)t.nv[2 * p + 1]);
-            const float d0 = mix_lo(sv[p], t.dav[2 * p]);
-            const float d1 = mix_hi(sv[p], t.dav[2 * p + 1]);
-            acc = __builtin_fmaf(d0, (float)s0, acc);
-            acc = __builtin_fmaf(d1, (float)s1, acc);
-        }
+        const uint32_t lo = qv[p] & 0x0F0F0F0Fu, hi = (qv[p] >> 4) & 0x0F0F0F0Fu;
+        s[0] = sdot4(lo, t.av[2 * p], (int)t.nv[2 * p]);
+        s[1] = sdot4(hi, t.av[2 * p + 1], (int)t.nv[2 * p + 1]);
+        d[0] = mix_lo(sv[p], t.dav[2 * p]);
+        d[1] = mix_hi(sv[p], t.dav[2 * p + 1]);
     } else {
-        const uint32_t sv[2] = {scv.x, scv.y};
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const int s = sdot4(qv[p], t.av[p], 0);
-            const float d = (p & 1) ? mix_hi(sv[p >> 1], t.dav[p]) : mix_lo(sv[p >> 1], t.dav[p]);
-            acc = __builtin_fmaf(d, (float)s, acc);
-        }
+        s[0] = sdot4(qv[p], t.av[p], 0);
+        d[0] = (p & 1) ? mix_hi(sv[p >> 1], t.dav[p]) : mix_lo(sv[p >> 1], t.dav[p]);
     }
-    return acc;
 }
-
-// STASH: store the exact (d, (float)isum) terms for the carry instead of accumulating
-template <int WT, bool STASH, bool NSA>
-__device__ __forceinline__ float tile_dot(uint4 q, uint4 scv, const uint8_t *smem, const lds_map &m, int64_t bt, int l,
-                                          float acc, void *st_s_, float *st_d, int j0) {
-    float *st_s = (float *)st_s_;
-    const float *da = (const float *)(smem + m.da);
-    const uint4 *act = (const uint4 *)(smem + m.act);
-    const uint32_t qv[4] = {q.x, q.y, q.z, q.w};
-    if (WT == T_Q4_0) {
-        const uint4 A0 = act[(bt * 2) * 8 + l], A1 = act[(bt * 2 + 1) * 8 + l];
-        const uint32_t av[8] = {A0.x, A0.y, A0.z, A0.w, A1.x, A1.y, A1.z, A1.w};
-        uint32_t nv[8];
-        if (NSA) {
-            const uint4 *ns = (const uint4 *)(smem + m.ns);
-            const uint4 N0 = ns[(bt * 2) * 8 + l], N1 = ns[(bt * 2 + 1) * 8 + l];
-            nv[0] = N0.x; nv[1] = N0.y; nv[2] = N0.z; nv[3] = N0.w; nv[4] = N1.x; nv[5] = N1.y; nv[6] = N1.z; nv[7] = N1.w;
-        }
-        const float4 DA0 = *(const float4 *)(da + bt * 8), DA1 = *(const float4 *)(da + bt * 8 + 4);
-        const float dav[8] = {DA0.x, DA0.y, DA0.z, DA0.w, DA1.x, DA1.y, DA1.z, DA1.w};
-        const uint32_t sv[4] = {scv.x, scv.y, scv.z, scv.w};
-        uint32_t pk[4];
-        float dk[8];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const uint32_t lo = qv[p] & 0x0F0F0F0Fu, hi = (qv[p] >> 4) & 0x0F0F0F0Fu;
-            // sum((nib - 8) * a) = sum(nib * a) - 8 * sum(a), exact in int32
-            const int n0 = NSA ? (int)nv[2 * p] : sdot4(av[2 * p], 0xF8F8F8F8u, 0);
-            const int n1 = NSA ? (int)nv[2 * p + 1] : sdot4(av[2 * p + 1], 0xF8F8F8F8u, 0);
-            const int s0 = sdot4(lo, av[2 * p], n0);
-            const int s1 = sdot4(hi, av[2 * p + 1], n1);
-            const float d0 = mix_lo(sv[p], dav[2 * p]);
-            const float d1 = mix_hi(sv[p], dav[2 * p + 1]);
-            if (STASH) {
-                pk[p] = ((uint32_t)s0 & 0xFFFFu) | ((uint32_t)s1 << 16);
-                dk[2 * p] = d0;
-                dk[2 * p + 1] = d1;
-            } else {
-                acc = __builtin_fmaf(d0, (float)s0, acc);
-                acc = __builtin_fmaf(d1, (float)s1, acc);
-            }
-        }
-        if (STASH) {
-            *(uint4 *)((int16_t *)st_s_ + j0) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-            if (l == 0) {
-                *(float4 *)(st_d + j0) = make_float4(dk[0], dk[1], dk[2], dk[3]);
-                *(float4 *)(st_d + j0 + 4) = make_float4(dk[4], dk[5], dk[6], dk[7]);
-            }
-        }
-    } else {
-        const uint4 A = act[bt * 8 + l];
-        const uint32_t av[4] = {A.x, A.y, A.z, A.w};
-        const float4 DA = *(const float4 *)(da + bt * 4);
-        const float dav[4] = {DA.x, DA.y, DA.z, DA.w};
-        const uint32_t sv[2] = {scv.x, scv.y};
-        float dd[4], ss[4];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const int s = sdot4(qv[p], av[p], 0);
-            const float d = (p & 1) ? mix_hi(sv[p >> 1], dav[p]) : mix_lo(sv[p >> 1], dav[p]);
-            dd[p] = d;
-            ss[p] = (float)s;
-            if (!STASH) acc = __builtin_fmaf(d, (float)s, acc);
-        }
-        if (STASH) {
-            *(float4 *)(st_s + j0) = make_float4(ss[0], ss[1], ss[2], ss[3]);
-            if (l == 0) *(float4 *)(st_d + j0) = make_float4(dd[0], dd[1], dd[2], dd[3]);
-        }
-    }
-    return acc;
-}
-
+template <int WT> struct tile_tm {
+    float d[wfmt<WT>::BT];
+    int s[wfmt<WT>::BT];
+};
 template <int WT>
-__device__ __forceinline__ uint4 load_scale(const uint8_t *sc, int64_t tile, int rr) {
-    if (WT == T_Q4_0) return ((const uint4 *)sc)[tile * 8 + rr];
-    const uint2 v = ((const uint2 *)sc)[tile * 8 + rr];
-    return make_uint4(v.x, v.y, 0, 0);
+__device__ __forceinline__ tile_tm<WT> tile_terms(uint4 q, uint4 scv, const act_tile<WT> &t) {
+    constexpr int SB = wfmt<WT>::BT / 4;  // blocks per step
+    const uint32_t qv[4] = {q.x, q.y, q.z, q.w}, sv[4] = {scv.x, scv.y, scv.z, scv.w};
+    tile_tm<WT> r;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) tile_step<WT>(p, qv, sv, t, r.d + p * SB, r.s + p * SB);
+    return r;
+}
+
+// accumulate: the lane's fma chain continued through the tile, one fmaf per block in block order.
+// Each step's terms are applied as they are formed: with all of a tile's terms formed first the
+// same arithmetic was scheduled differently, and the Q8_0 gate/up kernel ran 0.06-0.07 us longer
+// per launch; in this order its code is the earlier hand-written form's.
+template <int WT>
+__device__ __forceinline__ float tile_acc(uint4 q, uint4 scv, const act_tile<WT> &t, float acc) {
+    constexpr int SB = wfmt<WT>::BT / 4;
+    const uint32_t qv[4] = {q.x, q.y, q.z, q.w}, sv[4] = {scv.x, scv.y, scv.z, scv.w};
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        float d[SB];
+        int s[SB];
+        tile_step<WT>(p, qv, sv, t, d, s);
+#pragma unroll
+        for (int j = 0; j < SB; ++j) acc = __builtin_fmaf(d[j], (float)s[j], acc);
+    }
+    return acc;
+}
+
+// Stashes: the terms stored for a carrier wave instead of accumulated (st_s: this lane's run, st_d:
+// this row's, both at the tile's first block).  d is the same for the 8 lanes of a row: lane 0 stores it.
+template <int WT>
+__device__ __forceinline__ void stash_d(const tile_tm<WT> &r, int l, float *st_d) {
+    if (l == 0) {
+#pragma unroll
+        for (int j = 0; j < wfmt<WT>::BT; j += 4) *(float4 *)(st_d + j) = make_float4(r.d[j], r.d[j + 1], r.d[j + 2], r.d[j + 3]);
+    }
+}
+// s as f32: the carrier's chain is then LDS reads + fmaf only
+template <int WT>
+__device__ __forceinline__ void stash_f32(const tile_tm<WT> &r, int l, float *st_s, float *st_d) {
+#pragma unroll
+    for (int j = 0; j < wfmt<WT>::BT; j += 4)
+        *(float4 *)(st_s + j) = make_float4((float)r.s[j], (float)r.s[j + 1], (float)r.s[j + 2], (float)r.s[j + 3]);
+    stash_d<WT>(r, l, st_d);
+}
+// Q4_0, s as int16 (|s| <= 4064): blocks (2p, 2p+1) in dword p — the chunk carry_fma<true> reads
+__device__ __forceinline__ void stash_i16(const tile_tm<T_Q4_0> &r, int l, int16_t *st_s, float *st_d) {
+    uint32_t pk[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) pk[p] = ((uint32_t)r.s[2 * p] & 0xFFFFu) | ((uint32_t)r.s[2 * p + 1] << 16);
+    *(uint4 *)st_s = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+    stash_d<T_Q4_0>(r, l, st_d);
 }
 
 // ordered fold of the 8 lanes (hsum_float_8): xor 4, then 2, then 1
@@ -540,10 +504,11 @@ __device__ __forceinline__ float fold8(float v) {
     return fold8_dpp(v);
 }
 
-__device__ __forceinline__ float gelu_tab(const mv_args &a, float x) {
-    if (a.gelu_clamp && x <= -10.0f) return 0.0f;
-    if (a.gelu_clamp && x >= 10.0f) return x;
-    return h2f(a.gelu_tab[f2h(x)]);
+// ggml's GELU: the fp16 table indexed by the fp16 bits of x, with its clamp where the model asks for it
+__device__ __forceinline__ float gelu_lookup(const uint16_t *tab, int clamp, float x) {
+    if (clamp && x <= -10.0f) return 0.0f;
+    if (clamp && x >= 10.0f) return x;
+    return h2f(tab[f2h(x)]);
 }
 
 template <int EPI>
@@ -553,7 +518,7 @@ __device__ __forceinline__ void epilogue(const mv_args &a, int col, int64_t row,
     float *y = a.y + (int64_t)col * a.y_col_stride;
     if (EPI == EPI_STORE) y[row] = v;
     if (EPI == EPI_ADD) y[row] = v + a.resid[(int64_t)col * a.y_col_stride + row];
-    if (EPI == EPI_GELU_MUL) y[row] = gelu_tab(a, v) * vb;  // gelu(gate) then ggml_mul by up
+    if (EPI == EPI_GELU_MUL) y[row] = gelu_lookup(a.gelu_tab, a.gelu_clamp, v) * vb;  // gelu(gate) then ggml_mul by up
     if (EPI == EPI_ARGMAX) {
         y[row] = v;
         const unsigned long long k = argmax_key(v, row);
@@ -587,97 +552,22 @@ struct cursor {
 
 // Ordered carry (wave 0): acc continues through the stashed (d, isum) terms of segments 1..KS-1 in
 // block order — the exact fmaf chain of the sequential loop.  The run is linear in LDS (stash
-// layout above) and read AHEAD chunks of 4 blocks ahead of the FMAs, so the chain runs at FMA
-// latency, not LDS latency.  Reads are never inside a branch: past the end the index is clamped.
-template <int G, bool EXACT>
-__device__ __forceinline__ float carry_run(const float4 *ps, const float4 *pd, int total, float acc) {
-    float4 as[G], ad[G], bs[G], bd[G];
-    auto load = [&](float4 (&S)[G], float4 (&D)[G], int c0) {
-#pragma unroll
-        for (int r = 0; r < G; ++r) {
-            const int i = EXACT ? c0 + r : (c0 + r < total - 1 ? c0 + r : total - 1);
-            S[r] = ps[i];
-            D[r] = pd[i];
-        }
-    };
-    auto chain = [&](const float4 (&S)[G], const float4 (&D)[G], int c0) {
-#pragma unroll
-        for (int r = 0; r < G; ++r) {
-            if (EXACT || c0 + r < total) {
-                acc = __builtin_fmaf(D[r].x, S[r].x, acc);
-                acc = __builtin_fmaf(D[r].y, S[r].y, acc);
-                acc = __builtin_fmaf(D[r].z, S[r].z, acc);
-                acc = __builtin_fmaf(D[r].w, S[r].w, acc);
-            }
-        }
-    };
-    load(as, ad, 0);
-    load(bs, bd, G);
-    for (int c = 0; c < total; c += 2 * G) {
-        // the empty asm statements pin each set's reads one half-step ahead of their FMAs
-        asm volatile("" ::: "memory");
-        chain(as, ad, c);
-        asm volatile("" ::: "memory");
-        if (!EXACT || c + 2 * G < total) load(as, ad, c + 2 * G);
-        asm volatile("" ::: "memory");
-        chain(bs, bd, c + G);
-        asm volatile("" ::: "memory");
-        if (!EXACT || c + 3 * G < total) load(bs, bd, c + 3 * G);
-    }
-    return acc;
-}
-
-// Q4_0 form: chunks of 8 blocks = one b128 of int16 sums + two b128 of d.  total % (2G) == 0; the
-// reloads are unconditional (a set is refilled in place right after its FMAs, so the register
-// allocator needs no copies and the waitcnt before a set's FMAs only covers that set).  The final
-// reloads run up to 2G chunks past the run: they stay inside the LDS image (the stash pads and the
-// regions behind it) and are never used.
-template <int G>
-__device__ __forceinline__ float carry_run16(const uint4 *ps, const float4 *pd, int total, float acc) {
-    uint4 as[G], bs[G];
-    float4 ad[G][2], bd[G][2];
-    auto load = [&](uint4 (&S)[G], float4 (&D)[G][2], int c0) {
-#pragma unroll
-        for (int r = 0; r < G; ++r) {
-            S[r] = ps[c0 + r];
-            D[r][0] = pd[2 * (c0 + r)];
-            D[r][1] = pd[2 * (c0 + r) + 1];
-        }
-    };
-    auto chain = [&](const uint4 (&S)[G], const float4 (&D)[G][2]) {
-#pragma unroll
-        for (int r = 0; r < G; ++r) {
-            const uint32_t w[4] = {S[r].x, S[r].y, S[r].z, S[r].w};
-            const float d[8] = {D[r][0].x, D[r][0].y, D[r][0].z, D[r][0].w,
-                                D[r][1].x, D[r][1].y, D[r][1].z, D[r][1].w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                acc = __builtin_fmaf(d[2 * k], (float)(int)(int16_t)(w[k] & 0xFFFFu), acc);
-                acc = __builtin_fmaf(d[2 * k + 1], (float)((int)w[k] >> 16), acc);
-            }
-        }
-    };
-    load(as, ad, 0);
-    load(bs, bd, G);
-    for (int c = 0; c < total; c += 2 * G) {
-        asm volatile("" ::: "memory");
-        chain(as, ad);
-        asm volatile("" ::: "memory");
-        load(as, ad, c + 2 * G);
-        asm volatile("" ::: "memory");
-        chain(bs, bd);
-        asm volatile("" ::: "memory");
-        load(bs, bd, c + 3 * G);
-    }
-    return acc;
-}
-
+// layout above) and read in chunks ahead of the FMAs, so the chain runs at FMA latency, not LDS
+// latency.  A chunk is I16 (Q4_0) 8 blocks (s: 8 x int16 in one uint4, d: two float4), else (Q8_0,
+// and the f32 stashes of the round-pipelined kernels) 4 blocks (s: 4 x f32, d: one float4);
+// carry_load and carry_fma are the only place one is read and applied.
 // Explicitly pipelined carry: NS = 4 chunk sets in flight.  Each set is refilled in place right
 // after its FMAs, and sched_barrier(0) pins every load group and FMA group where it is written, so
 // the scheduler can neither sink a refill next to its use nor hoist it above the FMAs that still
 // read the set (the compiler's own waitcnt insertion then waits, before a set's FMAs, only for that
-// set: LDS ops retire in order).  The ring over-reads up to NS chunks past the run (inside the LDS
-// image: stash pads, the d stash, the red area); those values are never used.
+// set: LDS ops retire in order).  The ring over-reads up to NS chunks past the chunks it is given
+// (inside the LDS image: stash pads, the d stash, the red area); those values are never used.
+// The bound is the ring's NS = 4 chunks past the end of a run, for every run length; it is not "no more
+// than the earlier code read for that same length".  carry_chain hands the ring the first total & ~3
+// chunks: a run of whole ring turns is over-read by 4 chunks, as it always was; with 1, 2 or 3 chunks
+// remaining the ring's last refills read those and then 3, 2 or 1 chunks past the run (total 5, 9, ...:
+// 3 chunks, where the earlier two-set run read 1).  For the last lane and row that is at most 64 B (s)
+// and 128 B (d, Q4_0) past the run: the 16-B pad and the d stash or the 512-B red area cover it.
 template <bool I16>
 struct carry_set {
     uint4 s;
@@ -712,8 +602,7 @@ __device__ __forceinline__ float carry_fma(const carry_set<I16> &k, float acc) {
     return acc;
 }
 
-// chunks [0, total) of the run; total % 4 == 0.  I16 (Q4_0): chunk = 8 blocks (s: 8 x int16 in one
-// uint4, d: two float4); else (Q8_0): 4 blocks (s: 4 x f32, d: one float4).
+// chunks [0, total) of the run; total % 4 == 0
 template <bool I16>
 __device__ __forceinline__ float carry_ring(const uint4 *ps, const float4 *pd, int total, float acc) {
     carry_set<I16> A, B, C, D;
@@ -743,48 +632,41 @@ __device__ __forceinline__ float carry_ring(const uint4 *ps, const float4 *pd, i
     return acc;
 }
 
-// gl = row * 8 + lane-of-row in the wave-0 numbering of the stash
+// The K-split carry of one lane: gl = row * 8 + lane-of-row in the wave-0 numbering of the stash.
+// One path for every run length: the ring over the first total & ~3 chunks, then the remaining 0-3
+// chunks one by one through the same carry_load + carry_fma, in chunk order.  The remainder is one
+// uniform branch (taken when total % 4 != 0).  Inside it always three chunk reads go out together, no
+// branch per chunk: an index past the end is clamped to the last chunk (that chunk is then read again
+// and not used; no over-read), and only the FMAs are predicated, on the uniform count.
 template <int WT, int KS>
 __device__ __forceinline__ float carry_chain(const void *st_s, const float *st_d, const lds_map &m, int seg_blocks,
                                              int gl, float acc) {
+    constexpr bool I16 = WT == T_Q4_0;
+    constexpr int CB = I16 ? 8 : 4, SW = I16 ? 2 : 4;  // blocks per chunk, bytes per stashed s
+    const uint4 *ps = (const uint4 *)((const uint8_t *)st_s + (size_t)gl * m.sbp * SW);
     const float4 *pd = (const float4 *)(st_d + (size_t)(gl >> 3) * m.sbpd);
-    if (WT == T_Q4_0) {
-        const uint4 *ps = (const uint4 *)((const int16_t *)st_s + (size_t)gl * m.sbp);
-        const int total = (KS - 1) * (seg_blocks >> 3);  // chunks of 8 blocks
-        if (total % 4 == 0) return carry_ring<true>(ps, pd, total, acc);
-        if (total % 4 == 0) return carry_run16<2>(ps, pd, total, acc);
-        if (total % 2 == 0) return carry_run16<1>(ps, pd, total, acc);
-        // odd: the last chunk alone, after an even run
-        acc = total > 1 ? carry_run16<1>(ps, pd, total - 1, acc) : acc;
-        const uint4 S = ps[total - 1];
-        const float4 D0 = pd[2 * (total - 1)], D1 = pd[2 * (total - 1) + 1];
-        const uint32_t w[4] = {S.x, S.y, S.z, S.w};
-        const float d[8] = {D0.x, D0.y, D0.z, D0.w, D1.x, D1.y, D1.z, D1.w};
+    const int total = (KS - 1) * (seg_blocks / CB), ring = total & ~3;
+    if (ring) acc = carry_ring<I16>(ps, pd, ring, acc);
+    if (ring != total) {
+        carry_set<I16> k[3];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            acc = __builtin_fmaf(d[2 * k], (float)(int)(int16_t)(w[k] & 0xFFFFu), acc);
-            acc = __builtin_fmaf(d[2 * k + 1], (float)((int)w[k] >> 16), acc);
-        }
-        return acc;
+        for (int r = 0; r < 3; ++r) carry_load<I16>(k[r], ps, pd, ring + r < total ? ring + r : total - 1);
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+            if (ring + r < total) acc = carry_fma<I16>(k[r], acc);
     }
-    const float4 *ps = (const float4 *)((const float *)st_s + (size_t)gl * m.sbp);
-    const int total = (KS - 1) * (seg_blocks >> 2);  // chunks of 4 blocks
-    if (total % 4 == 0) return carry_ring<false>((const uint4 *)ps, pd, total, acc);
-    // whole double-steps: no bounds test inside the dependent chain
-    if (total % 8 == 0) return carry_run<4, true>(ps, pd, total, acc);
-    if (total % 4 == 0) return carry_run<2, true>(ps, pd, total, acc);
-    return carry_run<2, false>(ps, pd, total, acc);
+    return acc;
 }
 
 // the timing ablations a kernel sees: a constant 0 unless the library is the GHIP_ABLATE variant,
 // so the product kernels never read (or wait for) mv_args::ablate
 #define MV_ABLATE(a) (GHIP_ABLATE ? (a).ablate : 0)
-#ifndef GHIP_NOSCALE
-#define GHIP_NOSCALE 0
-#endif
-#ifndef GHIP_HOSTDIV
-#define GHIP_HOSTDIV 1  // 1: the wave's item count from launch_t's precomputed quotient (no 64-bit division)
-#endif
+// stamp slot i of this workgroup's 16 (GHIP_STAMPS builds; tests/stamp_*.py read the slot numbers)
+#define MV_STAMP(i)                                                                                                  \
+    do {                                                                                                             \
+        if (GHIP_STAMPS && a.dbg_t && tid == 0)                                                                      \
+            a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)] = __builtin_amdgcn_s_memrealtime();   \
+    } while (0)
 #ifndef GHIP_UPRE
 #define GHIP_UPRE 4
 #endif
@@ -814,12 +696,12 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rr = lane >> 3, l = lane & 7;
     const int col = blockIdx.y;
-    if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 0] = __builtin_amdgcn_s_memrealtime();
+    MV_STAMP(0);
     const int64_t seg_tiles = KS > 1 ? a.n_bt / KS : a.n_bt;
     // EPI_GELU_MUL with an image output: row-tile groups (4 consecutive tiles = one Q8_0 block of y)
     // this workgroup produces, buffered in LDS until the end
     const bool yimg = EPI == EPI_GELU_MUL && KS == 1 && a.out_act != nullptr;
-    const int64_t ygroups = !yimg ? 0 : GHIP_HOSTDIV ? a.ygroups : ((a.n_rt >> 2) + gridDim.x - 1) / gridDim.x;
+    const int64_t ygroups = yimg ? a.ygroups : 0;  // launch_t's count (no 64-bit division here)
     const lds_map m = make_lds_map<WT, NSA>(KS, a.n_bt, seg_tiles, ygroups);
     const int nbt = (int)seg_tiles;
     const int bt0 = KS > 1 ? wave * nbt : 0;
@@ -833,8 +715,7 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
         rt0 = blockIdx.x;
         rstride = gridDim.x;
     }
-    const int64_t n_my_rt = GHIP_HOSTDIV ? a.rt_q + (rt0 < a.rt_r ? 1 : 0)
-                                         : rt0 < a.n_rt ? (a.n_rt - rt0 + rstride - 1) / rstride : 0;
+    const int64_t n_my_rt = a.rt_q + (rt0 < a.rt_r ? 1 : 0);  // launch_t's quotient and remainder
     const int64_t n_items = n_my_rt * NM * nbt;
 
     // SCL (gate/up, every wave at most one row tile whose scale planes are 1 KiB each): the wave's
@@ -855,8 +736,8 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
     uint4 scl_g = make_uint4(0, 0, 0, 0), scl_u = scl_g;
     if constexpr (SCL) {
         const int64_t rts = n_items ? rt0 : 0;
-        scl_g = ld_sc16(a.sc + rts * 1024 + lane * 16);
-        scl_u = ld_sc16(a.sc2 + rts * 1024 + lane * 16);
+        scl_g = ld_nt16(a.sc + rts * 1024 + lane * 16);
+        scl_u = ld_nt16(a.sc2 + rts * 1024 + lane * 16);
     }
     // GHIP_MV_XFIRST: every wave's activation loads go out before any wave's weight ring (one
     // s_barrier, no wait) — the K-quant prologue's measured +0.5-1 % (kquant.hip GHIP_KQ_EARLY 2)
@@ -878,17 +759,7 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
         // weights are read once per token by one CU: non-temporal loads (MI355X_MICROARCH nt-weights:
         // issued -> landed -18 %, decode layer -5..10 %)
         qd = ld_nt16(qt + q_off);
-#if GHIP_NOSCALE  // timing only: no scale loads (wrong results)
-        sd = make_uint4(0x3c003c00u, 0x3c003c00u, 0x3c003c00u, 0x3c003c00u);
-        (void)st;
-#else
-        if (WT == T_Q4_0) {
-            sd = ld_sc16(st + s_off);
-        } else {
-            const uint2 v = ld_sc8(st + s_off);
-            sd = make_uint4(v.x, v.y, 0, 0);
-        }
-#endif
+        sd = ld_scale<WT>(st + s_off);
         ++issued;
         if (issued < n_items) {
             if (NM == 2) {  // gate and up of one block tile back to back (shared act operands)
@@ -925,7 +796,7 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
         if constexpr (SCL) issue_mm(u, qb[u]);
         else issue(qb[u], sb[u]);
     }
-    if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 1] = __builtin_amdgcn_s_memrealtime();
+    MV_STAMP(1);
 
     // 2) activation image in LDS
     norm_state ns;
@@ -940,14 +811,14 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
         if constexpr (SCL) issue_mm(u, qb[u]);
         else issue(qb[u], sb[u]);
     }
-    if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 2] = __builtin_amdgcn_s_memrealtime();
+    MV_STAMP(2);
     uint8_t *scl_w = smem + m.total + (size_t)wave * 2048;  // SCL: this wave's [gate | up] scale runs
     if constexpr (SCL) {
         *(uint4 *)(scl_w + lane * 16) = scl_g;
         *(uint4 *)(scl_w + 1024 + lane * 16) = scl_u;
     }
     __syncthreads();
-    if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 3] = __builtin_amdgcn_s_memrealtime();
+    MV_STAMP(3);
 
     // 3) stream
     const int seg_blocks = nbt * BT;
@@ -991,8 +862,8 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
                 acc += __builtin_bit_cast(float, q.x ^ s.x);
             } else {
                 const act_tile<WT> at = load_act<WT, NSA>(smem, m, bt, l);
-                if (i < NB) acc = tile_dot_a<WT>(q, s, at, acc);
-                else accu = tile_dot_a<WT>(q, s, at, accu);
+                if (i < NB) acc = tile_acc<WT>(q, s, at, acc);
+                else accu = tile_acc<WT>(q, s, at, accu);
             }
             if (i == NB - 1) {
                 vg = fold8(acc);
@@ -1001,7 +872,7 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
             }
         }
         float vu = fold8(accu);
-        if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 8] = __builtin_amdgcn_s_memrealtime();
+        MV_STAMP(8);
         asm volatile("" : "+v"(th), "+v"(vu));  // the lookup is waited for here, after the last up tile
         float g = h2f(th);
         if (a.gelu_clamp) g = vg <= -10.0f ? 0.0f : vg >= 10.0f ? vg : g;
@@ -1010,7 +881,7 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
             epilogue<EPI_STORE>(a, col, rt0 * 8 + rr, yv, 0.0f, best);
             if (yimg) ((float *)(smem + m.ybuf))[wave * 8 + rr] = yv;
         }
-        if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 9] = __builtin_amdgcn_s_memrealtime();
+        MV_STAMP(9);
     } else if constexpr (NM == 2) {
         // (gate, up) item pairs of the same block tile; two ordered chains (acc: gate, acc2: up)
         static_assert(KS == 1 && U % 2 == 0, "gate/up pairing");
@@ -1027,20 +898,20 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
                         acc += __builtin_bit_cast(float, q0.x ^ s0.x ^ q1.y ^ s1.y);
                     } else {
                         const act_tile<WT> at = load_act<WT, NSA>(smem, m, cc.bt, l);
-                        acc = tile_dot_a<WT>(q0, s0, at, acc);
-                        acc2 = tile_dot_a<WT>(q1, s1, at, acc2);
+                        acc = tile_acc<WT>(q0, s0, at, acc);
+                        acc2 = tile_acc<WT>(q1, s1, at, acc2);
                     }
                     if (cc.bt + 1 == nbt) {
                         const float vg = fold8(acc), vu = fold8(acc2);
                         acc = 0.0f;
                         acc2 = 0.0f;
-                        if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 8] = __builtin_amdgcn_s_memrealtime();
+                        MV_STAMP(8);
                         if ((lane & 7) == 0) {  // one lookup: y and the image buffer take the same value
-                            const float yv = gelu_tab(a, vg) * vu;  // gelu(gate) then ggml_mul by up
+                            const float yv = gelu_lookup(a.gelu_tab, a.gelu_clamp, vg) * vu;  // gelu(gate) then ggml_mul by up
                             epilogue<EPI_STORE>(a, col, cc.rt * 8 + rr, yv, 0.0f, best);
                             if (yimg) ((float *)(smem + m.ybuf))[y_it * 32 + wave * 8 + rr] = yv;
                         }
-                        if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 9] = __builtin_amdgcn_s_memrealtime();
+                        MV_STAMP(9);
                         ++y_it;
                         cc.bt = 0;
                         cc.rt += rstride;
@@ -1060,9 +931,12 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
             if (k + u < n_items) {
                 const int64_t bt = bt0 + cc.bt;
                 if (KS == 1 || wave == 0)
-                    acc = tile_dot<WT, false, NSA>(qc, scc, smem, m, bt, l, acc, nullptr, nullptr, 0);
-                else
-                    tile_dot<WT, true, NSA>(qc, scc, smem, m, bt, l, 0.0f, my_s, my_d, cc.bt * BT);
+                    acc = tile_acc<WT>(qc, scc, load_act<WT, NSA>(smem, m, bt, l), acc);
+                else {
+                    const tile_tm<WT> t = tile_terms<WT>(qc, scc, load_act<WT, NSA>(smem, m, bt, l));
+                    if constexpr (WT == T_Q4_0) stash_i16(t, l, (int16_t *)my_s + cc.bt * BT, my_d + cc.bt * BT);
+                    else stash_f32<WT>(t, l, (float *)my_s + cc.bt * BT, my_d + cc.bt * BT);
+                }
                 if (cc.bt + 1 == nbt) {
                     // end of this wave's part of a (matrix, row tile)
                     if (KS == 1) {
@@ -1077,9 +951,9 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
                         // (7.5 clk/step): tests/micro/carry_bench*.hip.
                         float *hand = (float *)(smem + m.red);
                         if (wave == 0) hand[lane] = acc;
-                        if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 6] = __builtin_amdgcn_s_memrealtime();
+                        MV_STAMP(6);
                         __syncthreads();
-                        if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 7] = __builtin_amdgcn_s_memrealtime();
+                        MV_STAMP(7);
                         {
                             // one carrier wave: a wave pays ~16-21 clk per ds_read_b128 whatever its
                             // active lanes, so more carriers only add LDS-array contention
@@ -1088,7 +962,7 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
                             if (wave < NCAR && lane < RPW * 8) {
                                 float c = hand[gl];
                                 if (!(MV_ABLATE(a) & 4)) c = carry_chain<WT, KS>(st_s, st_d, m, seg_blocks, gl, c);
-                                if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 8] = __builtin_amdgcn_s_memrealtime();
+                                MV_STAMP(8);
                                 const float v = fold8(c);
                                 if constexpr (EPI == EPI_ADD) {
                                     if ((lane & 7) == 0) {
@@ -1100,12 +974,12 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
                                 } else if ((lane & 7) == 0) {
                                     epilogue<EPI>(a, col, cc.rt * 8 + (gl >> 3), v, 0.0f, best);
                                 }
-                                if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 9] = __builtin_amdgcn_s_memrealtime();
+                                MV_STAMP(9);
                             }
                         }
                         acc = 0.0f;
                         __syncthreads();
-                        if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 10] = __builtin_amdgcn_s_memrealtime();
+                        MV_STAMP(10);
                     }
                 }
                 if (++cc.bt == nbt) {
@@ -1118,7 +992,7 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
             }
         }
     }
-    if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 4] = __builtin_amdgcn_s_memrealtime();
+    MV_STAMP(4);
     if (EPI == EPI_GELU_MUL && yimg) {
         // y's Q8_0 image: group g = blockIdx.x + k*gridDim.x of 4 row tiles is block g of y
         __syncthreads();
@@ -1146,7 +1020,7 @@ __global__ void __launch_bounds__(512) k_matvec(const uint8_t *qs, const uint8_t
             a.argmax_key[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = best;
         }
     }
-    if (GHIP_STAMPS && a.dbg_t && tid == 0) a.dbg_t[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + 5] = __builtin_amdgcn_s_memrealtime();
+    MV_STAMP(5);
 }
 
 // gate/up with the two matrices on separate waves (launch_matvec ks = 2, EPI_GELU_MUL): wave w of a
@@ -1178,12 +1052,7 @@ __global__ void __launch_bounds__(512) k_matvec_gu2(mv_args a) {
     auto issue = [&](uint4 &qd, uint4 &sd) {  // past the last item the cursor stays (L2 re-read)
         const int64_t tile = rt_i * a.n_bt + bt_i;
         qd = ld_nt16(qsm + tile * 1024 + q_off);
-        if (WT == T_Q4_0) {
-            sd = ld_sc16(scm + tile * 8 * SB + s_off);
-        } else {
-            const uint2 v = ld_sc8(scm + tile * 8 * SB + s_off);
-            sd = make_uint4(v.x, v.y, 0, 0);
-        }
+        sd = ld_scale<WT>(scm + tile * 8 * SB + s_off);
         ++issued;
         if (issued < n_items && ++bt_i == nbt) {
             bt_i = 0;
@@ -1208,7 +1077,7 @@ __global__ void __launch_bounds__(512) k_matvec_gu2(mv_args a) {
             if (!ONE_SHOT) issue(qb[u], sb[u]);
             if (k + u < n_items) {
                 const act_tile<WT> at = load_act<WT, NSA>(smem, m, bt_c, l);
-                acc = tile_dot_a<WT>(q, sc, at, acc);
+                acc = tile_acc<WT>(q, sc, at, acc);
                 if (++bt_c == nbt) {
                     const float v = fold8(acc);
                     acc = 0.0f;
@@ -1227,7 +1096,7 @@ __global__ void __launch_bounds__(512) k_matvec_gu2(mv_args a) {
         const int j = (int)(t & 31);
         const int64_t rt = (int64_t)blockIdx.x * 4 + k * rstride + (j >> 3);
         if (rt >= a.n_rt) continue;
-        const float yv = gelu_tab(a, vbuf[(k * 2) * 32 + j]) * vbuf[(k * 2 + 1) * 32 + j];
+        const float yv = gelu_lookup(a.gelu_tab, a.gelu_clamp, vbuf[(k * 2) * 32 + j]) * vbuf[(k * 2 + 1) * 32 + j];
         const int64_t row = rt * 8 + (j & 7);
         if (row < a.rows) a.y[row] = yv;
         if (yimg) vbuf[(k * 2) * 32 + j] = yv;  // the image reads y from the gate slot
@@ -1272,8 +1141,8 @@ int launch_gu2(const mv_args &a, int grid_x, hipStream_t s) {
     const bool one_shot = rounds <= 1 && a.n_bt <= U;
     const void *fn = one_shot ? (const void *)k_matvec_gu2<WT, U, true> : (const void *)k_matvec_gu2<WT, U, false>;
     if (lds > 64 * 1024) GHIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (one_shot) hipLaunchKernelGGL((k_matvec_gu2<WT, U, true>), dim3(grid_x), dim3(512), lds, s, la);
-    else hipLaunchKernelGGL((k_matvec_gu2<WT, U, false>), dim3(grid_x), dim3(512), lds, s, la);
+    void *args[] = {(void *)&la};
+    GHIP_CHECK(hipLaunchKernel(fn, dim3(grid_x), dim3(512), args, lds, s));
     GHIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1296,10 +1165,6 @@ int launch_t(const mv_args &a, int grid_x, hipStream_t s) {
     const int threads = KS > 1 ? 64 * KS : 256;  // = k_matvec's NTH
     if (KS > 1 && a.n_bt % KS != 0) {
         set_error("matvec: n_bt not divisible by KS");
-        return -1;
-    }
-    if (m.total > 160 * 1024) {
-        set_error("matvec: LDS image too large");
         return -1;
     }
     // register ring depth (16 for gate/up measured slower: issue stalls at 32 loads per wave)
@@ -1326,12 +1191,9 @@ int launch_t(const mv_args &a, int grid_x, hipStream_t s) {
     const void *fn = os ? (const void *)k_matvec<WT, KS, PRO, EPI, U, R, NSA, KS != 1 || EPI == EPI_GELU_MUL>
                         : (const void *)k_matvec<WT, KS, PRO, EPI, U, R, NSA, false>;
     if (lds > 64 * 1024) GHIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (os)
-        hipLaunchKernelGGL((k_matvec<WT, KS, PRO, EPI, U, R, NSA, KS != 1 || EPI == EPI_GELU_MUL>), dim3(grid_x, a.ncols),
-                           dim3(threads), lds, s, la.qs, la.sc, la.qs2, la.sc2, la.n_bt, la.rt_q, la.rt_r, la);
-    else
-        hipLaunchKernelGGL((k_matvec<WT, KS, PRO, EPI, U, R, NSA, false>), dim3(grid_x, a.ncols), dim3(threads), lds, s, la.qs,
-                           la.sc, la.qs2, la.sc2, la.n_bt, la.rt_q, la.rt_r, la);
+    void *args[] = {(void *)&la.qs, (void *)&la.sc, (void *)&la.qs2, (void *)&la.sc2, (void *)&la.n_bt, (void *)&la.rt_q,
+                    (void *)&la.rt_r, (void *)&la};
+    GHIP_CHECK(hipLaunchKernel(fn, dim3(grid_x, a.ncols), dim3(threads), args, lds, s));
     GHIP_CHECK(hipGetLastError());
     return 0;
 }

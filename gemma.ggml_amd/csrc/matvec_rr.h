@@ -28,32 +28,18 @@ template <int WT> struct rr_geom {
     static constexpr size_t SLOT = S_BYTES + D_BYTES;
 };
 
-// exact (d, (float)isum) terms of one tile for this thread's (row, lane): the operands of the BT
-// fmaf steps tile_dot<WT, false> would apply, stored for the carrier (s as f32: the carrier's
-// chain is then LDS reads + fmaf only)
+// a loader's tile of a round: block tile bt's exact terms (tile_terms) into the f32 stash, at block
+// j0 of this lane's s run and this row's d run.
+// Q8_0 keeps its terms written out here, each sum converted before the block's scale product: the
+// same four tile_step terms through stash_f32 compile to another schedule of k_matvec_rr (the Q8_0
+// down, NR 16: 94 -> 96 VGPRs), traced 9.69 -> 9.74-9.77 us per launch, part of a Q8_0 decode
+// measured 0.4 % below the parent.  Written this way the kernel's code is unchanged.
 template <int WT>
-__device__ __forceinline__ void tile_terms(uint4 q, uint4 scv, const uint8_t *smem, const lds_map &m, int64_t bt, int l,
-                                           float *st_s, float *st_d, int j0) {
+__device__ __forceinline__ void rr_stash(uint4 q, uint4 scv, const uint8_t *smem, const lds_map &m, int64_t bt, int l,
+                                         float *st_s, float *st_d, int j0) {
     const act_tile<WT> t = load_act<WT, true>(smem, m, bt, l);
-    const uint32_t qv[4] = {q.x, q.y, q.z, q.w};
-    if constexpr (WT == T_Q4_0) {
-        const uint32_t sv[4] = {scv.x, scv.y, scv.z, scv.w};
-        float dd[8], ss[8];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const uint32_t lo = qv[p] & 0x0F0F0F0Fu, hi = (qv[p] >> 4) & 0x0F0F0F0Fu;
-            ss[2 * p] = (float)sdot4(lo, t.av[2 * p], (int)t.nv[2 * p]);
-            ss[2 * p + 1] = (float)sdot4(hi, t.av[2 * p + 1], (int)t.nv[2 * p + 1]);
-            dd[2 * p] = mix_lo(sv[p], t.dav[2 * p]);
-            dd[2 * p + 1] = mix_hi(sv[p], t.dav[2 * p + 1]);
-        }
-        *(float4 *)(st_s + j0) = make_float4(ss[0], ss[1], ss[2], ss[3]);
-        *(float4 *)(st_s + j0 + 4) = make_float4(ss[4], ss[5], ss[6], ss[7]);
-        if (l == 0) {
-            *(float4 *)(st_d + j0) = make_float4(dd[0], dd[1], dd[2], dd[3]);
-            *(float4 *)(st_d + j0 + 4) = make_float4(dd[4], dd[5], dd[6], dd[7]);
-        }
-    } else {
+    if constexpr (WT == T_Q8_0) {
+        const uint32_t qv[4] = {q.x, q.y, q.z, q.w};
         const uint32_t sv[2] = {scv.x, scv.y};
         float dd[4], ss[4];
 #pragma unroll
@@ -63,6 +49,8 @@ __device__ __forceinline__ void tile_terms(uint4 q, uint4 scv, const uint8_t *sm
         }
         *(float4 *)(st_s + j0) = make_float4(ss[0], ss[1], ss[2], ss[3]);
         if (l == 0) *(float4 *)(st_d + j0) = make_float4(dd[0], dd[1], dd[2], dd[3]);
+    } else {
+        stash_f32<WT>(tile_terms<WT>(q, scv, t), l, st_s + j0, st_d + j0);
     }
 }
 

@@ -54,12 +54,7 @@ __global__ void __launch_bounds__(RR_NTH) k_matvec_rr(const void *x, const float
     auto issue = [&](int r) {
         const int64_t tile = rt * a.n_bt + (loader ? wave : 0) + RR_NL * r;
         qb[r % D] = ld_nt16(a.qs + tile * 1024 + q_off);
-        if (WT == T_Q4_0) {
-            sb[r % D] = ld_sc16(a.sc + tile * 8 * SB + s_off);
-        } else {
-            const uint2 v = ld_sc8(a.sc + tile * 8 * SB + s_off);
-            sb[r % D] = make_uint4(v.x, v.y, 0, 0);
-        }
+        sb[r % D] = ld_scale<WT>(a.sc + tile * 8 * SB + s_off);
     };
     // (weight rounds issued before the activation, or right behind its loads, measured slower: DESIGN.md §10)
     act_regs<R> ar;
@@ -117,7 +112,7 @@ __global__ void __launch_bounds__(RR_NTH) k_matvec_rr(const void *x, const float
             if (MV_ABLATE(a) & 8)  // timing only: consume the loads without the dot products
                 acc += __builtin_bit_cast(float, q.x ^ sc.y);
             else
-                tile_terms<WT>(q, sc, smem, m, wave + RR_NL * r, l, st, sd, wave * BT);
+                rr_stash<WT>(q, sc, smem, m, wave + RR_NL * r, l, st, sd, wave * BT);
             if (r + D < NR) issue(r + D);
             if (GHIP_STAMPS && stp && lane == 0 && wave == 0 && r < 8) stp[2 + r] = __builtin_amdgcn_s_memrealtime();
             if (GHIP_STAMPS && stp && lane == 0 && wave == RR_NL - 1 && r == NR - 1) stp[15] = __builtin_amdgcn_s_memrealtime();

@@ -284,31 +284,6 @@ __device__ void norm_quant(bool aux, int atid, const float *xf, const norm_w<E> 
     }
 }
 
-// Q4_0 exact terms of one tile into the int16 stash (tile_dot<T_Q4_0, STASH>'s packing, on the
-// operands of load_act): s of blocks (2p, 2p+1) in dword p, d as 8 floats (lane 0 of the row)
-template <bool NSA>
-__device__ __forceinline__ void terms16(uint4 q, uint4 scv, const uint8_t *img, const lds_map &m, int bt, int l,
-                                        int16_t *st_s, float *st_d) {
-    const act_tile<T_Q4_0> t = load_act<T_Q4_0, NSA>(img, m, bt, l);
-    const uint32_t qv[4] = {q.x, q.y, q.z, q.w}, sv[4] = {scv.x, scv.y, scv.z, scv.w};
-    uint32_t pk[4];
-    float dk[8];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const uint32_t lo = qv[p] & 0x0F0F0F0Fu, hi = (qv[p] >> 4) & 0x0F0F0F0Fu;
-        const int s0 = sdot4(lo, t.av[2 * p], (int)t.nv[2 * p]);
-        const int s1 = sdot4(hi, t.av[2 * p + 1], (int)t.nv[2 * p + 1]);
-        pk[p] = ((uint32_t)s0 & 0xFFFFu) | ((uint32_t)s1 << 16);
-        dk[2 * p] = mix_lo(sv[p], t.dav[2 * p]);
-        dk[2 * p + 1] = mix_hi(sv[p], t.dav[2 * p + 1]);
-    }
-    *(uint4 *)st_s = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-    if (l == 0) {
-        *(float4 *)st_d = make_float4(dk[0], dk[1], dk[2], dk[3]);
-        *(float4 *)(st_d + 4) = make_float4(dk[4], dk[5], dk[6], dk[7]);
-    }
-}
-
 // the carrier wave pulls a norm weight vector (E floats) into its XCD's L2 ahead of the norm that
 // reads it (the ring's nt weight stream leaves it cold otherwise); the loads are consumed by a
 // test that never holds
@@ -316,12 +291,6 @@ __device__ __forceinline__ void touch_l2(const float *p, int n, int lane, float 
     float acc = 0.0f;
     for (int i = lane * 4; i < n; i += 256) acc += *(const float *)(p + i);
     if (acc == 1.0e-30f) *sink = acc;
-}
-
-__device__ __forceinline__ float gelu_of(ctok &a, float x) {
-    if (a.gelu_clamp && x <= -10.0f) return 0.0f;
-    if (a.gelu_clamp && x >= 10.0f) return x;
-    return h2f(a.gelu_tab[f2h(x)]);
 }
 
 // the args live in device memory and are re-read (scalar cache) where used: an opaque copy of the
@@ -494,12 +463,14 @@ __global__ void __launch_bounds__(TK_NTH) k_token(const tok_args *ap) {
                 pop(q, s);
                 const int bt = wave + TK_TW * (r % per_rt);
                 uint8_t *sb = slot_base(r);
+                // the tile's exact terms into the round's stash (Q4_0: s as int16, the carry_ring<true> chunks)
+                float *st_d = (float *)(sb + ST::S_BYTES) + rr * ST::SBPD + wave * BT;
                 if constexpr (ST::I16)
-                    terms16<NSA>(q, s, img, m, bt, l, (int16_t *)sb + lane * ST::SBP + wave * BT,
-                                 (float *)(sb + ST::S_BYTES) + rr * ST::SBPD + wave * BT);
+                    stash_i16(tile_terms<WT>(q, s, load_act<WT, NSA>(img, m, bt, l)), l,
+                              (int16_t *)sb + lane * ST::SBP + wave * BT, st_d);
                 else
-                    tile_terms<WT>(q, s, img, m, bt, l, (float *)sb + lane * ST::SBP, (float *)(sb + ST::S_BYTES) + rr * ST::SBPD,
-                                   wave * BT);
+                    stash_f32<WT>(tile_terms<WT>(q, s, load_act<WT, true>(img, m, bt, l)), l,
+                                  (float *)sb + lane * ST::SBP + wave * BT, st_d);
                 if (nround > 4 && r == 0) TK_STAMP(stamp_layer, 14);
                 if (nround > 4 && r == nround - 1) TK_STAMP(stamp_layer, 15);
                 lds_barrier();
@@ -651,8 +622,8 @@ __global__ void __launch_bounds__(TK_NTH) k_token(const tok_args *ap) {
                 pop(qg, sg);
                 pop(qu, su);
                 const act_tile<WT> at = load_act<WT, true>(img, m_e, bt, l);
-                accg = tile_dot_a<WT>(qg, sg, at, accg);
-                accu = tile_dot_a<WT>(qu, su, at, accu);
+                accg = tile_acc<WT>(qg, sg, at, accg);
+                accu = tile_acc<WT>(qu, su, at, accu);
             }
             const float vg = fold8(accg), vu = fold8(accu);
             if (l == 0) {  // gelu on the aux side: the table lookup is a load the ring would hold up
@@ -676,7 +647,7 @@ __global__ void __launch_bounds__(TK_NTH) k_token(const tok_args *ap) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const int row = bl * 32 + q * 8 + j;
-                    v[j] = gelu_of(a, hbuf[row]) * hbuf[64 + row];  // gelu(gate) then ggml_mul by up
+                    v[j] = gelu_lookup(a.gelu_tab, a.gelu_clamp, hbuf[row]) * hbuf[64 + row];  // gelu(gate) then ggml_mul by up
                 }
                 image_put_quad_gran(a.gh, a.gh_da, tg, (int64_t)2 * c + bl, q, v);
             }

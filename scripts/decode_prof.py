@@ -29,7 +29,7 @@ BENCH_R04_PLAN = "9,1,0,9,1,0,1,1,0,9,1,1,1,8,0"
 def main():
     steps = int(sys.argv[1]) if len(sys.argv) > 1 else 32
     graph = os.environ.get("GHIP_PROF_GRAPH", "0") == "1"
-    e = G.Engine(GEMMA_2B, n_ctx=512, device=0)
+    e = G.Engine(GEMMA_2B, n_ctx=512, device=0, wtype=int(os.environ.get("WTYPE", "2")))  # 8: the Q8_0 leg
     if os.environ.get("PROF_MAPS"):  # the process's mappings (symbolizes a native crash exactly)
         with open("/proc/self/maps") as f, open(os.environ["PROF_MAPS"], "w") as g:
             g.write(f.read())

@@ -198,6 +198,28 @@ def test_matvec_rr(wtype, ncols, pro, epi):
     _run(wtype, KS_RR, pro, epi, rows=20, K=_smallest_rr_k(wtype), ncols=ncols, grid=1, seed=13 + pro)
 
 
+# K-split carry: the smallest (ks, K) of each chunk count class.  The carrier chains (ks-1) * n_bt / ks
+# chunks (a block tile: K 256 for Q4_0, 128 for Q8_0): whole ring turns of 4, then 0-3 remaining chunks.
+_CARRY = {  # chunk count -> (ks, K) for (Q4_0, Q8_0)
+    1: ((2, 512), (2, 256)),     # remainder only
+    2: ((2, 1024), (2, 512)),
+    3: ((4, 1024), (4, 512)),
+    4: ((2, 2048), (2, 1024)),   # ring only
+    7: ((8, 2048), (8, 1024)),   # ring + 3; the ks 8 LDS map (without the ns plane)
+}
+
+
+@gpu
+@TYPES
+@NCOLS
+@pytest.mark.parametrize("chunks", sorted(_CARRY), ids=[f"chunks{c}" for c in sorted(_CARRY)])
+@pytest.mark.parametrize("pro,epi", [(PRO_F32, EPI_ADD), (PRO_NORM, EPI_STORE)], ids=["f32_add", "norm_store"])
+def test_matvec_ksplit_carry(wtype, ncols, chunks, pro, epi):
+    """13 rows = two row tiles, the second partial; one workgroup takes both through the refilled ring"""
+    ks, K = _CARRY[chunks][0 if wtype == O.Q4_0 else 1]
+    _run(wtype, ks, pro, epi, rows=13, K=K, ncols=ncols, grid=1, seed=20 + chunks)
+
+
 def _attn_case(rng, pos, H, Hkv, hd, ctx):
     qkv = rng.standard_normal((H + 2 * Hkv) * hd).astype(np.float32)
     kvw = Hkv * hd
