@@ -776,8 +776,9 @@ int seq_alloc(gemma_engine *e, dev_pool &M, seq_state &S, bool caches, int *toke
     S = seq_state{};
     if (caches && (M.get_zeroed(&S.kc, kv_bytes, s) || M.get_zeroed(&S.vc, kv_bytes, s))) return -1;
     if (M.get_zeroed(&S.hist, (size_t)(c.n_ctx + 1) * 4, s) || M.get_zeroed(&S.pos, 4, s) || M.get_zeroed(&S.nfix, 4, s) ||
-        M.get_zeroed(&S.rope, (size_t)(c.head_dim + 4) * 4, s))
+        M.get_zeroed(&S.rope, (size_t)(c.head_dim + 4) * 4, s) || M.get(&S.lp, (size_t)(c.n_ctx + 1) * 8))
         return -1;
+    GHIP_CHECK(hipMemsetAsync(S.lp, 0xFF, (size_t)(c.n_ctx + 1) * 8, s));  // NaN: nothing is scored
     S.token = token_word;
     return token_word ? 0 : M.get_zeroed(&S.token, 4, s);
 }
@@ -796,6 +797,7 @@ int seq_begin(gemma_engine *e, seq_state &S, const int32_t *tokens, int n) {
     }
     GHIP_CHECK(hipMemsetAsync(S.hist, 0, (size_t)(c.n_ctx + 1) * 4, s));
     GHIP_CHECK(hipMemcpyAsync(S.hist, tokens, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    GHIP_CHECK(hipMemsetAsync(S.lp, 0xFF, (size_t)(c.n_ctx + 1) * 8, s));  // all-ones bytes: an f64 NaN, "not scored"
     GHIP_CHECK(hipMemsetAsync(S.pos, 0, 4, s));
     const size_t half = (size_t)c.head_dim / 2;  // RoPE row of position 0
     GHIP_CHECK(hipMemcpyAsync(S.rope, e->rope_cos, half * 4, hipMemcpyDeviceToDevice, s));
@@ -817,6 +819,7 @@ int seq_copy(gemma_engine *e, seq_state &dst, const seq_state &src) {
         GHIP_CHECK(hipMemcpyAsync(vc_of(e, dst, il), vc_of(e, src, il), layer * 2, hipMemcpyDeviceToDevice, s));
     }
     GHIP_CHECK(hipMemcpyAsync(dst.hist, src.hist, (size_t)(c.n_ctx + 1) * 4, hipMemcpyDeviceToDevice, s));
+    GHIP_CHECK(hipMemcpyAsync(dst.lp, src.lp, (size_t)(c.n_ctx + 1) * 8, hipMemcpyDeviceToDevice, s));
     GHIP_CHECK(hipMemcpyAsync(dst.pos, src.pos, 4, hipMemcpyDeviceToDevice, s));
     GHIP_CHECK(hipMemcpyAsync(dst.nfix, src.nfix, 4, hipMemcpyDeviceToDevice, s));
     GHIP_CHECK(hipMemcpyAsync(dst.token, src.hist + src.host_pos, 4, hipMemcpyDeviceToDevice, s));
@@ -842,6 +845,19 @@ int seq_kv_read(gemma_engine *e, const seq_state &S, int layer, int p0, int n, u
     for (size_t j = 0; j < kvw; ++j)
         for (size_t r = 0; r < (size_t)n; ++r) v_rows[r * kvw + j] = vt[j * (size_t)n + r];
     return 0;
+}
+
+int seq_logprobs(gemma_engine *e, const seq_state &S, int p0, int n, double *out, const char *fn) {
+    const int n_seq = std::max(S.host_pos + 1, S.n_given);  // the sequence so far: given tokens and the pending pick
+    if (p0 < 0 || n < 0 || (int64_t)p0 + n > n_seq || (n > 0 && !out)) {
+        set_error(std::string(fn) + ": [" + std::to_string(p0) + ", " + std::to_string((int64_t)p0 + n) + ") outside [0, n_seq = " +
+                  std::to_string(n_seq) + "), or a null buffer");
+        return -1;
+    }
+    (void)hipSetDevice(e->device);
+    GHIP_CHECK(hipStreamSynchronize(e->stream));
+    if (n) GHIP_CHECK(hipMemcpy(out, S.lp + p0, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return n;
 }
 
 int seq_tokens(const seq_state &S, int32_t *out, int cap) {
@@ -892,6 +908,8 @@ extern "C" int gemma_engine_extend(gemma_engine *e, int keep, const int32_t *tok
     }
     GHIP_CHECK(hipMemsetAsync(e->seq.hist + keep, 0, (ctx + 1 - (size_t)keep) * 4, s));
     GHIP_CHECK(hipMemcpyAsync(e->seq.hist + keep, tokens, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    // row keep - 1 is not recomputed: lp[keep] is "not scored" with everything behind it
+    GHIP_CHECK(hipMemsetAsync(e->seq.lp + keep, 0xFF, (ctx + 1 - (size_t)keep) * 8, s));
     GHIP_CHECK(hipMemsetAsync(e->key, 0, (size_t)e->grid_big * 8, s));
     // *pos = keep, its RoPE row with the position word, *n_fixed = keep + n, the epoch bump
     if (launch_set_position(tokens[0], keep, e->seq.pos, e->seq.hist, e->seq.nfix, keep + n, rope_of(e), s)) return -1;
@@ -982,6 +1000,11 @@ extern "C" int gemma_engine_tokens(gemma_engine *e, int32_t *out, int cap) {
 }
 
 extern "C" int gemma_engine_pos(gemma_engine *e) { return e->seq.host_pos; }
+
+extern "C" int gemma_engine_logprobs(gemma_engine *e, int p0, int n, double *out) {
+    set_error("");
+    return seq_logprobs(e, e->seq, p0, n, out, "gemma_engine_logprobs");
+}
 
 extern "C" int64_t gemma_engine_tensor(gemma_engine *e, int tid, void *dst, int64_t cap) {
     set_error("");

@@ -74,6 +74,7 @@ static int batch_open(gemma_engine *e, int n_slots, int max_slots, const std::st
         set_error(fn + ": " + why);
         return -1;
     }
+    b.picks.lp_parts = b.pf.LP;  // more rows than the engine's partials hold: the scratch's own (else null)
     b.n_slots = n_slots;
     b.open = true;
     return 0;
@@ -161,7 +162,7 @@ static int batch_write_rows(gemma_engine *e) {
         r.out = b.pf.ATT + (size_t)R * e->qw;
         const seq_state &S = b.slot[i];
         r.kc = S.kc; r.vc = S.vc; r.rope = S.rope;
-        r.hist = S.hist; r.pos = S.pos; r.nfix = S.nfix; r.last = S.token;
+        r.hist = S.hist; r.pos = S.pos; r.nfix = S.nfix; r.last = S.token; r.lp = S.lp;
         h[R] = r;
         b.row_slot[R] = i;
         GHIP_CHECK(hipMemcpyAsync(b.row_tok + R, S.token, 4, hipMemcpyDeviceToDevice, s));  // = hist[pos]
@@ -223,6 +224,7 @@ extern "C" int gemma_engine_batch_step(gemma_engine *e, int n, float *logits) {
         if (logits)
             GHIP_CHECK(hipMemcpyAsync(logits + (size_t)i * R * c.n_vocab, b.pf.LG, (size_t)R * c.n_vocab * 4, hipMemcpyDeviceToHost, s));
         if (launch_batch_advance(b.rows, R, pk.keys, pk.n_parts, pk.stride, b.row_tok, c.n_ctx, rope_of(e), s)) return -1;
+        if (enqueue_lp_finish(e, b.pf.LG, R, b.picks.lp_parts, nullptr, b.rows, nullptr)) return -1;
     }
     GHIP_CHECK(hipStreamSynchronize(s));
     for (int i = 0; i < b.n_slots; ++i)
@@ -295,4 +297,14 @@ extern "C" int gemma_engine_batch_kv_read(gemma_engine *e, int slot, int layer, 
     set_error("");
     if (!slot_ok(e, slot, "gemma_engine_batch_kv_read")) return -1;
     return seq_kv_read(e, e->bt.slot[slot], layer, p0, n, k_rows, v_rows, "gemma_engine_batch_kv_read");
+}
+
+extern "C" int gemma_engine_batch_logprobs(gemma_engine *e, int slot, int p0, int n, double *out) {
+    set_error("");
+    if (!slot_ok(e, slot, "gemma_engine_batch_logprobs")) return -1;
+    if (!e->bt.slot[slot].active) {
+        set_error("gemma_engine_batch_logprobs: slot " + std::to_string(slot) + " is not active");
+        return -1;
+    }
+    return seq_logprobs(e, e->bt.slot[slot], p0, n, out, "gemma_engine_batch_logprobs");
 }

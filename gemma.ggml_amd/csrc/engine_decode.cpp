@@ -174,9 +174,40 @@ int enqueue_pick_keys(gemma_engine *e, const float *row, const int *pos, const u
     return 0;
 }
 
-int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *keys, int n_parts) {
+int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *keys, int n_parts, const float *rows0, int R,
+                 lse_part *own) {
+    if (!rows0) { rows0 = row; R = 1; }
+    if (enqueue_lp_parts(e, rows0, R, own)) return -1;
     if (enqueue_pick_keys(e, row, e->seq.pos, &keys, &n_parts)) return -1;
-    return launch_advance(keys, n_parts, e->seq.token, e->seq.pos, e->seq.hist, e->cfg.n_ctx, e->seq.nfix, rope_of(e), e->stream);
+    if (launch_advance(keys, n_parts, e->seq.token, e->seq.pos, e->seq.hist, e->cfg.n_ctx, e->seq.nfix, rope_of(e), e->stream)) return -1;
+    return enqueue_lp_finish(e, rows0, R, own, &e->seq, nullptr, nullptr);
+}
+
+// The log-probabilities of a pass's rows (logprob.hip): the partials need the rows only and go right
+// behind the logits launch; the finish reads the token the advance settled.  Off: nothing is launched.
+static lse_part *lp_parts_of(gemma_engine *e, int R, lse_part *own) {
+    if (own) return own;
+    if (R <= GEMM_SKINNY_MAX_T && e->lp_parts) return e->lp_parts;
+    set_error("logprobs: no partials for a pass of " + std::to_string(R) + " rows");
+    return nullptr;
+}
+
+int enqueue_lp_parts(gemma_engine *e, const float *LG, int R, lse_part *own) {
+    if (!e->logprobs) return 0;
+    lse_part *parts = lp_parts_of(e, R, own);
+    return parts ? launch_lse_parts(LG, e->cfg.n_vocab, R, e->cfg.n_vocab, parts, e->stream) : -1;
+}
+
+int enqueue_lp_finish(gemma_engine *e, const float *LG, int R, lse_part *own, const seq_state *S, const slot_row *tab,
+                      const int *acc) {
+    if (!e->logprobs) return 0;
+    lse_finish_args a;
+    a.lg = LG; a.ld = e->cfg.n_vocab; a.n = e->cfg.n_vocab; a.R = R; a.G = lse_grid(e->cfg.n_vocab); a.n_ctx = e->cfg.n_ctx;
+    a.parts = lp_parts_of(e, R, own);
+    if (!a.parts) return -1;
+    a.tab = tab; a.acc = acc;
+    if (S) { a.pos = S->pos; a.hist = S->hist; a.lp = S->lp; }
+    return launch_lse_finish(a, e->stream);
 }
 
 // The picks of a pass's T rows, none advancing: the verify pass then accepts a prefix, the batch pass
@@ -193,6 +224,7 @@ int enqueue_row_picks(gemma_engine *e, const float *LG, int T, const int *pos, c
         set_error("row picks: a pass of " + std::to_string(T) + " rows");
         return -1;
     }
+    if (enqueue_lp_parts(e, LG, T, b.lp_parts)) return -1;  // (the caller's advance is followed by enqueue_lp_finish)
     if (!e->sampling) {
         if (launch_row_argmax(LG, V, b.keys, 256, e->stream, T, V)) return -1;
         *out = row_picks{b.keys, 256, 256};

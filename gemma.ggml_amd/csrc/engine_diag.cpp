@@ -398,6 +398,69 @@ extern "C" int gemma_engine_sampler(const gemma_engine *e, gemma_sampler *out) {
     return e->sampling ? 1 : 0;
 }
 
+// Per-token log-probabilities on / off (include/gemma_hpc.h).  On adds k_lse_parts and k_lse_finish
+// behind every pick, so the decode graph's node set changes and it is dropped, as for the sampler.
+// The engine's 8 rows of partials are made once and kept (the captured graph holds them).
+extern "C" int gemma_engine_set_logprobs(gemma_engine *e, int on) {
+    set_error("");
+    if (on < 0) return e->logprobs ? 1 : 0;
+    if (on && (row_split(e) || e->tp_n_keys)) {
+        set_error("gemma_engine_set_logprobs: row-split engines hold a vocabulary shard per rank; a log-probability needs the "
+                  "whole row (single-GPU engines only)");
+        return -1;
+    }
+    if (on && e->cfg.n_vocab > (int64_t)LSE_MAX_G * LSE_CHUNK) {
+        set_error("gemma_engine_set_logprobs: n_vocab above " + std::to_string((int64_t)LSE_MAX_G * LSE_CHUNK));
+        return -1;
+    }
+    (void)hipSetDevice(e->device);
+    if (on && !e->lp_parts &&
+        e->mem.get(&e->lp_parts, (size_t)GEMM_SKINNY_MAX_T * lse_grid(e->cfg.n_vocab) * sizeof(lse_part)))
+        return -1;
+    if ((on != 0) != e->logprobs) {
+        e->logprobs = on != 0;
+        drop_graph(e);
+    }
+    return e->logprobs ? 1 : 0;
+}
+
+// Test hook: logprob(rows[r], tokens[r]) through the two kernels, the rows as one sequence: row r
+// predicts sequence index r + 1, whose token is tokens[r]
+extern "C" int gemma_test_logprob(const float *logits, int rows, int n_vocab, const int32_t *tokens, double *out) {
+    set_error("");
+    if (!logits || !tokens || !out || rows < 1 || rows > 65535 || n_vocab < 1 || n_vocab > LSE_MAX_G * LSE_CHUNK) {
+        set_error("gemma_test_logprob: logits, tokens, out, rows in [1, 65535] and n_vocab in [1, " +
+                  std::to_string(LSE_MAX_G * LSE_CHUNK) + "] are required");
+        return -1;
+    }
+    for (int r = 0; r < rows; ++r)
+        if (tokens[r] < 0 || tokens[r] >= n_vocab) {
+            set_error("gemma_test_logprob: token id " + std::to_string(tokens[r]) + " out of range [0, n_vocab)");
+            return -1;
+        }
+    dev_pool tmp;
+    float *dl = nullptr;
+    int *dh = nullptr, *dpos = nullptr;
+    double *dlp = nullptr;
+    lse_part *dp = nullptr;
+    const size_t row_b = (size_t)n_vocab * 4;
+    if (tmp.get(&dl, row_b * rows) || tmp.get(&dh, (size_t)(rows + 1) * 4) || tmp.get(&dpos, 4) ||
+        tmp.get(&dlp, (size_t)(rows + 1) * 8) || tmp.get(&dp, (size_t)rows * lse_grid(n_vocab) * sizeof(lse_part)))
+        return -1;
+    GHIP_CHECK(hipMemcpy(dl, logits, row_b * rows, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemset(dh, 0, 4));
+    GHIP_CHECK(hipMemcpy(dh + 1, tokens, (size_t)rows * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(dpos, &rows, 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemset(dlp, 0xFF, (size_t)(rows + 1) * 8));
+    lse_finish_args a;
+    a.lg = dl; a.ld = n_vocab; a.n = n_vocab; a.R = rows; a.G = lse_grid(n_vocab); a.n_ctx = rows;
+    a.parts = dp; a.pos = dpos; a.hist = dh; a.lp = dlp;
+    if (launch_lse_parts(dl, n_vocab, rows, n_vocab, dp, nullptr) || launch_lse_finish(a, nullptr)) return -1;
+    GHIP_CHECK(hipDeviceSynchronize());
+    GHIP_CHECK(hipMemcpy(out, dlp + 1, (size_t)rows * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // Test hook: the sampler's three launches on `rows` host rows of n_vocab logits, row r at sequence
 // index positions[r]; the same kernels, scratch and device parameter struct as the engine's step.
 extern "C" int gemma_test_sample(const float *logits, int rows, int n_vocab, const gemma_sampler *sp, const int32_t *positions,

@@ -67,6 +67,9 @@ struct pf_scratch {
     uint16_t *XM = nullptr;  // K-quant prefill: the Q4_K mins operand of the Q8_K image (k_q8k_expand)
     uint8_t *XQ8K = nullptr;  // Q6_K head: the T Q8_K rows of rms_norm(x)*out_norm
     void *keys = nullptr;
+    // log-probabilities: the partials of a pass of more than 8 rows, [T][G] (the engine's scratch: made
+    // while they are on; a wide batch's: always, so nothing moves while it is open); else null
+    lse_part *LP = nullptr;
 };
 
 // ---- a sequence (engine.cpp) ---- ---------------------------------------------------
@@ -77,6 +80,7 @@ struct pf_scratch {
 struct seq_state {
     uint16_t *kc = nullptr, *vc = nullptr;  // [L][ctx][kvw], [L][kvw][ctx] (null: the engine's own on external caches)
     int *hist = nullptr;                    // [ctx + 1] the tokens by position
+    double *lp = nullptr;                   // [ctx + 1] log-probability of hist[i] under the row before it (NaN: not scored)
     int *pos = nullptr, *nfix = nullptr;    // processed positions; given tokens (hist below *nfix is never overwritten)
     // the token word.  The engine's own: always the last pick (also inside the given tokens).  A
     // slot's: the pending token hist[*pos] (-1: inactive), a word of batch_state::last
@@ -91,6 +95,7 @@ static constexpr int PICK_MAX_ROWS = GEMMA_BATCH_WIDE_MAX_SLOTS;
 struct pick_buf {
     unsigned long long *keys = nullptr;  // device: [64][256] greedy partial keys, then [64] sampler key slots
     sample_ws ws;                        // a wide batch's own sampler workspaces (else the engine's 8: smp_ws)
+    lse_part *lp_parts = nullptr;        // a wide batch's own log-probability partials (else the engine's 8 rows: lp_parts)
 };
 
 // ---- batched decode (engine_batch.cpp, DESIGN.md §5b⁗) ------------------------------------------
@@ -230,6 +235,9 @@ struct gemma_engine {
     sampler_params smp_host;              // their device form (source of the stream-ordered copy)
     sampler_params *smp_dev = nullptr;
     sample_ws smp_ws;                     // allocated when sampling is first turned on
+    // per-token log-probabilities (gemma_engine_set_logprobs; logprob.hip): off = nothing below is used
+    bool logprobs = false;
+    lse_part *lp_parts = nullptr;         // [8][G] partials (step, verify, narrow batch); allocated when first turned on
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     // flow control of gemma_engine_step: an event every FC_EVERY graph launches, FC_SLOTS of them
@@ -380,7 +388,9 @@ int seq_tokens(const seq_state &S, int32_t *out, int cap);
 int enqueue_step(gemma_engine *e);
 // the token of position *pos + 1 and the advance: the sampler on `row` when sampling is on, else
 // the greedy argmax keys (n_parts of them) exactly as before
-int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *keys, int n_parts);
+// rows0 / R: the pass's R rows that end with `row` (a prefill), all scored when log-probabilities are on
+int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *keys, int n_parts, const float *rows0 = nullptr,
+                 int R = 1, lse_part *own = nullptr);
 // the pick alone, no advance: with sampling on, the sampler's draw for sequence index *pos + 1 from
 // `row` into the sampler's own key slot, *keys / *n_parts set to that one key; sampling off: nothing
 // is launched and the caller's greedy keys stand
@@ -394,6 +404,16 @@ struct row_picks {
     int n_parts = 0, stride = 0;
 };
 int pick_buf_alloc(dev_pool &M, pick_buf &b, hipStream_t s);  // zeroed on s
+// Log-probabilities of a pass's R rows LG [R][n_vocab] (nothing is launched while they are off).
+// enqueue_lp_parts: the rows' partials, right after the logits (enqueue_pick and enqueue_row_picks
+// issue it); own: partials of the pass's own, else the engine's 8 rows.  enqueue_lp_finish: after the
+// advance, lp[q] of every row; the rows are a row table's (tab), or consecutive positions of S ending
+// at *S.pos (acc: the device word of a verify pass's accepted count, rows past it are not scored)
+int enqueue_lp_parts(gemma_engine *e, const float *LG, int R, lse_part *own);
+int enqueue_lp_finish(gemma_engine *e, const float *LG, int R, lse_part *own, const seq_state *S, const slot_row *tab,
+                      const int *acc);
+// lp[p0 .. p0 + n) of S into out after one synchronise; fn names the caller in the range error
+int seq_logprobs(gemma_engine *e, const seq_state &S, int p0, int n, double *out, const char *fn);
 int enqueue_row_picks(gemma_engine *e, const float *LG, int T, const int *pos, const slot_row *tab, const pick_buf &b,
                       row_picks *out);
 int tok_prepare(gemma_engine *e);

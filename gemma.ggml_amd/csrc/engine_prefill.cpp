@@ -8,8 +8,10 @@
 // prefill buffers (lazily sized for the largest pass seen: the prompt, or a gemma_engine_prefill_next
 // chunk).  A regrow drops the whole scratch and makes it anew; pf.T is set last, so a failed regrow
 // leaves T = 0 and no pointer to freed memory.
-static int scratch_alloc(gemma_engine *e, dev_pool &M, pf_scratch &p, int T) {
-    if (p.T >= T) return 0;
+// parts: the scratch also holds the log-probability partials of its rows (passes of more than 8 rows)
+static int scratch_alloc(gemma_engine *e, dev_pool &M, pf_scratch &p, int T, bool parts) {
+    if (p.T >= T && (!parts || p.LP)) return 0;
+    T = std::max(T, p.T);
     M.clear();
     p = {};
     const gemma_hip_config &c = e->cfg;
@@ -23,7 +25,8 @@ static int scratch_alloc(gemma_engine *e, dev_pool &M, pf_scratch &p, int T) {
         // K-quant layers: XQ holds T Q8_K columns (292 B per 256 values) instead of the int8 image
         M.get(&p.XQ, (size_t)T * (e->kq ? p.ldq / 256 * 292 : p.ldq)) || M.get(&p.XH, (size_t)T * p.ldq * 2) ||
         M.get(&p.XM, (size_t)T * (p.ldq / 256) * 32) || M.get(&p.keys, 256 * 8) ||
-        (e->out_type == T_Q6_K && M.get(&p.XQ8K, (size_t)T * (E / 256) * 292))) {
+        (e->out_type == T_Q6_K && M.get(&p.XQ8K, (size_t)T * (E / 256) * 292)) ||
+        (parts && M.get(&p.LP, (size_t)T * lse_grid(c.n_vocab) * sizeof(lse_part)))) {
         M.clear();
         p = {};
         return -1;
@@ -31,7 +34,9 @@ static int scratch_alloc(gemma_engine *e, dev_pool &M, pf_scratch &p, int T) {
     p.T = T;
     return 0;
 }
-static int prefill_alloc(gemma_engine *e, int T) { return scratch_alloc(e, e->pf_mem, e->pf, T); }
+static int prefill_alloc(gemma_engine *e, int T) {
+    return scratch_alloc(e, e->pf_mem, e->pf, T, e->logprobs && T > GEMM_SKINNY_MAX_T);
+}
 
 // What the T rows of a pass are.  Every scratch buffer is indexed by the row t; the rows description
 // says where the T token ids come from and what runs at a layer's attention step:
@@ -62,6 +67,7 @@ static pf_scratch scratch_of(gemma_engine *e, const pass_rows &rows) {
     p.XQ += r * (e->kq ? p.ldq / 256 * 292 : p.ldq); p.XH += r * p.ldq;
     p.XM += r * (p.ldq / 256) * 16;  // 32 bytes per 256 values
     if (p.XQ8K) p.XQ8K += r * (c.n_embd / 256) * 292;
+    if (p.LP) p.LP += r * lse_grid(c.n_vocab);
     return p;
 }
 
@@ -200,7 +206,8 @@ static int enqueue_prefill(gemma_engine *e, int T, const pass_rows &rows, bool e
     if (!e->sampling && launch_row_argmax(last_row, c.n_vocab, (unsigned long long *)p.keys, 256, s)) return -1;
     const int last = p0 + T - 1;
     GHIP_CHECK(hipMemcpyAsync(e->seq.pos, &last, 4, hipMemcpyHostToDevice, s));
-    return enqueue_pick(e, last_row, (const unsigned long long *)p.keys, 256);
+    // (log-probabilities on: all T rows are scored, row t against hist[p0 + t + 1])
+    return enqueue_pick(e, last_row, (const unsigned long long *)p.keys, 256, p.LG, T, T > GEMM_SKINNY_MAX_T ? p.LP : nullptr);
 }
 
 // Batched prefill for K-quant layers (the reference's shipped Q4_K_M model, src/app.cpp:36): the
@@ -281,7 +288,7 @@ int enqueue_verify_pass(gemma_engine *e, int T, int p0) {
 
 int batch_scratch_alloc(gemma_engine *e, int rows) {
     e->bt.pf = {};
-    return scratch_alloc(e, e->bt_mem, e->bt.pf, std::max(rows, GEMM_SKINNY_MAX_T));
+    return scratch_alloc(e, e->bt_mem, e->bt.pf, std::max(rows, GEMM_SKINNY_MAX_T), rows > GEMM_SKINNY_MAX_T);
 }
 
 // a pass over the batch's rows [r0, r0 + T): tokens from the row-token array, the attention step by

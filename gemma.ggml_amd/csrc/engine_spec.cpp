@@ -64,6 +64,8 @@ extern "C" int gemma_engine_verify(gemma_engine *e, const int32_t *draft, int k,
     v.k = k; v.p0 = p0; v.token = e->seq.token; v.pos = e->seq.pos; v.hist = e->seq.hist; v.r = rope_of(e);
     v.zero_keys = e->key; v.n_zero = e->grid_big; v.out = d_out;
     if (launch_verify_accept(v, s)) return -1;
+    // (log-probabilities on: rows 0 .. a against the tokens the accept settled; rejected rows write nothing)
+    if (enqueue_lp_finish(e, e->pf.LG, T, nullptr, &e->seq, nullptr, d_out)) return -1;
     // 5. the rejected rows leave the caches
     if (e->kc_ext.empty()) {
         if (launch_verify_clean(e->seq.kc, e->seq.vc, c.n_layer, (int64_t)c.n_ctx * e->kvw, c.n_ctx, e->kvw, p0, k, d_out, s)) return -1;

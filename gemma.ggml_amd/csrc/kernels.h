@@ -457,6 +457,7 @@ struct slot_row {
     float *rope = nullptr;       // the slot's [cos | sin | (int)pos]: the position is read on the device
     int *hist = nullptr, *pos = nullptr, *last = nullptr;
     const int *nfix = nullptr;
+    double *lp = nullptr;        // the slot's log-probabilities by sequence index (k_lse_finish)
 };
 // k_attn_slots: the decode attention (attn_head_dev, per-head form) for R rows, each against its own
 // slot's caches at its own position.  a: the shared fields (geometry, tables, dsplit); qkv, kc, vc,
@@ -498,6 +499,32 @@ void sample_ws_free(dev_pool &mem, sample_ws *w);
 // geometry depends on n and rows only
 int launch_sample(const float *lg, int64_t ld, int rows, int64_t n, const sampler_params *prm, const int *pos,
                   const slot_row *tab, const sample_ws &w, const sample_dbg &dbg, hipStream_t s);
+
+// ---- per-token log-probabilities (logprob.hip; the rule: include/gemma_hpc.h, DESIGN.md §5b⁗′) ----
+constexpr int LSE_CHUNK = 1024;  // logits per workgroup of k_lse_parts: G = ceil(n_vocab / LSE_CHUNK), n_vocab alone
+constexpr int LSE_MAX_G = 1024;  // partials k_lse_finish merges (n_vocab <= 2^20)
+struct lse_part {                // one chunk of one row: its float max and sum exp((double)l - (double)m)
+    double s;
+    float m, pad;
+};
+int lse_grid(int64_t n_vocab);
+// parts[r][g] for the `rows` rows lg + r * ld of n logits, grid (G, rows); needs no token and no position
+int launch_lse_parts(const float *lg, int64_t ld, int rows, int64_t n, lse_part *parts, hipStream_t s);
+struct lse_finish_args {  // grid (1, R): lp[q_r] = logprob(row r, hist[q_r]) once the advance has settled hist[q_r]
+    const float *lg = nullptr;
+    int64_t ld = 0;
+    int n = 0, R = 0, G = 0, n_ctx = 0;
+    const lse_part *parts = nullptr;
+    // the sequence index q_r row r predicts, its history and its lp array: tab[r]'s (*pos after the
+    // slot's advance) when the pass has a row table; else one sequence whose rows are consecutive
+    // positions ending at *pos: q_r = *pos - (last - r), last = R - 1, or *acc when acc is set (a verify
+    // pass: rows past the accepted count write nothing).  q outside [1, n_ctx] or a token outside
+    // [0, n): nothing is written
+    const slot_row *tab = nullptr;
+    const int *pos = nullptr, *hist = nullptr, *acc = nullptr;
+    double *lp = nullptr;
+};
+int launch_lse_finish(const lse_finish_args &a, hipStream_t s);
 
 // ---- generic ggml-op kernels used by the C-ABI and the ggml-compatible executor ----------------
 int launch_mul_mat_f16(const uint16_t *src0, int64_t nb01_elems, int64_t ne01, const uint16_t *src1,

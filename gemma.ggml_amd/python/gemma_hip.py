@@ -43,7 +43,8 @@ EXPORTS = ["mul_mat", "hpc_init", "hpc_shutdown", "hpc_register_weight", "hpc_la
            "gemma_engine_batch_open", "gemma_engine_batch_close", "gemma_engine_batch_begin", "gemma_engine_batch_adopt",
            "gemma_engine_batch_release", "gemma_engine_batch_step", "gemma_engine_batch_pos", "gemma_engine_batch_tokens",
            "gemma_engine_batch_last", "gemma_engine_batch_kv_read", "gemma_engine_batch_open_wide",
-           "gemma_engine_batch_last_n"]
+           "gemma_engine_batch_last_n",
+           "gemma_engine_set_logprobs", "gemma_engine_logprobs", "gemma_engine_batch_logprobs", "gemma_test_logprob"]
 
 
 def build():
@@ -205,6 +206,14 @@ def lib():
                    ("open_wide", [C.c_int]), ("last_n", [vp, C.c_int])):
         getattr(L, "gemma_engine_batch_" + fn).restype = C.c_int
         getattr(L, "gemma_engine_batch_" + fn).argtypes = [vp] + at
+    L.gemma_engine_set_logprobs.restype = C.c_int
+    L.gemma_engine_set_logprobs.argtypes = [vp, C.c_int]
+    L.gemma_engine_logprobs.restype = C.c_int
+    L.gemma_engine_logprobs.argtypes = [vp, C.c_int, C.c_int, vp]
+    L.gemma_engine_batch_logprobs.restype = C.c_int
+    L.gemma_engine_batch_logprobs.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    L.gemma_test_logprob.restype = C.c_int
+    L.gemma_test_logprob.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     # GGUF reader (include/ggml.h)
     L.gguf_init_from_file.restype = vp
     L.gguf_init_from_file.argtypes = [C.c_char_p, GGUFInitParams]
@@ -552,6 +561,34 @@ class Engine:
         on = self.L.gemma_engine_sampler(self.h, C.byref(s))
         return on == 1, dict(temperature=s.temperature, top_k=s.top_k, top_p=s.top_p, seed=s.seed)
 
+    def set_logprobs(self, on=-1):
+        """Per-token log-probabilities under the raw softmax of every logits row a pass computes
+        (include/gemma_hpc.h has the rule): on 1 / off 0 / keep -1; returns the setting.  On / off drops
+        the captured graph; raises on a row-split engine."""
+        r = self.L.gemma_engine_set_logprobs(self.h, int(on))
+        if r < 0:
+            raise RuntimeError("set_logprobs failed: " + last_error())
+        return r == 1
+
+    def logprobs(self, p0=0, n=None):
+        """lp[p0 .. p0+n) of the engine's sequence as f64 (n=None: through the sequence's end, the
+        pending pick included); NaN where no scored row predicted the index."""
+        if n is None:
+            n = max(self.pos() + 1, getattr(self, "_n_seq", 0)) - int(p0)
+        out = np.zeros(max(int(n), 0), dtype=np.float64)
+        if self.L.gemma_engine_logprobs(self.h, int(p0), int(n), _p(out)) < 0:
+            raise RuntimeError("logprobs failed: " + last_error())
+        return out
+
+    def batch_logprobs(self, slot, p0=0, n=None):
+        """logprobs() of an active slot of the open batch"""
+        if n is None:
+            n = self.batch_pos(slot) + 1 - int(p0)
+        out = np.zeros(max(int(n), 0), dtype=np.float64)
+        if self.L.gemma_engine_batch_logprobs(self.h, int(slot), int(p0), int(n), _p(out)) < 0:
+            raise RuntimeError("batch_logprobs failed: " + last_error())
+        return out
+
     def set_att_o(self, on=-1):
         """decode attention + attn-out in one launch per layer: on 1 / off 0 / keep -1; returns the setting"""
         return self.L.gemma_engine_set_att_o(self.h, on) == 1
@@ -639,6 +676,26 @@ def test_sample(rows, sampler, positions):
 
 
 test_sample.__test__ = False  # a library wrapper, not a pytest test
+
+
+def test_logprob(rows, tokens):
+    """logprob(rows[r], tokens[r]) for host logits rows [R][V] through the engine's two kernels
+    (gemma_test_logprob); returns f64 [R]; raises RuntimeError with the library's message on a
+    refused argument."""
+    x = np.ascontiguousarray(rows, dtype=np.float32)
+    if x.ndim == 1:
+        x = x[None, :]
+    R, V = x.shape
+    t = np.ascontiguousarray(tokens, dtype=np.int32)
+    if t.shape != (R,):
+        raise ValueError("tokens: one per row")
+    out = np.zeros(R, dtype=np.float64)
+    if lib().gemma_test_logprob(_p(x), R, V, _p(t), _p(out)) != 0:
+        raise RuntimeError("gemma_test_logprob failed: " + last_error())
+    return out
+
+
+test_logprob.__test__ = False  # a library wrapper, not a pytest test
 
 
 def lookup_draft(seq, ngram_max, k):

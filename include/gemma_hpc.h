@@ -165,6 +165,34 @@ int gemma_engine_sampler(const gemma_engine *e, gemma_sampler *out);   /* 1 = sa
  * n_kept[rows] = m */
 int gemma_test_sample(const float *logits, int rows, int n_vocab, const gemma_sampler *s,
                       const int32_t *positions, int32_t *tokens, int32_t *cand, int32_t *n_cand, int32_t *n_kept);
+/* Per-token log-probabilities on the device (DESIGN.md §5b⁗′).  For a logits row l[0..V) (f32) and a
+ * token t: M = max_i l[i] compared as floats (-0 == +0); S = sum_i exp((double)l[i] - (double)M) in
+ * f64 (an -inf entry contributes 0; S >= 1); logprob(l, t) = ((double)l[t] - (double)M) - log(S), -inf
+ * when l[t] is -inf.  This is the raw distribution softmax(l): the sampler's temperature, top-k and
+ * top-p do not enter.  Rows with a NaN or whose maximum is -inf are outside the contract.
+ * With log-probabilities on, every logits row a pass computes is scored against the token that ends up
+ * behind it: the row that processed sequence index p gives lp[p + 1] = logprob(row_p, hist[p + 1]) once
+ * the pick or advance has settled hist[p + 1], a given token or the pick alike.  Steps, prefill,
+ * prefill_fast, prefill_next (all rows of the pass), verify (the accepted rows) and batch_step (every
+ * slot) all score; a prefill of a T-token text scores its tokens 1 .. T-1 plus the appended pick, and
+ * the text's perplexity is exp(-mean(lp[1..T))).  lp[i] is NaN where no scored row predicted index i:
+ * index 0, indices processed while off, and everything from `keep` on after gemma_engine_extend(keep)
+ * (row keep - 1 is not recomputed).  The value depends on the row and the token only, bit for bit: it
+ * is the same from eager and graph steps, any split of the steps, a prefill pass or chunk, a verify
+ * pass and a batch slot.  Off (the default) nothing is launched; turning it on or off drops the
+ * captured decode graph, which then has exactly two more kernels per token.
+ * 1 = on, 0 = off, -1 = keep; returns the setting.  -1 + hpc_last_error on a row-split engine (a
+ * vocabulary shard per rank, as for the sampler). */
+int gemma_engine_set_logprobs(gemma_engine *e, int on);
+/* lp of sequence indices [p0, p0+n) of the engine's sequence into out (f64; NaN = not scored);
+ * 0 <= p0, p0 + n <= n_seq (the sequence so far: the given tokens, or through the pending pick);
+ * returns n; -1 + hpc_last_error, state untouched, on a bad range.  One synchronise. */
+int gemma_engine_logprobs(gemma_engine *e, int p0, int n, double *out);
+/* the same for an active slot of the open batch */
+int gemma_engine_batch_logprobs(gemma_engine *e, int slot, int p0, int n, double *out);
+/* per-op test entry: out[r] = logprob(rows[r], tokens[r]) on host rows [rows][n_vocab] through the two
+ * kernels of the engine (rows <= 65535, n_vocab <= 2^20, ids in [0, n_vocab)) */
+int gemma_test_logprob(const float *logits, int rows, int n_vocab, const int32_t *tokens, double *out);
 /* Speculative decoding without a quality trade-off (DESIGN.md §5b‴).  A batched exact pass over
  * [pending token, k drafted tokens] computes the logits rows k + 1 single steps would compute, bit for
  * bit, and a pick depends on its row and position alone (greedy, or the sampler's (seed, p) rule), so
