@@ -272,7 +272,10 @@ __device__ __forceinline__ void attn_prefetch(const attn_args &a, const int h, a
 // each CU streams.
 // SC1O: the output's Q8_0 image stored write-through (sc1) for a consumer inside the same launch
 // (k_attn_o, layer_front.hip); defaults to SC1 (the inputs were handed off in-launch too)
-template <int NTH, bool SC1, int KPF = AH_KPF, int VPF = AH_VPF, bool PRE = false, bool SC1O = SC1>
+// CACHED: this position's K row and V column are in the cache already (an earlier launch stored them:
+// k_rows_rope_kv, batch.hip), so every K / V operand is read from there, the row's own position
+// included, and nothing is stored to a cache; the k / v of a.qkv are not read
+template <int NTH, bool SC1, int KPF = AH_KPF, int VPF = AH_VPF, bool PRE = false, bool SC1O = SC1, bool CACHED = false>
 __device__ void attn_head_dev(const attn_args &a, const int h, uint8_t *smem, const attn_pre<KPF, VPF> *pre = nullptr,
                               const int sp = 0, const int tid_in = -1) {
     // tid_in: the caller's (opaque) thread index, so that a persistent caller's loop does not keep
@@ -297,7 +300,7 @@ __device__ void attn_head_dev(const attn_args &a, const int h, uint8_t *smem, co
     float4 qa{}, qb{}, ka{}, kb{}, ca{}, sa{};
     if (wave * 64 < n4) {
         qa = ld4<SC1>(qh + i4); qb = ld4<SC1>(qh + i4 + half);
-        ka = ld4<SC1>(kh + i4); kb = ld4<SC1>(kh + i4 + half);
+        if (!CACHED) { ka = ld4<SC1>(kh + i4); kb = ld4<SC1>(kh + i4 + half); }
         ca = *(const float4 *)(cs + i4); sa = *(const float4 *)(sn + i4);
     }
     attn_pre<KPF, VPF> own;
@@ -305,7 +308,7 @@ __device__ void attn_head_dev(const attn_args &a, const int h, uint8_t *smem, co
     const attn_pre<KPF, VPF> &P = PRE ? *pre : own;
     const uint4 *kpre = P.k, *vpre = P.v;
     const int d0 = d_lo + quad < d_hi ? d_lo + quad : d_lo;
-    const float vx0 = ld1<SC1>(vh + d0);
+    const float vx0 = CACHED ? 0.0f : ld1<SC1>(vh + d0);
 
     uint16_t *q16 = (uint16_t *)smem;  // hd
     uint16_t *k16 = q16 + hd;          // hd (this token's k, post-rope)
@@ -336,7 +339,7 @@ __device__ void attn_head_dev(const attn_args &a, const int h, uint8_t *smem, co
     };
     if (rl >= 0 && rl < n4) {
         rope4(qa, qb, a.q_scale, true, q16 + i4, q16 + i4 + half);
-        rope4(ka, kb, 1.0f, false, k16 + i4, k16 + i4 + half);
+        if (!CACHED) rope4(ka, kb, 1.0f, false, k16 + i4, k16 + i4 + half);
     }
     if (rl == 0) {  // (the RoPE wave: its loads are drained here; another wave could wait on them)
         *mx_key = 0u;  // below the key of every float, -inf included
@@ -350,7 +353,7 @@ __device__ void attn_head_dev(const attn_args &a, const int h, uint8_t *smem, co
     AH_STAMP(1);
     // this token's cache entries (src/gemma_model.cpp:506-517), by the group's first head; readers
     // in this launch use k16 / the v values instead
-    if (h % G == 0 && sp == 0) {
+    if (!CACHED && h % G == 0 && sp == 0) {
         for (int i = tid; i < hd; i += NTH) a.kc[(int64_t)pos * kvw + (int64_t)kvh * hd + i] = k16[i];
         for (int d = quad; d < hd; d += NTH / 4)
             if (t4 == 0) a.vc[((int64_t)kvh * hd + d) * a.ctx + pos] = f2h(d == d0 ? vx0 : ld1<SC1>(vh + d));
@@ -390,7 +393,7 @@ __device__ void attn_head_dev(const attn_args &a, const int h, uint8_t *smem, co
                 if (s < 8) kx[s] = kpre[s];
             // this token's own row (its cache store may not be visible): only the quad of j == pos
             // swaps its operands for k16 from LDS — one divergent LDS read, not a second dot
-            if (j == pos) {
+            if (!CACHED && j == pos) {
 #pragma unroll
                 for (int s = 0; s < 8; ++s)
                     if (s * 32 < hd) kx[s] = *(const uint4 *)(k16 + s * 32 + t4 * 8);
@@ -406,12 +409,12 @@ __device__ void attn_head_dev(const attn_args &a, const int h, uint8_t *smem, co
 #pragma unroll
             for (int s = 0; s < 8; ++s)
                 if (s * 32 < hd && (!(GHIP_AH_ABL & 16) || s < 4)) f16_step8(acc, kx[s], qr[s]);
-        } else if (j == pos) {
+        } else if (!CACHED && j == pos) {
 #pragma unroll
             for (int s = 0; s < 8; ++s)
                 if (s * 32 < hd) f16_step8(acc, *(const uint4 *)(k16 + s * 32 + t4 * 8), qr[s]);
         } else {
-            const int jc = j < pos ? j : 0;  // j > pos is masked below
+            const int jc = (CACHED ? j <= pos : j < pos) ? j : 0;  // j > pos is masked below
             const uint16_t *krow = a.kc + (int64_t)jc * kvw + (int64_t)kvh * hd;
 #pragma unroll
             for (int s = 0; s < 8; ++s)
@@ -473,14 +476,14 @@ __device__ void attn_head_dev(const attn_args &a, const int h, uint8_t *smem, co
 #pragma unroll
         for (int y = 0; y < 8; ++y) acc[y] = 0.0f;
         const uint16_t *vr = a.vc + ((int64_t)kvh * hd + d) * a.ctx;
-        const float vx = d == d0 ? vx0 : ld1<SC1>(vh + d);
+        const float vx = CACHED ? 0.0f : d == d0 ? vx0 : ld1<SC1>(vh + d);
         // this token's V: its cache write may not be visible.  Element pos sits in step pos/32, on
         // quad lane (pos/8)%4, dword (pos%8)/2, half pos%2 — all wave-uniform but the lane test, so
         // the patch holds no per-step VGPRs (the per-step e0 form was hoisted and spilled)
         const int p_s = pos >> 5, p_t = (pos >> 3) & 3, p_w = (pos >> 1) & 3;
         const uint32_t p_sh = 16 * (pos & 1), p_msk = ~(0xFFFFu << p_sh);
         auto patch = [&](uint4 &xv, int s) {
-            if (s == p_s && t4 == p_t) {
+            if (!CACHED && s == p_s && t4 == p_t) {
                 const uint32_t hv = f2h(vx) << p_sh;
                 if (p_w == 0) xv.x = (xv.x & p_msk) | hv;
                 else if (p_w == 1) xv.y = (xv.y & p_msk) | hv;

@@ -1,4 +1,4 @@
-// batch.hip — batched decode (gemma_engine_batch_*, DESIGN.md §5b⁗): the two kernels that let one
+// batch.hip — batched decode (gemma_engine_batch_*, DESIGN.md §5b⁗): the kernels that let one
 // weight pass serve up to 64 independent sequences (8 on the skinny GEMM, more on the MFMA GEMMs).
 //
 //  * k_attn_slots: the decode attention for R rows, row r against the caches of its own slot at its
@@ -8,6 +8,10 @@
 //    (slot_row); the position is the word published with the slot's RoPE row.  No workgroup waits on
 //    another.
 //  * k_batch_advance: k_advance per row — the pick-key reduction and the slot's token feedback.
+//  * several rows per slot (gemma_engine_batch_step_rows, "Several rows per slot" in §5b⁗):
+//    k_rows_prepare (the rows' positions, RoPE rows and tokens), per layer k_rows_rope_kv (the K / V
+//    stores of all rows) then k_attn_slot_rows (attn_head_dev with every K / V operand read from the
+//    cache), and k_rows_advance (k_batch_advance per slot, pos += m).
 #include "attn_impl.h"
 #include "pick.h"
 
@@ -52,6 +56,87 @@ __global__ void __launch_bounds__(256) k_batch_advance(const slot_row *rows, con
     }
 }
 
+// ---- several rows per slot (gemma_engine_batch_step_rows) -----------------------------------------
+// k_attn_slots stores its own position's K / V and patches its own row from LDS: right only while no
+// other row of the launch reads that position.  Rows that share a slot at consecutive positions do,
+// so their pass runs two launches per layer, the kernel boundary between them the only ordering.
+
+// one workgroup per row, before the first layer: the row's position, RoPE row and token
+__global__ void __launch_bounds__(256) k_rows_prepare(const slot_row *mrows, const row_src *src, int *row_tok, rope_row r) {
+    const slot_row sr = mrows[blockIdx.x];
+    const row_src rs = src[blockIdx.x];
+    int p = *rs.spos + rs.off;
+    if (p >= r.ctx) p = r.ctx - 1;  // (the host refused such a pass: its mirror of *spos is exact)
+    publish_rope_row(sr.rope, r.cos, r.sin, r.half, p);
+    if (threadIdx.x == 0) row_tok[blockIdx.x] = sr.hist[p];
+}
+
+// step 1 of a layer, one workgroup per row: k_rope_kv_prefill's arithmetic (the decode attention's)
+// for the row's k and v at the row's position p, into K row p and V column p of its slot's caches
+__global__ void __launch_bounds__(256) k_rows_rope_kv(attn_args a, const slot_row *mrows, int64_t layer_off) {
+    const slot_row r = mrows[blockIdx.x];
+    const int tid = threadIdx.x, hd = a.hd, half = hd / 2, kvw = a.Hkv * hd;
+    const int p = ((const int *)r.rope)[hd];
+    const float *cs = a.rope_cos + (int64_t)p * half, *sn = a.rope_sin + (int64_t)p * half;
+    const float *kr = r.qkv + (int64_t)a.H * hd, *vr = kr + kvw;
+    uint16_t *kc = r.kc + layer_off, *vc = r.vc + layer_off;
+    for (int i = tid; i < a.Hkv * half; i += 256) {
+        const int kh = i / half, e = i % half;
+        const float x0 = kr[kh * hd + e], x1 = kr[kh * hd + e + half], c = cs[e], s = sn[e];
+        const float p0 = x0 * c, p1 = x1 * s, p2 = x0 * s, p3 = x1 * c;
+        kc[(int64_t)p * kvw + kh * hd + e] = (uint16_t)f2h(p0 - p1);
+        kc[(int64_t)p * kvw + kh * hd + e + half] = (uint16_t)f2h(p2 + p3);
+    }
+    for (int d = tid; d < kvw; d += 256) vc[(int64_t)d * a.ctx + p] = (uint16_t)f2h(vr[d]);
+}
+
+// step 2, grid (8 * H * dsplit, T): attn_head_dev per (row, head, dsplit part) with every K / V
+// operand from the cache.  Placement as k_attn_slots: the G * dsplit workgroups of a (row, kv head)
+// share an XCD; so do 8 consecutive rows of one slot, which read the same K rows through its L2 (a
+// slot with many rows is spread over the XCDs in runs of 8, not piled onto one)
+__global__ void __launch_bounds__(AH_THREADS) k_attn_slot_rows(attn_args a, const slot_row *mrows, const row_src *src,
+                                                               int64_t layer_off) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int S = a.dsplit, G = a.H / a.Hkv;
+    const int row = blockIdx.y, hs = blockIdx.x >> 3, h = hs / S, sp = hs % S;
+    const row_src rs = src[row];
+    if ((int)(blockIdx.x & 7) != ((h / G + rs.rank + (rs.off >> 3)) & 7)) return;
+    const slot_row r = mrows[row];
+    a.qkv = r.qkv;
+    a.kc = r.kc + layer_off;
+    a.vc = r.vc + layer_off;
+    a.rope_cur = r.rope;
+    a.out = r.out;
+    attn_head_dev<AH_THREADS, false, AH_KPF, AH_VPF, false, false, true>(a, h, smem, nullptr, sp);
+}
+
+// k_batch_advance per slot, for a slot that had m rows in the pass
+__global__ void __launch_bounds__(256) k_rows_advance(const slot_row *rows, const slot_row *mrows, const slot_span *spans,
+                                                      const unsigned long long *keys, int n_parts, int key_stride,
+                                                      int *row_tok, int hist_cap, rope_row r) {
+    __shared__ unsigned long long red[4];
+    const slot_row sr = rows[blockIdx.x];
+    const slot_span sp = spans[blockIdx.x];
+    keys += (int64_t)(sp.row0 + sp.m - 1) * key_stride;  // the slot's last row picks
+    // every thread reads the position before the barrier; thread 0 writes it after (as k_advance)
+    const int p = *sr.pos + sp.m;
+    const int fixed = *sr.nfix;
+    if (p < r.ctx) publish_rope_row(sr.rope, r.cos, r.sin, r.half, p);
+    // row (s, i) predicts sequence index pos + i + 1: what k_lse_finish reads as its position
+    if ((int)threadIdx.x < sp.m) *mrows[sp.row0 + threadIdx.x].pos += 1;
+    const unsigned long long best = block_max_key(keys, n_parts, red);
+    if (threadIdx.x == 0) {
+        int tok = key_index(best);
+        if (p < hist_cap) {
+            if (p >= fixed) sr.hist[p] = tok;  // never overwrite a given token
+            else tok = sr.hist[p];
+        }
+        *sr.pos = p;
+        *sr.last = tok;
+        row_tok[blockIdx.x] = tok;  // what the slot's row processes in a following batch_step pass
+    }
+}
+
 }  // namespace
 
 int launch_attn_slots(const attn_args &a, const slot_row *rows, int R, int64_t layer_off, hipStream_t s) {
@@ -74,6 +159,50 @@ int launch_attn_slots(const attn_args &a, const slot_row *rows, int R, int64_t l
 int launch_batch_advance(const slot_row *rows, int R, const unsigned long long *keys, int n_parts, int key_stride,
                          int *row_tok, int hist_cap, const rope_row &r, hipStream_t s) {
     hipLaunchKernelGGL(k_batch_advance, dim3(R), dim3(256), 0, s, rows, keys, n_parts, key_stride, row_tok, hist_cap, r);
+    GHIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_rows_prepare(const slot_row *mrows, const row_src *src, int T, int *row_tok, const rope_row &r, hipStream_t s) {
+    if (!mrows || !src || !row_tok || T < 1 || T > ATTN_SLOTS_MAX_R) {
+        set_error("rows_prepare: a pass outside [1, 64] rows, or no row table");
+        return -1;
+    }
+    hipLaunchKernelGGL(k_rows_prepare, dim3(T), dim3(256), 0, s, mrows, src, row_tok, r);
+    GHIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_attn_slot_rows(const attn_args &a, const slot_row *mrows, const row_src *src, int T, int64_t layer_off,
+                          hipStream_t s) {
+    if (!src) {
+        set_error("attn_slot_rows: no row sources");
+        return -1;
+    }
+    // the same shapes, rows and LDS image as k_attn_slots
+    if (a.mode != ATTN_PER_HEAD || a.hd % 32 != 0 || a.hd > 256 || a.ctx % 32 != 0 || a.Hkv <= 0 || a.H % a.Hkv != 0 ||
+        a.dsplit < 1 || a.hd % (32 * a.dsplit) || 4 * (a.hd / a.dsplit) > AH_THREADS || a.out_act || a.out_q8k ||
+        a.out_gran || !mrows || T < 1 || T > ATTN_SLOTS_MAX_R) {
+        set_error("attn_slot_rows: unsupported shape for the per-head form, or a pass outside [1, 64] rows");
+        return -1;
+    }
+    const size_t lds = ((2 * (size_t)a.hd * 2 + 15) & ~(size_t)15) + (size_t)a.ctx * 4 + (size_t)a.ctx * 2 + 16;
+    if (lds > 64 * 1024) {
+        set_error("attn_slot_rows: context too long for the LDS image");
+        return -1;
+    }
+    hipLaunchKernelGGL(k_rows_rope_kv, dim3(T), dim3(256), 0, s, a, mrows, layer_off);
+    GHIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_attn_slot_rows, dim3(8 * a.H * a.dsplit, T), dim3(AH_THREADS), lds, s, a, mrows, src, layer_off);
+    GHIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_rows_advance(const slot_row *rows, const slot_row *mrows, const slot_span *spans, int R,
+                        const unsigned long long *keys, int n_parts, int key_stride, int *row_tok, int hist_cap,
+                        const rope_row &r, hipStream_t s) {
+    hipLaunchKernelGGL(k_rows_advance, dim3(R), dim3(256), 0, s, rows, mrows, spans, keys, n_parts, key_stride, row_tok,
+                       hist_cap, r);
     GHIP_CHECK(hipGetLastError());
     return 0;
 }

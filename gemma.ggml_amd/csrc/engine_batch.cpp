@@ -8,6 +8,10 @@
 // gemma_engine_step gives that sequence alone, bit for bit, in every form.  All slot state lives in
 // bt_mem and advances on the device; the engine's own sequence, its captured decode graph and its
 // buffers are not touched.
+// gemma_engine_batch_step_rows gives a slot that still has given tokens to consume several rows of one
+// pass (gemma_batch_plan_rows states the allotment): the same pass over a row table of its own, the
+// attention step in two launches (K / V stores of all rows, then the attention from the cache), the
+// advance per slot.  The slot's state afterwards is byte for byte what one-row passes leave.
 #include "engine_impl.h"
 
 static constexpr int NS = GEMMA_BATCH_WIDE_MAX_SLOTS;  // every table's size
@@ -31,8 +35,10 @@ static void batch_drop(gemma_engine *e) {
     e->bt = batch_state{};
 }
 
-// gemma_engine_batch_open (max_slots 8) and gemma_engine_batch_open_wide (64): the same open
-static int batch_open(gemma_engine *e, int n_slots, int max_slots, const std::string &fn) {
+// gemma_engine_batch_open (max_slots 8), gemma_engine_batch_open_wide (64) and
+// gemma_engine_batch_open_rows (64, a row capacity of its own): the same open.  rows: what the pass
+// scratch, the sampler workspaces and the log-probability partials are sized for (at least 8)
+static int batch_open(gemma_engine *e, int n_slots, int max_slots, int rows, const std::string &fn) {
     set_error("");
     if (e->bt.open) {
         set_error(fn + ": a batch is already open (gemma_engine_batch_close)");
@@ -55,12 +61,18 @@ static int batch_open(gemma_engine *e, int n_slots, int max_slots, const std::st
     dev_pool &M = e->bt_mem;
     batch_state &b = e->bt;
     b = batch_state{};
-    bool bad = batch_scratch_alloc(e, n_slots) != 0 || M.get_zeroed(&b.last, NS * 4, s);
+    const size_t rope_words = (size_t)e->cfg.head_dim + 4;
+    const size_t mtab = NS * (sizeof(slot_row) + sizeof(row_src) + sizeof(slot_span));
+    bool bad = batch_scratch_alloc(e, rows) != 0 || M.get_zeroed(&b.last, NS * 4, s);
     for (int i = 0; i < n_slots && !bad; ++i) bad = seq_alloc(e, M, b.slot[i], true, b.last + i) != 0;
     bad = bad || M.get_zeroed(&b.rows, NS * sizeof(slot_row), s) || M.get_zeroed(&b.row_tok, NS * 4, s) ||
           pick_buf_alloc(M, b.picks, s) || M.get(&b.stage, NS * sizeof(slot_row), MEM_PINNED) ||
-          // more rows than the engine's sampler has workspaces: the batch brings its own, one per slot
-          (n_slots > NARROW && sample_ws_alloc(M, &b.picks.ws, e->cfg.n_vocab, s, n_slots));
+          // more rows than the engine's sampler has workspaces: the batch brings its own, one per row
+          (rows > NARROW && sample_ws_alloc(M, &b.picks.ws, e->cfg.n_vocab, s, rows)) ||
+          // the tables of a pass with several rows per slot (gemma_engine_batch_step_rows)
+          M.get_zeroed(&b.mrows, NS * sizeof(slot_row), s) || M.get_zeroed(&b.msrc, NS * sizeof(row_src), s) ||
+          M.get_zeroed(&b.mspans, NS * sizeof(slot_span), s) || M.get_zeroed(&b.mrope, NS * rope_words * 4, s) ||
+          M.get(&b.mstage, mtab, MEM_PINNED);
     if (!bad) {  // no slot is active: every pending token reads -1
         int *h = (int *)b.stage;
         for (int i = 0; i < NS; ++i) h[i] = -1;
@@ -81,11 +93,21 @@ static int batch_open(gemma_engine *e, int n_slots, int max_slots, const std::st
 }
 
 extern "C" int gemma_engine_batch_open(gemma_engine *e, int n_slots) {
-    return batch_open(e, n_slots, NARROW, "gemma_engine_batch_open");
+    return batch_open(e, n_slots, NARROW, n_slots, "gemma_engine_batch_open");
 }
 
 extern "C" int gemma_engine_batch_open_wide(gemma_engine *e, int n_slots) {
-    return batch_open(e, n_slots, NS, "gemma_engine_batch_open_wide");
+    return batch_open(e, n_slots, NS, n_slots, "gemma_engine_batch_open_wide");
+}
+
+extern "C" int gemma_engine_batch_open_rows(gemma_engine *e, int n_slots, int max_rows) {
+    const char *fn = "gemma_engine_batch_open_rows";
+    if (n_slots >= 1 && n_slots <= NS && (max_rows < std::max(NARROW, n_slots) || max_rows > NS)) {
+        set_error(std::string(fn) + ": max_rows = " + std::to_string(max_rows) + " outside [" +
+                  std::to_string(std::max(NARROW, n_slots)) + ", " + std::to_string(NS) + "]");
+        return -1;
+    }
+    return batch_open(e, n_slots, NS, max_rows, fn);
 }
 
 extern "C" int gemma_engine_batch_close(gemma_engine *e) {
@@ -177,6 +199,8 @@ static int batch_write_rows(gemma_engine *e) {
 int enqueue_batch_attention(gemma_engine *e, int il, int r0, int T) {
     attn_args t = attn_of(e, il);
     t.dsplit = e->att_dsplit;
+    if (e->bt.multi)  // rows that share slots: the K / V stores, a kernel boundary, the attention
+        return launch_attn_slot_rows(t, e->bt.mrows + r0, e->bt.msrc + r0, T, (int64_t)il * e->cfg.n_ctx * e->kvw, e->stream);
     return launch_attn_slots(t, e->bt.rows + r0, T, (int64_t)il * e->cfg.n_ctx * e->kvw, e->stream);
 }
 
@@ -230,6 +254,138 @@ extern "C" int gemma_engine_batch_step(gemma_engine *e, int n, float *logits) {
     for (int i = 0; i < b.n_slots; ++i)
         if (b.slot[i].active) b.slot[i].host_pos += n;
     return 0;
+}
+
+// ---- several rows per slot ---------------------------------------------------------------------
+// The one statement of the allotment (a host function, no GPU): every active slot one row, then the
+// rest of the budget in ascending slot order to the slots with more given tokens to consume.
+extern "C" int gemma_batch_plan_rows(const int32_t *need, int n_slots, int max_rows, int32_t *rows_of) {
+    set_error("");
+    const char *fn = "gemma_batch_plan_rows";
+    if (!need || !rows_of || n_slots < 1 || n_slots > NS) {
+        set_error(std::string(fn) + ": n_slots = " + std::to_string(n_slots) + " outside [1, " + std::to_string(NS) + "], or a null array");
+        return -1;
+    }
+    int R = 0;
+    for (int s = 0; s < n_slots; ++s) {
+        if (need[s] < 0) {
+            set_error(std::string(fn) + ": need[" + std::to_string(s) + "] is negative");
+            return -1;
+        }
+        R += need[s] > 0;
+    }
+    if (R == 0) {
+        set_error(std::string(fn) + ": no slot is active");
+        return -1;
+    }
+    if (max_rows < R || max_rows > NS) {
+        set_error(std::string(fn) + ": max_rows = " + std::to_string(max_rows) + " outside [" + std::to_string(R) + ", " +
+                  std::to_string(NS) + "]");
+        return -1;
+    }
+    int budget = max_rows - R, T = 0;
+    for (int s = 0; s < n_slots; ++s) {
+        const int extra = need[s] > 0 ? std::min(budget, need[s] - 1) : 0;
+        rows_of[s] = need[s] > 0 ? 1 + extra : 0;
+        budget -= extra;
+        T += rows_of[s];
+    }
+    return T;
+}
+
+extern "C" int gemma_engine_batch_step_rows(gemma_engine *e, int max_rows, float *logits, int32_t *rows_of) {
+    set_error("");
+    const char *fn = "gemma_engine_batch_step_rows";
+    const gemma_hip_config &c = e->cfg;
+    batch_state &b = e->bt;
+    if (!b.open) {
+        set_error(std::string(fn) + ": no batch is open (gemma_engine_batch_open_rows)");
+        return -1;
+    }
+    int32_t need[NS], m_of[NS];
+    int R = 0;
+    for (int i = 0; i < b.n_slots; ++i) {
+        const seq_state &S = b.slot[i];
+        need[i] = S.active ? std::max(1, S.n_given - S.host_pos) : 0;
+        R += S.active;
+    }
+    if (R == 0) {
+        set_error(std::string(fn) + ": no slot is active (gemma_engine_batch_begin / _adopt)");
+        return -1;
+    }
+    if (max_rows < R || max_rows > b.pf.T) {
+        set_error(std::string(fn) + ": max_rows = " + std::to_string(max_rows) + " outside [" + std::to_string(R) +
+                  " active slots, the batch's row capacity " + std::to_string(b.pf.T) + "]");
+        return -1;
+    }
+    const int T = gemma_batch_plan_rows(need, b.n_slots, max_rows, m_of);
+    if (T < 0) {
+        set_error(std::string(fn) + ": " + last_error());
+        return -1;
+    }
+    for (int i = 0; i < b.n_slots; ++i)
+        if (b.slot[i].active && (int64_t)b.slot[i].host_pos + m_of[i] >= c.n_ctx) {
+            set_error(std::string(fn) + ": context full (slot " + std::to_string(i) + " at position " +
+                      std::to_string(b.slot[i].host_pos) + ", " + std::to_string(m_of[i]) + " rows, n_ctx = " +
+                      std::to_string(c.n_ctx) + ")");
+            return -1;
+        }
+    (void)hipSetDevice(e->device);
+    hipStream_t s = e->stream;
+    if (b.dirty && batch_write_rows(e)) return -1;
+    // the pass's tables, rows by ascending slot then position.  Row t's RoPE row (k_rows_prepare fills
+    // it) ends with the row's position word: `pos` of its table entry
+    slot_row *hr = (slot_row *)b.mstage;
+    row_src *hs = (row_src *)(hr + NS);
+    slot_span *hp = (slot_span *)(hs + NS);
+    const size_t rope_words = (size_t)c.head_dim + 4;
+    for (int i = 0, t = 0, rank = 0; i < b.n_slots; ++i) {
+        const seq_state &S = b.slot[i];
+        if (!S.active) continue;
+        hp[rank] = slot_span{t, m_of[i]};
+        for (int k = 0; k < m_of[i]; ++k, ++t) {
+            slot_row r;
+            r.qkv = b.pf.QKV + (size_t)t * e->qkv_rows;
+            r.out = b.pf.ATT + (size_t)t * e->qw;
+            r.kc = S.kc; r.vc = S.vc;
+            r.rope = b.mrope + (size_t)t * rope_words;
+            r.pos = (int *)(r.rope + c.head_dim);
+            r.hist = S.hist; r.nfix = S.nfix; r.last = S.token; r.lp = S.lp;
+            hr[t] = r;
+            hs[t] = row_src{S.pos, k, rank};
+        }
+        ++rank;
+    }
+    GHIP_CHECK(hipMemcpyAsync(b.mrows, hr, (size_t)T * sizeof(slot_row), hipMemcpyHostToDevice, s));
+    GHIP_CHECK(hipMemcpyAsync(b.msrc, hs, (size_t)T * sizeof(row_src), hipMemcpyHostToDevice, s));
+    GHIP_CHECK(hipMemcpyAsync(b.mspans, hp, (size_t)R * sizeof(slot_span), hipMemcpyHostToDevice, s));
+    if (launch_rows_prepare(b.mrows, b.msrc, T, b.row_tok, rope_of(e), s)) return -1;
+    // the form by T exactly as batch_step's by R; a slot's rows may straddle groups: a group runs all
+    // its layers before the next starts, so later rows find the earlier rows' K / V in the cache
+    const bool mfma = T > NARROW && T >= e->bt_mfma_min;
+    b.multi = true;
+    int bad = 0;
+    if (T <= NARROW || mfma) {
+        bad = enqueue_batch_pass(e, 0, T, !mfma);
+    } else {
+        for (int r0 = 0; r0 < T && !bad; r0 += NARROW) bad = enqueue_batch_pass(e, r0, std::min(NARROW, T - r0), true);
+    }
+    b.multi = false;
+    if (bad) return -1;
+    // a pick from every row (one launch whatever T; only each slot's last row's is used), the
+    // sampler's position word the row's own
+    row_picks pk;
+    if (enqueue_row_picks(e, b.pf.LG, T, nullptr, b.mrows, b.picks, &pk)) return -1;
+    if (logits) GHIP_CHECK(hipMemcpyAsync(logits, b.pf.LG, (size_t)T * c.n_vocab * 4, hipMemcpyDeviceToHost, s));
+    if (launch_rows_advance(b.rows, b.mrows, b.mspans, R, pk.keys, pk.n_parts, pk.stride, b.row_tok, c.n_ctx, rope_of(e), s))
+        return -1;
+    if (enqueue_lp_finish(e, b.pf.LG, T, b.picks.lp_parts, nullptr, b.mrows, nullptr)) return -1;
+    GHIP_CHECK(hipStreamSynchronize(s));
+    for (int i = 0; i < b.n_slots; ++i) {
+        if (b.slot[i].active) b.slot[i].host_pos += m_of[i];
+        if (rows_of) rows_of[i] = m_of[i];
+    }
+    return T;
 }
 
 extern "C" int gemma_engine_batch_pos(gemma_engine *e, int slot) {

@@ -115,9 +115,17 @@ struct batch_state {
     int *row_tok = nullptr;    // device: [64] the token each row of the next pass processes
     pick_buf picks;
     void *stage = nullptr;     // pinned: the row table's source, batch_last's result
-    pf_scratch pf;             // the pass's scratch (max(8, n_slots) rows), never reallocated while the batch is open
+    pf_scratch pf;             // the pass's scratch (pf.T rows: max(8, n_slots), or open_rows' max_rows), never reallocated while the batch is open
     bool dirty = true;         // the active set changed since the table was written
     int n_rows = 0, row_slot[GEMMA_BATCH_WIDE_MAX_SLOTS] = {};
+    // several rows per slot (gemma_engine_batch_step_rows): the pass's own row table, rewritten by
+    // every such pass from the plan, and each row's [cos | sin | (int)p]
+    slot_row *mrows = nullptr;   // device: [64], row t's `rope` / `pos` its own RoPE row / position word
+    row_src *msrc = nullptr;     // device: [64]
+    slot_span *mspans = nullptr; // device: [64] by the slot's rank among the active slots
+    float *mrope = nullptr;      // device: [64][head_dim + 4]
+    void *mstage = nullptr;      // pinned: the three tables' source
+    bool multi = false;          // the pass being enqueued is such a pass (enqueue_batch_attention)
 };
 
 struct gemma_engine {

@@ -43,7 +43,8 @@ static int prefill_alloc(gemma_engine *e, int T) {
 //   slots == false  rows are positions p0 .. p0+T-1 of the engine's own sequence: RoPE + K / V store
 //                   into the engine's caches, then the causal attention (prefill_attention)
 //   slots == true   rows are the batch's (engine_batch.cpp): row t is the next token of its own slot,
-//                   the attention is enqueue_batch_attention and the scratch is the batch's (bt.pf)
+//                   (or, in a step_rows pass, one of several consecutive tokens of its slot), the
+//                   attention is enqueue_batch_attention and the scratch is the batch's (bt.pf)
 //                   r0 > 0: the pass is rows [r0, r0 + T) of the batch (a group of a wide batch): its
 //                   tokens, its part of the row table and a view of the scratch shifted by r0 rows
 struct pass_rows {

@@ -469,6 +469,33 @@ int launch_attn_slots(const attn_args &a, const slot_row *rows, int R, int64_t l
 // pass's token hist[p] into row_tok[r] and the slot's `last`
 int launch_batch_advance(const slot_row *rows, int R, const unsigned long long *keys, int n_parts, int key_stride,
                          int *row_tok, int hist_cap, const rope_row &r, hipStream_t s);
+// Several rows per slot (gemma_engine_batch_step_rows): a pass of T rows ordered by slot, then by
+// position.  Row t has a slot_row of its own whose `rope` is the row's own [cos | sin | (int)p] and
+// whose `pos` is that row's position word, so the sampler and k_lse_finish read the row's position,
+// not the slot's.  row_src says where the row comes from; slot_span which rows are a slot's.
+struct row_src {
+    const int *spos = nullptr;  // the slot's device position word
+    int off = 0;                // the row processes hist[*spos + off]
+    int rank = 0;               // the slot's index among the active slots (its row of a batch_step pass)
+};
+struct slot_span {
+    int row0 = 0, m = 0;  // the slot's rows [row0, row0 + m) of the pass
+};
+// before the first layer, one workgroup per row: p = *spos + off, the row's RoPE row with its
+// position word, and the row's token hist[p] into row_tok[t]
+int launch_rows_prepare(const slot_row *mrows, const row_src *src, int T, int *row_tok, const rope_row &r, hipStream_t s);
+// a layer's attention step for T such rows, two launches with a kernel boundary between them:
+// k_rows_rope_kv (RoPE of k from the full tables at the row's position, K row p and V column p of the
+// slot's caches), then k_attn_slot_rows (attn_head_dev with every K / V operand read from the cache,
+// the row's own position included; it stores nothing to a cache)
+int launch_attn_slot_rows(const attn_args &a, const slot_row *mrows, const row_src *src, int T, int64_t layer_off,
+                          hipStream_t s);
+// per active slot (rows: the batch_step table, by rank): the key reduction of the slot's last row,
+// pos += m, the guarded hist write, the slot's RoPE row, `last` and row_tok[rank]; every row's
+// position word becomes the sequence index it predicts (k_lse_finish)
+int launch_rows_advance(const slot_row *rows, const slot_row *mrows, const slot_span *spans, int R,
+                        const unsigned long long *keys, int n_parts, int key_stride, int *row_tok, int hist_cap,
+                        const rope_row &r, hipStream_t s);
 
 // ---- on-device sampling (sample.hip; the rule: include/gemma_hpc.h, DESIGN.md §5b″) ------------
 constexpr int SAMPLE_MAX_K = 1024;  // candidates at most (top_k == 0 means this many)

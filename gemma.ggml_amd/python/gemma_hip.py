@@ -43,7 +43,8 @@ EXPORTS = ["mul_mat", "hpc_init", "hpc_shutdown", "hpc_register_weight", "hpc_la
            "gemma_engine_batch_open", "gemma_engine_batch_close", "gemma_engine_batch_begin", "gemma_engine_batch_adopt",
            "gemma_engine_batch_release", "gemma_engine_batch_step", "gemma_engine_batch_pos", "gemma_engine_batch_tokens",
            "gemma_engine_batch_last", "gemma_engine_batch_kv_read", "gemma_engine_batch_open_wide",
-           "gemma_engine_batch_last_n",
+           "gemma_engine_batch_last_n", "gemma_batch_plan_rows", "gemma_engine_batch_open_rows",
+           "gemma_engine_batch_step_rows",
            "gemma_engine_set_logprobs", "gemma_engine_logprobs", "gemma_engine_batch_logprobs", "gemma_test_logprob"]
 
 
@@ -203,9 +204,12 @@ def lib():
     for fn, at in (("open", [C.c_int]), ("close", []), ("begin", [C.c_int, vp, C.c_int]), ("adopt", [C.c_int]),
                    ("release", [C.c_int]), ("step", [C.c_int, vp]), ("pos", [C.c_int]), ("tokens", [C.c_int, vp, C.c_int]),
                    ("last", [vp]), ("kv_read", [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
-                   ("open_wide", [C.c_int]), ("last_n", [vp, C.c_int])):
+                   ("open_wide", [C.c_int]), ("last_n", [vp, C.c_int]), ("open_rows", [C.c_int, C.c_int]),
+                   ("step_rows", [C.c_int, vp, vp])):
         getattr(L, "gemma_engine_batch_" + fn).restype = C.c_int
         getattr(L, "gemma_engine_batch_" + fn).argtypes = [vp] + at
+    L.gemma_batch_plan_rows.restype = C.c_int
+    L.gemma_batch_plan_rows.argtypes = [vp, C.c_int, C.c_int, vp]
     L.gemma_engine_set_logprobs.restype = C.c_int
     L.gemma_engine_set_logprobs.argtypes = [vp, C.c_int]
     L.gemma_engine_logprobs.restype = C.c_int
@@ -407,11 +411,30 @@ class Engine:
     def batch_open(self, n_slots):
         """Open the engine's batch with n_slots (1 .. BATCH_MAX_SLOTS) sequence slots."""
         self._chk(self.L.gemma_engine_batch_open(self.h, int(n_slots)), "batch_open")
+        self._bt_slots = int(n_slots)
 
     def batch_open_wide(self, n_slots):
         """Open the engine's batch with n_slots (1 .. BATCH_WIDE_MAX_SLOTS) sequence slots: passes of
         more than 8 rows run on the exact MFMA GEMMs (option "bt_mfma_min"), the same bits."""
         self._chk(self.L.gemma_engine_batch_open_wide(self.h, int(n_slots)), "batch_open_wide")
+        self._bt_slots = int(n_slots)
+
+    def batch_open_rows(self, n_slots, max_rows):
+        """batch_open_wide with the pass scratch sized for max_rows rows (max(8, n_slots) .. 64): the
+        row capacity of batch_step_rows."""
+        self._chk(self.L.gemma_engine_batch_open_rows(self.h, int(n_slots), int(max_rows)), "batch_open_rows")
+        self._bt_slots = int(n_slots)
+
+    def batch_step_rows(self, max_rows, want_logits=False):
+        """One pass of up to max_rows rows, several per slot that still has given tokens to consume
+        (batch_plan_rows states the allotment).  Returns (rows_of [n_slots], logits [T][n_vocab] in
+        row order — ascending slot, then position — or None)."""
+        rows_of = np.zeros(BATCH_WIDE_MAX_SLOTS, dtype=np.int32)
+        lg = np.zeros((max(int(max_rows), 1), self.cfg.n_vocab), dtype=np.float32) if want_logits else None
+        T = self.L.gemma_engine_batch_step_rows(self.h, int(max_rows), _p(lg) if want_logits else None, _p(rows_of))
+        if T < 0:
+            raise RuntimeError("batch_step_rows failed: " + last_error())
+        return rows_of[:self._bt_slots].copy(), (lg[:T] if want_logits else None)
 
     def batch_close(self):
         self._chk(self.L.gemma_engine_batch_close(self.h), "batch_close")
@@ -696,6 +719,16 @@ def test_logprob(rows, tokens):
 
 
 test_logprob.__test__ = False  # a library wrapper, not a pytest test
+
+
+def batch_plan_rows(need, max_rows):
+    """The row allotment of batch_step_rows (gemma_batch_plan_rows, a host function: no GPU): need[s]
+    is 0 for an inactive slot, else max(1, given - pos).  Returns rows_of [len(need)]."""
+    a = np.ascontiguousarray(need, dtype=np.int32)
+    out = np.zeros(max(len(a), 1), dtype=np.int32)
+    if lib().gemma_batch_plan_rows(_p(a), len(a), int(max_rows), _p(out)) < 0:
+        raise ValueError("gemma_batch_plan_rows: " + last_error())
+    return out[:len(a)]
 
 
 def lookup_draft(seq, ngram_max, k):

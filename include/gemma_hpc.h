@@ -252,7 +252,34 @@ int gemma_engine_kv_read(gemma_engine *e, int layer, int p0, int n, uint16_t *k_
  *            else as consecutive groups of up to 8 rows.  The same bits in every form.
  *   last_n   the pending tokens of slots [0, n_slots) into out[0 .. n_slots), -1 for inactive slots;
  *            returns n_slots, -1 when cap < n_slots.  gemma_engine_batch_last serves batches of up to 8
- *            slots only (it returns -1 on a wider one). */
+ *            slots only (it returns -1 on a wider one).
+ * Several rows per slot: a slot that still has given tokens to consume takes the pass's idle rows, so a
+ * prompt enters a slot beside the decoding slots instead of one token per pass.
+ *   plan_rows  gemma_batch_plan_rows, a pure host function (no GPU), the one statement of the allotment.
+ *            need[s] is 0 for an inactive slot, else max(1, given - pos): the slot's given-but-unprocessed
+ *            tokens, or 1 when its pending token is a pick.  Every active slot (R of them) gets one row;
+ *            the remaining budget max_rows - R is dealt in ascending slot order, extra_s = min(budget,
+ *            need[s] - 1).  Writes rows_of[0 .. n_slots) and returns their sum T; -1 on n_slots outside
+ *            [1, 64], a negative need, no active slot, or max_rows outside [R, 64].
+ *   open_rows  open with n_slots in [1, 64] and the pass scratch, pick keys, sampler workspaces and
+ *            log-probability partials sized for max_rows rows, max(8, n_slots) <= max_rows <= 64; the
+ *            same refusals as open.  A batch opened by open / open_wide has a row capacity of
+ *            max(8, n_slots).
+ *   step_rows  one pass of T = plan_rows(need from the slots' positions and given counts, max_rows)
+ *            rows, ordered by ascending slot, then ascending position.  Row (s, i), i < m_s, processes
+ *            hist_s[pos_s + i], stores that position's K / V in the slot's caches and attends positions
+ *            0 .. pos_s + i; then pos_s += m_s, and if the new pos_s >= the slot's given-token count the
+ *            last row's pick (greedy, or the sampler with (seed, p = new pos_s)) becomes hist_s[pos_s].
+ *            Given tokens are never overwritten; picks of other rows are not used.  With
+ *            log-probabilities on, row (s, i) scores hist_s[pos_s + i + 1].  Afterwards every slot's
+ *            device state (caches, history, position, given count, RoPE row, token word, lp) is byte for
+ *            byte what m_s calls of step(e, 1, ...) leave on it, and every row's logits are the row
+ *            those passes compute.  The pass form goes by T as step's goes by R (T <= 8 skinny, T >=
+ *            bt_mfma_min one MFMA pass, else groups of up to 8 rows; a slot's rows may straddle groups).
+ *            logits: NULL or [T][n_vocab] in row order; rows_of: NULL or [n_slots] (the plan).  Returns
+ *            T; one host synchronise at the end.  Refused (-1, no slot advanced): no batch, no active
+ *            slot, max_rows below the active count or above the batch's row capacity, any slot with
+ *            pos_s + m_s >= n_ctx. */
 #define GEMMA_BATCH_MAX_SLOTS 8
 #define GEMMA_BATCH_WIDE_MAX_SLOTS 64
 int gemma_engine_batch_open(gemma_engine *e, int n_slots);
@@ -267,6 +294,9 @@ int gemma_engine_batch_last(gemma_engine *e, int32_t *out8);
 int gemma_engine_batch_kv_read(gemma_engine *e, int slot, int layer, int p0, int n, uint16_t *k_rows, uint16_t *v_rows);
 int gemma_engine_batch_open_wide(gemma_engine *e, int n_slots);
 int gemma_engine_batch_last_n(gemma_engine *e, int32_t *out, int cap);
+int gemma_batch_plan_rows(const int32_t *need, int n_slots, int max_rows, int32_t *rows_of);
+int gemma_engine_batch_open_rows(gemma_engine *e, int n_slots, int max_rows);
+int gemma_engine_batch_step_rows(gemma_engine *e, int max_rows, float *logits, int32_t *rows_of);
 /* Prompt-lookup draft for the sequence seq[0..n) (pure host function, no GPU): for g = min(ngram_max,
  * n - 1) down to 1, the largest s < n - g with seq[s..s+g) == seq[n-g..n); the first g with a match
  * wins and the draft is seq[s+g .. min(s+g+k, n)).  Returns its length (0: no g matches), -1 on
