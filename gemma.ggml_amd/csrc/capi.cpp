@@ -469,9 +469,10 @@ static int test_matvec(const gemma_test_matvec_args *t, int gelu_clamp, uint32_t
         return bad("bad arguments");
     if (t->ncols < 1 || t->ncols > 8 || t->grid < 1 || t->grid > 4096 || t->y_stride < t->rows) return bad("bad geometry");
     const int pro = t->pro, epi = t->epi;
-    if (pro != PRO_F32 && pro != PRO_NORM && pro != PRO_EMBED && pro != PRO_IMG) return bad("prologue not covered");
+    if (pro != PRO_F32 && pro != PRO_NORM && pro != PRO_Q8 && pro != PRO_EMBED && pro != PRO_IMG) return bad("prologue not covered");
     if (epi < EPI_STORE || epi > EPI_ARGMAX) return bad("bad epilogue");
     if ((pro == PRO_F32 || pro == PRO_NORM) && t->x_stride < t->K) return bad("x_stride < K");
+    if (pro == PRO_Q8 && t->x_stride < t->K / 32 * 34) return bad("x_stride < the Q8_0 row's bytes");
     if ((pro == PRO_NORM || pro == PRO_EMBED) && !t->norm_w) return bad("norm_w missing");
     if (pro == PRO_IMG && (!t->x_da || t->K % 128)) return bad("the image needs x_da and K % 128 == 0");
     if (epi == EPI_ADD && !t->resid) return bad("resid missing");
@@ -487,7 +488,10 @@ static int test_matvec(const gemma_test_matvec_args *t, int gelu_clamp, uint32_t
     const int bb = t->type == T_Q4_0 ? 18 : 34;
     const int64_t K = t->K, rows = t->rows, nb = K / 32, row_bytes = nb * bb;
     const size_t y_floats = (size_t)((t->ncols - 1) * t->y_stride + rows);
-    const size_t x_bytes = pro == PRO_EMBED ? (size_t)t->n_tok * 4 : pro == PRO_IMG ? (size_t)K : (size_t)((t->ncols - 1) * t->x_stride + K) * 4;
+    const size_t x_bytes = pro == PRO_EMBED ? (size_t)t->n_tok * 4
+                           : pro == PRO_IMG ? (size_t)K
+                           : pro == PRO_Q8  ? (size_t)((t->ncols - 1) * t->x_stride + nb * 34)
+                                            : (size_t)((t->ncols - 1) * t->x_stride + K) * 4;
     dev_pool tmp;
     uint8_t *d_rows = nullptr, *d_x = nullptr;
     float *d_y = nullptr, *d_r = nullptr, *d_nw = nullptr, *d_da = nullptr, *d_eo = nullptr;
@@ -523,7 +527,7 @@ static int test_matvec(const gemma_test_matvec_args *t, int gelu_clamp, uint32_t
     GHIP_CHECK(hipMemset(d_keys, 0, n_keys * 8));
     mv_args a;
     set_mat(a, m);
-    a.x = d_x; a.x_col_stride = pro == PRO_F32 || pro == PRO_NORM ? t->x_stride * 4 : 0;
+    a.x = d_x; a.x_col_stride = pro == PRO_F32 || pro == PRO_NORM ? t->x_stride * 4 : pro == PRO_Q8 ? t->x_stride : 0;
     a.y = d_y; a.y_col_stride = t->y_stride; a.ncols = t->ncols; a.eps = t->eps;
     if (t->norm_w) {
         GHIP_CHECK(hipMemcpy(d_nw, t->norm_w, (size_t)K * 4, hipMemcpyHostToDevice));

@@ -272,7 +272,9 @@ struct act_src {
     }
 };
 
-template <int WT, int PRO, int R, bool NSA, int NTH>
+// IMG_TAIL (PRO_IMG): false where the caller's 2R items per thread cover the whole image, so the long-K
+// loop below (a load and a full wait in front of the rounds) is not compiled in
+template <int WT, int PRO, int R, bool NSA, int NTH, bool IMG_TAIL = true>
 __device__ norm_state build_activation(const mv_args &a, int col, uint8_t *smem, const lds_map &m, const act_regs<R> &r) {
     constexpr int BT = wfmt<WT>::BT;
     const int tid = threadIdx.x, nth = NTH;
@@ -312,7 +314,8 @@ __device__ norm_state build_activation(const mv_args &a, int col, uint8_t *smem,
                 put(it, make_uint4(__builtin_bit_cast(uint32_t, src[0]), __builtin_bit_cast(uint32_t, src[1]),
                                    __builtin_bit_cast(uint32_t, src[2]), __builtin_bit_cast(uint32_t, src[3])));
         }
-        for (int64_t it = tid + (int64_t)2 * R * nth; it < T; it += nth) put(it, *img_item(a, it));  // long K
+        if (IMG_TAIL)
+            for (int64_t it = tid + (int64_t)2 * R * nth; it < T; it += nth) put(it, *img_item(a, it));  // long K
         return ns;
     }
     const act_src<WT, PRO, R, NSA, NTH> src(a, col, r);

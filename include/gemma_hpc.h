@@ -384,6 +384,7 @@ int gemma_test_gemm_skinny(int type, int64_t rows, int64_t K, int64_t T, const v
 /* per-op test entry: ONE decode matvec launch (either form) on host buffers, every argument of the
  * launch set by the caller, so that a test can make each of them distinguishable.
  * pro: 0 x = ncols columns of K floats (x_stride floats apart), 1 the same through rms_norm * norm_w,
+ *      2 x = ncols rows of ggml block_q8_0 [K/32] (x_stride bytes apart),
  *      3 x = int32 tokens[n_tok], the row tokens[tok_pos] of emb (ggml rows [emb_rows][K/32] of `type`)
  *      * emb_scale through rms_norm * norm_w, 4 x = the Q8_0 activation image u32 [K/4] + x_da f32 [K/32]
  * epi: 0 y = dot, 1 y = dot + resid, 2 y = gelu(W . x) * (W2 . x), 3 y = dot and keys[ncols][grid]
