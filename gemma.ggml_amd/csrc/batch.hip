@@ -12,6 +12,10 @@
 //    k_rows_prepare (the rows' positions, RoPE rows and tokens), per layer k_rows_rope_kv (the K / V
 //    stores of all rows) then k_attn_slot_rows (attn_head_dev with every K / V operand read from the
 //    cache), and k_rows_advance (k_batch_advance per slot, pos += m).
+//  * drafts in the batch (gemma_engine_batch_verify, "Drafts in the batch" in §5b⁗): such a pass over the
+//    participating slots, with k_bverify_stage in front (the drafts into hist) and, instead of
+//    k_rows_advance, k_bverify_accept (the accept rule and the advance over the accepted prefix per
+//    slot) and k_bverify_clean (the rejected rows' K / V back to zero).
 #include "attn_impl.h"
 #include "pick.h"
 
@@ -137,6 +141,85 @@ __global__ void __launch_bounds__(256) k_rows_advance(const slot_row *rows, cons
     }
 }
 
+// ---- drafts in the batch (gemma_engine_batch_verify) ------------------------------------------------
+// The pass is a several-rows-per-slot pass (k_rows_prepare, k_rows_rope_kv, k_attn_slot_rows) whose
+// rows past a slot's first process drafts.  Three kernels of its own, each over the participating
+// slots (vs[blockIdx]; rows[vs.rank] is the slot's entry of the batch_step table).
+
+// before k_rows_prepare reads the rows' tokens: the drafts become hist[pos + 1 .. pos + m)
+__global__ void __launch_bounds__(64) k_bverify_stage(const slot_row *rows, const bv_slot *vs, int hist_cap) {
+    const bv_slot *v = vs + blockIdx.x;
+    const slot_row sr = rows[v->rank];
+    const int i = threadIdx.x, q = *sr.pos + 1 + i;
+    if (i < v->m - 1 && i < BV_MAX_ROWS - 1 && q < hist_cap) sr.hist[q] = v->draft[i];
+}
+
+// k_verify_accept per slot, the advance k_batch_advance's: row (s, i) picked g_i for sequence index
+// p0 + i + 1, hist[p0 + 1 + i] holds draft[i] (i < k = m - 1); a = the leading drafts that equal their
+// row's pick.  Then what a + 1 one-row passes leave on the slot.
+__global__ void __launch_bounds__(256) k_bverify_accept(const slot_row *rows, const slot_row *mrows, const bv_slot *vs,
+                                                        const unsigned long long *keys, int n_parts, int key_stride,
+                                                        int *row_tok, int hist_cap, rope_row r, int *out) {
+    __shared__ unsigned long long red[4];
+    __shared__ int gs[BV_MAX_ROWS], a_sh;
+    const int tid = threadIdx.x;
+    const bv_slot *v = vs + blockIdx.x;
+    const int row0 = v->row0, m = min(v->m, BV_MAX_ROWS), rank = v->rank;
+    const slot_row sr = rows[rank];
+    // every thread reads the position before the first barrier; thread 0 writes it after (as k_advance)
+    const int p0 = *sr.pos;
+    const int fixed = *sr.nfix;
+    for (int i = 0; i < m; ++i) {
+        const unsigned long long best = block_max_key(keys + (int64_t)(row0 + i) * key_stride, n_parts, red);
+        if (tid == 0) gs[i] = key_index(best);
+        __syncthreads();  // red[] is reused by the next row: thread 0 has read it
+    }
+    if (tid == 0) {
+        const int k = m - 1;
+        int a = 0;
+        while (a < k && sr.hist[p0 + 1 + a] == gs[a]) ++a;  // stops at the first mismatch
+        for (int i = 0; i <= a; ++i) {
+            const int q = p0 + 1 + i;
+            if (q < hist_cap) {
+                if (q >= fixed) sr.hist[q] = gs[i];  // never overwrite a given token (a k = 0 slot still ingesting)
+                else gs[i] = sr.hist[q];
+            }
+        }
+        for (int i = a + 1; i < k; ++i) sr.hist[p0 + 1 + i] = 0;  // the rejected drafts behind them
+        *sr.pos = p0 + a + 1;
+        *sr.last = gs[a];
+        row_tok[rank] = gs[a];  // what the slot's row processes in a following batch_step pass
+        int *o = out + blockIdx.x * BV_OUT_WORDS;
+        o[0] = a;
+        for (int i = 0; i < m; ++i) o[1 + i] = gs[i];
+        a_sh = a;
+    }
+    __syncthreads();
+    const int a = a_sh, p = p0 + a + 1;
+    if (p < r.ctx) publish_rope_row(sr.rope, r.cos, r.sin, r.half, p);
+    // an accepted row's position word becomes the sequence index it predicts (what k_lse_finish reads);
+    // a rejected row's -1: outside [1, n_ctx], nothing is scored
+    if (tid < m) *mrows[row0 + tid].pos = tid <= a ? p0 + tid + 1 : -1;
+}
+
+// grid (layer, slot): the K rows and V columns the pass stored under the slot's rejected drafts, p0 + a
+// + 1 .. p0 + k = pos .. pos + (k - a) - 1 with pos the position the accept left, back to zero
+__global__ void __launch_bounds__(256) k_bverify_clean(const slot_row *rows, const bv_slot *vs, const int *out,
+                                                       int64_t layer_stride, int ctx, int kvw) {
+    const bv_slot *v = vs + blockIdx.y;
+    const int k = v->m - 1, a = out[blockIdx.y * BV_OUT_WORDS];
+    if (a < 0 || a >= k) return;
+    const slot_row sr = rows[v->rank];
+    const int r0 = *sr.pos, n = k - a;
+    if (r0 < 0 || r0 + n > ctx) return;
+    uint16_t *K = sr.kc + (int64_t)blockIdx.x * layer_stride, *V = sr.vc + (int64_t)blockIdx.x * layer_stride;
+    for (int idx = threadIdx.x; idx < n * kvw; idx += 256) {
+        const int rr = r0 + idx / kvw, j = idx % kvw;
+        K[(int64_t)rr * kvw + j] = 0;
+        V[(int64_t)j * ctx + rr] = 0;
+    }
+}
+
 }  // namespace
 
 int launch_attn_slots(const attn_args &a, const slot_row *rows, int R, int64_t layer_off, hipStream_t s) {
@@ -203,6 +286,45 @@ int launch_rows_advance(const slot_row *rows, const slot_row *mrows, const slot_
                         const rope_row &r, hipStream_t s) {
     hipLaunchKernelGGL(k_rows_advance, dim3(R), dim3(256), 0, s, rows, mrows, spans, keys, n_parts, key_stride, row_tok,
                        hist_cap, r);
+    GHIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+static bool bverify_tables_ok(const slot_row *rows, const bv_slot *vs, int P, const char *what) {
+    if (rows && vs && P >= 1 && P <= ATTN_SLOTS_MAX_R) return true;
+    set_error(std::string(what) + ": a pass outside [1, 64] slots, or no table");
+    return false;
+}
+
+int launch_bverify_stage(const slot_row *rows, const bv_slot *vs, int P, int hist_cap, hipStream_t s) {
+    if (!bverify_tables_ok(rows, vs, P, "bverify_stage")) return -1;
+    hipLaunchKernelGGL(k_bverify_stage, dim3(P), dim3(64), 0, s, rows, vs, hist_cap);
+    GHIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_bverify_accept(const slot_row *rows, const slot_row *mrows, const bv_slot *vs, int P,
+                          const unsigned long long *keys, int n_parts, int key_stride, int *row_tok, int hist_cap,
+                          const rope_row &r, int *out, hipStream_t s) {
+    if (!bverify_tables_ok(rows, vs, P, "bverify_accept")) return -1;
+    if (!mrows || !keys || !row_tok || !out || n_parts < 1) {
+        set_error("bverify_accept: no row table, keys or result buffer");
+        return -1;
+    }
+    hipLaunchKernelGGL(k_bverify_accept, dim3(P), dim3(256), 0, s, rows, mrows, vs, keys, n_parts, key_stride, row_tok,
+                       hist_cap, r, out);
+    GHIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_bverify_clean(const slot_row *rows, const bv_slot *vs, int P, const int *out, int n_layer, int64_t layer_stride,
+                         int ctx, int kvw, hipStream_t s) {
+    if (!bverify_tables_ok(rows, vs, P, "bverify_clean")) return -1;
+    if (!out || n_layer < 1 || ctx < 1 || kvw < 1) {
+        set_error("bverify_clean: no accepted counts, or an empty cache");
+        return -1;
+    }
+    hipLaunchKernelGGL(k_bverify_clean, dim3(n_layer, P), dim3(256), 0, s, rows, vs, out, layer_stride, ctx, kvw);
     GHIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -12,6 +12,9 @@
 // pass (gemma_batch_plan_rows states the allotment): the same pass over a row table of its own, the
 // attention step in two launches (K / V stores of all rows, then the attention from the cache), the
 // advance per slot.  The slot's state afterwards is byte for byte what one-row passes leave.
+// gemma_engine_batch_verify is gemma_engine_verify for the slots: such a pass whose rows past a slot's
+// first process drafts, then per slot the accept rule, the advance over the accepted prefix and the
+// rejected rows' K / V cleared, all on the device; a slot may sit the pass out.
 #include "engine_impl.h"
 
 static constexpr int NS = GEMMA_BATCH_WIDE_MAX_SLOTS;  // every table's size
@@ -72,7 +75,10 @@ static int batch_open(gemma_engine *e, int n_slots, int max_slots, int rows, con
           // the tables of a pass with several rows per slot (gemma_engine_batch_step_rows)
           M.get_zeroed(&b.mrows, NS * sizeof(slot_row), s) || M.get_zeroed(&b.msrc, NS * sizeof(row_src), s) ||
           M.get_zeroed(&b.mspans, NS * sizeof(slot_span), s) || M.get_zeroed(&b.mrope, NS * rope_words * 4, s) ||
-          M.get(&b.mstage, mtab, MEM_PINNED);
+          M.get(&b.mstage, mtab, MEM_PINNED) ||
+          // the tables of a pass with drafts (gemma_engine_batch_verify)
+          M.get_zeroed(&b.vslots, NS * sizeof(bv_slot), s) || M.get_zeroed(&b.vout, NS * BV_OUT_WORDS * 4, s) ||
+          M.get_zeroed(&b.vtok, NS * 4, s) || M.get(&b.vstage, NS * (sizeof(bv_slot) + BV_OUT_WORDS * 4), MEM_PINNED);
     if (!bad) {  // no slot is active: every pending token reads -1
         int *h = (int *)b.stage;
         for (int i = 0; i < NS; ++i) h[i] = -1;
@@ -384,6 +390,147 @@ extern "C" int gemma_engine_batch_step_rows(gemma_engine *e, int max_rows, float
     for (int i = 0; i < b.n_slots; ++i) {
         if (b.slot[i].active) b.slot[i].host_pos += m_of[i];
         if (rows_of) rows_of[i] = m_of[i];
+    }
+    return T;
+}
+
+// ---- drafts in the batch -------------------------------------------------------------------------
+// One exact pass in which every participating slot has its pending token and k_s drafts at consecutive
+// positions (a several-rows-per-slot pass over tables of its own), then per slot on the device the
+// accept rule, the advance over the accepted prefix and the rejected rows' K / V cleared: afterwards
+// the slot's state is what a_s + 1 one-row passes leave.  A slot that sits out is in no table.
+static_assert(GEMMA_VERIFY_MAX_DRAFT + 1 == BV_MAX_ROWS, "a slot's rows: its pending token and the drafts");
+extern "C" int gemma_engine_batch_verify(gemma_engine *e, const int32_t *draft, const int32_t *k_of, int32_t *out_tokens,
+                                         int32_t *n_out, float *logits) {
+    set_error("");
+    const std::string fn = "gemma_engine_batch_verify";
+    const gemma_hip_config &c = e->cfg;
+    batch_state &b = e->bt;
+    constexpr int KD = GEMMA_VERIFY_MAX_DRAFT;
+    if (!b.open) {
+        set_error(fn + ": no batch is open (gemma_engine_batch_open)");
+        return -1;
+    }
+    if (!draft || !k_of || !out_tokens || !n_out) {
+        set_error(fn + ": a null draft, k_of, out_tokens or n_out");
+        return -1;
+    }
+    int P = 0, T = 0;
+    for (int i = 0; i < b.n_slots; ++i) {
+        const seq_state &S = b.slot[i];
+        if (!S.active) continue;
+        const int k = k_of[i];
+        if (k < -1 || k > KD) {
+            set_error(fn + ": k_of[" + std::to_string(i) + "] = " + std::to_string(k) + " outside [-1, " + std::to_string(KD) + "]");
+            return -1;
+        }
+        if (k < 0) continue;
+        if (k >= 1 && (S.host_pos < S.n_given || S.host_pos < 1)) {
+            set_error(fn + ": slot " + std::to_string(i) + " has " + std::to_string(std::max(S.n_given - S.host_pos, 0)) +
+                      " given tokens still pending (the drafts follow the pending picked token)");
+            return -1;
+        }
+        if (k >= 1 && !token_ids_ok(e, draft + (size_t)i * KD, k, fn.c_str())) return -1;
+        if ((int64_t)S.host_pos + k + 1 >= c.n_ctx) {
+            set_error(fn + ": context full (slot " + std::to_string(i) + ": pos + k + 1 = " +
+                      std::to_string((int64_t)S.host_pos + k + 1) + " does not fit n_ctx = " + std::to_string(c.n_ctx) + ")");
+            return -1;
+        }
+        ++P;
+        T += 1 + k;
+    }
+    if (P == 0) {
+        set_error(fn + ": no slot takes part (no active slot, or every k_of is -1)");
+        return -1;
+    }
+    if (T > b.pf.T) {
+        set_error(fn + ": " + std::to_string(T) + " rows exceed the batch's row capacity " + std::to_string(b.pf.T));
+        return -1;
+    }
+    (void)hipSetDevice(e->device);
+    hipStream_t s = e->stream;
+    if (b.dirty && batch_write_rows(e)) return -1;
+    // the pass's tables: rows by ascending slot then position (as step_rows'), the per-slot table by
+    // the slot's index among the participating slots, with its rank in the batch_step table
+    slot_row *hr = (slot_row *)b.mstage;
+    row_src *hs = (row_src *)(hr + NS);
+    bv_slot *hv = (bv_slot *)b.vstage;
+    int *h_out = (int *)(hv + NS);
+    int part[NS];
+    const size_t rope_words = (size_t)c.head_dim + 4;
+    for (int i = 0, t = 0, rank = 0, p = 0; i < b.n_slots; ++i) {
+        const seq_state &S = b.slot[i];
+        if (!S.active) continue;
+        if (k_of[i] >= 0) {
+            const int m = 1 + k_of[i];
+            bv_slot v;
+            v.row0 = t; v.m = m; v.rank = rank;
+            for (int j = 0; j < m - 1; ++j) v.draft[j] = draft[(size_t)i * KD + j];
+            hv[p] = v;
+            part[p++] = i;
+            for (int j = 0; j < m; ++j, ++t) {
+                slot_row r;
+                r.qkv = b.pf.QKV + (size_t)t * e->qkv_rows;
+                r.out = b.pf.ATT + (size_t)t * e->qw;
+                r.kc = S.kc; r.vc = S.vc;
+                r.rope = b.mrope + (size_t)t * rope_words;
+                r.pos = (int *)(r.rope + c.head_dim);
+                r.hist = S.hist; r.nfix = S.nfix; r.last = S.token; r.lp = S.lp;
+                hr[t] = r;
+                hs[t] = row_src{S.pos, j, rank};
+            }
+        }
+        ++rank;
+    }
+    GHIP_CHECK(hipMemcpyAsync(b.mrows, hr, (size_t)T * sizeof(slot_row), hipMemcpyHostToDevice, s));
+    GHIP_CHECK(hipMemcpyAsync(b.msrc, hs, (size_t)T * sizeof(row_src), hipMemcpyHostToDevice, s));
+    GHIP_CHECK(hipMemcpyAsync(b.vslots, hv, (size_t)P * sizeof(bv_slot), hipMemcpyHostToDevice, s));
+    // 1. stage: the drafts become hist_s[pos_s + 1 ..], the tokens of the slot's rows 1 .. k_s
+    if (T > P && launch_bverify_stage(b.rows, b.vslots, P, c.n_ctx, s)) return -1;
+    if (launch_rows_prepare(b.mrows, b.msrc, T, b.vtok, rope_of(e), s)) return -1;
+    // 2. the pass, its form by T exactly as step_rows'
+    const bool mfma = T > NARROW && T >= e->bt_mfma_min;
+    b.multi = true;
+    b.pass_tok = b.vtok;
+    int bad = 0;
+    if (T <= NARROW || mfma) {
+        bad = enqueue_batch_pass(e, 0, T, !mfma);
+    } else {
+        for (int r0 = 0; r0 < T && !bad; r0 += NARROW) bad = enqueue_batch_pass(e, r0, std::min(NARROW, T - r0), true);
+    }
+    b.multi = false;
+    b.pass_tok = nullptr;
+    if (bad) return -1;
+    // 3. a pick from every row (the sampler's position word the row's own), none advances
+    row_picks pk;
+    if (enqueue_row_picks(e, b.pf.LG, T, nullptr, b.mrows, b.picks, &pk)) return -1;
+    if (logits) GHIP_CHECK(hipMemcpyAsync(logits, b.pf.LG, (size_t)T * c.n_vocab * 4, hipMemcpyDeviceToHost, s));
+    // 4. accept + advance per slot; (log-probabilities on) rows 0 .. a_s score what the accept settled
+    if (launch_bverify_accept(b.rows, b.mrows, b.vslots, P, pk.keys, pk.n_parts, pk.stride, b.row_tok, c.n_ctx, rope_of(e),
+                              b.vout, s))
+        return -1;
+    if (enqueue_lp_finish(e, b.pf.LG, T, b.picks.lp_parts, nullptr, b.mrows, nullptr)) return -1;
+    // 5. the rejected rows leave the caches
+    if (T > P && launch_bverify_clean(b.rows, b.vslots, P, b.vout, c.n_layer, (int64_t)c.n_ctx * e->kvw, c.n_ctx, e->kvw, s))
+        return -1;
+    // 6. results: one synchronise
+    GHIP_CHECK(hipMemcpyAsync(h_out, b.vout, (size_t)P * BV_OUT_WORDS * 4, hipMemcpyDeviceToHost, s));
+    GHIP_CHECK(hipStreamSynchronize(s));
+    for (int i = 0; i < b.n_slots; ++i) n_out[i] = 0;
+    int wrong = -1;
+    for (int p = 0; p < P; ++p) {
+        const int i = part[p], a = h_out[p * BV_OUT_WORDS];
+        if (a < 0 || a > k_of[i]) {
+            wrong = i;
+            continue;
+        }
+        for (int j = 0; j <= a; ++j) out_tokens[(size_t)i * (KD + 1) + j] = h_out[p * BV_OUT_WORDS + 1 + j];
+        n_out[i] = a + 1;
+        b.slot[i].host_pos += a + 1;
+    }
+    if (wrong >= 0) {
+        set_error(fn + ": the accept kernel reported a count outside [0, k] for slot " + std::to_string(wrong));
+        return -1;
     }
     return T;
 }

@@ -126,6 +126,13 @@ struct batch_state {
     float *mrope = nullptr;      // device: [64][head_dim + 4]
     void *mstage = nullptr;      // pinned: the three tables' source
     bool multi = false;          // the pass being enqueued is such a pass (enqueue_batch_attention)
+    // drafts in the batch (gemma_engine_batch_verify): such a pass over the participating slots only.
+    // Its rows' tokens are its own, so row_tok keeps the entries of the slots that sit out
+    bv_slot *vslots = nullptr;   // device: [64] by the slot's index among the participating slots
+    int *vout = nullptr;         // device: [64][BV_OUT_WORDS] each slot's accepted count and picks
+    int *vtok = nullptr;         // device: [64] the tokens of the pass's rows
+    void *vstage = nullptr;      // pinned: vslots' source, vout's copy
+    const int *pass_tok = nullptr;  // the tokens of the pass being enqueued when they are not row_tok's (enqueue_batch_pass)
 };
 
 struct gemma_engine {

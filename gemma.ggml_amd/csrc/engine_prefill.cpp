@@ -301,7 +301,8 @@ int enqueue_batch_pass(gemma_engine *e, int r0, int T, bool skinny) {
                   ", or no batch scratch");
         return -1;
     }
-    return enqueue_prefill(e, T, pass_rows{e->bt.row_tok + r0, 0, true, r0}, true, nullptr, pass_end{true, skinny});
+    const int *tok = e->bt.pass_tok ? e->bt.pass_tok : e->bt.row_tok;
+    return enqueue_prefill(e, T, pass_rows{tok + r0, 0, true, r0}, true, nullptr, pass_end{true, skinny});
 }
 
 // one pass over rows [p0, p0+T) and its results: the last row's logits, all rows' [T][n_vocab], the

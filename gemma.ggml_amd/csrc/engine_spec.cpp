@@ -110,6 +110,22 @@ extern "C" int gemma_lookup_draft(const int32_t *seq, int n, int ngram_max, int 
     return 0;
 }
 
+// The draft of a generate loop, grown by repeated lookups: one lookup stops at the sequence end (in a
+// repeating run the most recent match sits right before it and yields a single token), so what it
+// drafted is appended to the mirror as a guess and the rule applied again, until kd_max tokens or no
+// match.  seq: the mirror, n tokens of it the sequence (room for kd_max more); the guesses past n are
+// overwritten by what the pass accepts.  Returns the draft's length.
+static int grow_lookup_draft(int32_t *seq, int n, int ngram_max, int kd_max, int32_t *draft) {
+    int kd = 0;
+    while (kd < kd_max) {
+        const int m = gemma_lookup_draft(seq, n + kd, ngram_max, kd_max - kd, draft + kd);
+        if (m <= 0) break;
+        for (int i = 0; i < m; ++i) seq[n + kd + i] = draft[kd + i];
+        kd += m;
+    }
+    return kd;
+}
+
 extern "C" int gemma_engine_generate_lookup(gemma_engine *e, int n_new, int k, int ngram_max, int32_t *out,
                                             gemma_spec_stats *stats) {
     set_error("");
@@ -136,17 +152,7 @@ extern "C" int gemma_engine_generate_lookup(gemma_engine *e, int n_new, int k, i
     while (done < n_new) {
         // a pass over kd drafts appends up to kd + 1 tokens: never more than remain
         const int kd_max = std::min(k, n_new - done - 1);
-        // The draft is grown by repeated lookups: one lookup stops at the sequence end (in a repeating
-        // run the most recent match sits right before it and yields a single token), so what it drafted
-        // is appended to the mirror as a guess and the rule applied again, until kd_max tokens or no
-        // match.  The guesses past n are overwritten below by what the pass accepts.
-        int kd = 0;
-        while (kd < kd_max) {
-            const int m = gemma_lookup_draft(seq.data(), n + kd, ngram_max, kd_max - kd, draft + kd);
-            if (m <= 0) break;
-            for (int i = 0; i < m; ++i) seq[n + kd + i] = draft[kd + i];
-            kd += m;
-        }
+        int kd = grow_lookup_draft(seq.data(), n, ngram_max, kd_max, draft);
         if (kd > 0 && (int64_t)e->seq.host_pos + kd + 1 >= c.n_ctx) kd = 0;
         if (kd > 0) {
             const int m = gemma_engine_verify(e, draft, kd, got, nullptr);
@@ -162,5 +168,96 @@ extern "C" int gemma_engine_generate_lookup(gemma_engine *e, int n_new, int k, i
         }
     }
     if (stats) *stats = st;
+    return 0;
+}
+
+// The same loop over the open batch's slots: per pass every unfinished slot drafts from its own mirror,
+// one gemma_engine_batch_verify pass serves them all, finished slots sit out.
+extern "C" int gemma_engine_batch_generate_lookup(gemma_engine *e, int n_new, int k, int ngram_max, int32_t *out,
+                                                  gemma_spec_stats *stats) {
+    set_error("");
+    const std::string fn = "gemma_engine_batch_generate_lookup";
+    const gemma_hip_config &c = e->cfg;
+    batch_state &b = e->bt;
+    constexpr int KD = GEMMA_VERIFY_MAX_DRAFT, NS = GEMMA_BATCH_WIDE_MAX_SLOTS;
+    if (!b.open) {
+        set_error(fn + ": no batch is open (gemma_engine_batch_open)");
+        return -1;
+    }
+    if (n_new < 0 || (n_new > 0 && !out) || k < 1 || k > KD || ngram_max < 1) {
+        set_error(fn + ": needs n_new >= 0, 1 <= k <= " + std::to_string(KD) + " and ngram_max >= 1");
+        return -1;
+    }
+    int R = 0;
+    for (int i = 0; i < b.n_slots; ++i) {
+        const seq_state &S = b.slot[i];
+        if (!S.active) continue;
+        ++R;
+        if (S.host_pos < S.n_given || S.host_pos < 1) {
+            set_error(fn + ": slot " + std::to_string(i) + " has given tokens still pending (consume the prompts first)");
+            return -1;
+        }
+        if ((int64_t)S.host_pos + n_new >= c.n_ctx) {
+            set_error(fn + ": context full (slot " + std::to_string(i) + ")");
+            return -1;
+        }
+    }
+    if (R == 0) {
+        set_error(fn + ": no slot is active (gemma_engine_batch_begin / _adopt)");
+        return -1;
+    }
+    // per active slot the sequence so far, the pending token included, and what it has appended
+    const size_t ld = (size_t)c.n_ctx + 1;
+    std::vector<int32_t> seq((size_t)b.n_slots * ld), draft((size_t)b.n_slots * KD), got((size_t)b.n_slots * (KD + 1));
+    std::vector<gemma_spec_stats> st((size_t)b.n_slots, gemma_spec_stats{0, 0, 0, 0});
+    int32_t n_of[NS] = {}, done[NS] = {}, k_of[NS], need[NS], rows_of[NS], n_out[NS];
+    int left = 0;
+    for (int i = 0; i < b.n_slots; ++i) {
+        if (!b.slot[i].active) continue;
+        n_of[i] = gemma_engine_batch_tokens(e, i, seq.data() + i * ld, (int)ld);
+        if (n_of[i] != b.slot[i].host_pos + 1) return -1;
+        left += n_new > 0;
+    }
+    while (left > 0) {
+        int T = 0;
+        for (int i = 0; i < b.n_slots; ++i) {
+            need[i] = 0;
+            k_of[i] = -1;  // inactive and finished slots sit out
+            if (!b.slot[i].active || done[i] >= n_new) continue;
+            // a pass over kd drafts appends up to kd + 1 tokens: never more than remain
+            int kd = grow_lookup_draft(seq.data() + i * ld, n_of[i], ngram_max, std::min(k, n_new - done[i] - 1),
+                                       draft.data() + (size_t)i * KD);
+            if (kd > 0 && (int64_t)b.slot[i].host_pos + kd + 1 >= c.n_ctx) kd = 0;
+            k_of[i] = kd;
+            need[i] = 1 + kd;
+            T += need[i];
+        }
+        if (T > b.pf.T) {  // more rows than the batch holds: the drafts are cut by the one allotment rule
+            if (gemma_batch_plan_rows(need, b.n_slots, b.pf.T, rows_of) < 0) {
+                set_error(fn + ": " + last_error());
+                return -1;
+            }
+            for (int i = 0; i < b.n_slots; ++i)
+                if (need[i] > 0) k_of[i] = rows_of[i] - 1;
+        }
+        if (gemma_engine_batch_verify(e, draft.data(), k_of, got.data(), n_out, nullptr) < 0) {
+            set_error(fn + ": " + last_error());
+            return -1;
+        }
+        for (int i = 0; i < b.n_slots; ++i) {
+            if (k_of[i] < 0) continue;
+            const int m = n_out[i];
+            if (k_of[i] > 0) {
+                st[i].passes += 1; st[i].drafted += k_of[i]; st[i].accepted += m - 1;
+            } else {
+                st[i].plain_steps += 1;
+            }
+            for (int j = 0; j < m; ++j)
+                seq[i * ld + n_of[i]++] = out[(size_t)i * n_new + done[i]++] = got[(size_t)i * (KD + 1) + j];
+            left -= done[i] >= n_new;
+        }
+    }
+    if (stats)
+        for (int i = 0; i < b.n_slots; ++i) stats[i] = st[i];
     return 0;
 }

@@ -496,6 +496,30 @@ int launch_attn_slot_rows(const attn_args &a, const slot_row *mrows, const row_s
 int launch_rows_advance(const slot_row *rows, const slot_row *mrows, const slot_span *spans, int R,
                         const unsigned long long *keys, int n_parts, int key_stride, int *row_tok, int hist_cap,
                         const rope_row &r, hipStream_t s);
+// Drafts in the batch (gemma_engine_batch_verify): a pass of such rows in which a participating slot
+// has its pending token and up to 7 drafts.  The per-slot table is the pass's own, by the slot's index
+// among the participating slots; slots that sit out appear in no table of the pass.
+constexpr int BV_MAX_ROWS = 8;                // rows of one slot: 1 + GEMMA_VERIFY_MAX_DRAFT
+constexpr int BV_OUT_WORDS = 1 + BV_MAX_ROWS; // per slot: [0] = a (accepted drafts), [1 + i] = g_i for i < m
+struct bv_slot {
+    int row0 = 0, m = 0;  // the slot's rows [row0, row0 + m) of the pass; m - 1 drafts
+    int rank = 0;         // the slot's index in the batch_step table (rows, row_tok)
+    int pad = 0;
+    int draft[BV_MAX_ROWS] = {};  // draft[i], i < m - 1: the guess for sequence index pos + 1 + i
+};
+// before k_rows_prepare, one workgroup per participating slot: hist[pos + 1 + i] = draft[i], i < m - 1
+int launch_bverify_stage(const slot_row *rows, const bv_slot *vs, int P, int hist_cap, hipStream_t s);
+// per participating slot: the key reduction of each of its m rows, a = the leading drafts that equal
+// their row's pick, then what a + 1 calls of k_batch_advance leave (hist under the nfix guard, pos, the
+// RoPE row, `last`, row_tok[rank]); the rejected drafts behind them zeroed in hist; row (s, i)'s
+// position word the index it predicts (i <= a) or -1 (k_lse_finish writes nothing); out[s] = a, g_0 ..
+int launch_bverify_accept(const slot_row *rows, const slot_row *mrows, const bv_slot *vs, int P,
+                          const unsigned long long *keys, int n_parts, int key_stride, int *row_tok, int hist_cap,
+                          const rope_row &r, int *out, hipStream_t s);
+// grid (layer, slot): K rows and V columns pos .. pos + (m - 1 - a) - 1 of the slot's caches back to
+// zero, pos the slot's position after the accept and a = out[s][0] read on the device
+int launch_bverify_clean(const slot_row *rows, const bv_slot *vs, int P, const int *out, int n_layer, int64_t layer_stride,
+                         int ctx, int kvw, hipStream_t s);
 
 // ---- on-device sampling (sample.hip; the rule: include/gemma_hpc.h, DESIGN.md §5b″) ------------
 constexpr int SAMPLE_MAX_K = 1024;  // candidates at most (top_k == 0 means this many)

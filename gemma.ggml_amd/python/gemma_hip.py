@@ -44,7 +44,7 @@ EXPORTS = ["mul_mat", "hpc_init", "hpc_shutdown", "hpc_register_weight", "hpc_la
            "gemma_engine_batch_release", "gemma_engine_batch_step", "gemma_engine_batch_pos", "gemma_engine_batch_tokens",
            "gemma_engine_batch_last", "gemma_engine_batch_kv_read", "gemma_engine_batch_open_wide",
            "gemma_engine_batch_last_n", "gemma_batch_plan_rows", "gemma_engine_batch_open_rows",
-           "gemma_engine_batch_step_rows",
+           "gemma_engine_batch_step_rows", "gemma_engine_batch_verify", "gemma_engine_batch_generate_lookup",
            "gemma_engine_set_logprobs", "gemma_engine_logprobs", "gemma_engine_batch_logprobs", "gemma_test_logprob"]
 
 
@@ -205,7 +205,8 @@ def lib():
                    ("release", [C.c_int]), ("step", [C.c_int, vp]), ("pos", [C.c_int]), ("tokens", [C.c_int, vp, C.c_int]),
                    ("last", [vp]), ("kv_read", [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
                    ("open_wide", [C.c_int]), ("last_n", [vp, C.c_int]), ("open_rows", [C.c_int, C.c_int]),
-                   ("step_rows", [C.c_int, vp, vp])):
+                   ("step_rows", [C.c_int, vp, vp]), ("verify", [vp, vp, vp, vp, vp]),
+                   ("generate_lookup", [C.c_int, C.c_int, C.c_int, vp, C.POINTER(SpecStats)])):
         getattr(L, "gemma_engine_batch_" + fn).restype = C.c_int
         getattr(L, "gemma_engine_batch_" + fn).argtypes = [vp] + at
     L.gemma_batch_plan_rows.restype = C.c_int
@@ -435,6 +436,44 @@ class Engine:
         if T < 0:
             raise RuntimeError("batch_step_rows failed: " + last_error())
         return rows_of[:self._bt_slots].copy(), (lg[:T] if want_logits else None)
+
+    def batch_verify(self, drafts, want_logits=False):
+        """One exact pass with per-slot drafts (gemma_engine_batch_verify).  drafts: {slot: draft list}
+        or a list by slot; an empty list is a plain row (k = 0), None or a missing slot sits out (-1).
+        Returns {slot: tokens appended} for the participating slots, with want_logits also the pass's
+        rows [T][n_vocab] in row order (ascending slot, then position)."""
+        ns = self._bt_slots
+        get = drafts.get if isinstance(drafts, dict) else (lambda s: drafts[s] if s < len(drafts) else None)
+        d = np.zeros((ns, VERIFY_MAX_DRAFT), dtype=np.int32)
+        k_of = np.full(ns, -1, dtype=np.int32)
+        for s in range(ns):
+            ds = get(s)
+            if ds is None:
+                continue
+            ds = [int(x) for x in ds]
+            k_of[s] = len(ds)
+            d[s, :min(len(ds), VERIFY_MAX_DRAFT)] = ds[:VERIFY_MAX_DRAFT]
+        out = np.zeros((ns, VERIFY_MAX_DRAFT + 1), dtype=np.int32)
+        n_out = np.zeros(ns, dtype=np.int32)
+        rows = int(np.clip(k_of, -1, VERIFY_MAX_DRAFT).sum()) + ns
+        lg = np.zeros((max(rows, 1), self.cfg.n_vocab), dtype=np.float32) if want_logits else None
+        T = self.L.gemma_engine_batch_verify(self.h, _p(d), _p(k_of), _p(out), _p(n_out), _p(lg) if want_logits else None)
+        if T < 0:
+            raise RuntimeError("batch_verify failed: " + last_error())
+        toks = {s: [int(t) for t in out[s, :n_out[s]]] for s in range(ns) if n_out[s] > 0}
+        return (toks, lg[:T]) if want_logits else toks
+
+    def batch_generate_lookup(self, n_new, k=4, ngram_max=3):
+        """n_new tokens for every active slot by prompt-lookup drafts and batch_verify passes
+        (gemma_engine_batch_generate_lookup): (out [n_slots][n_new], per-slot list of dict(passes,
+        drafted, accepted, plain_steps)); rows of inactive slots stay zero."""
+        ns = self._bt_slots
+        out = np.zeros((ns, max(int(n_new), 1)), dtype=np.int32)
+        st = (SpecStats * ns)()
+        r = self.L.gemma_engine_batch_generate_lookup(self.h, int(n_new), int(k), int(ngram_max), _p(out), st)
+        self._chk(r, "batch_generate_lookup")
+        return out[:, :n_new], [dict(passes=x.passes, drafted=x.drafted, accepted=x.accepted, plain_steps=x.plain_steps)
+                                for x in st]
 
     def batch_close(self):
         self._chk(self.L.gemma_engine_batch_close(self.h), "batch_close")

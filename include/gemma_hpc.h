@@ -297,6 +297,37 @@ int gemma_engine_batch_last_n(gemma_engine *e, int32_t *out, int cap);
 int gemma_batch_plan_rows(const int32_t *need, int n_slots, int max_rows, int32_t *rows_of);
 int gemma_engine_batch_open_rows(gemma_engine *e, int n_slots, int max_rows);
 int gemma_engine_batch_step_rows(gemma_engine *e, int max_rows, float *logits, int32_t *rows_of);
+/* Drafts in the batch (DESIGN.md §5b⁗ "Drafts in the batch"): gemma_engine_verify for the slots of the
+ * open batch, all in one exact pass.  draft is [n_slots][GEMMA_VERIFY_MAX_DRAFT], k_of [n_slots]; k_of[s]
+ * is read for active slots only:
+ *   -1      the slot sits this pass out: it takes no row and not a byte of its state changes.
+ *   0       one row, exactly batch_step's row for that slot (it may still be consuming given tokens:
+ *           a given token is never overwritten).
+ *   1 .. 7  the slot's given tokens must be consumed (pos_s >= given_s, pos_s >= 1); draft[s][0 .. k_s)
+ *           are guesses for sequence indices pos_s + 1 .. pos_s + k_s.
+ * The pass has T = sum (1 + k_s) rows over the participating slots, ordered by ascending slot, then
+ * ascending position.  Row (s, i) processes hist_s[pos_s] for i = 0, else draft[s][i - 1], at position
+ * pos_s + i: it stores that position's K / V in the slot's caches and attends positions 0 .. pos_s + i.
+ * Every row gives a pick g_{s,i} for index pos_s + i + 1 (greedy, or the engine's sampler with (seed,
+ * p = pos_s + i + 1)).  Then on the device, per slot: a_s = the number of leading i < k_s with
+ * draft[s][i] == g_{s,i} (it stops at the first mismatch); hist_s[pos_s + 1 .. pos_s + a_s + 1] =
+ * g_{s,0 .. a_s} (a given token stands); the rejected drafts behind them are zeroed in hist; pos_s +=
+ * a_s + 1; the slot's token word, pending-token entry and RoPE row follow; K rows and V columns of the
+ * rejected rows go back to zero in every layer.  With log-probabilities on, rows 0 .. a_s score
+ * hist_s[pos_s + i + 1]; rejected rows write nothing.  Afterwards each participating slot's device state
+ * (caches, history, position, given count, RoPE row, token word, lp) is byte for byte what a_s + 1 calls
+ * of batch_step(e, 1, ...) leave on it, and a following batch_step, batch_step_rows or batch_verify
+ * continues from it.  The pass form goes by T exactly as step_rows' does, the same bits in each.
+ * out_tokens is [n_slots][GEMMA_VERIFY_MAX_DRAFT + 1]: out_tokens[s][0 .. a_s] = g_{s,0 .. a_s};
+ * n_out[s] = a_s + 1 for a participating slot, 0 otherwise.  logits: NULL or [T][n_vocab] in row order;
+ * rows past a_s are returned as computed under the rejected drafts.  Returns T; one host synchronise, at
+ * the end.  Refused (-1, hpc_last_error naming gemma_engine_batch_verify, no slot advanced, the state
+ * untouched): no batch open; a null draft, k_of, out_tokens or n_out; k_of[s] outside [-1, 7]; no
+ * participating slot; k_s >= 1 on a slot with given tokens pending or at pos 0; a used draft id outside
+ * [0, n_vocab); pos_s + k_s + 1 >= n_ctx; T above the batch's row capacity (max(8, n_slots), or
+ * open_rows' max_rows). */
+int gemma_engine_batch_verify(gemma_engine *e, const int32_t *draft, const int32_t *k_of,
+                              int32_t *out_tokens, int32_t *n_out, float *logits);
 /* Prompt-lookup draft for the sequence seq[0..n) (pure host function, no GPU): for g = min(ngram_max,
  * n - 1) down to 1, the largest s < n - g with seq[s..s+g) == seq[n-g..n); the first g with a match
  * wins and the draft is seq[s+g .. min(s+g+k, n)).  Returns its length (0: no g matches), -1 on
@@ -312,6 +343,19 @@ typedef struct gemma_spec_stats { int passes, drafted, accepted, plain_steps; } 
  * tokens are appended.  out[0..n_new) and the final pos equal
  * gemma_engine_step(n_new) token for token, sampler on or off.  0, or -1 with hpc_last_error. */
 int gemma_engine_generate_lookup(gemma_engine *e, int n_new, int k, int ngram_max, int32_t *out, gemma_spec_stats *stats);
+/* The same loop for every active slot of the open batch, the passes gemma_engine_batch_verify's.  out is
+ * [n_slots][n_new] (rows of inactive slots are not written), stats [n_slots] or NULL.  Every active slot
+ * must have its prompt consumed, and every active slot gets exactly n_new tokens.  Per pass and per
+ * unfinished slot the draft is grown from the slot's host mirror by the rule above, capped at min(k,
+ * n_new - done_s - 1) and dropped when it would not fit n_ctx; when the pass's rows exceed the batch's row
+ * capacity the drafts are cut by gemma_batch_plan_rows(need = 1 + draft length, capacity); finished
+ * slots sit out (-1).  out[s] and each slot's final position equal what batch_step gives that slot, token
+ * for token, sampler on or off.  Per slot: passes = passes in which it carried a draft, plain_steps =
+ * passes in which it carried none; tokens appended = passes + accepted + plain_steps = n_new.  0, or -1
+ * with hpc_last_error naming gemma_engine_batch_generate_lookup: no batch, no active slot, bad n_new / k /
+ * ngram_max, a slot with given tokens pending, or pos_s + n_new >= n_ctx for a slot. */
+int gemma_engine_batch_generate_lookup(gemma_engine *e, int n_new, int k, int ngram_max,
+                                       int32_t *out, gemma_spec_stats *stats);
 /* weights back in ggml row-major layout (tests); tid as in DESIGN.md §Synthetic weights */
 int64_t gemma_engine_tensor(gemma_engine *e, int tid, void *dst, int64_t cap);
 /* time `iters` launches of one hot kernel with hipEvents on the engine stream; returns avg µs and
