@@ -15,6 +15,9 @@
 // gemma_engine_batch_verify is gemma_engine_verify for the slots: such a pass whose rows past a slot's
 // first process drafts, then per slot the accept rule, the advance over the accepted prefix and the
 // rejected rows' K / V cleared, all on the device; a slot may sit the pass out.
+// gemma_engine_batch_set_sampler gives a slot a sampler of its own (or its own greedy) beside slots that
+// follow the engine's: every row reads its parameters from its row-table entry, and the picks of a pass take
+// one, three or four launches by the mix of the participating slots; gemma_engine_batch_fork copies a slot.
 #include "engine_impl.h"
 
 static constexpr int NS = GEMMA_BATCH_WIDE_MAX_SLOTS;  // every table's size
@@ -31,6 +34,24 @@ static bool slot_ok(const gemma_engine *e, int slot, const char *fn) {
         return false;
     }
     return true;
+}
+
+// A sampler per slot: the parameters the slot's rows carry (its own, else the engine's while that
+// sampler is on, else greedy), and which launches a pass's picks take, from the host mirror of the
+// participating slots' modes (n_sample of n_slots sample)
+static sampler_params slot_params(const gemma_engine *e, int slot) {
+    const batch_state &b = e->bt;
+    sampler_params p;  // temperature 0: greedy
+    if (b.smp_own[slot]) {
+        const gemma_sampler &s = b.smp[slot];
+        p.temperature = s.temperature; p.top_k = s.top_k; p.top_p = s.top_p; p.seed = s.seed;
+    } else if (e->sampling) {
+        p = e->smp_host;
+    }
+    return p;
+}
+static int picks_mix(int n_sample, int n_slots) {
+    return n_sample == 0 ? PICKS_GREEDY : n_sample == n_slots ? PICKS_SAMPLE : PICKS_MIXED;
 }
 
 static void batch_drop(gemma_engine *e) {
@@ -177,6 +198,70 @@ extern "C" int gemma_engine_batch_release(gemma_engine *e, int slot) {
     return 0;
 }
 
+// ---- a sampler per slot ----------------------------------------------------------------------------
+// The setting belongs to the slot (active or not) and lives until batch_close: begin, adopt, release
+// and fork leave it.  NULL: the slot follows the engine's sampler.  The parameters in force travel by
+// value in the slot's rows of the row tables (slot_row::smp: one load in the kernels, as deep as the
+// engine's one struct): a change here or of the engine's sampler marks the batch_step table dirty, and
+// it is rewritten, a stream-ordered copy, ahead of the next pass; the other tables are built per pass.
+extern "C" int gemma_engine_batch_set_sampler(gemma_engine *e, int slot, const gemma_sampler *sp) {
+    set_error("");
+    const std::string fn = "gemma_engine_batch_set_sampler";
+    if (!slot_ok(e, slot, fn.c_str())) return -1;
+    if (sp) {
+        const std::string why = sampler_invalid(*sp);
+        if (!why.empty()) {
+            set_error(fn + ": " + why);
+            return -1;
+        }
+    }
+    (void)hipSetDevice(e->device);
+    batch_state &b = e->bt;
+    // a sampling slot needs a workspace per row of a pass: a wide batch has its own, a narrow one the
+    // engine's 8 when the engine's sampler was ever on; else the batch makes its own now
+    if (sp && sp->temperature > 0.0f && !b.picks.ws.hist && !e->smp_ws.hist &&
+        sample_ws_alloc(e->bt_mem, &b.picks.ws, e->cfg.n_vocab, e->stream, b.pf.T)) {
+        const std::string why = last_error();
+        set_error(fn + ": " + why);
+        return -1;
+    }
+    b.smp[slot] = sp ? *sp : gemma_sampler{0.0f, 0, 1.0f, 0};
+    b.smp_own[slot] = sp != nullptr;
+    b.dirty = true;  // the slot's rows carry other parameters
+    return 0;
+}
+
+extern "C" int gemma_engine_batch_sampler(gemma_engine *e, int slot, gemma_sampler *out, int *own) {
+    set_error("");
+    if (!slot_ok(e, slot, "gemma_engine_batch_sampler")) return -1;
+    const batch_state &b = e->bt;
+    if (out) *out = b.smp_own[slot] ? b.smp[slot] : e->smp;
+    if (own) *own = b.smp_own[slot] ? 1 : 0;
+    return slot_samples(e, slot) ? 1 : 0;
+}
+
+// dst = a device-to-device copy of src's sequence (seq_copy: what adopt does from the engine's own);
+// a copy, not a shared prefix.  The sampler settings stay with their slots.
+extern "C" int gemma_engine_batch_fork(gemma_engine *e, int src, int dst) {
+    set_error("");
+    const std::string fn = "gemma_engine_batch_fork";
+    if (!slot_ok(e, src, fn.c_str()) || !slot_ok(e, dst, fn.c_str())) return -1;
+    batch_state &b = e->bt;
+    if (!b.slot[src].active) {
+        set_error(fn + ": slot " + std::to_string(src) + " (src) is not active");
+        return -1;
+    }
+    if (src == dst) {
+        set_error(fn + ": src == dst (slot " + std::to_string(src) + ")");
+        return -1;
+    }
+    (void)hipSetDevice(e->device);
+    if (seq_copy(e, b.slot[dst], b.slot[src])) return -1;
+    b.slot[dst].active = true;
+    b.dirty = true;
+    return 0;
+}
+
 // the row -> slot table of the active set (ascending slot order) and the rows' first tokens
 static int batch_write_rows(gemma_engine *e) {
     batch_state &b = e->bt;
@@ -191,6 +276,7 @@ static int batch_write_rows(gemma_engine *e) {
         const seq_state &S = b.slot[i];
         r.kc = S.kc; r.vc = S.vc; r.rope = S.rope;
         r.hist = S.hist; r.pos = S.pos; r.nfix = S.nfix; r.last = S.token; r.lp = S.lp;
+        r.smp = slot_params(e, i);
         h[R] = r;
         b.row_slot[R] = i;
         GHIP_CHECK(hipMemcpyAsync(b.row_tok + R, S.token, 4, hipMemcpyDeviceToDevice, s));  // = hist[pos]
@@ -218,10 +304,11 @@ extern "C" int gemma_engine_batch_step(gemma_engine *e, int n, float *logits) {
         set_error("gemma_engine_batch_step: no batch is open (gemma_engine_batch_open)");
         return -1;
     }
-    int R = 0;
+    int R = 0, n_sample = 0;
     for (int i = 0; i < b.n_slots; ++i) {
         if (!b.slot[i].active) continue;
         ++R;
+        n_sample += slot_samples(e, i);
         if ((int64_t)b.slot[i].host_pos + n >= c.n_ctx) {
             set_error("gemma_engine_batch_step: context full (slot " + std::to_string(i) + " at position " +
                       std::to_string(b.slot[i].host_pos) + ", n = " + std::to_string(n) + ", n_ctx = " + std::to_string(c.n_ctx) + ")");
@@ -248,9 +335,9 @@ extern "C" int gemma_engine_batch_step(gemma_engine *e, int n, float *logits) {
                 if (enqueue_batch_pass(e, r0, std::min(NARROW, R - r0), true)) return -1;
         }
         // a pick from every row: row r gives the token of its slot's sequence index pos + 1 (the
-        // sampler reads the slot's position word through the row table)
+        // sampler reads the slot's position word and its parameters through the row table)
         row_picks pk;
-        if (enqueue_row_picks(e, b.pf.LG, R, nullptr, b.rows, b.picks, &pk)) return -1;
+        if (enqueue_row_picks(e, b.pf.LG, R, nullptr, b.rows, b.picks, &pk, picks_mix(n_sample, R))) return -1;
         if (logits)
             GHIP_CHECK(hipMemcpyAsync(logits + (size_t)i * R * c.n_vocab, b.pf.LG, (size_t)R * c.n_vocab * 4, hipMemcpyDeviceToHost, s));
         if (launch_batch_advance(b.rows, R, pk.keys, pk.n_parts, pk.stride, b.row_tok, c.n_ctx, rope_of(e), s)) return -1;
@@ -309,11 +396,12 @@ extern "C" int gemma_engine_batch_step_rows(gemma_engine *e, int max_rows, float
         return -1;
     }
     int32_t need[NS], m_of[NS];
-    int R = 0;
+    int R = 0, n_sample = 0;
     for (int i = 0; i < b.n_slots; ++i) {
         const seq_state &S = b.slot[i];
         need[i] = S.active ? std::max(1, S.n_given - S.host_pos) : 0;
         R += S.active;
+        n_sample += S.active && slot_samples(e, i);
     }
     if (R == 0) {
         set_error(std::string(fn) + ": no slot is active (gemma_engine_batch_begin / _adopt)");
@@ -357,6 +445,7 @@ extern "C" int gemma_engine_batch_step_rows(gemma_engine *e, int max_rows, float
             r.rope = b.mrope + (size_t)t * rope_words;
             r.pos = (int *)(r.rope + c.head_dim);
             r.hist = S.hist; r.nfix = S.nfix; r.last = S.token; r.lp = S.lp;
+            r.smp = slot_params(e, i);
             hr[t] = r;
             hs[t] = row_src{S.pos, k, rank};
         }
@@ -379,9 +468,9 @@ extern "C" int gemma_engine_batch_step_rows(gemma_engine *e, int max_rows, float
     b.multi = false;
     if (bad) return -1;
     // a pick from every row (one launch whatever T; only each slot's last row's is used), the
-    // sampler's position word the row's own
+    // sampler's position word the row's own, its parameters its slot's
     row_picks pk;
-    if (enqueue_row_picks(e, b.pf.LG, T, nullptr, b.mrows, b.picks, &pk)) return -1;
+    if (enqueue_row_picks(e, b.pf.LG, T, nullptr, b.mrows, b.picks, &pk, picks_mix(n_sample, R))) return -1;
     if (logits) GHIP_CHECK(hipMemcpyAsync(logits, b.pf.LG, (size_t)T * c.n_vocab * 4, hipMemcpyDeviceToHost, s));
     if (launch_rows_advance(b.rows, b.mrows, b.mspans, R, pk.keys, pk.n_parts, pk.stride, b.row_tok, c.n_ctx, rope_of(e), s))
         return -1;
@@ -415,7 +504,7 @@ extern "C" int gemma_engine_batch_verify(gemma_engine *e, const int32_t *draft, 
         set_error(fn + ": a null draft, k_of, out_tokens or n_out");
         return -1;
     }
-    int P = 0, T = 0;
+    int P = 0, T = 0, n_sample = 0;
     for (int i = 0; i < b.n_slots; ++i) {
         const seq_state &S = b.slot[i];
         if (!S.active) continue;
@@ -438,6 +527,7 @@ extern "C" int gemma_engine_batch_verify(gemma_engine *e, const int32_t *draft, 
         }
         ++P;
         T += 1 + k;
+        n_sample += slot_samples(e, i);
     }
     if (P == 0) {
         set_error(fn + ": no slot takes part (no active slot, or every k_of is -1)");
@@ -476,6 +566,7 @@ extern "C" int gemma_engine_batch_verify(gemma_engine *e, const int32_t *draft, 
                 r.rope = b.mrope + (size_t)t * rope_words;
                 r.pos = (int *)(r.rope + c.head_dim);
                 r.hist = S.hist; r.nfix = S.nfix; r.last = S.token; r.lp = S.lp;
+                r.smp = slot_params(e, i);
                 hr[t] = r;
                 hs[t] = row_src{S.pos, j, rank};
             }
@@ -501,9 +592,10 @@ extern "C" int gemma_engine_batch_verify(gemma_engine *e, const int32_t *draft, 
     b.multi = false;
     b.pass_tok = nullptr;
     if (bad) return -1;
-    // 3. a pick from every row (the sampler's position word the row's own), none advances
+    // 3. a pick from every row (the sampler's position word the row's own, its parameters its slot's),
+    // none advances
     row_picks pk;
-    if (enqueue_row_picks(e, b.pf.LG, T, nullptr, b.mrows, b.picks, &pk)) return -1;
+    if (enqueue_row_picks(e, b.pf.LG, T, nullptr, b.mrows, b.picks, &pk, picks_mix(n_sample, P))) return -1;
     if (logits) GHIP_CHECK(hipMemcpyAsync(logits, b.pf.LG, (size_t)T * c.n_vocab * 4, hipMemcpyDeviceToHost, s));
     // 4. accept + advance per slot; (log-probabilities on) rows 0 .. a_s score what the accept settled
     if (launch_bverify_accept(b.rows, b.mrows, b.vslots, P, pk.keys, pk.n_parts, pk.stride, b.row_tok, c.n_ctx, rope_of(e),

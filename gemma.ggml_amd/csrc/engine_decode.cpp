@@ -211,31 +211,29 @@ int enqueue_lp_finish(gemma_engine *e, const float *LG, int R, lse_part *own, co
 }
 
 // The picks of a pass's T rows, none advancing: the verify pass then accepts a prefix, the batch pass
-// advances every row's slot.  The launch count does not depend on T: one row-argmax launch (greedy)
-// or the sampler's three (sampling), each with the row in grid.y.
+// advances every row's slot.  The launch count does not depend on T: one row-argmax launch (greedy),
+// the sampler's three (sampling), or both (a batch pass whose slots differ), each with the row in grid.y.
 int pick_buf_alloc(dev_pool &M, pick_buf &b, hipStream_t s) {
     return M.get_zeroed(&b.keys, (size_t)(PICK_MAX_ROWS * 256 + PICK_MAX_ROWS) * 8, s);
 }
 
+// mix: which of the pass's rows sample (PICKS_*: none, all, some), decided by the caller from its host
+// mirror of each participating slot's mode; -1: by the engine's sampler, the same for every row.  A
+// mixed pass keeps the greedy key layout: a sampling row's tail overwrites its partial keys.
 int enqueue_row_picks(gemma_engine *e, const float *LG, int T, const int *pos, const slot_row *tab, const pick_buf &b,
-                      row_picks *out) {
+                      row_picks *out, int mix) {
     const int64_t V = e->cfg.n_vocab;
     if (T < 1 || T > PICK_MAX_ROWS) {
         set_error("row picks: a pass of " + std::to_string(T) + " rows");
         return -1;
     }
+    if (mix < 0) mix = e->sampling ? PICKS_SAMPLE : PICKS_GREEDY;
     if (enqueue_lp_parts(e, LG, T, b.lp_parts)) return -1;  // (the caller's advance is followed by enqueue_lp_finish)
-    if (!e->sampling) {
-        if (launch_row_argmax(LG, V, b.keys, 256, e->stream, T, V)) return -1;
-        *out = row_picks{b.keys, 256, 256};
-        return 0;
-    }
-    // every row in its own workspace: the buffer's own (a wide batch's), else the engine's 8
-    sample_ws w = b.ws.hist ? b.ws : e->smp_ws;
-    w.key = b.keys + PICK_MAX_ROWS * 256;
-    if (launch_sample(LG, V, T, V, e->smp_dev, pos, tab, w, sample_dbg{}, e->stream)) return -1;
-    *out = row_picks{w.key, 1, 1};
-    return 0;
+    // every sampling row in its own workspace: the buffer's own (a wide batch's, or a narrow batch's on
+    // an engine that has none), else the engine's 8
+    const sample_ws &w = b.ws.hist ? b.ws : e->smp_ws;
+    return launch_picks(mix, LG, V, T, V, e->smp_dev, pos, tab, w, b.keys, PICK_MAX_ROWS, sample_dbg{}, e->stream, &out->keys,
+                        &out->n_parts, &out->stride);
 }
 
 // the decode tail of a Q6_K tied output: rms_norm*out_norm -> Q8_K (have_img: the last down handed

@@ -390,6 +390,7 @@ extern "C" int gemma_engine_set_sampler(gemma_engine *e, const gemma_sampler *sp
         e->sampling = on;
         drop_graph(e);
     }
+    e->bt.dirty = true;  // the rows of an open batch's slots that follow the engine carry these parameters
     return 0;
 }
 
@@ -509,6 +510,82 @@ extern "C" int gemma_test_sample(const float *logits, int rows, int n_vocab, con
     }
     GHIP_CHECK(hipDeviceSynchronize());
     if (tokens) GHIP_CHECK(hipMemcpy(tokens, dtok, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    if (n_cand) GHIP_CHECK(hipMemcpy(n_cand, dnc, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    if (n_kept) GHIP_CHECK(hipMemcpy(n_kept, dnk, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    if (cand) GHIP_CHECK(hipMemcpy(cand, dcand, (size_t)rows * SAMPLE_MAX_K * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Test hook: gemma_test_sample with one sampler per row, through launch_picks: the launches a batch
+// pass takes for this mix of rows (none sample: the row argmax; all: the sampler's three; else both).
+// Every row's token is its pick key reduced as the advance kernels reduce it.
+extern "C" int gemma_test_sample_rows(const float *logits, int rows, int n_vocab, const gemma_sampler *s_of,
+                                      const int32_t *positions, int32_t *tokens, int32_t *cand, int32_t *n_cand,
+                                      int32_t *n_kept) {
+    set_error("");
+    const std::string fn = "gemma_test_sample_rows";
+    if (!logits || !s_of || !positions || rows <= 0 || n_vocab <= 0) {
+        set_error(fn + ": logits, samplers, positions, rows >= 1 and n_vocab >= 1 are required");
+        return -1;
+    }
+    int n_sample = 0;
+    for (int r = 0; r < rows; ++r) {
+        std::string why = sampler_invalid(s_of[r]);
+        if (why.empty() && (positions[r] < 0 || positions[r] == INT32_MAX)) why = "positions must be in [0, 2^31 - 1)";
+        if (!why.empty()) {
+            set_error(fn + ": row " + std::to_string(r) + ": " + why);
+            return -1;
+        }
+        n_sample += s_of[r].temperature > 0.0f;
+    }
+    const int mix = n_sample == 0 ? PICKS_GREEDY : n_sample == rows ? PICKS_SAMPLE : PICKS_MIXED;
+    dev_pool tmp;
+    sample_ws ws;
+    const int chunk = std::min(rows, (int)PICK_MAX_ROWS);
+    const size_t row_b = (size_t)n_vocab * 4, n_keys = (size_t)chunk * 256 + chunk;
+    slot_row *dtab = nullptr;
+    float *dl = nullptr;
+    int *dpos = nullptr, *dcand = nullptr, *dnc = nullptr, *dnk = nullptr;
+    unsigned long long *dkeys = nullptr;
+    if (mix != PICKS_GREEDY && sample_ws_alloc(tmp, &ws, n_vocab, nullptr, chunk)) return -1;
+    if (tmp.get(&dtab, (size_t)rows * sizeof(slot_row)) ||
+        tmp.get(&dl, row_b * rows) || tmp.get(&dpos, (size_t)rows * 4) ||
+        tmp.get(&dnc, (size_t)rows * 4) || tmp.get(&dnk, (size_t)rows * 4) ||
+        tmp.get(&dcand, (size_t)rows * SAMPLE_MAX_K * 4) || tmp.get(&dkeys, n_keys * 8))
+        return -1;
+    std::vector<slot_row> htab(rows);
+    std::vector<int> pm1(positions, positions + rows);
+    for (int r = 0; r < rows; ++r) {
+        sampler_params &p = htab[r].smp;
+        p.temperature = s_of[r].temperature; p.top_k = s_of[r].top_k; p.top_p = s_of[r].top_p; p.seed = s_of[r].seed;
+        pm1[r] -= 1;  // the kernels read *pos + 1, as k_advance does
+        htab[r].pos = dpos + r;
+    }
+    GHIP_CHECK(hipMemcpy(dtab, htab.data(), (size_t)rows * sizeof(slot_row), hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(dl, logits, row_b * rows, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(dpos, pm1.data(), (size_t)rows * 4, hipMemcpyHostToDevice));
+    // a greedy row writes no debug output: n_cand = n_kept = 0 and cand = -1 stand
+    GHIP_CHECK(hipMemset(dnc, 0, (size_t)rows * 4));
+    GHIP_CHECK(hipMemset(dnk, 0, (size_t)rows * 4));
+    GHIP_CHECK(hipMemset(dcand, 0xFF, (size_t)rows * SAMPLE_MAX_K * 4));
+    std::vector<unsigned long long> hk(n_keys);
+    for (int r = 0; r < rows; r += chunk) {
+        const int T = std::min(chunk, rows - r);
+        sample_dbg d;
+        d.cand = dcand + (size_t)r * SAMPLE_MAX_K; d.n_cand = dnc + r; d.n_kept = dnk + r;
+        const unsigned long long *keys = nullptr;
+        int n_parts = 0, stride = 0;
+        if (launch_picks(mix, dl + (size_t)r * n_vocab, n_vocab, T, n_vocab, nullptr, nullptr, dtab + r, ws, dkeys, chunk, d,
+                         nullptr, &keys, &n_parts, &stride))
+            return -1;
+        GHIP_CHECK(hipDeviceSynchronize());
+        GHIP_CHECK(hipMemcpy(hk.data(), keys, ((size_t)(T - 1) * stride + n_parts) * 8, hipMemcpyDeviceToHost));
+        for (int t = 0; tokens && t < T; ++t) {  // the maximum key's index: block_max_key, key_index (pick.h)
+            unsigned long long best = 0;
+            for (int i = 0; i < n_parts; ++i) best = std::max(best, hk[(size_t)t * stride + i]);
+            tokens[r + t] = (int32_t)(0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull));
+        }
+    }
     if (n_cand) GHIP_CHECK(hipMemcpy(n_cand, dnc, (size_t)rows * 4, hipMemcpyDeviceToHost));
     if (n_kept) GHIP_CHECK(hipMemcpy(n_kept, dnk, (size_t)rows * 4, hipMemcpyDeviceToHost));
     if (cand) GHIP_CHECK(hipMemcpy(cand, dcand, (size_t)rows * SAMPLE_MAX_K * 4, hipMemcpyDeviceToHost));

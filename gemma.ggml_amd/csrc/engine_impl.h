@@ -94,7 +94,8 @@ struct seq_state {
 static constexpr int PICK_MAX_ROWS = GEMMA_BATCH_WIDE_MAX_SLOTS;
 struct pick_buf {
     unsigned long long *keys = nullptr;  // device: [64][256] greedy partial keys, then [64] sampler key slots
-    sample_ws ws;                        // a wide batch's own sampler workspaces (else the engine's 8: smp_ws)
+    sample_ws ws;                        // a batch's own sampler workspaces: a wide batch's, or a narrow one's made by
+                                         // batch_set_sampler on an engine that has none (else the engine's 8: smp_ws)
     lse_part *lp_parts = nullptr;        // a wide batch's own log-probability partials (else the engine's 8 rows: lp_parts)
 };
 
@@ -133,6 +134,10 @@ struct batch_state {
     int *vtok = nullptr;         // device: [64] the tokens of the pass's rows
     void *vstage = nullptr;      // pinned: vslots' source, vout's copy
     const int *pass_tok = nullptr;  // the tokens of the pass being enqueued when they are not row_tok's (enqueue_batch_pass)
+    // a sampler per slot (gemma_engine_batch_set_sampler): the setting belongs to the slot, active or not
+    // (the device copy travels in the slot's rows of the row tables, slot_row::smp)
+    bool smp_own[GEMMA_BATCH_WIDE_MAX_SLOTS] = {};      // the slot has a setting of its own ...
+    gemma_sampler smp[GEMMA_BATCH_WIDE_MAX_SLOTS] = {};  // ... and its parameters as given (mode: temperature > 0)
 };
 
 struct gemma_engine {
@@ -304,6 +309,11 @@ static inline uint16_t *vc_of(const gemma_engine *e, const seq_state &S, int il)
 // (prefill_run / prefill_next test tp_n > 1 || comm without n_virtual and are left exactly so.)
 static inline bool row_split(const gemma_engine *e) { return e->tp_n > 1 || e->comm || e->n_virtual > 1; }
 
+// a batch slot's picks sample: by its own setting, else by the engine's sampler
+static inline bool slot_samples(const gemma_engine *e, int slot) {
+    return e->bt.smp_own[slot] ? e->bt.smp[slot].temperature > 0.0f : e->sampling;
+}
+
 // attention can hand attn-out the Q8_0 image of its output (per-head form; split form with 32-dim slices)
 static inline bool att_img_ok(const gemma_engine *e) { return e->att_mode == ATTN_PER_HEAD || e->ag.img; }
 
@@ -429,8 +439,10 @@ int enqueue_lp_finish(gemma_engine *e, const float *LG, int R, lse_part *own, co
                       const int *acc);
 // lp[p0 .. p0 + n) of S into out after one synchronise; fn names the caller in the range error
 int seq_logprobs(gemma_engine *e, const seq_state &S, int p0, int n, double *out, const char *fn);
+// mix: PICKS_GREEDY / _SAMPLE / _MIXED from the caller's mirror of its rows' modes (a batch pass: each row
+// reads its parameters from tab[t].smp); -1: the engine's sampler for every row
 int enqueue_row_picks(gemma_engine *e, const float *LG, int T, const int *pos, const slot_row *tab, const pick_buf &b,
-                      row_picks *out);
+                      row_picks *out, int mix = -1);
 int tok_prepare(gemma_engine *e);
 int persist_report(gemma_engine *e, const int *w);
 int persist_check(gemma_engine *e);

@@ -450,6 +450,13 @@ int launch_verify_clean(uint16_t *kc, uint16_t *vc, int n_layer, int64_t layer_s
 // ---- batched decode (batch.hip; gemma_engine_batch_*, DESIGN.md §5b⁗) ---------------------------
 // One row of a batch pass: the next token of its own sequence (slot).  The table lives in device
 // memory and is rewritten when the set of active slots changes; no entry depends on a position.
+struct sampler_params {  // a sampler's parameters as the kernels of sample.hip read them (device memory)
+    float temperature = 0.0f;
+    int top_k = 0;
+    float top_p = 1.0f;
+    int pad = 0;
+    unsigned long long seed = 0;
+};
 struct slot_row {
     const float *qkv = nullptr;  // the row's q | k | v in the pass's scratch
     float *out = nullptr;        // the row's attention output [H*hd]
@@ -458,6 +465,9 @@ struct slot_row {
     int *hist = nullptr, *pos = nullptr, *last = nullptr;
     const int *nfix = nullptr;
     double *lp = nullptr;        // the slot's log-probabilities by sequence index (k_lse_finish)
+    // the sampler in force on the row's slot, by value (the slot's own, else the engine's; temperature
+    // <= 0: greedy): the sampler's kernels of a pass with a row table read it with the entry, one load
+    sampler_params smp;
 };
 // k_attn_slots: the decode attention (attn_head_dev, per-head form) for R rows, each against its own
 // slot's caches at its own position.  a: the shared fields (geometry, tables, dsplit); qkv, kc, vc,
@@ -523,13 +533,7 @@ int launch_bverify_clean(const slot_row *rows, const bv_slot *vs, int P, const i
 
 // ---- on-device sampling (sample.hip; the rule: include/gemma_hpc.h, DESIGN.md §5b″) ------------
 constexpr int SAMPLE_MAX_K = 1024;  // candidates at most (top_k == 0 means this many)
-struct sampler_params {             // lives in device memory: a change is a stream-ordered copy
-    float temperature = 0.0f;
-    int top_k = 0;
-    float top_p = 1.0f;
-    int pad = 0;
-    unsigned long long seed = 0;
-};
+// (sampler_params, above slot_row: the engine's lives in device memory, a change is a stream-ordered copy)
 constexpr int SAMPLE_WS_HIST = 4096 + 16;  // words of one row's histogram and list cursors
 struct sample_ws {  // scratch of `rows` samplers, one per row of a launch (sample_ws_alloc); the tail
                     // launch leaves every row's hist and cur zero
@@ -547,9 +551,24 @@ void sample_ws_free(dev_pool &mem, sample_ws *w);
 // The rows of a pass, three launches in all (grid.y = row): row r's token for sequence index
 // *pos_r + 1 from lg[r * ld .. + n) into w.key[r], in row r's own workspace.  pos_r is tab[r].pos when
 // a row table is given, else pos + r.  prm, pos and tab are device pointers read by the kernels; the
-// geometry depends on n and rows only
+// geometry depends on n and rows only.
+// Parameters per row: with a row table row r's parameters are tab[r].smp (prm is not read); a row
+// whose temperature is <= 0 is greedy: it leaves all three kernels before its first
+// atomic, its workspace stays zero and its key slot is not written.  key_parts > 1: row r's key slot
+// is w.key + r * key_parts and the tail fills it [pick, 0, 0, ...]: the layout of the row-argmax
+// partial keys, so an advance kernel reduces greedy and sampling rows of one pass alike.
 int launch_sample(const float *lg, int64_t ld, int rows, int64_t n, const sampler_params *prm, const int *pos,
-                  const slot_row *tab, const sample_ws &w, const sample_dbg &dbg, hipStream_t s);
+                  const slot_row *tab, const sample_ws &w, const sample_dbg &dbg, hipStream_t s, int key_parts = 1);
+// The picks of a pass's rows, one key layout per pass, the launch count by `mix` alone:
+//   PICKS_GREEDY  no row samples: the one row-argmax launch, 256 partial keys per row at keys
+//   PICKS_SAMPLE  every row samples: the sampler's three launches, one key per row at keys + rows_cap * 256
+//   PICKS_MIXED   both, four launches: the row argmax over every row, then the sampler, whose tail
+//                 overwrites a sampling row's 256 partial keys with [pick, 0 ...]
+// keys: [rows_cap * 256 + rows_cap] u64.  out_*: what the advance kernel takes
+enum { PICKS_GREEDY = 0, PICKS_SAMPLE = 1, PICKS_MIXED = 2 };
+int launch_picks(int mix, const float *lg, int64_t ld, int rows, int64_t n, const sampler_params *prm, const int *pos,
+                 const slot_row *tab, const sample_ws &w, unsigned long long *keys, int rows_cap, const sample_dbg &dbg,
+                 hipStream_t s, const unsigned long long **out_keys, int *out_parts, int *out_stride);
 
 // ---- per-token log-probabilities (logprob.hip; the rule: include/gemma_hpc.h, DESIGN.md §5b⁗′) ----
 constexpr int LSE_CHUNK = 1024;  // logits per workgroup of k_lse_parts: G = ceil(n_vocab / LSE_CHUNK), n_vocab alone

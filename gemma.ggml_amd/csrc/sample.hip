@@ -18,6 +18,12 @@
 //                     f64 weights, prefix sums, the top-p cut, the splitmix64 draw keyed by
 //                     (seed, p = *pos + 1); one key in the argmax format for k_advance.  It also
 //                     zeroes the histogram and the list cursors for the next call.
+// Parameters per row (a batch pass, "A sampler per slot" in DESIGN.md §5b⁗): with a row table row r
+// reads its own sampler_params from its entry, tab[r].smp, wave-uniformly (a scalar load of the same
+// depth as the one struct's, as k_attn_slots reads its table entry).  A row whose temperature is <= 0
+// is greedy: its workgroups leave all three kernels on that wave-uniform branch before their first
+// atomic, so its workspace stays as it was (zero) and its key slot (the row-argmax launch's partial
+// keys) stands.
 // The result depends on the row and the parameters only.  K <= 1024; the launch geometry does not
 // depend on top_k (it is read from the device struct), so only sampling on / off changes a graph.
 #include <algorithm>
@@ -48,9 +54,17 @@ __device__ __forceinline__ int sample_k(const sampler_params &p, int64_t n) {
 
 // All three kernels: grid.y = the row of the pass.  A row's logits are lg + row * ld and its
 // workspace the row-th of each sample_ws array; the offsets are wave-uniform (scalar registers).
-__global__ void __launch_bounds__(SM_TH) k_sample_hist(const float *lg, int64_t ld, int64_t n, unsigned *ghist) {
+// the row's parameters: its table entry's, else the launch's one struct
+__device__ __forceinline__ sampler_params row_params(const sampler_params *prm, const slot_row *tab) {
+    return tab ? tab[blockIdx.y].smp : *prm;
+}
+
+__global__ void __launch_bounds__(SM_TH) k_sample_hist(const float *lg, int64_t ld, int64_t n, const slot_row *tab,
+                                                       unsigned *ghist) {
     __shared__ unsigned h[SM_BINS];
     const int tid = threadIdx.x;
+    // a greedy row of a mixed pass leaves here (rows without a table always sample, nothing is read)
+    if (tab && !(tab[blockIdx.y].smp.temperature > 0.0f)) return;
     const float *row = lg + (int64_t)blockIdx.y * ld;
     ghist += (int64_t)blockIdx.y * SAMPLE_WS_HIST;
     for (int i = tid; i < SM_BINS; i += SM_TH) h[i] = 0;
@@ -70,8 +84,9 @@ __global__ void __launch_bounds__(SM_TH) k_sample_hist(const float *lg, int64_t 
 }
 
 __global__ void __launch_bounds__(SM_TH) k_sample_compact(const float *lg, int64_t ld, int64_t n, const sampler_params *prm,
-                                                          const unsigned *ghist, unsigned *cur, unsigned long long *list_a,
-                                                          unsigned long long *list_b, int64_t cap_b) {
+                                                          const slot_row *tab, const unsigned *ghist, unsigned *cur,
+                                                          unsigned long long *list_a, unsigned long long *list_b,
+                                                          int64_t cap_b) {
     __shared__ unsigned wtot[SM_TH / 64];
     __shared__ unsigned s_bin, s_cnt[2], s_base[2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -81,7 +96,9 @@ __global__ void __launch_bounds__(SM_TH) k_sample_compact(const float *lg, int64
     cur += r * SAMPLE_WS_HIST;
     list_a += r * SAMPLE_MAX_K;
     list_b += r * cap_b;
-    const unsigned K = (unsigned)sample_k(*prm, n);
+    const sampler_params P = row_params(prm, tab);
+    if (tab && !(P.temperature > 0.0f)) return;  // a greedy row: before the first barrier and atomic
+    const unsigned K = (unsigned)sample_k(P, n);
     // b*: the bin with (entries in bins above it) < K <= (those + its own); thread t owns bins 16t .. 16t+15
     unsigned loc[16], sum = 0;
 #pragma unroll
@@ -157,7 +174,9 @@ __device__ __forceinline__ uint64_t splitmix64_mix(uint64_t z) {
 __global__ void __launch_bounds__(SM_TAIL) k_sample_tail(const sampler_params *prm, const int *pos, const slot_row *tab, int64_t n,
                                                          unsigned *ghist, unsigned *cur, const unsigned long long *list_a,
                                                          const unsigned long long *list_b, int64_t cap_b,
-                                                         unsigned long long *key_out, sample_dbg dbg) {
+                                                         unsigned long long *key_out, int key_parts, sample_dbg dbg) {
+    const sampler_params P = row_params(prm, tab);
+    if (tab && !(P.temperature > 0.0f)) return;  // a greedy row: workspace and key slot untouched
     {  // this row's position word, workspace, key slot and debug outputs
         const int64_t r = blockIdx.y;
         pos = tab ? tab[r].pos : pos + r;
@@ -165,7 +184,7 @@ __global__ void __launch_bounds__(SM_TAIL) k_sample_tail(const sampler_params *p
         cur += r * SAMPLE_WS_HIST;
         list_a += r * SAMPLE_MAX_K;
         list_b += r * cap_b;
-        key_out += r;
+        key_out += r * key_parts;
         if (dbg.token) dbg.token += r;
         if (dbg.n_cand) dbg.n_cand += r;
         if (dbg.n_kept) dbg.n_kept += r;
@@ -178,7 +197,6 @@ __global__ void __launch_bounds__(SM_TAIL) k_sample_tail(const sampler_params *p
     __shared__ unsigned s_d, s_rem, s_cnt, s_cursor;
     __shared__ int s_m, s_j;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const sampler_params P = *prm;
     const int K = sample_k(P, n);
     const int p = *pos + 1;
     const unsigned ca = cur[0], cb = cur[1];
@@ -246,7 +264,7 @@ __global__ void __launch_bounds__(SM_TAIL) k_sample_tail(const sampler_params *p
     // k_advance an index outside the row: fewer candidates, or token 0
     const int Ke = K < n_s ? K : n_s;
     if (Ke <= 0) {
-        if (tid == 0) *key_out = 0x80000000FFFFFFFFull;
+        if (tid < key_parts) key_out[tid] = tid == 0 ? 0x80000000FFFFFFFFull : 0ull;
         return;
     }
     int P2 = 2;
@@ -304,8 +322,9 @@ __global__ void __launch_bounds__(SM_TAIL) k_sample_tail(const sampler_params *p
     if (tid < m && c_i > r && (tid == 0 || cs[tid - 1] <= r)) s_j = tid;
     __syncthreads();
     const unsigned long long pick = ks[s_j];
+    // (key_parts > 1: the rest of the row's partial keys become key 0, below every candidate)
+    if (tid < key_parts) key_out[tid] = tid == 0 ? pick : 0ull;
     if (tid == 0) {
-        *key_out = pick;
         if (dbg.token) *dbg.token = key_index(pick);
         if (dbg.n_cand) *dbg.n_cand = Ke;
         if (dbg.n_kept) *dbg.n_kept = m;
@@ -342,18 +361,41 @@ void sample_ws_free(dev_pool &mem, sample_ws *w) {
 }
 
 int launch_sample(const float *lg, int64_t ld, int rows, int64_t n, const sampler_params *prm, const int *pos,
-                  const slot_row *tab, const sample_ws &w, const sample_dbg &dbg, hipStream_t s) {
-    if (!w.hist || n <= 0 || n > w.cap_b || rows < 1 || rows > w.rows || (!pos && !tab)) {
+                  const slot_row *tab, const sample_ws &w, const sample_dbg &dbg, hipStream_t s, int key_parts) {
+    if (!w.hist || n <= 0 || n > w.cap_b || rows < 1 || rows > w.rows || (!pos && !tab) || (!prm && !tab) || key_parts < 1 ||
+        key_parts > SM_TAIL) {
         set_error("sampler: scratch not sized for these rows");
         return -1;
     }
     const int grid = (int)std::min<int64_t>((n + SM_CHUNK - 1) / SM_CHUNK, SM_GRID_MAX);
-    hipLaunchKernelGGL(k_sample_hist, dim3(grid, rows), dim3(SM_TH), 0, s, lg, ld, n, w.hist);
-    hipLaunchKernelGGL(k_sample_compact, dim3(grid, rows), dim3(SM_TH), 0, s, lg, ld, n, prm, (const unsigned *)w.hist, w.cur,
-                       w.list_a, w.list_b, w.cap_b);
+    hipLaunchKernelGGL(k_sample_hist, dim3(grid, rows), dim3(SM_TH), 0, s, lg, ld, n, tab, w.hist);
+    hipLaunchKernelGGL(k_sample_compact, dim3(grid, rows), dim3(SM_TH), 0, s, lg, ld, n, prm, tab, (const unsigned *)w.hist,
+                       w.cur, w.list_a, w.list_b, w.cap_b);
     hipLaunchKernelGGL(k_sample_tail, dim3(1, rows), dim3(SM_TAIL), 0, s, prm, pos, tab, n, w.hist, w.cur,
-                       (const unsigned long long *)w.list_a, (const unsigned long long *)w.list_b, w.cap_b, w.key, dbg);
+                       (const unsigned long long *)w.list_a, (const unsigned long long *)w.list_b, w.cap_b, w.key, key_parts, dbg);
     GHIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_picks(int mix, const float *lg, int64_t ld, int rows, int64_t n, const sampler_params *prm, const int *pos,
+                 const slot_row *tab, const sample_ws &w, unsigned long long *keys, int rows_cap, const sample_dbg &dbg,
+                 hipStream_t s, const unsigned long long **out_keys, int *out_parts, int *out_stride) {
+    if (!keys || rows < 1 || rows > rows_cap || mix < PICKS_GREEDY || mix > PICKS_MIXED) {
+        set_error("picks: no key buffer, or a pass outside its rows");
+        return -1;
+    }
+    constexpr int PARTS = 256;  // the row argmax's partial keys per row
+    if (mix != PICKS_SAMPLE && launch_row_argmax(lg, n, keys, PARTS, s, rows, ld)) return -1;
+    if (mix == PICKS_GREEDY || mix == PICKS_MIXED) {
+        *out_keys = keys; *out_parts = PARTS; *out_stride = PARTS;
+    }
+    if (mix == PICKS_GREEDY) return 0;
+    sample_ws v = w;
+    v.key = mix == PICKS_MIXED ? keys : keys + (size_t)rows_cap * PARTS;
+    if (launch_sample(lg, ld, rows, n, prm, pos, tab, v, dbg, s, mix == PICKS_MIXED ? PARTS : 1)) return -1;
+    if (mix == PICKS_SAMPLE) {
+        *out_keys = v.key; *out_parts = 1; *out_stride = 1;
+    }
     return 0;
 }
 

@@ -45,7 +45,9 @@ EXPORTS = ["mul_mat", "hpc_init", "hpc_shutdown", "hpc_register_weight", "hpc_la
            "gemma_engine_batch_last", "gemma_engine_batch_kv_read", "gemma_engine_batch_open_wide",
            "gemma_engine_batch_last_n", "gemma_batch_plan_rows", "gemma_engine_batch_open_rows",
            "gemma_engine_batch_step_rows", "gemma_engine_batch_verify", "gemma_engine_batch_generate_lookup",
-           "gemma_engine_set_logprobs", "gemma_engine_logprobs", "gemma_engine_batch_logprobs", "gemma_test_logprob"]
+           "gemma_engine_set_logprobs", "gemma_engine_logprobs", "gemma_engine_batch_logprobs", "gemma_test_logprob",
+           "gemma_engine_batch_set_sampler", "gemma_engine_batch_sampler", "gemma_engine_batch_fork",
+           "gemma_test_sample_rows"]
 
 
 def build():
@@ -191,6 +193,8 @@ def lib():
     L.gemma_engine_sampler.argtypes = [vp, C.POINTER(GemmaSampler)]
     L.gemma_test_sample.restype = C.c_int
     L.gemma_test_sample.argtypes = [vp, C.c_int, C.c_int, C.POINTER(GemmaSampler), vp, vp, vp, vp, vp]
+    L.gemma_test_sample_rows.restype = C.c_int
+    L.gemma_test_sample_rows.argtypes = [vp, C.c_int, C.c_int, C.POINTER(GemmaSampler), vp, vp, vp, vp, vp]
     L.gemma_engine_verify.restype = C.c_int
     L.gemma_engine_verify.argtypes = [vp, vp, C.c_int, vp, vp]
     L.gemma_engine_kv_read.restype = C.c_int
@@ -206,7 +210,9 @@ def lib():
                    ("last", [vp]), ("kv_read", [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
                    ("open_wide", [C.c_int]), ("last_n", [vp, C.c_int]), ("open_rows", [C.c_int, C.c_int]),
                    ("step_rows", [C.c_int, vp, vp]), ("verify", [vp, vp, vp, vp, vp]),
-                   ("generate_lookup", [C.c_int, C.c_int, C.c_int, vp, C.POINTER(SpecStats)])):
+                   ("generate_lookup", [C.c_int, C.c_int, C.c_int, vp, C.POINTER(SpecStats)]),
+                   ("set_sampler", [C.c_int, C.POINTER(GemmaSampler)]),
+                   ("sampler", [C.c_int, C.POINTER(GemmaSampler), C.POINTER(C.c_int)]), ("fork", [C.c_int, C.c_int])):
         getattr(L, "gemma_engine_batch_" + fn).restype = C.c_int
         getattr(L, "gemma_engine_batch_" + fn).argtypes = [vp] + at
     L.gemma_batch_plan_rows.restype = C.c_int
@@ -475,6 +481,32 @@ class Engine:
         return out[:, :n_new], [dict(passes=x.passes, drafted=x.drafted, accepted=x.accepted, plain_steps=x.plain_steps)
                                 for x in st]
 
+    def batch_set_sampler(self, slot, temperature=None, top_k=0, top_p=1.0, seed=0):
+        """A sampler of the slot's own (gemma_engine_batch_set_sampler).  No parameters or temperature
+        None: the slot follows the engine's sampler again.  temperature <= 0: the slot picks greedily
+        whatever the engine's sampler is.  The setting stays with the slot until batch_close."""
+        if temperature is None:
+            r = self.L.gemma_engine_batch_set_sampler(self.h, int(slot), None)
+        else:
+            s = GemmaSampler(float(temperature), int(top_k), float(top_p), int(seed) & (2 ** 64 - 1))
+            r = self.L.gemma_engine_batch_set_sampler(self.h, int(slot), C.byref(s))
+        self._chk(r, "batch_set_sampler")
+
+    def batch_sampler(self, slot):
+        """(the slot's picks sample, {temperature, top_k, top_p, seed} in force, the setting is the
+        slot's own)"""
+        s = GemmaSampler()
+        own = C.c_int(0)
+        on = self.L.gemma_engine_batch_sampler(self.h, int(slot), C.byref(s), C.byref(own))
+        if on < 0:
+            raise RuntimeError("batch_sampler failed: " + last_error())
+        return on == 1, dict(temperature=s.temperature, top_k=s.top_k, top_p=s.top_p, seed=s.seed), own.value == 1
+
+    def batch_fork(self, src, dst):
+        """Slot dst becomes a device-to-device copy of the active slot src's sequence (caches, history,
+        position, pending and unprocessed given tokens); each slot keeps its own sampler setting."""
+        self._chk(self.L.gemma_engine_batch_fork(self.h, int(src), int(dst)), "batch_fork")
+
     def batch_close(self):
         self._chk(self.L.gemma_engine_batch_close(self.h), "batch_close")
 
@@ -738,6 +770,37 @@ def test_sample(rows, sampler, positions):
 
 
 test_sample.__test__ = False  # a library wrapper, not a pytest test
+
+
+def test_sample_rows(rows, samplers, positions):
+    """test_sample with one sampler per row (gemma_test_sample_rows), all rows through one set of
+    launches.  samplers[r]: dict(temperature, top_k, top_p, seed), a (temperature, top_k, top_p, seed)
+    tuple, or None for a greedy row (then n_cand = n_kept = 0 and cand[r] is all -1)."""
+    x = np.ascontiguousarray(rows, dtype=np.float32)
+    if x.ndim == 1:
+        x = x[None, :]
+    R, V = x.shape
+    pos = np.ascontiguousarray(positions, dtype=np.int32)
+    if pos.shape != (R,) or len(samplers) != R:
+        raise ValueError("positions and samplers: one per row")
+    s_of = (GemmaSampler * R)()
+    for r, sp in enumerate(samplers):
+        if sp is None:
+            sp = (0.0, 0, 1.0, 0)
+        if isinstance(sp, dict):
+            sp = (sp.get("temperature", 1.0), sp.get("top_k", 0), sp.get("top_p", 1.0), sp.get("seed", 0))
+        s_of[r] = GemmaSampler(float(sp[0]), int(sp[1]), float(sp[2]), int(sp[3]) & (2 ** 64 - 1))
+    tokens = np.zeros(R, dtype=np.int32)
+    cand = np.zeros((R, SAMPLE_MAX_K), dtype=np.int32)
+    n_cand = np.zeros(R, dtype=np.int32)
+    n_kept = np.zeros(R, dtype=np.int32)
+    r = lib().gemma_test_sample_rows(_p(x), R, V, s_of, _p(pos), _p(tokens), _p(cand), _p(n_cand), _p(n_kept))
+    if r != 0:
+        raise RuntimeError("gemma_test_sample_rows failed: " + last_error())
+    return tokens, cand, n_cand, n_kept
+
+
+test_sample_rows.__test__ = False
 
 
 def test_logprob(rows, tokens):

@@ -165,6 +165,11 @@ int gemma_engine_sampler(const gemma_engine *e, gemma_sampler *out);   /* 1 = sa
  * n_kept[rows] = m */
 int gemma_test_sample(const float *logits, int rows, int n_vocab, const gemma_sampler *s,
                       const int32_t *positions, int32_t *tokens, int32_t *cand, int32_t *n_cand, int32_t *n_kept);
+/* the same with one sampler per row, s_of[rows], all rows through one set of launches (those of a batch
+ * pass with this mix of rows).  A row with temperature <= 0 returns the greedy pick (the row-argmax key,
+ * the launch the engine uses) with n_cand = n_kept = 0 and cand[r][*] = -1 */
+int gemma_test_sample_rows(const float *logits, int rows, int n_vocab, const gemma_sampler *s_of,
+                           const int32_t *positions, int32_t *tokens, int32_t *cand, int32_t *n_cand, int32_t *n_kept);
 /* Per-token log-probabilities on the device (DESIGN.md §5b⁗′).  For a logits row l[0..V) (f32) and a
  * token t: M = max_i l[i] compared as floats (-0 == +0); S = sum_i exp((double)l[i] - (double)M) in
  * f64 (an -inf entry contributes 0; S >= 1); logprob(l, t) = ((double)l[t] - (double)M) - log(S), -inf
@@ -220,8 +225,9 @@ int gemma_engine_kv_read(gemma_engine *e, int layer, int p0, int n, uint16_t *k_
  * GEMMA_BATCH_MAX_SLOTS independent sequences (slots).  Each slot has its own KV caches, history and
  * position; one weight pass (the verify pass's skinny GEMMs, weights streamed once) advances every
  * active slot by one token.  Every slot's logits and tokens are bit for bit what gemma_engine_step gives
- * that sequence alone, and a pick needs its row and position only (greedy, or the engine's sampler with
- * (seed, p)).  The engine's own sequence, its captured decode graph and its buffers are not touched.
+ * that sequence alone, and a pick needs its row and position only (greedy, or the sampler in force on
+ * the slot with (seed, p): the engine's, or the slot's own, "A sampler per slot" below).  The engine's own
+ * sequence, its captured decode graph and its buffers are not touched.
  * Every call returns 0 or a count; -1 with hpc_last_error naming the function and the state untouched
  * on a bad argument.
  *   open     n_slots in [1, 8]: allocates the slots, the pass's tables and its scratch.  Refused: a
@@ -279,7 +285,38 @@ int gemma_engine_kv_read(gemma_engine *e, int layer, int p0, int n, uint16_t *k_
  *            logits: NULL or [T][n_vocab] in row order; rows_of: NULL or [n_slots] (the plan).  Returns
  *            T; one host synchronise at the end.  Refused (-1, no slot advanced): no batch, no active
  *            slot, max_rows below the active count or above the batch's row capacity, any slot with
- *            pos_s + m_s >= n_ctx. */
+ *            pos_s + m_s >= n_ctx.
+ * A sampler per slot (DESIGN.md §5b⁗ "A sampler per slot"): greedy and sampling slots, each with its own
+ * temperature, top_k, top_p and seed, share one pass.
+ *   set_sampler  slot in [0, n_slots), active or not.  s == NULL: the slot follows the engine's sampler
+ *            (the state after open; later gemma_engine_set_sampler calls included).  s->temperature <= 0:
+ *            the slot picks greedily whatever the engine's sampler is.  Else the slot samples with its
+ *            own parameters by the rule at gemma_engine_set_sampler, p the sequence index of the pick.
+ *            The parameters reach the device by a stream-ordered copy into memory the batch owns (the
+ *            slot's rows of the pass tables), ahead of the next pass: they govern every pick enqueued
+ *            after the call.  The setting belongs to the slot: it survives begin, adopt, release and fork and
+ *            ends with close.  The checks are gemma_engine_set_sampler's; a sampler workspace the batch
+ *            needs and lacks (a narrow batch on an engine whose sampler was never on) is allocated now
+ *            and freed by close.  Refused (-1, naming the function and the field, the state untouched):
+ *            no batch, a slot outside the range, a bad field, a failed allocation.
+ *   sampler  returns 1 when the slot's picks sample, 0 when they are greedy; *out = the parameters in
+ *            force, *own = 1 for a setting of the slot's own, 0 when it follows the engine (either may
+ *            be NULL).  -1: no batch, a bad slot.
+ *   fork     dst becomes a device-to-device copy of the active slot src's sequence: caches, history,
+ *            log-probabilities, position, given-token count, RoPE row, the pending token and any
+ *            given-but-unprocessed tokens; dst is active afterwards, src unchanged.  The sampler settings
+ *            are not copied: each slot keeps its own, so n samples of a prompt cost one prefill (begin,
+ *            prefill, adopt, fork n - 1 times, a seed per slot).  A copy, not a shared prefix.  Refused
+ *            (-1, nothing changed): no batch, a slot outside the range, src inactive, src == dst.
+ * The guarantee: whatever the other slots do, a slot's logits rows, tokens, caches, history and
+ * log-probabilities are bit for bit what a plain engine gives that sequence through gemma_engine_step
+ * with gemma_engine_set_sampler set to the sampler in force on the slot at each pick.  It holds for
+ * step, step_rows, gemma_engine_batch_verify (row (s, i) picks with slot s's sampler at p = pos_s + i + 1)
+ * and gemma_engine_batch_generate_lookup, in every pass form (skinny, groups of 8, MFMA).  A greedy
+ * slot's pick is the engine's greedy pick as it stands, not the sampler with top_k = 1: the two orders
+ * differ on a signed-zero tie (the sampler's key folds -0 into +0, the argmax key does not).
+ * The pick launches of a pass depend on the mix alone, decided on the host: no participating slot
+ * samples, the one row-argmax launch; all sample, the sampler's three; else both, four. */
 #define GEMMA_BATCH_MAX_SLOTS 8
 #define GEMMA_BATCH_WIDE_MAX_SLOTS 64
 int gemma_engine_batch_open(gemma_engine *e, int n_slots);
@@ -297,6 +334,9 @@ int gemma_engine_batch_last_n(gemma_engine *e, int32_t *out, int cap);
 int gemma_batch_plan_rows(const int32_t *need, int n_slots, int max_rows, int32_t *rows_of);
 int gemma_engine_batch_open_rows(gemma_engine *e, int n_slots, int max_rows);
 int gemma_engine_batch_step_rows(gemma_engine *e, int max_rows, float *logits, int32_t *rows_of);
+int gemma_engine_batch_set_sampler(gemma_engine *e, int slot, const gemma_sampler *s);
+int gemma_engine_batch_sampler(gemma_engine *e, int slot, gemma_sampler *out, int *own);
+int gemma_engine_batch_fork(gemma_engine *e, int src, int dst);
 /* Drafts in the batch (DESIGN.md §5b⁗ "Drafts in the batch"): gemma_engine_verify for the slots of the
  * open batch, all in one exact pass.  draft is [n_slots][GEMMA_VERIFY_MAX_DRAFT], k_of [n_slots]; k_of[s]
  * is read for active slots only:
@@ -308,7 +348,7 @@ int gemma_engine_batch_step_rows(gemma_engine *e, int max_rows, float *logits, i
  * The pass has T = sum (1 + k_s) rows over the participating slots, ordered by ascending slot, then
  * ascending position.  Row (s, i) processes hist_s[pos_s] for i = 0, else draft[s][i - 1], at position
  * pos_s + i: it stores that position's K / V in the slot's caches and attends positions 0 .. pos_s + i.
- * Every row gives a pick g_{s,i} for index pos_s + i + 1 (greedy, or the engine's sampler with (seed,
+ * Every row gives a pick g_{s,i} for index pos_s + i + 1 (greedy, or slot s's sampler with (seed,
  * p = pos_s + i + 1)).  Then on the device, per slot: a_s = the number of leading i < k_s with
  * draft[s][i] == g_{s,i} (it stops at the first mismatch); hist_s[pos_s + 1 .. pos_s + a_s + 1] =
  * g_{s,0 .. a_s} (a given token stands); the rejected drafts behind them are zeroed in hist; pos_s +=
