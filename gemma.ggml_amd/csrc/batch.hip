@@ -256,6 +256,17 @@ int launch_rows_prepare(const slot_row *mrows, const row_src *src, int T, int *r
     return 0;
 }
 
+// k_rows_rope_kv alone, the first of launch_attn_slot_rows' two launches (the per-op test entry)
+int launch_rows_rope_kv(const attn_args &a, const slot_row *mrows, int T, int64_t layer_off, hipStream_t s) {
+    if (!mrows || T < 1 || T > ATTN_SLOTS_MAX_R || a.Hkv <= 0 || a.hd <= 0 || a.hd % 2) {
+        set_error("rows_rope_kv: a pass outside [1, 64] rows, no row table, or an odd head_dim");
+        return -1;
+    }
+    hipLaunchKernelGGL(k_rows_rope_kv, dim3(T), dim3(256), 0, s, a, mrows, layer_off);
+    GHIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 int launch_attn_slot_rows(const attn_args &a, const slot_row *mrows, const row_src *src, int T, int64_t layer_off,
                           hipStream_t s) {
     if (!src) {

@@ -807,6 +807,131 @@ extern "C" int gemma_test_attn_decode(const float *qkv, uint16_t *kc, uint16_t *
     return r;
 }
 
+// ---- per-op test entries: the prefill attention's kernels, each alone, on host buffers ----------
+// qkv [T][ldqkv] f32 rows q | k | v (pre-RoPE) of positions p0 .. p0 + T - 1; q16_out [T][H][hd] f16;
+// kc_inout [ctx][Hkv*hd], vc_inout [Hkv*hd][ctx] f16 (rows / columns p0 .. p0 + T - 1 written)
+extern "C" int gemma_test_rope_kv_prefill(const float *qkv, int64_t ldqkv, int T, int p0, int H, int Hkv, int hd, int ctx,
+                                          float rope_base, uint16_t *q16_out, uint16_t *kc_inout, uint16_t *vc_inout) {
+    set_error("");
+    if (!qkv || !q16_out || !kc_inout || !vc_inout || T <= 0 || p0 < 0 || H <= 0 || Hkv <= 0 || hd <= 0 || hd % 2 ||
+        hd > 1024 || ctx <= 0 || p0 + T > ctx || ldqkv < (int64_t)(H + 2 * Hkv) * hd) {
+        set_error("gemma_test_rope_kv_prefill: bad arguments (rows p0 .. p0 + T - 1 inside ctx, ldqkv >= (H + 2 Hkv) hd)");
+        return -1;
+    }
+    const size_t in_n = (size_t)T * ldqkv, q_n = (size_t)T * H * hd, cache_n = (size_t)ctx * Hkv * hd;
+    std::vector<float> rc, rs;
+    build_rope(ctx, hd, rope_base, rc, rs);
+    dev_pool tmp;
+    float *d_qkv, *d_c, *d_s;
+    uint16_t *d_q, *d_k, *d_v;
+    if (tmp.get(&d_qkv, in_n * 4) || tmp.get(&d_c, rc.size() * 4) || tmp.get(&d_s, rs.size() * 4) || tmp.get(&d_q, q_n * 2) ||
+        tmp.get(&d_k, cache_n * 2) || tmp.get(&d_v, cache_n * 2))
+        return -1;
+    GHIP_CHECK(hipMemcpy(d_qkv, qkv, in_n * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_c, rc.data(), rc.size() * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_s, rs.data(), rs.size() * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_q, q16_out, q_n * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_k, kc_inout, cache_n * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_v, vc_inout, cache_n * 2, hipMemcpyHostToDevice));
+    ropekv_args a;
+    a.qkv = d_qkv; a.ldqkv = ldqkv; a.rope_cos = d_c; a.rope_sin = d_s; a.q16 = d_q; a.kc = d_k; a.vc = d_v;
+    a.H = H; a.Hkv = Hkv; a.hd = hd; a.ctx = ctx; a.p0 = p0; a.q_scale = 1.0f / sqrtf((float)hd);
+    const int r = launch_rope_kv_prefill(a, T, nullptr);
+    GHIP_CHECK(hipDeviceSynchronize());
+    if (r == 0) {
+        GHIP_CHECK(hipMemcpy(q16_out, d_q, q_n * 2, hipMemcpyDeviceToHost));
+        GHIP_CHECK(hipMemcpy(kc_inout, d_k, cache_n * 2, hipMemcpyDeviceToHost));
+        GHIP_CHECK(hipMemcpy(vc_inout, d_v, cache_n * 2, hipMemcpyDeviceToHost));
+    }
+    return r;
+}
+
+// the same rows' K / V store through k_rows_rope_kv (batch.hip), which restates k_rope_kv_prefill for a
+// pass's row table: one slot_row per row, all on the same caches, the row's position in its RoPE row's word
+extern "C" int gemma_test_rows_rope_kv(const float *qkv, int64_t ldqkv, int T, int p0, int H, int Hkv, int hd, int ctx,
+                                       float rope_base, uint16_t *kc_inout, uint16_t *vc_inout) {
+    set_error("");
+    if (!qkv || !kc_inout || !vc_inout || T <= 0 || T > ATTN_SLOTS_MAX_R || p0 < 0 || H <= 0 || Hkv <= 0 || hd <= 0 ||
+        hd % 2 || hd > 1024 || ctx <= 0 || p0 + T > ctx || ldqkv < (int64_t)(H + 2 * Hkv) * hd) {
+        set_error("gemma_test_rows_rope_kv: bad arguments (1 .. 64 rows p0 .. p0 + T - 1 inside ctx, ldqkv >= (H + 2 Hkv) hd)");
+        return -1;
+    }
+    const size_t in_n = (size_t)T * ldqkv, cache_n = (size_t)ctx * Hkv * hd, rw = (size_t)hd + 4;
+    std::vector<float> rc, rs;
+    build_rope(ctx, hd, rope_base, rc, rs);
+    dev_pool tmp;
+    float *d_qkv, *d_c, *d_s, *d_rope;
+    uint16_t *d_k, *d_v;
+    slot_row *d_rows;
+    if (tmp.get(&d_qkv, in_n * 4) || tmp.get(&d_c, rc.size() * 4) || tmp.get(&d_s, rs.size() * 4) ||
+        tmp.get(&d_rope, T * rw * 4) || tmp.get(&d_k, cache_n * 2) || tmp.get(&d_v, cache_n * 2) ||
+        tmp.get(&d_rows, (size_t)T * sizeof(slot_row)))
+        return -1;
+    std::vector<float> rope(T * rw, 0.0f);
+    std::vector<slot_row> rows(T);
+    for (int t = 0; t < T; ++t) {
+        const int p = p0 + t;
+        memcpy(&rope[t * rw], rc.data() + (size_t)p * (hd / 2), (size_t)(hd / 2) * 4);
+        memcpy(&rope[t * rw + hd / 2], rs.data() + (size_t)p * (hd / 2), (size_t)(hd / 2) * 4);
+        memcpy(&rope[t * rw + hd], &p, 4);
+        rows[t].qkv = d_qkv + (size_t)t * ldqkv;
+        rows[t].kc = d_k;
+        rows[t].vc = d_v;
+        rows[t].rope = d_rope + t * rw;
+    }
+    GHIP_CHECK(hipMemcpy(d_qkv, qkv, in_n * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_c, rc.data(), rc.size() * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_s, rs.data(), rs.size() * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_rope, rope.data(), rope.size() * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_k, kc_inout, cache_n * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_v, vc_inout, cache_n * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_rows, rows.data(), (size_t)T * sizeof(slot_row), hipMemcpyHostToDevice));
+    attn_args a{};
+    a.rope_cos = d_c; a.rope_sin = d_s; a.H = H; a.Hkv = Hkv; a.hd = hd; a.ctx = ctx; a.q_scale = 1.0f / sqrtf((float)hd);
+    const int r = launch_rows_rope_kv(a, d_rows, T, 0, nullptr);
+    GHIP_CHECK(hipDeviceSynchronize());
+    if (r == 0) {
+        GHIP_CHECK(hipMemcpy(kc_inout, d_k, cache_n * 2, hipMemcpyDeviceToHost));
+        GHIP_CHECK(hipMemcpy(vc_inout, d_v, cache_n * 2, hipMemcpyDeviceToHost));
+    }
+    return r;
+}
+
+// q16 [T][H][hd], kc [ctx][Hkv*hd], vc [Hkv*hd][ctx] f16; out [T][ldo] f32, copied in before the launch
+// and back after it (columns past H*hd keep what the caller put there).  form 0 k_attn_rows, 1 k_attn_mx,
+// 2 k_attn_prefill; a shape the form's launcher refuses: non-zero with its message, out untouched
+extern "C" int gemma_test_attn_prefill(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, int T, int p0, int H,
+                                       int Hkv, int hd, int ctx, int n_kv, int64_t ldo, int form, float *out) {
+    set_error("");
+    if (!q16 || !kc || !vc || !out || T <= 0 || p0 < 0 || H <= 0 || Hkv <= 0 || hd <= 0 || ctx <= 0 || n_kv <= 0 ||
+        ldo < (int64_t)H * hd || form < 0 || form > 2) {
+        set_error("gemma_test_attn_prefill: bad arguments (form 0 rows, 1 mx, 2 f16 MFMA; ldo >= H * hd)");
+        return -1;
+    }
+    const size_t q_n = (size_t)T * H * hd, cache_n = (size_t)ctx * Hkv * hd, out_n = (size_t)T * ldo;
+    dev_pool tmp;
+    uint16_t *d_q, *d_k, *d_v;
+    float *d_out;
+    // (the kernels' 16-byte reads stay inside a row; the allocator's granule covers nothing else)
+    if (tmp.get(&d_q, q_n * 2) || tmp.get(&d_k, cache_n * 2) || tmp.get(&d_v, cache_n * 2) || tmp.get(&d_out, out_n * 4))
+        return -1;
+    GHIP_CHECK(hipMemcpy(d_q, q16, q_n * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_k, kc, cache_n * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_v, vc, cache_n * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_out, out, out_n * 4, hipMemcpyHostToDevice));
+    attnp_args a;
+    a.q16 = d_q; a.kc = d_k; a.vc = d_v; a.out = d_out; a.ldo = ldo;
+    a.T = T; a.H = H; a.Hkv = Hkv; a.hd = hd; a.ctx = ctx; a.n_kv = n_kv; a.p0 = p0;
+    if (form == 2 && (H % Hkv || n_kv > ctx || p0 + T > n_kv)) {  // (launch_attn_prefill checks the head shape only)
+        set_error("attn_prefill: unsupported shape (rows p0 .. p0 + T - 1 inside n_kv <= ctx)");
+        return -1;
+    }
+    const int r = form == 0 ? launch_attn_rows(a, nullptr) : form == 1 ? launch_attn_mx(a, nullptr) : launch_attn_prefill(a, nullptr);
+    GHIP_CHECK(hipDeviceSynchronize());
+    if (r == 0) GHIP_CHECK(hipMemcpy(out, d_out, out_n * 4, hipMemcpyDeviceToHost));
+    return r;
+}
+
 extern "C" int gemma_test_exp_f16(uint16_t *out) {
     set_error("");
     dev_pool tmp;

@@ -500,6 +500,8 @@ int launch_rows_prepare(const slot_row *mrows, const row_src *src, int T, int *r
 // the row's own position included; it stores nothing to a cache)
 int launch_attn_slot_rows(const attn_args &a, const slot_row *mrows, const row_src *src, int T, int64_t layer_off,
                           hipStream_t s);
+// the first of those two launches alone (gemma_test_rows_rope_kv)
+int launch_rows_rope_kv(const attn_args &a, const slot_row *mrows, int T, int64_t layer_off, hipStream_t s);
 // per active slot (rows: the batch_step table, by rank): the key reduction of the slot's last row,
 // pos += m, the guarded hist write, the slot's RoPE row, `last` and row_tok[rank]; every row's
 // position word becomes the sequence index it predicts (k_lse_finish)

@@ -453,6 +453,22 @@ int gemma_engine_token_stamps(gemma_engine *e, unsigned long long *out);
 int gemma_test_attn_decode(const float *qkv, uint16_t *kc, uint16_t *vc, int pos, int H, int Hkv, int hd, int ctx,
                            float rope_base, float *out, float *dbg_w, uint16_t *dbg_p, float *dbg_inv,
                            unsigned long long *dbg_t, int mode);
+/* per-op test entry: the prefill's RoPE / q scale / KV store kernel on host buffers.  qkv [T][ldqkv] f32 rows
+ * q | k | v (pre-RoPE) of positions p0 .. p0 + T - 1; q16_out [T][H][hd] f16 (q x 1/sqrt(hd)); kc_inout
+ * [ctx][Hkv*hd] and vc_inout [Hkv*hd][ctx] f16, copied in, rows / columns p0 .. p0 + T - 1 written, copied back */
+int gemma_test_rope_kv_prefill(const float *qkv, int64_t ldqkv, int T, int p0, int H, int Hkv, int hd, int ctx,
+                               float rope_base, uint16_t *q16_out, uint16_t *kc_inout, uint16_t *vc_inout);
+/* the same K / V store through the batch pass's restatement of that kernel (k_rows_rope_kv): one row-table entry
+ * per row, 1 <= T <= 64, every row on the same caches; q is not touched by that kernel */
+int gemma_test_rows_rope_kv(const float *qkv, int64_t ldqkv, int T, int p0, int H, int Hkv, int hd, int ctx,
+                            float rope_base, uint16_t *kc_inout, uint16_t *vc_inout);
+/* per-op test entry: one causal prefill attention launch on host buffers.  q16 [T][H][hd], kc [ctx][Hkv*hd],
+ * vc [Hkv*hd][ctx] f16; row t is position p0 + t; n_kv = the padded key count of the last row (<= ctx).
+ * form 0 = the exact rows kernel, 1 = the exact f32 matrix-core kernel, 2 = the approximate f16 MFMA kernel.
+ * out [T][ldo] f32 is copied to the device before the launch and back after it, so columns [H*hd, ldo) keep
+ * the caller's values.  A shape the form refuses: non-zero with the launcher's message, out untouched */
+int gemma_test_attn_prefill(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, int T, int p0, int H, int Hkv,
+                            int hd, int ctx, int n_kv, int64_t ldo, int form, float *out);
 
 /* per-op test entry: the prefill path's Q8_0 row quantization + int8 MFMA GEMM on host buffers */
 int gemma_test_gemm(int type, int64_t rows, int64_t K, int64_t T, const void *W, const float *X, float *Y,

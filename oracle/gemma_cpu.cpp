@@ -397,6 +397,55 @@ extern "C" float orc_synth_value(uint64_t seed, int tid, uint64_t idx, double st
     return (float)synth_int(tensor_key(seed, tid), idx) * synth_scale(stdv);
 }
 
+// The RoPE / q scale / KV store step of T prompt rows at positions p0 .. p0 + T - 1, from the pieces
+// orc_attn_decode uses inline: qkv [T][ldqkv] = q | k | v pre-rope; q16 [T][H][hd]; kc [ctx][Hkv*hd],
+// vc [Hkv*hd][ctx] (only rows / columns p0 .. p0 + T - 1 are written).
+extern "C" void orc_rope_kv_rows(const float *qkv, int64_t ldqkv, int T, int p0, int H, int Hkv, int hd, int ctx,
+                                 float rope_base, uint16_t *q16, uint16_t *kc, uint16_t *vc) {
+    const int qw = H * hd, kvw = Hkv * hd;
+    const float q_scale = 1.0f / sqrtf((float)hd);
+    for (int t = 0; t < T; ++t) {
+        const float *row = qkv + (size_t)t * ldqkv;
+        const int pos = p0 + t;
+        std::vector<float> Q(row, row + qw), K(row + qw, row + qw + kvw);
+        const float *V = row + qw + kvw;
+        orc_rope_neox(Q.data(), hd, H, pos, rope_base);
+        for (int i = 0; i < qw; ++i) Q[i] *= q_scale;
+        orc_rope_neox(K.data(), hd, Hkv, pos, rope_base);
+        for (int i = 0; i < qw; ++i) q16[(size_t)t * qw + i] = orc_fp32_to_fp16(Q[i]);
+        for (int i = 0; i < kvw; ++i) {
+            kc[(size_t)pos * kvw + i] = orc_fp32_to_fp16(K[i]);
+            vc[(size_t)i * ctx + pos] = orc_fp32_to_fp16(V[i]);
+        }
+    }
+}
+
+// Causal attention of T prompt rows against filled caches (the prefill slice of src/gemma_model.cpp:
+// 454-497), row by row as orc_attn_decode computes one: row t is position p0 + t, its keys the padded
+// n_kv(t) = min(ctx, 32*((p0+t+1)/32+1)) with -inf past its position.  q16 [T][H][hd]; out [T][ldo],
+// head h at h*hd (columns past H*hd are not written).
+extern "C" void orc_attn_rows(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, int T, int p0, int H, int Hkv,
+                              int hd, int ctx, int64_t ldo, float *out) {
+    const int kvw = Hkv * hd;
+    for (int t = 0; t < T; ++t) {
+        const int pos = p0 + t;
+        const int n_kv = std::min(ctx, 32 * ((pos + 1) / 32 + 1));
+        std::vector<float> kq(n_kv), mask(n_kv);
+        std::vector<uint16_t> p16(n_kv);
+        for (int j = 0; j < n_kv; ++j) mask[j] = j > pos ? -INFINITY : 0.0f;
+        for (int h = 0; h < H; ++h) {
+            const int kvh = h / (H / Hkv);
+            orc_mul_mat(n_kv, 1, 1, (int64_t)kvw * 2, 1, (int64_t)n_kv * 4, (int64_t)n_kv * 4, (size_t)hd * 2, hd,
+                        kc + (size_t)kvh * hd, kq.data(), ORC_F16, (const char *)(q16 + ((size_t)t * H + h) * hd), 1);
+            orc_soft_max_row(kq.data(), mask.data(), kq.data(), n_kv, 1.0f);
+            for (int j = 0; j < n_kv; ++j) p16[j] = orc_fp32_to_fp16(kq[j]);
+            orc_mul_mat(hd, 1, 1, (int64_t)ctx * 2, 1, (int64_t)hd * 4, (int64_t)hd * 4, (size_t)n_kv * 2, n_kv,
+                        vc + (size_t)kvh * hd * ctx, out + (size_t)t * ldo + (size_t)h * hd, ORC_F16,
+                        (const char *)p16.data(), 1);
+        }
+    }
+}
+
 // debugging taps of the last row of the last call: qkv (pre-rope matmul outputs), attn, layer out
 extern "C" int orc_model_taps(orc_model *m, int il, float *qkv, float *attn, float *xout) {
     if (il < 0 || il >= (int)m->hidden.size() || m->tap_qkv[il].empty()) return -1;

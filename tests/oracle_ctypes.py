@@ -84,6 +84,9 @@ def lib():
     L.orc_model_hidden.argtypes = [vp, C.c_int, vp, i64]
     L.orc_bench_run.restype = C.c_double
     L.orc_bench_run.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_double), vp]
+    L.orc_attn_decode.argtypes = [vp] * 3 + [C.c_int] * 5 + [C.c_float] + [vp] * 4
+    L.orc_rope_kv_rows.argtypes = [vp, i64] + [C.c_int] * 6 + [C.c_float] + [vp] * 3
+    L.orc_attn_rows.argtypes = [vp] * 3 + [C.c_int] * 6 + [i64, vp]
     L.orc_set_pool.argtypes = [C.c_int]
     L.orc_prof.argtypes = [C.c_int, vp]
     L.orc_make_prompt.argtypes = [C.c_uint64, C.c_int, C.c_int, vp]
@@ -176,6 +179,29 @@ def mul_mat_init(src0_type, x):
     out = np.zeros((ncols, rs), dtype=np.uint8)
     L.orc_mul_mat_init(src0_type, ptr(x), k, ncols, k, ptr(out))
     return out, rs
+
+
+def attn_n_kv(pos, ctx):
+    """the padded key count of a row at sequence position pos"""
+    return min(ctx, 32 * ((pos + 1) // 32 + 1))
+
+
+def attn_rows(q16, kc, vc, T, p0, H, Hkv, hd, ctx, ldo=None, out=None):
+    """orc_attn_rows: q16 [T][H][hd], kc [ctx][Hkv*hd], vc [Hkv*hd][ctx] u16 -> out [T][ldo] f32
+    (written over `out` when given, so that padding columns keep its values)."""
+    ldo = H * hd if ldo is None else ldo
+    out = np.zeros((T, ldo), np.float32) if out is None else out
+    assert out.shape == (T, ldo) and out.dtype == np.float32 and out.flags.c_contiguous
+    q16, kc, vc = (np.ascontiguousarray(a, np.uint16) for a in (q16, kc, vc))
+    assert q16.size == T * H * hd and kc.size == ctx * Hkv * hd and vc.size == kc.size
+    lib().orc_attn_rows(ptr(q16), ptr(kc), ptr(vc), T, p0, H, Hkv, hd, ctx, ldo, ptr(out))
+    return out
+
+
+def rope_kv_rows(qkv, T, p0, H, Hkv, hd, ctx, q16, kc, vc, rope_base=10000.0):
+    """orc_rope_kv_rows on qkv [T][ldqkv] f32; q16 / kc / vc (u16) are updated in place."""
+    assert qkv.dtype == np.float32 and qkv.flags.c_contiguous and qkv.shape[0] == T
+    lib().orc_rope_kv_rows(ptr(qkv), qkv.shape[1], T, p0, H, Hkv, hd, ctx, rope_base, ptr(q16), ptr(kc), ptr(vc))
 
 
 GEMMA_2B = dict(n_layer=18, n_embd=2048, n_head=8, n_head_kv=1, head_dim=256, n_ff=16384, n_vocab=256000)

@@ -39,7 +39,8 @@ def lib_path():
 
 def test_header_parse_finds_the_boundary():
     names = _declared_functions()
-    for must in ("mul_mat", "hpc_init", "hpc_last_error", "gemma_engine_create", "gemma_engine_step"):
+    for must in ("mul_mat", "hpc_init", "hpc_last_error", "gemma_engine_create", "gemma_engine_step",
+                 "gemma_test_rope_kv_prefill", "gemma_test_rows_rope_kv", "gemma_test_attn_prefill"):
         assert must in names, names
 
 

@@ -63,6 +63,24 @@ def _hooks():
         r = L.gemma_test_attn_decode(qkv.ctypes.data, kc.ctypes.data, vc.ctypes.data, pos, H, Hkv, hd, ctx, 10000.0,
                                      att.ctypes.data, dw.ctypes.data, dp.ctypes.data, None, None, mode)
         assert r == 0, G.last_error()
+    L.gemma_test_rope_kv_prefill.restype = C.c_int
+    L.gemma_test_rope_kv_prefill.argtypes = [C.c_void_p, C.c_int64] + [C.c_int] * 6 + [C.c_float] + [C.c_void_p] * 3
+    L.gemma_test_attn_prefill.restype = C.c_int
+    L.gemma_test_attn_prefill.argtypes = [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_int64, C.c_int, C.c_void_p]
+    T, ctx = 3, 64
+    rows = rng.standard_normal((T, (H + 2 * Hkv) * hd)).astype(np.float32)
+    q16 = np.zeros((T, H, hd), np.uint16)
+    kc, vc = np.zeros((ctx, Hkv * hd), np.uint16), np.zeros((Hkv * hd, ctx), np.uint16)
+    assert L.gemma_test_rope_kv_prefill(rows.ctypes.data, rows.shape[1], T, 0, H, Hkv, hd, ctx, 10000.0, q16.ctypes.data,
+                                        kc.ctypes.data, vc.ctypes.data) == 0, G.last_error()
+    L.gemma_test_rows_rope_kv.restype = C.c_int
+    L.gemma_test_rows_rope_kv.argtypes = [C.c_void_p, C.c_int64] + [C.c_int] * 6 + [C.c_float] + [C.c_void_p] * 2
+    assert L.gemma_test_rows_rope_kv(rows.ctypes.data, rows.shape[1], T, 0, H, Hkv, hd, ctx, 10000.0, kc.ctypes.data,
+                                     vc.ctypes.data) == 0, G.last_error()
+    rows_out = np.zeros((T, H * hd), np.float32)
+    for form in (0, 1, 2):  # exact rows, exact matrix-core, f16 MFMA
+        assert L.gemma_test_attn_prefill(q16.ctypes.data, kc.ctypes.data, vc.ctypes.data, T, 0, H, Hkv, hd, ctx, 32, H * hd,
+                                         form, rows_out.ctypes.data) == 0, G.last_error()
     G.test_sample(rng.standard_normal((2, 300)).astype(np.float32), dict(temperature=0.9, top_k=5, seed=1), [3, 4])
     W = O.quantize((rng.standard_normal((16, 64)) * 0.05).astype(np.float32), "q4_0_ref")
     xs = rng.standard_normal((3, 64)).astype(np.float32)
