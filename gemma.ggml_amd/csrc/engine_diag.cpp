@@ -932,6 +932,178 @@ extern "C" int gemma_test_attn_prefill(const uint16_t *q16, const uint16_t *kc, 
     return r;
 }
 
+// ---- per-op test entry: the decode attention's launch forms, R rows on host buffers (include/gemma_hpc.h) ----
+extern "C" int gemma_test_attn_decode_rows(gemma_test_attn_rows_args *t) {
+    set_error("");
+    if (!t) {
+        set_error("gemma_test_attn_decode_rows: no arguments");
+        return -1;
+    }
+    t->err_out = 0;
+    const int form = t->form, R = t->R, H = t->H, Hkv = t->Hkv, hd = t->hd, ctx = t->ctx;
+    if (form < 0 || form > 3 || R < 0 || R > 1024 || (form < 2 && R < 1) || t->n_slots < 1 || t->n_slots > 1024 || H <= 0 ||
+        H > 256 || Hkv <= 0 || Hkv > 256 || hd <= 0 || hd % 8 || hd > 1024 || ctx <= 0 || ctx % 8 || ctx > (1 << 20) ||
+        !t->qkv || t->ldqkv < (int64_t)(H + 2 * Hkv) * hd || t->ldqkv % 4 || !t->pos || !t->slot || !t->kc || !t->vc ||
+        !t->out || !t->img_act != !t->img_da || t->dsplit < 0 || t->nwg < 0) {
+        set_error("gemma_test_attn_decode_rows: bad arguments (form 0 .. 3; forms 0 / 1 need R >= 1; head_dim and ctx "
+                  "multiples of 8; ldqkv >= (H + 2 Hkv) hd, a multiple of 4; img_act and img_da together)");
+        return -1;
+    }
+    for (int r = 0; r < R; ++r)
+        if (t->pos[r] < 0 || t->pos[r] >= ctx || t->slot[r] < 0 || t->slot[r] >= t->n_slots) {
+            set_error("gemma_test_attn_decode_rows: a row's position outside [0, ctx) or its slot outside [0, n_slots)");
+            return -1;
+        }
+    if (form >= 2 && R > 1 && (t->dbg_w || t->dbg_p)) {
+        set_error("gemma_test_attn_decode_rows: the taps are indexed by head only: forms 2 and 3 take them for R == 1");
+        return -1;
+    }
+    if (form == 2)
+        for (int r = 0; r < R; ++r)
+            for (int q = 0; q < r; ++q)
+                if (t->slot[q] == t->slot[r]) {
+                    set_error("gemma_test_attn_decode_rows: form 2 needs a distinct slot per row");
+                    return -1;
+                }
+    // form 3: the rows of a slot adjacent and at consecutive positions; (off, rank) as the engine's planner numbers them
+    std::vector<int> off(std::max(R, 1), 0), rank(std::max(R, 1), 0), first(std::max(R, 1), 0);
+    if (form == 3)
+        for (int r = 0, n_rank = 0; r < R; ++r) {
+            if (r > 0 && t->slot[r] == t->slot[r - 1]) {
+                off[r] = off[r - 1] + 1;
+                rank[r] = rank[r - 1];
+                first[r] = first[r - 1];
+                if (t->pos[r] != t->pos[r - 1] + 1) {
+                    set_error("gemma_test_attn_decode_rows: form 3 needs a slot's rows at consecutive positions");
+                    return -1;
+                }
+            } else {
+                for (int q = 0; q < r; ++q)
+                    if (t->slot[q] == t->slot[r]) {
+                        set_error("gemma_test_attn_decode_rows: form 3 needs the rows of a slot adjacent");
+                        return -1;
+                    }
+                rank[r] = n_rank++;
+                first[r] = r;
+            }
+        }
+    const int Rn = std::max(R, 1);
+    const size_t qkv_n = (size_t)(R > 0 ? (R - 1) * t->ldqkv + (int64_t)(H + 2 * Hkv) * hd : 4), cache_n = (size_t)ctx * Hkv * hd;
+    const size_t out_n = (size_t)Rn * H * hd, tap_n = (size_t)Rn * H * ctx, rw = (size_t)hd + 4, half = (size_t)hd / 2;
+    const size_t blocks = ((size_t)H * hd + 31) / 32, act_n = (blocks + 3) / 4 * 32, q8k_n = (size_t)H * 292;
+    std::vector<uint16_t> et, gt;
+    build_f16_tables(et, gt);
+    std::vector<float> rc, rs;
+    if (t->rope_identity) {
+        rc.assign((size_t)ctx * half, 1.0f);
+        rs.assign((size_t)ctx * half, 0.0f);
+    } else {
+        build_rope(ctx, hd, t->rope_base, rc, rs);
+    }
+    std::vector<float> rope(Rn * rw, 0.0f);
+    for (int r = 0; r < R; ++r) {
+        const int p = t->pos[r];
+        memcpy(&rope[r * rw], rc.data() + (size_t)p * half, half * 4);
+        memcpy(&rope[r * rw + half], rs.data() + (size_t)p * half, half * 4);
+        memcpy(&rope[r * rw + hd], &p, 4);
+    }
+    const attn_geom g = attn_geometry(H, Hkv, hd, ctx);
+    dev_pool tmp;
+    float *d_qkv, *d_out, *d_c, *d_s, *d_rope, *d_dw = nullptr, *d_da = nullptr, *d_sb = nullptr;
+    uint16_t *d_k, *d_v, *d_e, *d_dp = nullptr;
+    uint32_t *d_act = nullptr;
+    uint8_t *d_q8k = nullptr;
+    int *d_pos, *d_sy = nullptr;
+    slot_row *d_rows;
+    row_src *d_src;
+    const size_t sync_n = (size_t)Hkv * 2;
+    if (tmp.get(&d_qkv, qkv_n * 4) || tmp.get(&d_out, out_n * 4) || tmp.get(&d_c, rc.size() * 4) || tmp.get(&d_s, rs.size() * 4) ||
+        tmp.get(&d_rope, rope.size() * 4) || tmp.get(&d_k, (size_t)t->n_slots * cache_n * 2) ||
+        tmp.get(&d_v, (size_t)t->n_slots * cache_n * 2) || tmp.get(&d_e, 65536 * 2) || tmp.get(&d_pos, (size_t)Rn * 4) ||
+        tmp.get(&d_rows, (size_t)Rn * sizeof(slot_row)) || tmp.get(&d_src, (size_t)Rn * sizeof(row_src)))
+        return -1;
+    if (t->dbg_w && tmp.get(&d_dw, tap_n * 4)) return -1;
+    if (t->dbg_p && tmp.get(&d_dp, tap_n * 2)) return -1;
+    if (t->img_act && (tmp.get(&d_act, Rn * act_n * 4) || tmp.get(&d_da, Rn * blocks * 4))) return -1;
+    if (t->img_q8k && tmp.get(&d_q8k, Rn * q8k_n)) return -1;
+    if (form == 1) {
+        if (tmp.get(&d_sb, std::max(g.sbuf_floats, (size_t)4) * 4) || tmp.get(&d_sy, (sync_n + 1) * 4)) return -1;
+        GHIP_CHECK(hipMemset(d_sy, 0, (sync_n + 1) * 4));
+    }
+    if (R > 0) {
+        GHIP_CHECK(hipMemcpy(d_qkv, t->qkv, qkv_n * 4, hipMemcpyHostToDevice));
+        GHIP_CHECK(hipMemcpy(d_out, t->out, out_n * 4, hipMemcpyHostToDevice));
+        GHIP_CHECK(hipMemcpy(d_pos, t->pos, (size_t)R * 4, hipMemcpyHostToDevice));
+        if (d_dw) GHIP_CHECK(hipMemcpy(d_dw, t->dbg_w, tap_n * 4, hipMemcpyHostToDevice));
+        if (d_dp) GHIP_CHECK(hipMemcpy(d_dp, t->dbg_p, tap_n * 2, hipMemcpyHostToDevice));
+        if (d_act) GHIP_CHECK(hipMemcpy(d_act, t->img_act, R * act_n * 4, hipMemcpyHostToDevice));
+        if (d_da) GHIP_CHECK(hipMemcpy(d_da, t->img_da, R * blocks * 4, hipMemcpyHostToDevice));
+        if (d_q8k) GHIP_CHECK(hipMemcpy(d_q8k, t->img_q8k, R * q8k_n, hipMemcpyHostToDevice));
+    }
+    GHIP_CHECK(hipMemcpy(d_c, rc.data(), rc.size() * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_s, rs.data(), rs.size() * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_rope, rope.data(), rope.size() * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_k, t->kc, (size_t)t->n_slots * cache_n * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_v, t->vc, (size_t)t->n_slots * cache_n * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_e, et.data(), 65536 * 2, hipMemcpyHostToDevice));
+    std::vector<slot_row> rows(Rn);
+    std::vector<row_src> src(Rn);
+    for (int r = 0; r < R; ++r) {
+        rows[r].qkv = d_qkv + (size_t)r * t->ldqkv;
+        rows[r].out = d_out + (size_t)r * H * hd;
+        rows[r].kc = d_k + (size_t)t->slot[r] * cache_n;
+        rows[r].vc = d_v + (size_t)t->slot[r] * cache_n;
+        rows[r].rope = d_rope + r * rw;
+        rows[r].pos = d_pos + r;
+        src[r].spos = d_pos + first[r];  // the slot's position word: its first row's
+        src[r].off = off[r];
+        src[r].rank = rank[r];
+    }
+    GHIP_CHECK(hipMemcpy(d_rows, rows.data(), (size_t)Rn * sizeof(slot_row), hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_src, src.data(), (size_t)Rn * sizeof(row_src), hipMemcpyHostToDevice));
+    attn_args a{};
+    a.rope_cos = d_c; a.rope_sin = d_s; a.exp_tab = d_e;
+    a.H = H; a.Hkv = Hkv; a.hd = hd; a.ctx = ctx; a.q_scale = t->q_scale;
+    a.mode = form == 1 ? ATTN_SPLIT : ATTN_PER_HEAD;
+    a.dsplit = form == 1 ? 1 : t->dsplit;
+    a.nwg = form == 1 ? (t->nwg ? t->nwg : g.nwg) : 0;
+    a.sbuf = d_sb; a.sync = d_sy; a.err = d_sy ? d_sy + sync_n : nullptr;
+    int r = 0;
+    if (form < 2) {
+        for (int i = 0; i < R && r == 0; ++i) {
+            a.qkv = rows[i].qkv; a.kc = rows[i].kc; a.vc = rows[i].vc; a.rope_cur = rows[i].rope; a.pos = rows[i].pos;
+            a.out = rows[i].out;
+            a.dbg_w = d_dw ? d_dw + (size_t)i * H * ctx : nullptr;
+            a.dbg_p = d_dp ? d_dp + (size_t)i * H * ctx : nullptr;
+            a.out_act = d_act ? d_act + i * act_n : nullptr;
+            a.out_da = d_da ? d_da + i * blocks : nullptr;
+            a.out_q8k = d_q8k ? d_q8k + i * q8k_n : nullptr;
+            r = launch_attn_decode(a, nullptr);
+        }
+    } else {
+        a.dbg_w = d_dw; a.dbg_p = d_dp;
+        a.out_act = d_act; a.out_da = d_da; a.out_q8k = d_q8k;  // (both launchers refuse an image)
+        r = form == 2 ? launch_attn_slots(a, d_rows, R, 0, nullptr) : launch_attn_slot_rows(a, d_rows, d_src, R, 0, nullptr);
+    }
+    GHIP_CHECK(hipDeviceSynchronize());
+    if (r != 0) return r;
+    if (d_sy) {
+        std::vector<int> sy(sync_n + 1);
+        GHIP_CHECK(hipMemcpy(sy.data(), d_sy, (sync_n + 1) * 4, hipMemcpyDeviceToHost));
+        if (t->sync_out) memcpy(t->sync_out, sy.data(), sync_n * 4);
+        t->err_out = sy[sync_n];
+    }
+    GHIP_CHECK(hipMemcpy(t->out, d_out, out_n * 4, hipMemcpyDeviceToHost));
+    GHIP_CHECK(hipMemcpy(t->kc, d_k, (size_t)t->n_slots * cache_n * 2, hipMemcpyDeviceToHost));
+    GHIP_CHECK(hipMemcpy(t->vc, d_v, (size_t)t->n_slots * cache_n * 2, hipMemcpyDeviceToHost));
+    if (d_dw) GHIP_CHECK(hipMemcpy(t->dbg_w, d_dw, tap_n * 4, hipMemcpyDeviceToHost));
+    if (d_dp) GHIP_CHECK(hipMemcpy(t->dbg_p, d_dp, tap_n * 2, hipMemcpyDeviceToHost));
+    if (d_act) GHIP_CHECK(hipMemcpy(t->img_act, d_act, R * act_n * 4, hipMemcpyDeviceToHost));
+    if (d_da) GHIP_CHECK(hipMemcpy(t->img_da, d_da, R * blocks * 4, hipMemcpyDeviceToHost));
+    if (d_q8k) GHIP_CHECK(hipMemcpy(t->img_q8k, d_q8k, R * q8k_n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" int gemma_test_exp_f16(uint16_t *out) {
     set_error("");
     dev_pool tmp;

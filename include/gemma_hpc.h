@@ -469,6 +469,38 @@ int gemma_test_rows_rope_kv(const float *qkv, int64_t ldqkv, int T, int p0, int 
  * the caller's values.  A shape the form refuses: non-zero with the launcher's message, out untouched */
 int gemma_test_attn_prefill(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, int T, int p0, int H, int Hkv,
                             int hd, int ctx, int n_kv, int64_t ldo, int form, float *out);
+/* per-op test entry: R decode-attention rows through ONE launch form on host buffers.
+ * form 0 the per-head kernel (with dsplit), 1 the position-split kernel, 2 the batch pass's one-row-per-slot
+ *      kernel, 3 the several-rows-per-slot pair (the K / V store launch, then the attention on cached K / V).
+ * Row r: q | k | v at qkv + r * ldqkv (pre-RoPE), position pos[r] in [0, ctx), caches of slot[r] in [0, n_slots).
+ * Forms 0 and 1 run the rows as R successive launches (form 1 on one scratch allocation: sync_out receives the
+ * hand-off counters' 2 * Hkv words after the last launch, err_out the sticky timeout word).  Form 2 is one
+ * launch and needs distinct slots.  Form 3 is one pair of launches: rows of a slot adjacent, at consecutive
+ * positions.  RoPE: rope_identity != 0 publishes cos 1 / sin 0 rows (and tables), else rope_base's.
+ * kc / vc [n_slots][ctx * Hkv * hd] f16 and out [R][H * hd] are copied in before and back after the launches;
+ * dbg_w f32 / dbg_p f16 [R][H][ctx] (optional; forms 2 and 3: R == 1 only); img_act u32 [R][ceil(H * hd / 128)
+ * * 32] + img_da f32 [R][H * hd / 32] (optional, both or neither: the Q8_0 image of out) and img_q8k u8
+ * [R][H * 292] (optional: its Q8_K image) are copied in and back too.  nwg: form 1's workgroups per kv head, 0 =
+ * the geometry's own.  Bad arguments: -1 with a message; a shape the launcher refuses: non-zero with the
+ * launcher's message; in both cases nothing is copied back */
+typedef struct gemma_test_attn_rows_args {
+    int form, R, n_slots, H, Hkv, hd, ctx, dsplit, nwg;
+    int rope_identity;
+    float rope_base, q_scale;
+    const float *qkv;
+    int64_t ldqkv;
+    const int *pos, *slot;
+    uint16_t *kc, *vc;
+    float *out;
+    float *dbg_w;
+    uint16_t *dbg_p;
+    uint32_t *img_act;
+    float *img_da;
+    uint8_t *img_q8k;
+    int *sync_out;
+    int err_out;
+} gemma_test_attn_rows_args;
+int gemma_test_attn_decode_rows(gemma_test_attn_rows_args *a);
 
 /* per-op test entry: the prefill path's Q8_0 row quantization + int8 MFMA GEMM on host buffers */
 int gemma_test_gemm(int type, int64_t rows, int64_t K, int64_t T, const void *W, const float *X, float *Y,

@@ -459,16 +459,12 @@ extern "C" int orc_model_taps(orc_model *m, int il, float *qkv, float *attn, flo
 // Single-token attention block (the DECODE slice of src/gemma_model.cpp:698-718 + :454-518),
 // standalone for the per-op parity test of the GPU attention kernel.  qkv = [q | k | v] pre-rope;
 // kc [ctx][Hkv*hd], vc [Hkv*hd][ctx] f16 caches (updated at `pos`); out [H*hd].
-extern "C" void orc_attn_decode(const float *qkv, uint16_t *kc, uint16_t *vc, int pos, int H, int Hkv, int hd, int ctx,
-                                float rope_base, float *out, float *dbg_w, uint16_t *dbg_p, float *dbg_inv) {
-    const int qw = H * hd, kvw = Hkv * hd;
+// This is the part after the RoPE and the q scale, shared by orc_attn_decode and orc_attn_decode_row:
+// the cache store at `pos`, then KQ / soft_max_ext / KQV per head; Q [H*hd] roped and scaled, K roped.
+static void attn_decode_scaled(const float *Q, const float *K, const float *V, uint16_t *kc, uint16_t *vc, int pos, int H,
+                               int Hkv, int hd, int ctx, float *out, float *dbg_w, uint16_t *dbg_p, float *dbg_inv) {
+    const int kvw = Hkv * hd;
     const int n_kv = std::min(ctx, 32 * ((pos + 1) / 32 + 1));
-    std::vector<float> Q(qkv, qkv + qw), K(qkv + qw, qkv + qw + kvw);
-    const float *V = qkv + qw + kvw;
-    orc_rope_neox(Q.data(), hd, H, pos, rope_base);
-    const float q_scale = 1.0f / sqrtf((float)hd);
-    for (int i = 0; i < qw; ++i) Q[i] *= q_scale;
-    orc_rope_neox(K.data(), hd, Hkv, pos, rope_base);
     for (int i = 0; i < kvw; ++i) {
         kc[(size_t)pos * kvw + i] = orc_fp32_to_fp16(K[i]);
         vc[(size_t)i * ctx + pos] = orc_fp32_to_fp16(V[i]);
@@ -498,4 +494,42 @@ extern "C" void orc_attn_decode(const float *qkv, uint16_t *kc, uint16_t *vc, in
         orc_mul_mat(hd, 1, 1, (int64_t)ctx * 2, 1, (int64_t)hd * 4, (int64_t)hd * 4, (size_t)n_kv * 2, n_kv,
                     vc + (size_t)kvh * hd * ctx, out + (size_t)h * hd, ORC_F16, (const char *)p16.data(), 1);
     }
+}
+
+extern "C" void orc_attn_decode(const float *qkv, uint16_t *kc, uint16_t *vc, int pos, int H, int Hkv, int hd, int ctx,
+                                float rope_base, float *out, float *dbg_w, uint16_t *dbg_p, float *dbg_inv) {
+    const int qw = H * hd, kvw = Hkv * hd;
+    std::vector<float> Q(qkv, qkv + qw), K(qkv + qw, qkv + qw + kvw);
+    const float *V = qkv + qw + kvw;
+    orc_rope_neox(Q.data(), hd, H, pos, rope_base);
+    const float q_scale = 1.0f / sqrtf((float)hd);
+    for (int i = 0; i < qw; ++i) Q[i] *= q_scale;
+    orc_rope_neox(K.data(), hd, Hkv, pos, rope_base);
+    attn_decode_scaled(Q.data(), K.data(), V, kc, vc, pos, H, Hkv, hd, ctx, out, dbg_w, dbg_p, dbg_inv);
+}
+
+// orc_attn_decode with the position's RoPE row given (rope_row = cos | sin, hd/2 floats each) and q_scale
+// given: orc_rope_neox's statements on that row (two products and one subtract / add per pair), then the
+// same scale, conversions, cache store and matmuls.  What a kernel computes that reads a published RoPE row.
+extern "C" void orc_attn_decode_row(const float *qkv, uint16_t *kc, uint16_t *vc, int pos, int H, int Hkv, int hd, int ctx,
+                                    const float *rope_row, float q_scale, float *out, float *dbg_w, uint16_t *dbg_p) {
+    const int qw = H * hd, kvw = Hkv * hd, half = hd / 2;
+    std::vector<float> Q(qkv, qkv + qw), K(qkv + qw, qkv + qw + kvw);
+    const float *V = qkv + qw + kvw, *c = rope_row, *s = rope_row + half;
+    auto rope = [&](float *x, int n_heads) {
+        for (int h = 0; h < n_heads; ++h) {
+            float *r = x + (size_t)h * hd;
+            for (int i = 0; i < half; ++i) {
+                const float x0 = r[i], x1 = r[i + half];
+                const float a = x0 * c[i], b = x1 * s[i];
+                const float e = x0 * s[i], f = x1 * c[i];
+                r[i] = a - b;
+                r[i + half] = e + f;
+            }
+        }
+    };
+    rope(Q.data(), H);
+    for (int i = 0; i < qw; ++i) Q[i] *= q_scale;
+    rope(K.data(), Hkv);
+    attn_decode_scaled(Q.data(), K.data(), V, kc, vc, pos, H, Hkv, hd, ctx, out, dbg_w, dbg_p, nullptr);
 }

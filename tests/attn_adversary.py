@@ -50,6 +50,15 @@ the test asserts >= 0.5), wrong accumulation in the product the case aims at:
   cancel_kqv p0 250, T 38:  H2 0.990  H3 0.961  H4 0.986  SPLIT 0.986
   benign     p0 250, T 38 (wrong KQ): 0.020, 0.020, 0.020, 0.007
 
+decode_case turns a case into ONE decode row (the f32 q | k | v whose values are the case's f16 words, the caches
+with finite non-zero garbage at the row's own position) for the decode attention's kernels, which see one row
+per workgroup: what they can get wrong is the quad fold of the 32 chain values (chain_dot mode FOLD) and the
+step order of a chain (REV).  Shares on single rows (H 4, Hkv 2, ctx 320, 29 rows at 3, 14, .. 311; hd 256 / 128;
+the whole table is in tests/test_attn_decode_adversary.py, which asserts its floors):
+  benign     FOLD in KQ: 0.523 / 0.510 of the score words, 0.0086 / 0 of the output words
+  cancel_kq  REV in KQ, each row at pos >= 31: 1.000 / 1.000 of the output words
+  cancel_kqv REV in KQV, pos >= 255: 0.995 .. 1.000; FOLD in KQV, pos >= 31: 0.231 .. 0.510
+
 rope_case builds q | k | v rows for which a contracted fma(x0, c, -(x1*s)) (and fma(x0, s, x1*c)) stores
 other f16 words than the separate multiplies: each pair has x0*c and x1*s (or x0*s and -x1*c) agree to
 2^-15 .. 2^-19, so the f32 rounding error of the first product is 2^-9 .. 2^-5 of the difference.  v, and
@@ -65,6 +74,7 @@ import oracle_ctypes as O
 F32, F16, U16 = np.float32, np.float16, np.uint16
 CASES = ("cancel_kq", "cancel_kqv", "underflow", "stale", "benign")
 MODES = ("H1", "H2", "H3", "H4", "SPLIT")
+DECODE_MODES = ("FOLD", "REV")  # what a one-row kernel can get wrong: the quad fold, the step order of a chain
 
 # cancel_kq: (chain, ((step, coefficient), ...), free step that carries the near-half-ulp term or None)
 PATTERNS = (
@@ -218,6 +228,39 @@ def make(case, T, p0, H, Hkv, hd, ctx, seed=0, base="cancel_kq"):
     return dict(case=case, base=name, q16=_bits(q).reshape(T, H, hd), kc=kc, vc=vc, T=T, p0=p0, H=H, Hkv=Hkv, hd=hd, ctx=ctx)
 
 
+def decode_case(case, pos, H, Hkv, hd, ctx, seed=0, base="cancel_kq", zero_v=None):
+    """One decode row at `pos`, from make(case, 1, pos, ...): -> that dict plus
+      qkv  f32 q | k | v whose values are the f16 values of q16[0], K row pos and V column pos: with the identity
+           RoPE row (cos 1, sin 0) and q_scale 1 a kernel's q16 / k16 / stored V are those words;
+      kc, vc  with row / column pos overwritten by finite non-zero garbage in every case: a kernel that
+           reads its own position from the cache instead of the row is wrong (for "stale", garbage past pos too).
+    zero_v = (kv head, first dim, dims): those V rows are zero at every position and in the row's v, so the
+    outputs of that kv head's query heads are zero there (a Q8_0 image block with d == 0)."""
+    cs = make(case, 1, pos, H, Hkv, hd, ctx, seed, base)
+    kc, vc = cs["kc"], cs["vc"]
+    if zero_v is not None:
+        kvh, d0, nd = zero_v
+        vc[kvh * hd + d0:kvh * hd + d0 + nd] = 0
+    qkv = np.concatenate([_h2f(cs["q16"][0]).ravel(), _h2f(kc[pos]), _h2f(vc[:, pos])]).astype(F32)
+    rng = np.random.default_rng([seed, 77, CASES.index(case), pos, H, Hkv, hd])
+    kc[pos] = _garbage(rng, kc.shape[1])
+    vc[:, pos] = _garbage(rng, vc.shape[0])
+    return dict(cs, qkv=qkv, pos=pos)
+
+
+def identity_rope(hd):
+    """cos 1 | sin 0: the RoPE row under which q16 / k16 are the row's own f16 values"""
+    return np.concatenate([np.ones(hd // 2, F32), np.zeros(hd // 2, F32)])
+
+
+def decode_oracle(cs, rope_row=None, q_scale=1.0, taps=True):
+    """orc_attn_decode_row on copies of the case's caches -> (out, scores, P16, kc, vc)"""
+    kc, vc = cs["kc"].copy(), cs["vc"].copy()
+    row = identity_rope(cs["hd"]) if rope_row is None else rope_row
+    out, w, p = O.attn_decode_row(cs["qkv"], kc, vc, cs["pos"], cs["H"], cs["Hkv"], cs["hd"], cs["ctx"], row, q_scale, taps)
+    return out, w, p, kc, vc
+
+
 def oracle_out(cs, ldo=None, out=None):
     return O.attn_rows(cs["q16"], cs["kc"], cs["vc"], cs["T"], cs["p0"], cs["H"], cs["Hkv"], cs["hd"], cs["ctx"], ldo, out)
 
@@ -231,13 +274,26 @@ def _fold32(acc):
     return (t0[..., 0] + t0[..., 1]) + (t0[..., 2] + t0[..., 3])
 
 
+def _fold32_rows_in_order(acc):
+    """FOLD: the four 8-wide accumulator rows added (a0 + a1) + (a2 + a3) where ggml adds (a0 + a2) + (a1 + a3):
+    a quad fold that takes xor-1 before xor-2"""
+    x0 = (acc[..., 0:8] + acc[..., 8:16]) + (acc[..., 16:24] + acc[..., 24:32])
+    t0 = x0[..., 0:4] + x0[..., 4:8]
+    return (t0[..., 0] + t0[..., 1]) + (t0[..., 2] + t0[..., 3])
+
+
 def chain_dot(x, y, mode="H1"):
     """vec_dot_f16 of f16-valued f32 arrays over the last axis (a multiple of 32), the chains carried in
-    groups of 4 steps as k_attn_mx's MFMAs carry them, each group accumulated as `mode` says."""
+    groups of 4 steps as k_attn_mx's MFMAs carry them, each group accumulated as `mode` says.  FOLD: H1's
+    chains, the final fold over the accumulator rows in another order; REV: every chain's steps last to first."""
     p = (x.astype(F32) * y.astype(F32))  # exact: 11-bit x 11-bit significands
     S = p.shape[-1] // 32
     p = p.reshape(p.shape[:-1] + (S, 32))
     acc = np.zeros(p.shape[:-2] + (32,), F32)
+    if mode in DECODE_MODES:
+        for s in (range(S) if mode == "FOLD" else reversed(range(S))):
+            acc = acc + p[..., s, :]
+        return _fold32_rows_in_order(acc) if mode == "FOLD" else _fold32(acc)
     for g0 in range(0, S, 4):
         st = [p[..., s, :] for s in range(g0, min(g0 + 4, S))]
         if mode == "H1":

@@ -85,6 +85,7 @@ def lib():
     L.orc_bench_run.restype = C.c_double
     L.orc_bench_run.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_double), vp]
     L.orc_attn_decode.argtypes = [vp] * 3 + [C.c_int] * 5 + [C.c_float] + [vp] * 4
+    L.orc_attn_decode_row.argtypes = [vp] * 3 + [C.c_int] * 5 + [vp, C.c_float] + [vp] * 3
     L.orc_rope_kv_rows.argtypes = [vp, i64] + [C.c_int] * 6 + [C.c_float] + [vp] * 3
     L.orc_attn_rows.argtypes = [vp] * 3 + [C.c_int] * 6 + [i64, vp]
     L.orc_set_pool.argtypes = [C.c_int]
@@ -202,6 +203,36 @@ def rope_kv_rows(qkv, T, p0, H, Hkv, hd, ctx, q16, kc, vc, rope_base=10000.0):
     """orc_rope_kv_rows on qkv [T][ldqkv] f32; q16 / kc / vc (u16) are updated in place."""
     assert qkv.dtype == np.float32 and qkv.flags.c_contiguous and qkv.shape[0] == T
     lib().orc_rope_kv_rows(ptr(qkv), qkv.shape[1], T, p0, H, Hkv, hd, ctx, rope_base, ptr(q16), ptr(kc), ptr(vc))
+
+
+def attn_decode_row(qkv, kc, vc, pos, H, Hkv, hd, ctx, rope_row, q_scale, taps=True):
+    """orc_attn_decode_row: qkv [(H + 2 Hkv) hd] f32, rope_row [hd] f32 (cos | sin); kc / vc (u16) are updated
+    at `pos` in place -> (out [H*hd] f32, masked scores [H][ctx] f32 or None, P16 [H][ctx] u16 or None)"""
+    qkv, rope_row = np.ascontiguousarray(qkv, np.float32), np.ascontiguousarray(rope_row, np.float32)
+    assert qkv.size == (H + 2 * Hkv) * hd and rope_row.size == hd and 0 <= pos < ctx
+    assert all(a.dtype == np.uint16 and a.flags.c_contiguous and a.size == ctx * Hkv * hd for a in (kc, vc))
+    out = np.zeros(H * hd, np.float32)
+    w = np.zeros((H, ctx), np.float32) if taps else None
+    p = np.zeros((H, ctx), np.uint16) if taps else None
+    lib().orc_attn_decode_row(ptr(qkv), ptr(kc), ptr(vc), pos, H, Hkv, hd, ctx, ptr(rope_row), q_scale, ptr(out),
+                              ptr(w) if taps else None, ptr(p) if taps else None)
+    return out, w, p
+
+
+def image_of(y):
+    """quantize_row_q8_0 of y as the activation image (csrc/device_util.h): -> (qs [block][8] u32, the dword
+    l of block b sits at image word ((b >> 2) * 8 + l) * 4 + (b & 3); da [block] f32 block scales)"""
+    q = quantize(np.ascontiguousarray(y)[None], "q8_0")[0]
+    nb = q.size // 34
+    blk = q.reshape(nb, 34)
+    da = blk[:, :2].copy().view(np.float16).astype(np.float32).ravel()
+    qs = blk[:, 2:].copy().view(np.uint32).reshape(nb, 8)  # [b][l]
+    return qs, da
+
+
+def image_words(b):
+    """the 8 word indices of block b in the activation image"""
+    return ((b >> 2) * 8 + np.arange(8)) * 4 + (b & 3)
 
 
 GEMMA_2B = dict(n_layer=18, n_embd=2048, n_head=8, n_head_kv=1, head_dim=256, n_ff=16384, n_vocab=256000)

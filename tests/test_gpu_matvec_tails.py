@@ -106,16 +106,6 @@ def _add_run(wtype, ks, pro, K, rows, ncols, grid):
         assert not y[c * y_stride + rows: (c + 1) * y_stride].any()
 
 
-def _image_of(y):
-    """quantize_row_q8_0 of y as the activation image: whole groups of 4 blocks (csrc/device_util.h)"""
-    q = O.quantize(np.ascontiguousarray(y)[None], "q8_0")[0]
-    nb = q.size // 34
-    blk = q.reshape(nb, 34)
-    da = blk[:, :2].copy().view(np.float16).astype(np.float32).ravel()
-    qs = blk[:, 2:].copy().view(np.uint32).reshape(nb, 8)  # [b][l]
-    return qs, da
-
-
 _GELU_REF = {}
 
 
@@ -179,7 +169,7 @@ def test_gelu_one_lookup(wtype, clamp, scale, rows, grid):
     assert not ia[unused].any(), "the image was written outside y's blocks"
     if finite.any():
         safe = np.where(np.repeat(finite, 32), want, np.float32(0.0)).astype(np.float32)
-        qs, da = _image_of(safe)
+        qs, da = O.image_of(safe)
         for b in np.flatnonzero(finite):
             got = ia[((b >> 2) * 8 + np.arange(8)) * 4 + (b & 3)]
             assert np.array_equal(got, qs[b]), f"image block {b} differs"

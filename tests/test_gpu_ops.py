@@ -50,12 +50,14 @@ def test_attn_decode_bitexact(H, Hkv, mode):
             assert r == 0, G.last_error()
             assert np.array_equal(k1, k2) and np.array_equal(v1, v2), f"cache update differs at pos {pos}"
             nd = int((got.view(np.uint32) != ref.view(np.uint32)).sum())
-            if nd:
-                n_kv = min(ctx, 32 * ((pos + 1) // 32 + 1))
-                w1 = w1.reshape(H, ctx)[:, :n_kv]; w2 = w2.reshape(H, ctx)[:, :n_kv]
-                p1 = p1.reshape(H, ctx)[:, :n_kv]; p2 = p2.reshape(H, ctx)[:, :n_kv]
-                wd = np.argwhere(w1.view(np.uint32) != w2.view(np.uint32))
-                pd = np.argwhere(p1 != p2)
+            # the score words (j <= pos) and the P16 words (j < n_kv) on every case: on these inputs a wrong KQ
+            # accumulation moves half of the scores and no output word (tests/test_attn_decode_adversary.py)
+            n_kv = min(ctx, 32 * ((pos + 1) // 32 + 1))
+            w1 = w1.reshape(H, ctx)[:, :n_kv]; w2 = w2.reshape(H, ctx)[:, :n_kv]
+            p1 = p1.reshape(H, ctx)[:, :n_kv]; p2 = p2.reshape(H, ctx)[:, :n_kv]
+            wd = np.argwhere(w1[:, :pos + 1].view(np.uint32) != w2[:, :pos + 1].view(np.uint32))
+            pd = np.argwhere(p1 != p2)
+            if nd or len(wd) or len(pd):
                 info = dict(w_diffs=wd[:3].tolist(), p_diffs=pd[:3].tolist())
                 if len(pd):
                     h, j = pd[0]
