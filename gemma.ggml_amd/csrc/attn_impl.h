@@ -8,6 +8,8 @@
 // §inter-workgroup visibility, row 1 of the sc1 table.
 #pragma once
 
+#include <type_traits>
+
 #include "device_util.h"
 #include "kernels.h"
 #include "q8k.h"
@@ -239,11 +241,12 @@ struct attn_pre {
     uint4 k[KPF], v[VPF];
     int pos_v;
 };
-template <int NTH, int KPF, int VPF>
+// HD: head_dim at compile time (0: a.hd), and then kvh_in is the caller's h / G (no division here)
+template <int NTH, int KPF, int VPF, int HD = 0>
 __device__ __forceinline__ void attn_prefetch(const attn_args &a, const int h, attn_pre<KPF, VPF> &p, int d_lo = 0,
-                                              int d_hi = 1 << 30, int tid_in = -1) {
-    const int hd = a.hd, tid = tid_in >= 0 ? tid_in : (int)threadIdx.x, t4 = tid & 3, quad = tid >> 2;
-    const int G = a.H / a.Hkv, kvh = h / G, kvw = a.Hkv * hd;
+                                              int d_hi = 1 << 30, int tid_in = -1, int kvh_in = -1) {
+    const int hd = HD ? HD : a.hd, tid = tid_in >= 0 ? tid_in : (int)threadIdx.x, t4 = tid & 3, quad = tid >> 2;
+    const int kvh = HD ? kvh_in : h / (a.H / a.Hkv), kvw = a.Hkv * hd;
     // published with the row (k_advance / begin); a scalar load (constant address space): its own
     // counter, so reading pos waits for no vector load
 #if GHIP_AH_SPOS
@@ -275,16 +278,31 @@ __device__ __forceinline__ void attn_prefetch(const attn_args &a, const int h, a
 // CACHED: this position's K row and V column are in the cache already (an earlier launch stored them:
 // k_rows_rope_kv, batch.hip), so every K / V operand is read from there, the row's own position
 // included, and nothing is stored to a cache; the k / v of a.qkv are not read
-template <int NTH, bool SC1, int KPF = AH_KPF, int VPF = AH_VPF, bool PRE = false, bool SC1O = SC1, bool CACHED = false>
+// HD: head_dim at compile time (0: a.hd at run time).  With it every K / V group is 8 steps with no
+// test of hd in the stream, and the dims of a split come from a shift (dsplit is a power of two then).
+// TAPS: the debug taps (dbg_w, dbg_p, dbg_inv) are compiled in; the product instantiation has none.
+// kvh_in / G_in: with HD, the caller's h / G and G (no division in front of the first loads).
+//
+// Stream (issue order = wait order, every vmcnt wait by count): RoPE inputs and this token's v, the
+// K / V prefetch | RoPE, the K row appended from the RoPE wave's registers | barrier | per KQ pass of
+// NTH / 4 positions: 8 K steps in registers, dots, the next pass's 8 K loads, fold and store | the
+// V steps past the prefetch behind the wave's last pass | softmax | KQV in groups of 8 V steps.
+typedef uint32_t attn_u32x32 __attribute__((ext_vector_type(32)));
+template <int NTH, bool SC1, int KPF = AH_KPF, int VPF = AH_VPF, bool PRE = false, bool SC1O = SC1, bool CACHED = false,
+          int HD = 0, bool TAPS = true>
 __device__ void attn_head_dev(const attn_args &a, const int h, uint8_t *smem, const attn_pre<KPF, VPF> *pre = nullptr,
-                              const int sp = 0, const int tid_in = -1) {
+                              const int sp = 0, const int tid_in = -1, const int kvh_in = -1, const int G_in = 0) {
+    static_assert(HD % 32 == 0 && HD <= 256 && KPF <= 8 && VPF <= 8, "groups of 8 steps of 32");
     // tid_in: the caller's (opaque) thread index, so that a persistent caller's loop does not keep
     // this function's per-lane addresses live across its other phases
-    const int hd = a.hd, half = hd / 2, tid = tid_in >= 0 ? tid_in : (int)threadIdx.x, t4 = tid & 3, quad = tid >> 2;
-    const int dsz = hd / (a.dsplit > 1 ? a.dsplit : 1), d_lo = sp * dsz, d_hi = d_lo + dsz;
+    const int hd = HD ? HD : a.hd, half = hd / 2, tid = tid_in >= 0 ? tid_in : (int)threadIdx.x, t4 = tid & 3, quad = tid >> 2;
+    const int dsz = HD ? HD >> __builtin_ctz((unsigned)a.dsplit | 256u) : hd / (a.dsplit > 1 ? a.dsplit : 1);
+    const int d_lo = sp * dsz, d_hi = d_lo + dsz;
     // wave: uniform for the compiler too (readfirstlane), so branches on it are scalar branches
     const int lane = tid & 63, wave = GHIP_AH_SPOS ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6, nwave = NTH / 64;
-    const int G = a.H / a.Hkv, kvh = h / G;
+    const int G = HD ? G_in : a.H / a.Hkv, kvh = HD ? kvh_in : h / G;
+    constexpr bool ONE = NTH / 4 >= 256;  // a quad per output dim (hd <= 256): the KQV runs once
+    auto live = [&](int s) { return HD ? s * 32 < HD : s * 32 < hd; };  // step s of a K row exists
     AH_STAMP(0);
     AH_CLK0();
     const int kvw = a.Hkv * hd;
@@ -297,18 +315,23 @@ __device__ void attn_head_dev(const attn_args &a, const int h, uint8_t *smem, co
     // ~16 clk whatever its addresses; a wave-uniform branch skips the others)
     const int rl = tid;  // the RoPE lanes: wave 0 (hd <= 512: 64 lanes suffice)
     const int n4 = half / 4, i4 = (rl >= 0 && rl < n4 ? rl : 0) * 4;
-    float4 qa{}, qb{}, ka{}, kb{}, ca{}, sa{};
+    float4 qa, qb, ka, kb, ca, sa;  // set and read by the RoPE wave only (no zero to merge with: no copies)
     if (wave * 64 < n4) {
         qa = ld4<SC1>(qh + i4); qb = ld4<SC1>(qh + i4 + half);
         if (!CACHED) { ka = ld4<SC1>(kh + i4); kb = ld4<SC1>(kh + i4 + half); }
         ca = *(const float4 *)(cs + i4); sa = *(const float4 *)(sn + i4);
     }
+    // this token's v for the quad's output dim, in front of the K / V prefetch: the cache append below
+    // waits for it by count, with the prefetch still in flight.  The appending workgroup (the group's
+    // first head, split 0: its dims start at 0) loads dim `quad` in every quad and stores the column.
+    const bool append = !CACHED && h == kvh * G && sp == 0;
+    const int d0 = d_lo + quad < d_hi ? d_lo + quad : d_lo;
+    const float vx0 = CACHED ? 0.0f : ld1<SC1>(vh + (ONE && append && quad < hd ? quad : d0));
     attn_pre<KPF, VPF> own;
-    if (!PRE) attn_prefetch<NTH, KPF, VPF>(a, h, own, d_lo, d_hi, tid);
+    if (!PRE) attn_prefetch<NTH, KPF, VPF, HD>(a, h, own, d_lo, d_hi, tid, kvh);
     const attn_pre<KPF, VPF> &P = PRE ? *pre : own;
     const uint4 *kpre = P.k, *vpre = P.v;
-    const int d0 = d_lo + quad < d_hi ? d_lo + quad : d_lo;
-    const float vx0 = CACHED ? 0.0f : ld1<SC1>(vh + d0);
+    const int pos = __builtin_amdgcn_readfirstlane(P.pos_v);
 
     uint16_t *q16 = (uint16_t *)smem;  // hd
     uint16_t *k16 = q16 + hd;          // hd (this token's k, post-rope)
@@ -321,7 +344,9 @@ __device__ void attn_head_dev(const attn_args &a, const int h, uint8_t *smem, co
     unsigned long long *e_sum = (unsigned long long *)(mx_key + 2);
 
     // RoPE NEOX on q (then * q_scale) and on k; f32 -> f16 (ggml_cpy / MUL_MAT INIT conversions)
-    auto rope4 = [&](float4 x0v, float4 x1v, float scale, bool scaled, uint16_t *lo, uint16_t *hi) {
+    // glo / ghi: where the rotated halves also go in global memory (the cache append), or null
+    auto rope4 = [&](float4 x0v, float4 x1v, float scale, bool scaled, uint16_t *lo, uint16_t *hi, uint16_t *glo,
+                     uint16_t *ghi) {
         const float x0s[4] = {x0v.x, x0v.y, x0v.z, x0v.w}, x1s[4] = {x1v.x, x1v.y, x1v.z, x1v.w};
         const float cs4[4] = {ca.x, ca.y, ca.z, ca.w}, sn4[4] = {sa.x, sa.y, sa.z, sa.w};
         uint32_t l2[2] = {0, 0}, h2[2] = {0, 0};
@@ -336,27 +361,38 @@ __device__ void attn_head_dev(const attn_args &a, const int h, uint8_t *smem, co
         }
         *(uint2 *)lo = make_uint2(l2[0], l2[1]);
         *(uint2 *)hi = make_uint2(h2[0], h2[1]);
+        if (glo) {
+            *(uint2 *)glo = make_uint2(l2[0], l2[1]);
+            *(uint2 *)ghi = make_uint2(h2[0], h2[1]);
+        }
     };
+    // this token's cache entries (src/gemma_model.cpp:506-517), by the group's first head; readers in
+    // this launch use k16 / the v values instead.  The K row goes out from the RoPE wave's registers,
+    // 8 bytes a store, beside its LDS writes.
     if (rl >= 0 && rl < n4) {
-        rope4(qa, qb, a.q_scale, true, q16 + i4, q16 + i4 + half);
-        if (!CACHED) rope4(ka, kb, 1.0f, false, k16 + i4, k16 + i4 + half);
+        rope4(qa, qb, a.q_scale, true, q16 + i4, q16 + i4 + half, nullptr, nullptr);
+        if (!CACHED) {
+            uint16_t *gk = append ? a.kc + (int64_t)pos * kvw + (int64_t)kvh * hd + i4 : nullptr;
+            rope4(ka, kb, 1.0f, false, k16 + i4, k16 + i4 + half, gk, gk + half);
+        }
     }
     if (rl == 0) {  // (the RoPE wave: its loads are drained here; another wave could wait on them)
         *mx_key = 0u;  // below the key of every float, -inf included
         *e_sum = 0ull;
     }
-    const int pos = __builtin_amdgcn_readfirstlane(P.pos_v);
     const int n_total = pos + 1;
     int n_kv = 32 * (n_total / 32 + 1);  // src/gemma_model.cpp:429
     if (n_kv > a.ctx) n_kv = a.ctx;
     attn_barrier();  // LDS only: the K / V prefetch stays in flight
     AH_STAMP(1);
-    // this token's cache entries (src/gemma_model.cpp:506-517), by the group's first head; readers
-    // in this launch use k16 / the v values instead
-    if (!CACHED && h % G == 0 && sp == 0) {
-        for (int i = tid; i < hd; i += NTH) a.kc[(int64_t)pos * kvw + (int64_t)kvh * hd + i] = k16[i];
-        for (int d = quad; d < hd; d += NTH / 4)
-            if (t4 == 0) a.vc[((int64_t)kvh * hd + d) * a.ctx + pos] = f2h(d == d0 ? vx0 : ld1<SC1>(vh + d));
+    // the V column, by the lanes that hold the f32 values (a counted wait: vx0 precedes the prefetch)
+    if (append) {
+        if (ONE) {
+            if (t4 == 0 && quad < hd) a.vc[((int64_t)kvh * hd + quad) * a.ctx + pos] = f2h(vx0);
+        } else {
+            for (int d = quad; d < hd; d += NTH / 4)
+                if (t4 == 0) a.vc[((int64_t)kvh * hd + d) * a.ctx + pos] = f2h(d == d0 ? vx0 : ld1<SC1>(vh + d));
+        }
     }
     // ---- KQ (vec_dot_f16 over hd per kv position) + mask (j > pos -> -inf), scale 1.0
     float lmax = -INFINITY;
@@ -364,61 +400,71 @@ __device__ void attn_head_dev(const attn_args &a, const int h, uint8_t *smem, co
     // instead of one per step and position)
     uint4 qr[8];
 #pragma unroll
-    for (int s = 0; s < 8; ++s) qr[s] = *(const uint4 *)(q16 + (s * 32 < hd ? s * 32 : 0) + t4 * 8);
+    for (int s = 0; s < 8; ++s) qr[s] = *(const uint4 *)(q16 + (live(s) ? s * 32 : 0) + t4 * 8);
     if (GHIP_STAMPS == 4) {  // KQ sub-stamps (stamps build 4): q in registers
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         AH_STAMP(5);
     }
-    for (int j0 = 0; j0 < n_kv; j0 += NTH / 4) {
+    // A pass is NTH / 4 positions, a row's 8 K steps in kx.  The first pass's steps past the prefetch
+    // (at most 8 - KPF) are issued together here; a later pass's 8 are issued behind the dots of the
+    // pass before, in front of its fold and store: one round trip per pass, waited for by count.
+    const uint16_t *kbase = a.kc + (int64_t)kvh * hd + t4 * 8;
+    uint4 kx[8];
+    {
+        const uint16_t *krow = kbase + (int64_t)((GHIP_AH_ABL & 1) ? 0 : quad < a.ctx ? quad : 0) * kvw;
+#pragma unroll
+        for (int s = KPF; s < 8; ++s) kx[s] = *(const uint4 *)(krow + (live(s) ? s * 32 : 0));
+#pragma unroll
+        for (int s = 0; s < KPF; ++s) kx[s] = kpre[s];
+    }
+    // V steps VPF .. 7 of the quad's dim are issued behind the wave's last pass (K's and q's registers
+    // are free then, which a 1024-thread workgroup's 128 VGPRs need), in front of the softmax's
+    // barriers: the KQV starts with its first group's operands in registers.  v8 is the first V
+    // group (8 steps of 32 positions) as one register tuple: the own-position patch indexes it.
+    attn_u32x32 v8;
+    auto v_put = [&](int s, uint4 x) { v8[4 * s] = x.x; v8[4 * s + 1] = x.y; v8[4 * s + 2] = x.z; v8[4 * s + 3] = x.w; };
+    auto v_get = [&](int s) { return make_uint4(v8[4 * s], v8[4 * s + 1], v8[4 * s + 2], v8[4 * s + 3]); };
+    const uint16_t *vrow0 = a.vc + ((int64_t)kvh * hd + d0) * a.ctx + t4 * 8;
+    auto v_rest = [&]() {
+#pragma unroll
+        for (int s = VPF; s < 8; ++s) v_put(s, *(const uint4 *)(vrow0 + (s * 32 < n_kv ? s * 32 : 0)));
+    };
+    // a wave whose 16 positions all lie past n_kv has nothing to store: it runs no pass (wave-uniform;
+    // its lmax stays -inf, below every stored score).  n_kv is a multiple of 32, so a wave that runs a
+    // pass has all 16 positions below n_kv, and one that sits a pass out sits out every later one.
+    bool act = wave * 16 < n_kv && !(GHIP_AH_ABL & 4);
+    for (int j0 = 0; act; j0 += NTH / 4) {
         const int j = j0 + quad;
-        // a wave whose 16 positions all lie past n_kv has nothing to store: skip its dots (wave-
-        // uniform; its lmax stays -inf, below every stored score)
-        if (j0 + wave * 16 >= n_kv || (GHIP_AH_ABL & 4)) continue;
+        // this token's own row (its cache store may not be visible): only the wave that holds pos
+        // (a scalar test) reads k16 from LDS, and only the quad of j == pos keeps what it read
+        if (!CACHED && ((pos - j0) >> 4) == wave) {
+            if (j == pos) {
+#pragma unroll
+                for (int s = 0; s < 8; ++s)
+                    if (live(s)) kx[s] = *(const uint4 *)(k16 + s * 32 + t4 * 8);
+            }
+        }
+        if (GHIP_STAMPS == 4 && j0 + wave * 16 == 0) {  // the first K steps have landed
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            AH_STAMP(6);
+        }
         float acc[8];
 #pragma unroll
         for (int y = 0; y < 8; ++y) acc[y] = 0.0f;
-        if (j0 == 0) {
-            // the row's remaining K steps (hd <= 256: at most 8 - KPF) issued together before the
-            // prefetched steps' arithmetic: one round trip, not one per step
-            const uint16_t *krow = a.kc + (int64_t)((GHIP_AH_ABL & 1) ? 0 : j < a.ctx ? j : 0) * kvw + (int64_t)kvh * hd;
-            constexpr int KR = 8 - KPF > 0 ? 8 - KPF : 1;
-            uint4 kx[8];
+        if (GHIP_AH_ABL & 2) {
 #pragma unroll
-            for (int r = 0; r < KR; ++r) {
-                const int s = KPF + r;
-                if (s < 8) kx[s < 8 ? s : 0] = *(const uint4 *)(krow + (s * 32 < hd ? s * 32 : 0) + t4 * 8);
-            }
+            for (int s = 0; s < 8; ++s) acc[s] = __builtin_bit_cast(float, kx[s].x ^ qr[s].y);
+        } else
 #pragma unroll
-            for (int s = 0; s < KPF; ++s)
-                if (s < 8) kx[s] = kpre[s];
-            // this token's own row (its cache store may not be visible): only the quad of j == pos
-            // swaps its operands for k16 from LDS — one divergent LDS read, not a second dot
-            if (!CACHED && j == pos) {
-#pragma unroll
-                for (int s = 0; s < 8; ++s)
-                    if (s * 32 < hd) kx[s] = *(const uint4 *)(k16 + s * 32 + t4 * 8);
-            }
-            if (GHIP_STAMPS == 4 && j0 + wave * 16 == 0) {  // the first K steps have landed
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                AH_STAMP(6);
-            }
-            if (GHIP_AH_ABL & 2) {
-#pragma unroll
-                for (int s = 0; s < 8; ++s) acc[s] = __builtin_bit_cast(float, kx[s].x ^ qr[s].y);
-            } else
+        for (int s = 0; s < 8; ++s)
+            if (live(s) && (!(GHIP_AH_ABL & 16) || s < 4)) f16_step8(acc, kx[s], qr[s]);
+        const bool nxt = j0 + NTH / 4 + wave * 16 < n_kv;
+        if (nxt) {
+            const int jn = j + NTH / 4, jc = (CACHED ? jn <= pos : jn < pos) ? jn : 0;  // jn > pos is masked below
+            const uint16_t *krow = kbase + (int64_t)((GHIP_AH_ABL & 1) ? 0 : jc) * kvw;
 #pragma unroll
             for (int s = 0; s < 8; ++s)
-                if (s * 32 < hd && (!(GHIP_AH_ABL & 16) || s < 4)) f16_step8(acc, kx[s], qr[s]);
-        } else if (!CACHED && j == pos) {
-#pragma unroll
-            for (int s = 0; s < 8; ++s)
-                if (s * 32 < hd) f16_step8(acc, *(const uint4 *)(k16 + s * 32 + t4 * 8), qr[s]);
-        } else {
-            const int jc = (CACHED ? j <= pos : j < pos) ? j : 0;  // j > pos is masked below
-            const uint16_t *krow = a.kc + (int64_t)jc * kvw + (int64_t)kvh * hd;
-#pragma unroll
-            for (int s = 0; s < 8; ++s)
-                if (s * 32 < hd) f16_step8(acc, *(const uint4 *)(krow + s * 32 + t4 * 8), qr[s]);
+                if (live(s)) kx[s] = *(const uint4 *)(krow + s * 32);
         }
         const float kq = quad_reduce_f16(acc);
         if (GHIP_STAMPS == 4 && j0 == 0) AH_STAMP(7);  // dots folded (wave 0)
@@ -426,9 +472,13 @@ __device__ void attn_head_dev(const attn_args &a, const int h, uint8_t *smem, co
             const float w = (j > pos) ? -INFINITY : kq * 1.0f + 0.0f;
             S[j] = w;
             lmax = fmaxf(lmax, w);
-            if (a.dbg_w) a.dbg_w[(int64_t)h * a.ctx + j] = w;
+            if (TAPS && a.dbg_w) a.dbg_w[(int64_t)h * a.ctx + j] = w;
         }
+        act = nxt;
     }
+#pragma unroll
+    for (int s = 0; s < VPF; ++s) v_put(s, vpre[s]);
+    v_rest();
     // the row max, partial per wave (DPP) then one LDS max per wave, in the same barrier as S
     lmax = wave_max(lmax);
     if (lane == 0) {
@@ -460,85 +510,74 @@ __device__ void attn_head_dev(const attn_args &a, const int h, uint8_t *smem, co
         const double sum = (double)*e_sum * (1.0 / 16777216.0);
         const float inv = (float)(1.0 / sum);
         if (GHIP_STAMPS == 1) AH_STAMP(7);
-        if (a.dbg_inv && tid == 0) a.dbg_inv[h] = inv;
+        if (TAPS && a.dbg_inv && tid == 0) a.dbg_inv[h] = inv;
         for (int j = quad; j < n_kv; j += NTH / 4) {
             if (t4 != 0) break;
             const float e = h2f(P16[j]);  // this lane's own e from the first pass (no second exp)
             P16[j] = f2h(e * inv);
-            if (a.dbg_p) a.dbg_p[(int64_t)h * a.ctx + j] = P16[j];
+            if (TAPS && a.dbg_p) a.dbg_p[(int64_t)h * a.ctx + j] = P16[j];
         }
     }
     attn_barrier();
     AH_STAMP(3);
     // ---- KQV: out[d] = vec_dot_f16(n_kv, V[kvh][d][0..n_kv), P16); lane t4 runs accumulator j = t4
+    // V comes in groups of 8 steps (256 positions), all 8 loads of a group issued together and waited
+    // for by count: one round trip per group, P16 read from LDS per group.  The first group of the
+    // quad's first dim is in v8 already (the early loads).
+    bool first = true;  // the first dim of the quad: d == d0
     for (int d = d_lo + quad; d < d_hi; d += NTH / 4) {
         float acc[8];
 #pragma unroll
         for (int y = 0; y < 8; ++y) acc[y] = 0.0f;
-        const uint16_t *vr = a.vc + ((int64_t)kvh * hd + d) * a.ctx;
-        const float vx = CACHED ? 0.0f : d == d0 ? vx0 : ld1<SC1>(vh + d);
-        // this token's V: its cache write may not be visible.  Element pos sits in step pos/32, on
-        // quad lane (pos/8)%4, dword (pos%8)/2, half pos%2 — all wave-uniform but the lane test, so
-        // the patch holds no per-step VGPRs (the per-step e0 form was hoisted and spilled)
-        const int p_s = pos >> 5, p_t = (pos >> 3) & 3, p_w = (pos >> 1) & 3;
-        const uint32_t p_sh = 16 * (pos & 1), p_msk = ~(0xFFFFu << p_sh);
-        auto patch = [&](uint4 &xv, int s) {
-            if (!CACHED && s == p_s && t4 == p_t) {
-                const uint32_t hv = f2h(vx) << p_sh;
-                if (p_w == 0) xv.x = (xv.x & p_msk) | hv;
-                else if (p_w == 1) xv.y = (xv.y & p_msk) | hv;
-                else if (p_w == 2) xv.z = (xv.z & p_msk) | hv;
-                else xv.w = (xv.w & p_msk) | hv;
-            }
-        };
-        if (n_kv <= 256) {
-            // every step's V load issued before the first step's arithmetic (one round trip);
-            // the prefetched steps of the first dimension come from the early loads; P16 (the same
-            // for every dimension) read into registers once
-            uint4 xs8[8], pr8[8];
-            const bool first = d == d0;
+        const uint16_t *vr = a.vc + ((int64_t)kvh * hd + d) * a.ctx + t4 * 8;
+        const float vx = CACHED ? 0.0f : first ? vx0 : ld1<SC1>(vh + d);
+        // FULL: all 8 steps of the group lie below n_kv (no test per step, every load consumed); the
+        // row's last group, when n_kv is no multiple of 256, stops at n_kv
+        auto group = [&](const int g, auto full) {
+            constexpr bool FULL = decltype(full)::value;
+            const int st0 = g * 256;
+            if (g > 0 || !first) {
 #pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const int e0 = s * 32 + t4 * 8;
-                if (s < VPF && first) xs8[s] = vpre[s < VPF ? s : 0];
-                else xs8[s] = *(const uint4 *)(vr + (s * 32 < n_kv ? e0 : t4 * 8));
+                for (int s = 0; s < 8; ++s)
+                    v_put(s, *(const uint4 *)(vr + (FULL || st0 + s * 32 < n_kv ? st0 + s * 32 : 0)));
             }
+            uint4 pr8[8];
 #pragma unroll
             for (int s = 0; s < 8; ++s)
-                pr8[s] = *(const uint4 *)(P16 + (s * 32 < n_kv ? s * 32 : 0) + t4 * 8);
-            if (GHIP_STAMPS == 2 && d == d_lo + quad) {  // operands in registers (stamps build 2)
+                pr8[s] = *(const uint4 *)(P16 + (FULL || st0 + s * 32 < n_kv ? st0 + s * 32 : 0) + t4 * 8);
+            // this token's V: its cache write may not be visible.  Element pos sits in group pos/256,
+            // on quad lane (pos/8)%4, word (pos%256)/32*4 + (pos%8)/2 of the lane's group, half pos%2.
+            // The group and the word are wave-uniform: one indexed register move each way and a
+            // select on the lane, no test per step
+            if (!CACHED && (pos >> 8) == g) {
+                const int wi = ((pos >> 5) & 7) * 4 + ((pos >> 1) & 3);
+                const uint32_t p_sh = 16 * (pos & 1), old = v8[wi];
+                const uint32_t put = (old & ~(0xFFFFu << p_sh)) | (f2h(vx) << p_sh);
+                v8[wi] = t4 == ((pos >> 3) & 3) ? put : old;
+            }
+            if (GHIP_STAMPS == 2 && first && g == 0) {  // operands in registers (stamps build 2)
                 asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
                 AH_STAMP(5);
             }
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
-                if (s * 32 >= n_kv) break;
-                uint4 xv = xs8[s];
-                patch(xv, s);
+                if (!FULL && st0 + s * 32 >= n_kv) break;
+                const uint4 xv = v_get(s);
                 if (GHIP_AH_ABL & 8) acc[s] = __builtin_bit_cast(float, xv.x ^ pr8[s].y);
                 else f16_step8(acc, xv, pr8[s]);
             }
-        } else
-        for (int st = 0, s = 0; st < n_kv; st += 32, ++s) {
-            const int e0 = st + t4 * 8;
-            uint4 xv;
-            if (d == d0 && s < VPF) {
-                xv = vpre[0];  // statically-indexed pick from the early loads
-#pragma unroll
-                for (int k = 1; k < VPF; ++k)
-                    if (s == k) xv = vpre[k];
-            } else {
-                xv = *(const uint4 *)(vr + e0);
-            }
-            patch(xv, s);
-            f16_step8(acc, xv, *(const uint4 *)(P16 + e0));
-        }
+        };
+        const int n_full = n_kv >> 8;
+        for (int g = 0; g < n_full; ++g) group(g, std::true_type{});
+        if (n_kv & 255) group(n_full, std::false_type{});
+        first = false;
         const float o = quad_reduce_f16(acc);
         if (GHIP_STAMPS == 2 && d == d_lo + quad) AH_STAMP(6);  // chains folded
         if (t4 == 0) {
             a.out[(int64_t)h * hd + d] = o;
             if (a.out_act || a.out_q8k || a.out_gran) ((float *)smem)[d] = o;  // q16|k16 (hd floats) are dead after KQ
         }
+        if (ONE) break;  // d + NTH / 4 >= hd
     }
     if (a.out_gran) {  // the same image, handed on as granules inside the persistent launch
         __syncthreads();

@@ -528,6 +528,24 @@ __global__ void __launch_bounds__(AH_THREADS) k_attn_head(const float *qkv, uint
     attn_head_dev<AH_THREADS, false, AH_KPF, AH_VPF, false>(a, h, smem, nullptr, sp);
 }
 
+// The same body with head_dim HD at compile time (launch_attn_decode starts it at head_dim 256): no
+// test of hd in the K / V streams and no division in front of the first loads.  dsplit is a power of
+// two here (it divides HD / 32), so head and split come from a shift and a mask; h / G comes from the
+// launcher's multiplier ginv = ceil(2^20 / G), exact for h < H <= 1024 (h (G ginv - 2^20) < 2^20).  TAPS = false is the product form,
+// with no debug tap in its loops; the launcher starts TAPS = true when a tap pointer is set.
+template <int HD, bool TAPS>
+__global__ void __launch_bounds__(AH_THREADS) k_attn_head_hd(const float *qkv, uint16_t *kc, uint16_t *vc, const float *rope_cur,
+                                                             int Hkv, int G, int ginv, int ctx, int dsplit, attn_args a_rest) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    attn_args a = a_rest;
+    a.qkv = qkv; a.kc = kc; a.vc = vc; a.rope_cur = rope_cur;
+    a.H = Hkv * G; a.Hkv = Hkv; a.hd = HD; a.ctx = ctx; a.dsplit = dsplit;
+    const int hs = blockIdx.x >> 3, h = hs >> __builtin_ctz((unsigned)dsplit | 256u), sp = hs & (dsplit - 1);
+    const int kvh = (h * ginv) >> 20;
+    if ((int)(blockIdx.x & 7) != (kvh & 7)) return;  // as k_attn_head
+    attn_head_dev<AH_THREADS, false, AH_KPF, AH_VPF, false, false, false, HD, TAPS>(a, h, smem, nullptr, sp, -1, kvh, G);
+}
+
 // ---- exact causal attention for T prompt rows (the reference's prefill graph) -----------------
 // Row i of the prefill KQ / soft_max_ext / KQV (src/gemma_model.cpp:467-489 with T tokens) is the
 // decode computation at position i: positions j > i are masked to -inf (e = 0), and the KQV terms
@@ -865,6 +883,18 @@ int launch_attn_decode(const attn_args &a, hipStream_t s) {
         }
         // (V rows by LDS-DMA, and the heads spread over the XCDs, measured neutral / slower: removed,
         // DESIGN.md §10)
+        if (a.hd == 256 && a.H <= 1024) {
+            // head_dim 256 (Gemma 2B and 7B): the compile-time form, tapped only when a tap is asked for
+            const bool taps = a.dbg_w || a.dbg_p || a.dbg_inv;
+            auto *k = taps ? k_attn_head_hd<256, true> : k_attn_head_hd<256, false>;
+            const int G = a.H / a.Hkv, ginv = ((1 << 20) + G - 1) / G;
+            if (lds > 64 * 1024)
+                GHIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(k, dim3(8 * a.H * a.dsplit), dim3(AH_THREADS), lds, s, a.qkv, a.kc, a.vc, a.rope_cur, a.Hkv, G,
+                               ginv, a.ctx, a.dsplit, a);
+            GHIP_CHECK(hipGetLastError());
+            return 0;
+        }
         if (lds > 64 * 1024)
             GHIP_CHECK(hipFuncSetAttribute((const void *)k_attn_head, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(k_attn_head, dim3(8 * a.H * a.dsplit), dim3(AH_THREADS), lds, s, a.qkv, a.kc, a.vc, a.rope_cur, a.H,
