@@ -38,26 +38,33 @@ __global__ void __launch_bounds__(AH_THREADS) k_attn_slots(attn_args a, const sl
     attn_head_dev<AH_THREADS, false, AH_KPF, AH_VPF, false>(a, h, smem, nullptr, sp);
 }
 
+// What a pass leaves on a slot (sr: its entry of the batch_step table) that had m rows in it, the last
+// of which picks from `keys`: the position m further with its RoPE row, the pick committed there, the
+// pending token in *sr.last and *tok_out (what the slot's row processes in a following batch_step
+// pass).  own: the m rows' entries when they have position words of their own, else null.
+__device__ __forceinline__ void slot_advance_dev(const slot_row &sr, int m, const slot_row *own, const unsigned long long *keys,
+                                                 int n_parts, int *tok_out, int hist_cap, const rope_row &r,
+                                                 unsigned long long *red) {
+    // every thread reads the position before the barrier; thread 0 writes it after (as k_advance)
+    const int p = *sr.pos + m;
+    const int fixed = *sr.nfix;
+    if (p < r.ctx) publish_rope_row(sr.rope, r.cos, r.sin, r.half, p);  // the next position's, with its position word
+    // row (s, i) predicts sequence index pos + i + 1: what k_lse_finish reads as its position
+    if (own && (int)threadIdx.x < m) *own[threadIdx.x].pos += 1;
+    const unsigned long long best = block_max_key(keys, n_parts, red);
+    if (threadIdx.x == 0) {
+        const int tok = commit_pick(sr.hist, p, fixed, hist_cap, key_index(best));
+        *sr.pos = p;
+        *sr.last = tok;
+        *tok_out = tok;
+    }
+}
+
 __global__ void __launch_bounds__(256) k_batch_advance(const slot_row *rows, const unsigned long long *keys, int n_parts,
                                                        int key_stride, int *row_tok, int hist_cap, rope_row r) {
     __shared__ unsigned long long red[4];
     const slot_row sr = rows[blockIdx.x];
-    keys += (int64_t)blockIdx.x * key_stride;
-    // every thread reads the position before the barrier; thread 0 writes it after (as k_advance)
-    const int p = *sr.pos + 1;
-    const int fixed = *sr.nfix;
-    if (p < r.ctx) publish_rope_row(sr.rope, r.cos, r.sin, r.half, p);  // the next position's, with its position word
-    const unsigned long long best = block_max_key(keys, n_parts, red);
-    if (threadIdx.x == 0) {
-        int tok = key_index(best);
-        if (p < hist_cap) {
-            if (p >= fixed) sr.hist[p] = tok;  // never overwrite a given token
-            else tok = sr.hist[p];
-        }
-        *sr.pos = p;
-        *sr.last = tok;
-        row_tok[blockIdx.x] = tok;  // what the row processes in the next pass
-    }
+    slot_advance_dev(sr, 1, nullptr, keys + (int64_t)blockIdx.x * key_stride, n_parts, row_tok + blockIdx.x, hist_cap, r, red);
 }
 
 // ---- several rows per slot (gemma_engine_batch_step_rows) -----------------------------------------
@@ -121,24 +128,9 @@ __global__ void __launch_bounds__(256) k_rows_advance(const slot_row *rows, cons
     __shared__ unsigned long long red[4];
     const slot_row sr = rows[blockIdx.x];
     const slot_span sp = spans[blockIdx.x];
-    keys += (int64_t)(sp.row0 + sp.m - 1) * key_stride;  // the slot's last row picks
-    // every thread reads the position before the barrier; thread 0 writes it after (as k_advance)
-    const int p = *sr.pos + sp.m;
-    const int fixed = *sr.nfix;
-    if (p < r.ctx) publish_rope_row(sr.rope, r.cos, r.sin, r.half, p);
-    // row (s, i) predicts sequence index pos + i + 1: what k_lse_finish reads as its position
-    if ((int)threadIdx.x < sp.m) *mrows[sp.row0 + threadIdx.x].pos += 1;
-    const unsigned long long best = block_max_key(keys, n_parts, red);
-    if (threadIdx.x == 0) {
-        int tok = key_index(best);
-        if (p < hist_cap) {
-            if (p >= fixed) sr.hist[p] = tok;  // never overwrite a given token
-            else tok = sr.hist[p];
-        }
-        *sr.pos = p;
-        *sr.last = tok;
-        row_tok[blockIdx.x] = tok;  // what the slot's row processes in a following batch_step pass
-    }
+    // the slot's last row picks
+    slot_advance_dev(sr, sp.m, mrows + sp.row0, keys + (int64_t)(sp.row0 + sp.m - 1) * key_stride, n_parts,
+                     row_tok + blockIdx.x, hist_cap, r, red);
 }
 
 // ---- drafts in the batch (gemma_engine_batch_verify) ------------------------------------------------
@@ -178,13 +170,8 @@ __global__ void __launch_bounds__(256) k_bverify_accept(const slot_row *rows, co
         const int k = m - 1;
         int a = 0;
         while (a < k && sr.hist[p0 + 1 + a] == gs[a]) ++a;  // stops at the first mismatch
-        for (int i = 0; i <= a; ++i) {
-            const int q = p0 + 1 + i;
-            if (q < hist_cap) {
-                if (q >= fixed) sr.hist[q] = gs[i];  // never overwrite a given token (a k = 0 slot still ingesting)
-                else gs[i] = sr.hist[q];
-            }
-        }
+        // (a k = 0 slot may still be ingesting given tokens)
+        for (int i = 0; i <= a; ++i) gs[i] = commit_pick(sr.hist, p0 + 1 + i, fixed, hist_cap, gs[i]);
         for (int i = a + 1; i < k; ++i) sr.hist[p0 + 1 + i] = 0;  // the rejected drafts behind them
         *sr.pos = p0 + a + 1;
         *sr.last = gs[a];
@@ -222,18 +209,26 @@ __global__ void __launch_bounds__(256) k_bverify_clean(const slot_row *rows, con
 
 }  // namespace
 
-int launch_attn_slots(const attn_args &a, const slot_row *rows, int R, int64_t layer_off, hipStream_t s) {
+// the shapes and rows k_attn_slots and k_attn_slot_rows serve, and the LDS image they share (*lds);
+// what: the error's prefix
+static bool attn_slots_shape_ok(const attn_args &a, const slot_row *rows, int R, const char *what, size_t *lds) {
     if (a.mode != ATTN_PER_HEAD || a.hd % 32 != 0 || a.hd > 256 || a.ctx % 32 != 0 || a.Hkv <= 0 || a.H % a.Hkv != 0 ||
         a.dsplit < 1 || a.hd % (32 * a.dsplit) || 4 * (a.hd / a.dsplit) > AH_THREADS || a.out_act || a.out_q8k ||
         a.out_gran || !rows || R < 1 || R > ATTN_SLOTS_MAX_R) {
-        set_error("attn_slots: unsupported shape for the per-head form, or a pass outside [1, 64] rows");
-        return -1;
+        set_error(std::string(what) + ": unsupported shape for the per-head form, or a pass outside [1, 64] rows");
+        return false;
     }
-    const size_t lds = ((2 * (size_t)a.hd * 2 + 15) & ~(size_t)15) + (size_t)a.ctx * 4 + (size_t)a.ctx * 2 + 16;
-    if (lds > 64 * 1024) {  // n_ctx <= 2048 keeps it near 13 KiB
-        set_error("attn_slots: context too long for the LDS image");
-        return -1;
+    *lds = ((2 * (size_t)a.hd * 2 + 15) & ~(size_t)15) + (size_t)a.ctx * 4 + (size_t)a.ctx * 2 + 16;
+    if (*lds > 64 * 1024) {  // n_ctx <= 2048 keeps it near 13 KiB
+        set_error(std::string(what) + ": context too long for the LDS image");
+        return false;
     }
+    return true;
+}
+
+int launch_attn_slots(const attn_args &a, const slot_row *rows, int R, int64_t layer_off, hipStream_t s) {
+    size_t lds;
+    if (!attn_slots_shape_ok(a, rows, R, "attn_slots", &lds)) return -1;
     hipLaunchKernelGGL(k_attn_slots, dim3(8 * a.H * a.dsplit, R), dim3(AH_THREADS), lds, s, a, rows, layer_off);
     GHIP_CHECK(hipGetLastError());
     return 0;
@@ -273,18 +268,8 @@ int launch_attn_slot_rows(const attn_args &a, const slot_row *mrows, const row_s
         set_error("attn_slot_rows: no row sources");
         return -1;
     }
-    // the same shapes, rows and LDS image as k_attn_slots
-    if (a.mode != ATTN_PER_HEAD || a.hd % 32 != 0 || a.hd > 256 || a.ctx % 32 != 0 || a.Hkv <= 0 || a.H % a.Hkv != 0 ||
-        a.dsplit < 1 || a.hd % (32 * a.dsplit) || 4 * (a.hd / a.dsplit) > AH_THREADS || a.out_act || a.out_q8k ||
-        a.out_gran || !mrows || T < 1 || T > ATTN_SLOTS_MAX_R) {
-        set_error("attn_slot_rows: unsupported shape for the per-head form, or a pass outside [1, 64] rows");
-        return -1;
-    }
-    const size_t lds = ((2 * (size_t)a.hd * 2 + 15) & ~(size_t)15) + (size_t)a.ctx * 4 + (size_t)a.ctx * 2 + 16;
-    if (lds > 64 * 1024) {
-        set_error("attn_slot_rows: context too long for the LDS image");
-        return -1;
-    }
+    size_t lds;
+    if (!attn_slots_shape_ok(a, mrows, T, "attn_slot_rows", &lds)) return -1;
     hipLaunchKernelGGL(k_rows_rope_kv, dim3(T), dim3(256), 0, s, a, mrows, layer_off);
     GHIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_attn_slot_rows, dim3(8 * a.H * a.dsplit, T), dim3(AH_THREADS), lds, s, a, mrows, src, layer_off);

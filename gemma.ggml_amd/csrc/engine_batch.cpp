@@ -18,6 +18,16 @@
 // gemma_engine_batch_set_sampler gives a slot a sampler of its own (or its own greedy) beside slots that
 // follow the engine's: every row reads its parameters from its row-table entry, and the picks of a pass take
 // one, three or four launches by the mix of the participating slots; gemma_engine_batch_fork copies a slot.
+//
+// The three pass entries (batch_step, batch_step_rows, batch_verify) share everything but their per-slot
+// tables and their advance.  Each describes its pass by a batch_pass {row table, row sources, tokens, T}
+// and hands it to batch_run_pass, which alone decides the pass's form, enqueues it, picks from every
+// row and copies the logits rows out; the descriptor travels as an argument down to
+// enqueue_batch_attention, which alone chooses the attention kernels (by batch_pass::src).  A row-table
+// entry is made in one place (batch_row), the tables of a pass with several rows per slot in one place
+// (batch_build_rows: step_rows adds its slot_spans, batch_verify its bv_slots, both from the row0 and
+// rank the builder returns).  After batch_run_pass an entry launches its own advance
+// (launch_batch_advance / launch_rows_advance / launch_bverify_accept + _clean), then enqueue_lp_finish.
 #include "engine_impl.h"
 
 static constexpr int NS = GEMMA_BATCH_WIDE_MAX_SLOTS;  // every table's size
@@ -262,6 +272,24 @@ extern "C" int gemma_engine_batch_fork(gemma_engine *e, int src, int dst) {
     return 0;
 }
 
+// ---- the row tables ----------------------------------------------------------------------------------
+// Row t's entry of a row table, a row of slot `slot`: its part of the scratch, the slot's caches,
+// history, words and sampler parameters.  own: the row has a RoPE row and a position word of its own,
+// row t's of mrope (a pass with several rows per slot; k_rows_prepare fills them); else the slot's
+static slot_row batch_row(const gemma_engine *e, int slot, int t, bool own) {
+    const batch_state &b = e->bt;
+    const seq_state &S = b.slot[slot];
+    slot_row r;
+    r.qkv = b.pf.QKV + (size_t)t * e->qkv_rows;
+    r.out = b.pf.ATT + (size_t)t * e->qw;
+    r.kc = S.kc; r.vc = S.vc;
+    r.rope = own ? b.mrope + (size_t)t * (e->cfg.head_dim + 4) : S.rope;
+    r.pos = own ? (int *)(r.rope + e->cfg.head_dim) : S.pos;  // a RoPE row ends with its position word
+    r.hist = S.hist; r.nfix = S.nfix; r.last = S.token; r.lp = S.lp;
+    r.smp = slot_params(e, slot);
+    return r;
+}
+
 // the row -> slot table of the active set (ascending slot order) and the rows' first tokens
 static int batch_write_rows(gemma_engine *e) {
     batch_state &b = e->bt;
@@ -270,30 +298,71 @@ static int batch_write_rows(gemma_engine *e) {
     int R = 0;
     for (int i = 0; i < b.n_slots; ++i) {
         if (!b.slot[i].active) continue;
-        slot_row r;
-        r.qkv = b.pf.QKV + (size_t)R * e->qkv_rows;
-        r.out = b.pf.ATT + (size_t)R * e->qw;
-        const seq_state &S = b.slot[i];
-        r.kc = S.kc; r.vc = S.vc; r.rope = S.rope;
-        r.hist = S.hist; r.pos = S.pos; r.nfix = S.nfix; r.last = S.token; r.lp = S.lp;
-        r.smp = slot_params(e, i);
-        h[R] = r;
-        b.row_slot[R] = i;
-        GHIP_CHECK(hipMemcpyAsync(b.row_tok + R, S.token, 4, hipMemcpyDeviceToDevice, s));  // = hist[pos]
+        h[R] = batch_row(e, i, R, false);
+        GHIP_CHECK(hipMemcpyAsync(b.row_tok + R, b.slot[i].token, 4, hipMemcpyDeviceToDevice, s));  // = hist[pos]
         ++R;
     }
     if (R) GHIP_CHECK(hipMemcpyAsync(b.rows, h, (size_t)R * sizeof(slot_row), hipMemcpyHostToDevice, s));
-    b.n_rows = R;
     b.dirty = false;
     return 0;
 }
 
-int enqueue_batch_attention(gemma_engine *e, int il, int r0, int T) {
+// The tables of a pass with several rows per slot (mrows, msrc), from the rows each slot has in it:
+// m_of[i] for an active slot, 0 when it sits the pass out (an inactive slot's entry is not read).  Rows
+// by ascending slot then position; a slot's rank counts every active slot before it, sitting out or
+// not: its row of the batch_step table.  row0_of[i] / rank_of[i]: slot i's first row and rank, for the
+// caller's per-slot table.  Returns the pass's rows T, -1 on error.
+static int batch_build_rows(gemma_engine *e, const int32_t *m_of, int *row0_of, int *rank_of) {
+    batch_state &b = e->bt;
+    slot_row *hr = (slot_row *)b.mstage;
+    row_src *hs = (row_src *)(hr + NS);
+    int T = 0, rank = 0;
+    for (int i = 0; i < b.n_slots; ++i) {
+        if (!b.slot[i].active) continue;
+        row0_of[i] = T;
+        rank_of[i] = rank;
+        for (int k = 0; k < m_of[i]; ++k, ++T) {
+            hr[T] = batch_row(e, i, T, true);
+            hs[T] = row_src{b.slot[i].pos, k, rank};
+        }
+        ++rank;
+    }
+    GHIP_CHECK(hipMemcpyAsync(b.mrows, hr, (size_t)T * sizeof(slot_row), hipMemcpyHostToDevice, e->stream));
+    GHIP_CHECK(hipMemcpyAsync(b.msrc, hs, (size_t)T * sizeof(row_src), hipMemcpyHostToDevice, e->stream));
+    return T;
+}
+
+// ---- a pass --------------------------------------------------------------------------------------------
+// The attention step of rows [r0, r0 + T) of bp.  One row per slot: k_attn_slots.  Rows that share
+// slots: the K / V stores, a kernel boundary, the attention from the cache
+int enqueue_batch_attention(gemma_engine *e, const batch_pass &bp, int il, int r0, int T) {
     attn_args t = attn_of(e, il);
     t.dsplit = e->att_dsplit;
-    if (e->bt.multi)  // rows that share slots: the K / V stores, a kernel boundary, the attention
-        return launch_attn_slot_rows(t, e->bt.mrows + r0, e->bt.msrc + r0, T, (int64_t)il * e->cfg.n_ctx * e->kvw, e->stream);
-    return launch_attn_slots(t, e->bt.rows + r0, T, (int64_t)il * e->cfg.n_ctx * e->kvw, e->stream);
+    const int64_t layer_off = (int64_t)il * e->cfg.n_ctx * e->kvw;
+    if (bp.src) return launch_attn_slot_rows(t, bp.rows + r0, bp.src + r0, T, layer_off, e->stream);
+    return launch_attn_slots(t, bp.rows + r0, T, layer_off, e->stream);
+}
+
+// One pass over bp's rows and what every kind of pass does next: a pick from every row (row t reads
+// its position word and its sampler parameters through bp.rows; mix: picks_mix of the participating
+// slots) and, when asked, the logits rows to the host.  The advance and enqueue_lp_finish are the
+// caller's.  The form of the pass is decided here and nowhere else: up to 8 rows the skinny pass; more
+// rows one pass on the MFMA GEMMs from bt_mfma_min rows, else consecutive groups of up to 8 rows, each
+// a skinny pass over its own rows of the scratch (the tokens, the row table and the pick keys are
+// indexed by the pass's row).  A slot's rows may straddle groups: a group runs all its layers before
+// the next starts, so later rows find the earlier rows' K / V in the cache
+static int batch_run_pass(gemma_engine *e, const batch_pass &bp, int mix, float *logits, row_picks *pk) {
+    batch_state &b = e->bt;
+    const int T = bp.T;
+    if (T > NARROW && T >= e->bt_mfma_min) {
+        if (enqueue_batch_pass(e, bp, 0, T, false)) return -1;
+    } else {
+        for (int r0 = 0; r0 < T; r0 += NARROW)
+            if (enqueue_batch_pass(e, bp, r0, std::min(NARROW, T - r0), true)) return -1;
+    }
+    if (enqueue_row_picks(e, b.pf.LG, T, nullptr, bp.rows, b.picks, pk, mix)) return -1;
+    if (logits) GHIP_CHECK(hipMemcpyAsync(logits, b.pf.LG, (size_t)T * e->cfg.n_vocab * 4, hipMemcpyDeviceToHost, e->stream));
+    return 0;
 }
 
 extern "C" int gemma_engine_batch_step(gemma_engine *e, int n, float *logits) {
@@ -323,23 +392,11 @@ extern "C" int gemma_engine_batch_step(gemma_engine *e, int n, float *logits) {
     (void)hipSetDevice(e->device);
     hipStream_t s = e->stream;
     if (b.dirty && batch_write_rows(e)) return -1;
-    // the form of the call's passes: up to 8 rows the skinny pass; more rows one pass on the MFMA
-    // GEMMs from bt_mfma_min rows, else consecutive groups of up to 8 rows, each a skinny pass over its
-    // own rows of the scratch.  The tokens, the row table and the pick keys are indexed by the global row
-    const bool mfma = R > NARROW && R >= e->bt_mfma_min;
+    // one row per active slot: row r gives the token of its slot's sequence index pos + 1
+    const batch_pass bp{b.rows, nullptr, b.row_tok, R};
     for (int i = 0; i < n; ++i) {
-        if (R <= NARROW || mfma) {
-            if (enqueue_batch_pass(e, 0, R, !mfma)) return -1;
-        } else {
-            for (int r0 = 0; r0 < R; r0 += NARROW)
-                if (enqueue_batch_pass(e, r0, std::min(NARROW, R - r0), true)) return -1;
-        }
-        // a pick from every row: row r gives the token of its slot's sequence index pos + 1 (the
-        // sampler reads the slot's position word and its parameters through the row table)
         row_picks pk;
-        if (enqueue_row_picks(e, b.pf.LG, R, nullptr, b.rows, b.picks, &pk, picks_mix(n_sample, R))) return -1;
-        if (logits)
-            GHIP_CHECK(hipMemcpyAsync(logits + (size_t)i * R * c.n_vocab, b.pf.LG, (size_t)R * c.n_vocab * 4, hipMemcpyDeviceToHost, s));
+        if (batch_run_pass(e, bp, picks_mix(n_sample, R), logits ? logits + (size_t)i * R * c.n_vocab : nullptr, &pk)) return -1;
         if (launch_batch_advance(b.rows, R, pk.keys, pk.n_parts, pk.stride, b.row_tok, c.n_ctx, rope_of(e), s)) return -1;
         if (enqueue_lp_finish(e, b.pf.LG, R, b.picks.lp_parts, nullptr, b.rows, nullptr)) return -1;
     }
@@ -427,51 +484,18 @@ extern "C" int gemma_engine_batch_step_rows(gemma_engine *e, int max_rows, float
     (void)hipSetDevice(e->device);
     hipStream_t s = e->stream;
     if (b.dirty && batch_write_rows(e)) return -1;
-    // the pass's tables, rows by ascending slot then position.  Row t's RoPE row (k_rows_prepare fills
-    // it) ends with the row's position word: `pos` of its table entry
-    slot_row *hr = (slot_row *)b.mstage;
-    row_src *hs = (row_src *)(hr + NS);
-    slot_span *hp = (slot_span *)(hs + NS);
-    const size_t rope_words = (size_t)c.head_dim + 4;
-    for (int i = 0, t = 0, rank = 0; i < b.n_slots; ++i) {
-        const seq_state &S = b.slot[i];
-        if (!S.active) continue;
-        hp[rank] = slot_span{t, m_of[i]};
-        for (int k = 0; k < m_of[i]; ++k, ++t) {
-            slot_row r;
-            r.qkv = b.pf.QKV + (size_t)t * e->qkv_rows;
-            r.out = b.pf.ATT + (size_t)t * e->qw;
-            r.kc = S.kc; r.vc = S.vc;
-            r.rope = b.mrope + (size_t)t * rope_words;
-            r.pos = (int *)(r.rope + c.head_dim);
-            r.hist = S.hist; r.nfix = S.nfix; r.last = S.token; r.lp = S.lp;
-            r.smp = slot_params(e, i);
-            hr[t] = r;
-            hs[t] = row_src{S.pos, k, rank};
-        }
-        ++rank;
-    }
-    GHIP_CHECK(hipMemcpyAsync(b.mrows, hr, (size_t)T * sizeof(slot_row), hipMemcpyHostToDevice, s));
-    GHIP_CHECK(hipMemcpyAsync(b.msrc, hs, (size_t)T * sizeof(row_src), hipMemcpyHostToDevice, s));
+    // the pass's tables, and every active slot's span of rows by its rank
+    int row0_of[NS], rank_of[NS];
+    if (batch_build_rows(e, m_of, row0_of, rank_of) < 0) return -1;  // (= T, the plan's count)
+    slot_span *hp = (slot_span *)((row_src *)((slot_row *)b.mstage + NS) + NS);  // behind the builder's two tables
+    for (int i = 0; i < b.n_slots; ++i)
+        if (b.slot[i].active) hp[rank_of[i]] = slot_span{row0_of[i], m_of[i]};
     GHIP_CHECK(hipMemcpyAsync(b.mspans, hp, (size_t)R * sizeof(slot_span), hipMemcpyHostToDevice, s));
     if (launch_rows_prepare(b.mrows, b.msrc, T, b.row_tok, rope_of(e), s)) return -1;
-    // the form by T exactly as batch_step's by R; a slot's rows may straddle groups: a group runs all
-    // its layers before the next starts, so later rows find the earlier rows' K / V in the cache
-    const bool mfma = T > NARROW && T >= e->bt_mfma_min;
-    b.multi = true;
-    int bad = 0;
-    if (T <= NARROW || mfma) {
-        bad = enqueue_batch_pass(e, 0, T, !mfma);
-    } else {
-        for (int r0 = 0; r0 < T && !bad; r0 += NARROW) bad = enqueue_batch_pass(e, r0, std::min(NARROW, T - r0), true);
-    }
-    b.multi = false;
-    if (bad) return -1;
-    // a pick from every row (one launch whatever T; only each slot's last row's is used), the
-    // sampler's position word the row's own, its parameters its slot's
+    // a pick from every row (one launch whatever T; only each slot's last row's is used)
+    const batch_pass bp{b.mrows, b.msrc, b.row_tok, T};
     row_picks pk;
-    if (enqueue_row_picks(e, b.pf.LG, T, nullptr, b.mrows, b.picks, &pk, picks_mix(n_sample, R))) return -1;
-    if (logits) GHIP_CHECK(hipMemcpyAsync(logits, b.pf.LG, (size_t)T * c.n_vocab * 4, hipMemcpyDeviceToHost, s));
+    if (batch_run_pass(e, bp, picks_mix(n_sample, R), logits, &pk)) return -1;
     if (launch_rows_advance(b.rows, b.mrows, b.mspans, R, pk.keys, pk.n_parts, pk.stride, b.row_tok, c.n_ctx, rope_of(e), s))
         return -1;
     if (enqueue_lp_finish(e, b.pf.LG, T, b.picks.lp_parts, nullptr, b.mrows, nullptr)) return -1;
@@ -540,72 +564,39 @@ extern "C" int gemma_engine_batch_verify(gemma_engine *e, const int32_t *draft, 
     (void)hipSetDevice(e->device);
     hipStream_t s = e->stream;
     if (b.dirty && batch_write_rows(e)) return -1;
-    // the pass's tables: rows by ascending slot then position (as step_rows'), the per-slot table by
-    // the slot's index among the participating slots, with its rank in the batch_step table
-    slot_row *hr = (slot_row *)b.mstage;
-    row_src *hs = (row_src *)(hr + NS);
+    // the pass's tables, and the per-slot table by the slot's index among the participating slots,
+    // with its rank in the batch_step table
+    int32_t m_of[NS];
+    int row0_of[NS], rank_of[NS], part[NS];
+    for (int i = 0; i < b.n_slots; ++i) m_of[i] = b.slot[i].active && k_of[i] >= 0 ? 1 + k_of[i] : 0;
+    if (batch_build_rows(e, m_of, row0_of, rank_of) < 0) return -1;  // (= T)
     bv_slot *hv = (bv_slot *)b.vstage;
     int *h_out = (int *)(hv + NS);
-    int part[NS];
-    const size_t rope_words = (size_t)c.head_dim + 4;
-    for (int i = 0, t = 0, rank = 0, p = 0; i < b.n_slots; ++i) {
-        const seq_state &S = b.slot[i];
-        if (!S.active) continue;
-        if (k_of[i] >= 0) {
-            const int m = 1 + k_of[i];
-            bv_slot v;
-            v.row0 = t; v.m = m; v.rank = rank;
-            for (int j = 0; j < m - 1; ++j) v.draft[j] = draft[(size_t)i * KD + j];
-            hv[p] = v;
-            part[p++] = i;
-            for (int j = 0; j < m; ++j, ++t) {
-                slot_row r;
-                r.qkv = b.pf.QKV + (size_t)t * e->qkv_rows;
-                r.out = b.pf.ATT + (size_t)t * e->qw;
-                r.kc = S.kc; r.vc = S.vc;
-                r.rope = b.mrope + (size_t)t * rope_words;
-                r.pos = (int *)(r.rope + c.head_dim);
-                r.hist = S.hist; r.nfix = S.nfix; r.last = S.token; r.lp = S.lp;
-                r.smp = slot_params(e, i);
-                hr[t] = r;
-                hs[t] = row_src{S.pos, j, rank};
-            }
-        }
-        ++rank;
+    for (int i = 0, p = 0; i < b.n_slots; ++i) {
+        if (!m_of[i]) continue;
+        bv_slot v;
+        v.row0 = row0_of[i]; v.m = m_of[i]; v.rank = rank_of[i];
+        for (int j = 0; j < v.m - 1; ++j) v.draft[j] = draft[(size_t)i * KD + j];
+        hv[p] = v;
+        part[p++] = i;
     }
-    GHIP_CHECK(hipMemcpyAsync(b.mrows, hr, (size_t)T * sizeof(slot_row), hipMemcpyHostToDevice, s));
-    GHIP_CHECK(hipMemcpyAsync(b.msrc, hs, (size_t)T * sizeof(row_src), hipMemcpyHostToDevice, s));
     GHIP_CHECK(hipMemcpyAsync(b.vslots, hv, (size_t)P * sizeof(bv_slot), hipMemcpyHostToDevice, s));
     // 1. stage: the drafts become hist_s[pos_s + 1 ..], the tokens of the slot's rows 1 .. k_s
     if (T > P && launch_bverify_stage(b.rows, b.vslots, P, c.n_ctx, s)) return -1;
     if (launch_rows_prepare(b.mrows, b.msrc, T, b.vtok, rope_of(e), s)) return -1;
-    // 2. the pass, its form by T exactly as step_rows'
-    const bool mfma = T > NARROW && T >= e->bt_mfma_min;
-    b.multi = true;
-    b.pass_tok = b.vtok;
-    int bad = 0;
-    if (T <= NARROW || mfma) {
-        bad = enqueue_batch_pass(e, 0, T, !mfma);
-    } else {
-        for (int r0 = 0; r0 < T && !bad; r0 += NARROW) bad = enqueue_batch_pass(e, r0, std::min(NARROW, T - r0), true);
-    }
-    b.multi = false;
-    b.pass_tok = nullptr;
-    if (bad) return -1;
-    // 3. a pick from every row (the sampler's position word the row's own, its parameters its slot's),
-    // none advances
+    // 2. the pass over its own tokens, and a pick from every row: none advances
+    const batch_pass bp{b.mrows, b.msrc, b.vtok, T};
     row_picks pk;
-    if (enqueue_row_picks(e, b.pf.LG, T, nullptr, b.mrows, b.picks, &pk, picks_mix(n_sample, P))) return -1;
-    if (logits) GHIP_CHECK(hipMemcpyAsync(logits, b.pf.LG, (size_t)T * c.n_vocab * 4, hipMemcpyDeviceToHost, s));
-    // 4. accept + advance per slot; (log-probabilities on) rows 0 .. a_s score what the accept settled
+    if (batch_run_pass(e, bp, picks_mix(n_sample, P), logits, &pk)) return -1;
+    // 3. accept + advance per slot; (log-probabilities on) rows 0 .. a_s score what the accept settled
     if (launch_bverify_accept(b.rows, b.mrows, b.vslots, P, pk.keys, pk.n_parts, pk.stride, b.row_tok, c.n_ctx, rope_of(e),
                               b.vout, s))
         return -1;
     if (enqueue_lp_finish(e, b.pf.LG, T, b.picks.lp_parts, nullptr, b.mrows, nullptr)) return -1;
-    // 5. the rejected rows leave the caches
+    // 4. the rejected rows leave the caches
     if (T > P && launch_bverify_clean(b.rows, b.vslots, P, b.vout, c.n_layer, (int64_t)c.n_ctx * e->kvw, c.n_ctx, e->kvw, s))
         return -1;
-    // 6. results: one synchronise
+    // 5. results: one synchronise
     GHIP_CHECK(hipMemcpyAsync(h_out, b.vout, (size_t)P * BV_OUT_WORDS * 4, hipMemcpyDeviceToHost, s));
     GHIP_CHECK(hipStreamSynchronize(s));
     for (int i = 0; i < b.n_slots; ++i) n_out[i] = 0;

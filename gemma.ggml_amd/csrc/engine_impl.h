@@ -107,6 +107,16 @@ struct pick_buf {
 // µs per pass, groups / MFMA): R = 24 5,888 / 7,256, 28 7,293 / 7,398, 29 7,529 / 7,401,
 // 32 7,848 / 7,440, 48 11,887 / 7,866, 64 16,005 / 8,282.
 static constexpr int BT_MFMA_MIN_DEFAULT = 29;
+// What one pass over the batch's scratch is: T rows, row t with entry rows[t] and token tok[t].  It
+// travels as an argument from the entry that built it to the pass's attention step; the engine keeps
+// no note of the pass being enqueued.
+struct batch_pass {
+    const slot_row *rows;  // device: the pass's row table (bt.rows, or bt.mrows)
+    const row_src *src;    // device: null for one row per slot (k_attn_slots); else rows that share slots, which run
+                           // k_rows_rope_kv and k_attn_slot_rows
+    const int *tok;        // device: the rows' tokens (bt.row_tok, or bt.vtok)
+    int T;
+};
 struct batch_state {
     bool open = false;
     int n_slots = 0;
@@ -118,22 +128,20 @@ struct batch_state {
     void *stage = nullptr;     // pinned: the row table's source, batch_last's result
     pf_scratch pf;             // the pass's scratch (pf.T rows: max(8, n_slots), or open_rows' max_rows), never reallocated while the batch is open
     bool dirty = true;         // the active set changed since the table was written
-    int n_rows = 0, row_slot[GEMMA_BATCH_WIDE_MAX_SLOTS] = {};
-    // several rows per slot (gemma_engine_batch_step_rows): the pass's own row table, rewritten by
-    // every such pass from the plan, and each row's [cos | sin | (int)p]
+    // several rows per slot (gemma_engine_batch_step_rows, gemma_engine_batch_verify): the pass's own
+    // row table and row sources, rewritten by every such pass (batch_build_rows), and each row's
+    // [cos | sin | (int)p]
     slot_row *mrows = nullptr;   // device: [64], row t's `rope` / `pos` its own RoPE row / position word
     row_src *msrc = nullptr;     // device: [64]
-    slot_span *mspans = nullptr; // device: [64] by the slot's rank among the active slots
+    slot_span *mspans = nullptr; // device: [64] by the slot's rank among the active slots (step_rows)
     float *mrope = nullptr;      // device: [64][head_dim + 4]
     void *mstage = nullptr;      // pinned: the three tables' source
-    bool multi = false;          // the pass being enqueued is such a pass (enqueue_batch_attention)
     // drafts in the batch (gemma_engine_batch_verify): such a pass over the participating slots only.
     // Its rows' tokens are its own, so row_tok keeps the entries of the slots that sit out
     bv_slot *vslots = nullptr;   // device: [64] by the slot's index among the participating slots
     int *vout = nullptr;         // device: [64][BV_OUT_WORDS] each slot's accepted count and picks
     int *vtok = nullptr;         // device: [64] the tokens of the pass's rows
     void *vstage = nullptr;      // pinned: vslots' source, vout's copy
-    const int *pass_tok = nullptr;  // the tokens of the pass being enqueued when they are not row_tok's (enqueue_batch_pass)
     // a sampler per slot (gemma_engine_batch_set_sampler): the setting belongs to the slot, active or not
     // (the device copy travels in the slot's rows of the row tables, slot_row::smp)
     bool smp_own[GEMMA_BATCH_WIDE_MAX_SLOTS] = {};      // the slot has a setting of its own ...
@@ -453,12 +461,12 @@ int enqueue_logits_q6k(gemma_engine *e, const uint8_t *x, int ncols, float *y);
 // engine_prefill.cpp: the exact batched pass over hist[p0 .. p0+T), T <= 8, with the Q4_0 / Q8_0
 // GEMMs on launch_gemm_skinny and no pick: the logits rows are left in pf.LG [T][n_vocab]
 int enqueue_verify_pass(gemma_engine *e, int T, int p0);
-// the batch's scratch (bt.pf, `rows` >= 8 rows, from bt_mem), and one batched-decode pass over the
-// batch's rows [r0, r0 + T) (tokens bt.row_tok, attention by enqueue_batch_attention), their logits
-// left in bt.pf.LG.  skinny: T <= 8 on the skinny GEMM (the verify pass's form); else the exact MFMA GEMMs
+// the batch's scratch (bt.pf, `rows` >= 8 rows, from bt_mem), and one batched-decode pass over rows
+// [r0, r0 + T) of bp (tokens bp.tok, attention by enqueue_batch_attention), their logits left in
+// bt.pf.LG.  skinny: T <= 8 on the skinny GEMM (the verify pass's form); else the exact MFMA GEMMs
 int batch_scratch_alloc(gemma_engine *e, int rows);
-int enqueue_batch_pass(gemma_engine *e, int r0, int T, bool skinny);
-// engine_batch.cpp: layer il's attention step for rows [r0, r0 + T) of a batch pass (k_attn_slots
-// over the row table)
-int enqueue_batch_attention(gemma_engine *e, int il, int r0, int T);
+int enqueue_batch_pass(gemma_engine *e, const batch_pass &bp, int r0, int T, bool skinny);
+// engine_batch.cpp: layer il's attention step for rows [r0, r0 + T) of bp: the one place that chooses
+// a batch pass's attention (k_attn_slots, or k_rows_rope_kv + k_attn_slot_rows when bp.src is set)
+int enqueue_batch_attention(gemma_engine *e, const batch_pass &bp, int il, int r0, int T);
 #pragma GCC visibility pop

@@ -40,24 +40,24 @@ static int prefill_alloc(gemma_engine *e, int T) {
 
 // What the T rows of a pass are.  Every scratch buffer is indexed by the row t; the rows description
 // says where the T token ids come from and what runs at a layer's attention step:
-//   slots == false  rows are positions p0 .. p0+T-1 of the engine's own sequence: RoPE + K / V store
+//   batch == null   rows are positions p0 .. p0+T-1 of the engine's own sequence: RoPE + K / V store
 //                   into the engine's caches, then the causal attention (prefill_attention)
-//   slots == true   rows are the batch's (engine_batch.cpp): row t is the next token of its own slot,
-//                   (or, in a step_rows pass, one of several consecutive tokens of its slot), the
-//                   attention is enqueue_batch_attention and the scratch is the batch's (bt.pf)
-//                   r0 > 0: the pass is rows [r0, r0 + T) of the batch (a group of a wide batch): its
+//   batch           rows are a batch pass's (engine_batch.cpp): row t is the next token of its own
+//                   slot (or one of several consecutive tokens of its slot: batch->src), the attention
+//                   is enqueue_batch_attention and the scratch is the batch's (bt.pf)
+//                   r0 > 0: the pass is rows [r0, r0 + T) of the batch's (a group of a wide pass): its
 //                   tokens, its part of the row table and a view of the scratch shifted by r0 rows
 struct pass_rows {
     const int *tokens = nullptr;  // device array of the T token ids
     int p0 = 0;
-    bool slots = false;
+    const batch_pass *batch = nullptr;
     int r0 = 0;
 };
-static pass_rows own_rows(const gemma_engine *e, int p0) { return pass_rows{e->seq.hist + p0, p0, false, 0}; }
+static pass_rows own_rows(const gemma_engine *e, int p0) { return pass_rows{e->seq.hist + p0, p0, nullptr, 0}; }
 // the scratch of a pass, by value: the engine's or the batch's, every row-indexed buffer shifted by
 // the pass's first row (each by its own row stride: scratch_alloc)
 static pf_scratch scratch_of(gemma_engine *e, const pass_rows &rows) {
-    pf_scratch p = rows.slots ? e->bt.pf : e->pf;
+    pf_scratch p = rows.batch ? e->bt.pf : e->pf;
     if (!rows.r0) return p;
     const gemma_hip_config &c = e->cfg;
     const size_t r = (size_t)rows.r0;
@@ -100,7 +100,7 @@ static int launch_attn_exact(const attnp_args &at, bool mx, hipStream_t s) {
 // layer caches (which hold the positions before p0), then the causal attention into pf.ATT (exact:
 // the form *mx_form, resolved at the first layer; else f16 MFMA)
 static int prefill_attention(gemma_engine *e, int il, int T, const pass_rows &rows, bool exact, int *mx_form) {
-    if (rows.slots) return enqueue_batch_attention(e, il, rows.r0, T);
+    if (rows.batch) return enqueue_batch_attention(e, *rows.batch, il, rows.r0, T);
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
     auto &p = e->pf;
@@ -292,17 +292,16 @@ int batch_scratch_alloc(gemma_engine *e, int rows) {
     return scratch_alloc(e, e->bt_mem, e->bt.pf, std::max(rows, GEMM_SKINNY_MAX_T), rows > GEMM_SKINNY_MAX_T);
 }
 
-// a pass over the batch's rows [r0, r0 + T): tokens from the row-token array, the attention step by
-// k_attn_slots, the logits rows left in the scratch; the caller picks from every row and advances
-// the slots.  skinny: the verify pass's GEMMs (T <= 8); else the exact MFMA GEMMs, any T
-int enqueue_batch_pass(gemma_engine *e, int r0, int T, bool skinny) {
+// a pass over rows [r0, r0 + T) of the batch pass bp: tokens bp.tok, the attention step by
+// enqueue_batch_attention, the logits rows left in the scratch; the caller picks from every row and
+// advances the slots.  skinny: the verify pass's GEMMs (T <= 8); else the exact MFMA GEMMs, any T
+int enqueue_batch_pass(gemma_engine *e, const batch_pass &bp, int r0, int T, bool skinny) {
     if (T < 1 || r0 < 0 || r0 + T > e->bt.pf.T || (skinny && T > GEMM_SKINNY_MAX_T)) {
         set_error("gemma_engine_batch_step: a pass of " + std::to_string(T) + " rows from row " + std::to_string(r0) +
                   ", or no batch scratch");
         return -1;
     }
-    const int *tok = e->bt.pass_tok ? e->bt.pass_tok : e->bt.row_tok;
-    return enqueue_prefill(e, T, pass_rows{tok + r0, 0, true, r0}, true, nullptr, pass_end{true, skinny});
+    return enqueue_prefill(e, T, pass_rows{bp.tok + r0, 0, &bp, r0}, true, nullptr, pass_end{true, skinny});
 }
 
 // one pass over rows [p0, p0+T) and its results: the last row's logits, all rows' [T][n_vocab], the

@@ -6,6 +6,7 @@
 //    wins (src/gemma_model.cpp:538-543).  Key 0 is below every candidate.
 //  * block_max_key: the maximum key of a 256-thread workgroup, in thread 0.
 //  * publish_rope_row: the [cos | sin | (int)pos] row a sequence keeps current for its attention.
+//  * commit_pick: a batch slot's pick into its history, under the given-token rule.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -68,6 +69,18 @@ __device__ __forceinline__ void publish_rope_row(float *cur, const float *cos, c
         cur[half + i] = sin[(int64_t)p * half + i];
     }
     if (threadIdx.x == 0) ((int *)cur)[2 * half] = p;
+}
+
+// A batch slot's pick committed at sequence index q of its history (hist_cap tokens, the first `fixed`
+// of them given): a given token is never overwritten, below `fixed` the pick is replaced by hist[q].
+// Returns the token that stands at q.  (The single sequence's k_advance and k_verify_accept keep their
+// argmax in *token instead: another rule.)
+__device__ __forceinline__ int commit_pick(int *hist, int q, int fixed, int hist_cap, int pick) {
+    if (q < hist_cap) {
+        if (q >= fixed) hist[q] = pick;
+        else pick = hist[q];
+    }
+    return pick;
 }
 
 }  // namespace ghip
