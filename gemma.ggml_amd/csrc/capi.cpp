@@ -245,7 +245,7 @@ extern "C" int hpc_register_weight(const void *host, int type, int64_t ne00, int
 }
 
 extern "C" void hpc_set_kq_gemm_min(int min_cols) { set_kq_gemm_min(min_cols); }
-extern "C" void hpc_set_gemm_x4(int on) { set_gemm_x4(on); }
+extern "C" void hpc_set_gemm_x4(int mode) { set_gemm_x4(mode); }
 
 extern "C" void mul_mat(int64_t ne01, int64_t ne11, int64_t ne12, int64_t nb01, int64_t ne1, int64_t nb1, int64_t nb2,
                         size_t row_size, int64_t shared_edge, struct ggml_tensor *src0, struct ggml_tensor *src1,
@@ -385,13 +385,14 @@ static int test_gemm(bool exact, int type, int64_t rows, int64_t K, int64_t T, c
     tiled_mat m;
     if (alloc_tiled(tmp, &m, type, rows, K, nullptr)) return -1;
     int r = launch_repack(m, d_rows, row_bytes, nullptr);
-    qrow_args qa;
+    const gemm_form form = gemm_form_now();
+    qrow_args qa;  // both images, so whichever the form stages from is there (and xq_out returns the int8 one)
     qa.x = d_x; qa.ldx = K; qa.K = K; qa.q = d_q; qa.qh = exact ? d_h : nullptr; qa.ldq = ldq; qa.da = d_da; qa.ldd = ldd;
     if (r == 0) r = launch_quant_rows(QR_F32, qa, (int)T, nullptr);
     gemm_args g;
     set_mat(g, m);
     g.xq = d_q; g.xh = d_h; g.ldq = ldq; g.da = d_da; g.ldd = ldd; g.T = T; g.y = d_y; g.ldy = rows;
-    if (r == 0) r = exact ? launch_gemm_exact(type, EPI_STORE, g, nullptr) : launch_gemm_q(type, EPI_STORE, g, nullptr);
+    if (r == 0) r = exact ? launch_gemm_exact(type, EPI_STORE, form, g, nullptr) : launch_gemm_q(type, EPI_STORE, g, nullptr);
     if (r == 0) GHIP_CHECK(hipDeviceSynchronize());
     if (r == 0) {
         GHIP_CHECK(hipMemcpy(Y, d_y, (size_t)(T * rows * 4), hipMemcpyDeviceToHost));

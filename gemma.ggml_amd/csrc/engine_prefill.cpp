@@ -138,17 +138,18 @@ static int enqueue_prefill(gemma_engine *e, int T, const pass_rows &rows, bool e
     pf_scratch p = scratch_of(e, rows);
     const int wt = c.wtype;
     const int64_t E = c.n_embd, F = c.n_ff;
+    const gemm_form form = gemm_form_now();  // one form for the whole pass: every image is written for the GEMM that reads it
     auto gemm = [&](const tiled_mat &m, int epi, const float *resid, float *y, int64_t ldy) {
         gemm_args g;
         set_mat(g, m);
         g.xq = p.XQ; g.xh = p.XH; g.ldq = p.ldq; g.da = p.DA; g.ldd = p.ldd; g.T = T; g.y = y; g.resid = resid; g.ldy = ldy;
         if (end.skinny) return launch_gemm_skinny(wt, epi, g, s);
-        return exact ? launch_gemm_exact(wt, epi, g, s) : launch_gemm_q(wt, epi, g, s);
+        return exact ? launch_gemm_exact(wt, epi, form, g, s) : launch_gemm_q(wt, epi, g, s);
     };
     auto quant = [&](int mode, const float *x, const float *x2, int64_t K, const float *norm_w) {
         qrow_args a;
         a.x = x; a.x2 = x2; a.ldx = K; a.K = K; a.norm_w = norm_w; a.eps = c.eps;
-        const bool i8img = exact && (end.skinny || gemm_x4_i8());  // the int8-staged exact GEMM and the skinny GEMM read the int8 image
+        const bool i8img = exact && (end.skinny || form.i8);  // the int8-staged exact GEMM and the skinny GEMM read the int8 image
         a.q = (!exact || i8img) ? p.XQ : nullptr; a.qh = (exact && !i8img) ? p.XH : nullptr; a.ldq = p.ldq; a.da = p.DA; a.ldd = p.ldd;
         a.gelu_tab = e->gelu_tab; a.gelu_clamp = c.gelu_clamp;
         if (mode == QR_EMBED_NORM) {

@@ -447,8 +447,9 @@ int run_mul_mat(run_state &rs, ggml_tensor *node) {
     const int64_t ldq = (K + 255) / 256 * 256, ldd = ldq / 32;
     qrow_args q;
     q.x = (const float *)x; q.ldx = K; q.K = K;
-    // the image the exact GEMM's form stages from: int8 (gemm_x4_i8) or f16
-    const bool i8img = gemm_x4_i8();
+    // the image the exact GEMM's form stages from: int8 or f16
+    const gemm_form form = gemm_form_now();
+    const bool i8img = form.i8;
     q.q = i8img ? (int8_t *)scratch_take(rs, (size_t)(cols * ldq)) : nullptr;
     q.qh = i8img ? nullptr : (uint16_t *)scratch_take(rs, (size_t)(cols * ldq * 2));
     q.ldq = ldq;
@@ -458,7 +459,7 @@ int run_mul_mat(run_state &rs, ggml_tensor *node) {
     gemm_args g;
     set_mat(g, *W);
     g.xq = q.q; g.xh = q.qh; g.ldq = ldq; g.da = q.da; g.ldd = ldd; g.T = cols; g.y = y; g.ldy = a->ne[1];
-    return launch_gemm_exact(a->type, EPI_STORE, g, e.stream);
+    return launch_gemm_exact(a->type, EPI_STORE, form, g, e.stream);
 }
 
 int run_node(run_state &rs, ggml_tensor *n) {

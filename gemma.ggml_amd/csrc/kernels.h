@@ -233,16 +233,23 @@ struct gemm_args {  // Y[t][r] (stride ldy) = W (tiled) x Xq[t] (+ resid), t < T
     int64_t ldy = 0;
 };
 int launch_gemm_q(int wtype, int epi, const gemm_args &g, hipStream_t s);
+// The exact GEMM's form, one process-wide choice (hpc_set_gemm_x4(mode), modes 0-4, default 3) decoded
+// once.  A pass reads it once (gemm_form_now) and hands the same value to the quantizer step, which
+// writes the image the form stages from, and to every launch_gemm_exact of the pass.
+struct gemm_form {
+    bool x4 = true;  // k_gemm_x4 (the K = 4 multi-block MFMA); false: k_gemm_x (lane-masked W32)
+    int rgs = 2;     // k_gemm_x4: 16-row groups per workgroup, 2 (32 rows x 64 tokens) or 4 (64 x 32)
+    bool i8 = true;  // the activation is staged from the int8 image (xq); false: from the f16 image (xh)
+};
+gemm_form gemm_form_now();
+void set_gemm_x4(int mode);  // outside 0-4: the form stays as it was, set_error says so
 // the same product in ggml's AVX2 lane order (bit-identical to mul_mat)
-int launch_gemm_exact(int wtype, int epi, const gemm_args &g, hipStream_t s);
+int launch_gemm_exact(int wtype, int epi, const gemm_form &form, const gemm_args &g, hipStream_t s);
 // the same product for 1 <= T <= 8 rows (gemm_skinny.hip): every weight tile loaded once and applied
 // to all T columns, one thread per (row, AVX2 lane) as the decode matvec; reads the int8 image
 // (xq, da); EPI_STORE / EPI_ADD.  T outside [1, 8]: -1 with set_error
 constexpr int GEMM_SKINNY_MAX_T = 8;
 int launch_gemm_skinny(int wtype, int epi, const gemm_args &g, hipStream_t s);
-bool gemm_x4_i8();        // mode 3: k_gemm_x4 stages the activation from the int8 image (xq)
-bool gemm_x4_on();        // the exact GEMM's form: the K = 4 multi-block MFMA kernel (k_gemm_x4) or W32
-void set_gemm_x4(int v);
 
 struct ropekv_args {  // RoPE q (-> f16, x q_scale) and k, store k/v of positions p0.. in the layer caches
     const float *qkv = nullptr;  // [T][ldqkv] = q | k | v

@@ -320,22 +320,18 @@ __global__ void __launch_bounds__(256) k_gemm_q(gemm_args g) {
 // The reference computes each prompt row's MUL_MAT with the same vec_dot as decode:
 // eight fp32 lane chains acc_l = fmaf(d_w*d_a, isum_l, acc_l) in block order, isum_l = the exact
 // int32 dot of elements 4l..4l+3, then hsum ((a0+a4)+(a2+a6))+((a1+a5)+(a3+a7)).
-// The lane sums come from f16 MFMA with the lane structure in the M dimension: MFMA row m = 8*rr
-// + l is weight row rr's lane l, its A row holds only elements 4l..4l+3 of the block (zeros
-// elsewhere), so D[m][token] = isum_l exactly (products and sums of small integers are exact in
-// f32) and arrives as f32 — no conversion.  A lane's D registers are 4 consecutive m = 4 lanes of
-// one (row, token), so one d = d_w*d_a (exact: two fp16 significands) serves 4 fmaf; the chain
-// continues block after block in the same register: the identical operation sequence, so Y is
-// bit-identical to mul_mat.  Fold: lanes 0-3 / 4-7 of a pair sit in lanes j / j^16.
-// Workgroup tile XM = 32 rows x XN tokens: waves of 2*XRT rows x 16*XCT tokens (XRT x XCT MFMA
-// 16x16x32 per block; 4 x 2 measured best: the LDS fragment reads, not the MFMAs or the fmafs,
-// bound this loop).  K is staged XKB = 8 blocks at a time: weights as pre-masked 16-B A fragments per
-// (block, row, lane) (Q4_0 nibbles / Q8_0 int8 -> f16 by the 0x6400 exponent trick), tokens as
-// f16 rows (the quantizer's f16 image); the next stage's global loads are in flight during the
-// current stage's MFMAs.  blockIdx.x walks tokens so the token tiles of one weight tile run
+// The lane sums come from f16 MFMA with the lane structure in the M dimension: an MFMA row is one
+// (weight row, AVX2 lane l), its A row holds only elements 4l..4l+3 of the block (zeros elsewhere),
+// so D[m][token] = isum_l exactly (products and sums of small integers are exact in f32) and
+// arrives as f32 — no conversion.  A lane's D registers hold the lanes of one (row, token), so one
+// d = d_w*d_a (exact: two fp16 significands) serves their fmaf; the chain continues block after
+// block in the same register: the identical operation sequence, so Y is bit-identical to mul_mat.
+// Two kernels, five forms (gemm_form): k_gemm_x (the lane-masked 32x32x16 form, "W32") and
+// k_gemm_x4 (the K = 4 multi-block form, the default).  Both: K is staged XKB = 8 blocks at a time,
+// weights converted to f16 (Q4_0 nibbles / Q8_0 int8 by the 0x6400 exponent trick) on the way to
+// LDS, tokens as f16 rows; blockIdx.x walks tokens so the token tiles of one weight tile run
 // together and the weights leave HBM about once per XCD.
 typedef _Float16 xh8 __attribute__((ext_vector_type(8)));
-typedef float xf4 __attribute__((ext_vector_type(4)));
 typedef float xf16v __attribute__((ext_vector_type(16)));
 
 // four small integers (bytes of v, biased so they are in [0, 1024)) -> 2 dwords of f16 pairs
@@ -349,126 +345,68 @@ __device__ __forceinline__ uint2 bytes_to_f16x4(uint32_t v, uint32_t bias_pair) 
     return make_uint2(__builtin_bit_cast(uint32_t, l2), __builtin_bit_cast(uint32_t, h2v));
 }
 
-#ifndef GHIP_XCT
-#define GHIP_XCT 2
-#endif
-#ifndef GHIP_XPF
-#define GHIP_XPF 0
-#endif
-#ifndef GHIP_XWAVES
-#define GHIP_XWAVES 4
-#endif
-#ifndef GHIP_XRT
-#define GHIP_XRT 8
-#endif
-constexpr int XCT = GHIP_XCT;             // 16-token MFMA column tiles per wave
-constexpr int XRT = GHIP_XRT;             // 2-row MFMA row tiles per wave (W32: XRT/4 8-row groups; 8 measured best)
-constexpr int XW = GHIP_XWAVES;           // waves per workgroup: XWR row groups x XWC token groups
+constexpr int XCT = 2;                    // 16-token MFMA column tiles per wave
+constexpr int XRT = 8;                    // 2-row MFMA row tiles per wave, i.e. XRT/4 8-row groups (8 measured best)
+constexpr int XW = 4;                     // waves per workgroup: XWR row groups x XWC token groups
 constexpr int XNT = 64 * XW;
 constexpr int XM = 32, XWR = XM / (2 * XRT), XWC = XW / XWR, XN = XWC * 16 * XCT, XKB = 8;
 static_assert(XWR * XWC == XW && XWR * 2 * XRT == XM, "wave grid");
+static_assert(XRT % 4 == 0 && XCT == 2, "waves of 8*RG rows x 32 tokens");
 constexpr int XS_ROW = XKB * 32 * 2 + 16;  // bytes per staged token row (f16, padded)
 constexpr int XREC = XN * XKB * 64 / 16 / XNT;  // 16-B token records per thread per stage
-constexpr int XDA = (XN * XKB + XNT - 1) / XNT;  // token scales per thread per stage
 static_assert(XN * XKB * 64 / 16 % XNT == 0, "token records");
 
-#ifndef GHIP_XWPE
-#define GHIP_XWPE 0
-#endif
-#ifndef GHIP_X32
-#define GHIP_X32 1
-#endif
-#ifndef GHIP_XCOMPACT
-#define GHIP_XCOMPACT 0  // 1: W32 A fragments stored as their 8 nonzero bytes, placed in registers (90.2 vs 87.6 ms: off)
-#endif
-#ifndef GHIP_XZS
-#define GHIP_XZS 1  // W32: inactive lanes' zero reads spread over free bank slots (0: one shared slot)
-#endif
-#ifndef GHIP_XWFR
-#define GHIP_XWFR 9  // W32 fragment-row pitch in 16-B slots (9: the active lanes of a b128 group on distinct banks)
-#endif
-#ifndef GHIP_XMASK
-#define GHIP_XMASK 0  // 1: EXEC-masked A reads for the inactive lanes (measured slower: 99.6 vs 88.0 ms)
-#endif
-// W32: the lane sums from v_mfma_f32_32x32x16_f16 instead (the default).  K = 16 covers half a
-// block, and only the four AVX2 lanes 4h..4h+3 have elements in half h, so MFMA row m = 4*row + i
-// (i = lane & 3 of half h) wastes 3/4 of each A row instead of 7/8: a wave's 8 rows x 32 tokens per
-// block take two 32x32x16 MFMAs (h = 0, 1) instead of eight 16x16x32 ones, and four 16-B LDS
-// fragment reads instead of six.  D row m = (reg & 3) + 8*(reg >> 2) + 4*(lane >> 5) puts the
-// four lanes of one (row, token) in consecutive registers and both halves in the same lane, so the
-// hsum needs no lane exchange.  Same operands, same products, same fmaf chains: bit-identical.
-template <int WT, int EPI, bool W32>
-__global__ void __launch_bounds__(XNT)
-#if GHIP_XWPE
-__attribute__((amdgpu_waves_per_eu(GHIP_XWPE, GHIP_XWPE)))
-#endif
-k_gemm_x(gemm_args g) {
-    static_assert(!W32 || (XRT % 4 == 0 && XCT == 2), "W32: waves of 8*RG rows x 32 tokens");
-    constexpr int RG = W32 ? XRT / 4 : 1;  // W32: 8-row groups per wave
-    // A fragments: [b][row][lane] 16 B (lane l's 4 f16 in half l&1 of the fragment)
-    // + a zero region the inactive lanes read at the same strides (no per-lane select)
-    // W32 pads the fragment rows to 9 x 16 B: the 8 active lanes of a ds_read_b128 lane group then
-    // hit distinct banks (rows 2 apart would share them at 8 x 16 B)
-    constexpr int WFR = W32 ? GHIP_XWFR : 8;
-    // compact W32 image: 8 B per (block, row, lane), rows padded to 10 x 8 B (distinct banks for the
-    // 16 active lanes of a ds_read_b64 lane group); the LDS saved fits a third workgroup per CU
-    constexpr bool CW = W32 && GHIP_XCOMPACT;
-    constexpr int WFR2 = 10;
-    __shared__ __attribute__((aligned(16))) uint4 Wf[CW ? 1 : XKB * XM * WFR + 7 * 16 + 1];
-    __shared__ __attribute__((aligned(16))) uint2 Wf2[CW ? XKB * XM * WFR2 + 8 : 1];
+typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+
+// The W32 form (hpc_set_gemm_x4(0)): the lane sums from v_mfma_f32_32x32x16_f16.  K = 16 covers half
+// a block, and only the four AVX2 lanes 4h..4h+3 have elements in half h, so MFMA row m = 4*row + i
+// (i = lane & 3 of half h) wastes 3/4 of each A row: a wave's 8 rows x 32 tokens per block take two
+// 32x32x16 MFMAs (h = 0, 1) and four 16-B LDS fragment reads.  D row m = (reg & 3) + 8*(reg >> 2) +
+// 4*(lane >> 5) puts the four lanes of one (row, token) in consecutive registers and both halves in
+// the same lane, so the hsum needs no lane exchange.  Same operands, same products, same fmaf chains
+// as the 16x16x32 restatement it replaced: bit-identical.
+// Workgroup tile XM = 32 rows x XN = 64 tokens, 4 waves of 16 rows x 32 tokens; weights staged as
+// pre-masked 16-B A fragments per (block, row, lane), tokens from the quantizer's f16 image.
+template <int WT, int EPI>
+__global__ void __launch_bounds__(XNT) k_gemm_x(gemm_args g) {
+    constexpr int RG = XRT / 4;  // 8-row groups per wave
+    // A fragments: [b][row][lane] 16 B (lane l's 4 f16 in half l&1 of the fragment) + a zero region
+    // the inactive lanes read at the same strides (no per-lane select).  The fragment rows are padded
+    // to WFR = 9 x 16 B: the 8 active lanes of a ds_read_b128 lane group then hit distinct banks
+    // (rows 2 apart would share them at 8 x 16 B)
+    constexpr int WFR = 9;
+    __shared__ __attribute__((aligned(16))) uint4 Wf[XKB * XM * WFR + 7 * 16 + 1];
     __shared__ __attribute__((aligned(16))) uint8_t Xs[XN * XS_ROW];
     __shared__ __attribute__((aligned(16))) float dws[XKB][2][XM / 2];  // [b][row & 1][row >> 1]
     __shared__ __attribute__((aligned(16))) float das[XKB][XN];
-    constexpr int BT = wfmt<WT>::BT;
-    constexpr int WRECS = (WT == T_Q4_0) ? 256 : 512;  // 16-B weight records per stage
-    constexpr int WREC = (WRECS + XNT - 1) / XNT;      // per thread
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l16 = lane & 15, kg = lane >> 4;
     const int wr = (wave % XWR) * 2 * XRT, wt = (wave / XWR) * 16 * XCT;  // wave tile: rows wr.., tokens wt..
-    static_assert(XNT % 64 == 0, "waves");
     const int64_t t0 = (int64_t)blockIdx.x * XN, r0 = (int64_t)blockIdx.y * XM;
     const int64_t n_rt = g.n_rt, n_bt = g.n_bt, nb = g.nb;
-    // this lane's A fragment: MFMA row l16 = (weight row wr + 2*rt + (l16 >> 3), lane l16 & 7);
-    // nonzero only when the lane's 4 elements fall in the lane's k range 8*kg .. 8*kg+7
-    // W32: MFMA row (lane & 31) = 4 * row + (lane & 3); lane's k group 8*(lane >> 5) .. holds the
-    // elements of AVX2 lane 4h + (lane & 3) iff (lane >> 5) == (lane & 3) >> 1
-    const bool a_act = W32 ? (lane >> 5) == ((lane & 3) >> 1) : ((l16 & 7) >> 1) == kg;
-    // W32 inactive lanes read zeros from the slot of a 256-B zero row that none of the active lanes
-    // of their ds_read_b128 lane group uses (MI355X_MICROARCH §LDS: b128 lane groups {0-3,12-15,
+    // this lane's A fragment: MFMA row (lane & 31) = 4 * row + (lane & 3); the lane's k group
+    // 8*(lane >> 5) .. holds the elements of AVX2 lane 4h + (lane & 3) iff (lane >> 5) == (lane & 3) >> 1
+    const bool a_act = (lane >> 5) == ((lane & 3) >> 1);
+    // inactive lanes read zeros from the slot of a 256-B zero row that none of the active lanes of
+    // their ds_read_b128 lane group uses (MI355X_MICROARCH §LDS: b128 lane groups {0-3,12-15,
     // 20-27}, {4-11,16-19,28-31} and the same + 32; bank (a/4) mod 64): with one shared zero slot
     // the group read it as one more distinct 16-B address on busy banks (A reads 7 / 6 LDS cycles
     // instead of 4; scripts/lds_banks.py gemm_x_zero_search).  Table for WFR = 9: [group][half].
     constexpr int ZC[4][2] = {{2, 3}, {1, 0}, {1, 0}, {0, 1}};
     const int x32 = lane & 31;
     const int zg = 2 * (lane >> 5) + ((x32 >= 4 && x32 < 12) || (x32 >= 16 && x32 < 20) || x32 >= 28 ? 1 : 0);
-    const bool zs = W32 && !CW && WFR == 9 && GHIP_XZS;
-    const uint4 *a_ptr = CW      ? Wf
-                         : !a_act ? &Wf[XKB * XM * WFR + (zs ? ZC[zg][0] : 0)]
-                         : W32  ? &Wf[(wr + ((lane & 31) >> 2)) * WFR + (lane & 3)]
-                                : &Wf[(wr + (l16 >> 3)) * 8 + (l16 & 7)];
+    const uint4 *a_ptr = !a_act ? &Wf[XKB * XM * WFR + ZC[zg][0]] : &Wf[(wr + ((lane & 31) >> 2)) * WFR + (lane & 3)];
     const int a_bstride = a_act ? XM * WFR : 0;
-    // W32: the half-1 lanes' fragments (lane 4 + (lane & 3)); the next 8-row group (8 * WFR, i.e.
-    // the active slots move by 8 of 16: the zero slot moves with them)
-    const int a_hoff = a_act ? 4 : zs ? ZC[zg][1] - ZC[zg][0] : 0;
-    const int a_rgoff = a_act ? 8 * WFR : zs ? 8 : 0;
-    if (CW) {
-        for (int i = tid; i < 8; i += XNT) Wf2[XKB * XM * WFR2 + i] = make_uint2(0u, 0u);
-    } else {
-        for (int i = tid; i < 7 * 16 + 1; i += XNT) Wf[XKB * XM * WFR + i] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    const uint2 *a_ptr2 = !a_act ? &Wf2[CW ? XKB * XM * WFR2 : 0] : &Wf2[CW ? (wr + ((lane & 31) >> 2)) * WFR2 + (lane & 3) : 0];
-    const int a_bstride2 = a_act ? XM * WFR2 : 0, a_rgoff2 = a_act ? 8 * WFR2 : 0;
-    const bool a_hi = (lane & 1) != 0;  // W32: this lane's 4 elements sit in the upper half of its 8
+    // the half-1 lanes' fragments (lane 4 + (lane & 3)); the next 8-row group (8 * WFR, i.e. the
+    // active slots move by 8 of 16: the zero slot moves with them)
+    const int a_hoff = a_act ? 4 : ZC[zg][1] - ZC[zg][0];
+    const int a_rgoff = a_act ? 8 * WFR : 8;
+    for (int i = tid; i < 7 * 16 + 1; i += XNT) Wf[XKB * XM * WFR + i] = make_uint4(0u, 0u, 0u, 0u);
 
-    float acc[XRT][XCT][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < XCT; ++j)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) acc[i][j][v] = 0.0f;
-
-    typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+    // one stage's global loads, in registers: the next stage's are in flight during the current stage's MFMAs
+    constexpr int BT = wfmt<WT>::BT;
+    constexpr int WRECS = (WT == T_Q4_0) ? 256 : 512;  // 16-B weight records per stage
+    constexpr int WREC = (WRECS + XNT - 1) / XNT;      // per thread
+    constexpr int XDA = (XN * XKB + XNT - 1) / XNT;    // token scales per thread per stage
     u4v wq[WREC], ws[WREC], xr[XREC];
     float xd[XDA];
     auto gload = [&](int64_t kb0) {
@@ -510,8 +448,7 @@ k_gemm_x(gemm_args g) {
             const uint32_t qd[4] = {wq[k].x, wq[k].y, wq[k].z, wq[k].w};
             const uint32_t sd[4] = {ws[k].x, ws[k].y, ws[k].z, ws[k].w};
             auto put = [&](int b, uint2 f) {
-                if (CW) Wf2[(b * XM + row) * WFR2 + l] = f;
-                else Wf[(b * XM + row) * WFR + l] = (l & 1) ? make_uint4(0u, 0u, f.x, f.y) : make_uint4(f.x, f.y, 0u, 0u);
+                Wf[(b * XM + row) * WFR + l] = (l & 1) ? make_uint4(0u, 0u, f.x, f.y) : make_uint4(f.x, f.y, 0u, 0u);
             };
             if (WT == T_Q4_0) {
 #pragma unroll
@@ -540,79 +477,24 @@ k_gemm_x(gemm_args g) {
             if (c < XN * 8) das[c & 7][c >> 3] = xd[k];
         }
     };
-    // one block's operands from LDS: A fragments (8 row pairs), B fragments, d_w (rows wr + 2*rt +
-    // (kg >> 1)) and d_a (tokens wt + 16*ct + l16)
-    struct frag { xh8 a[XRT]; xh8 b[XCT]; float dw[XRT]; float da[XCT]; };
-    auto ldfrag = [&](int b, frag &f) {
-        const uint4 *ab = a_ptr + b * a_bstride;
-#pragma unroll
-        for (int rt = 0; rt < XRT; ++rt) f.a[rt] = *(const xh8 *)(ab + rt * 16);
-#pragma unroll
-        for (int ct = 0; ct < XCT; ++ct) {
-            f.b[ct] = *(const xh8 *)(Xs + (wt + ct * 16 + l16) * XS_ROW + b * 64 + kg * 16);
-            f.da[ct] = das[b][wt + ct * 16 + l16];
-        }
-#pragma unroll
-        for (int q = 0; q < XRT; q += 4) {
-            const float4 dwq = *(const float4 *)&dws[b][kg >> 1][wr / 2 + q];
-            f.dw[q] = dwq.x; f.dw[q + 1] = dwq.y; f.dw[q + 2] = dwq.z; f.dw[q + 3] = dwq.w;
-        }
-    };
-    // all MFMAs of the block first (back-to-back on the matrix pipe), then the lane-chain fmafs
-    auto block = [&](const frag &f) {
-        xf4 dd[XRT][XCT];
-#pragma unroll
-        for (int rt = 0; rt < XRT; ++rt)
-#pragma unroll
-            for (int ct = 0; ct < XCT; ++ct) {
-                const xf4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-                dd[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.a[rt], f.b[ct], z, 0, 0, 0);
-            }
-#pragma unroll
-        for (int rt = 0; rt < XRT; ++rt)
-#pragma unroll
-            for (int ct = 0; ct < XCT; ++ct) {
-                const float d = f.dw[rt] * f.da[ct];
-#pragma unroll
-                for (int v = 0; v < 4; ++v) acc[rt][ct][v] = __builtin_fmaf(d, dd[rt][ct][v], acc[rt][ct][v]);
-            }
-    };
 
-    // ---- W32 operands and block step ----
+    // one block's operands from LDS and its step: all MFMAs of the block first (back-to-back on the
+    // matrix pipe), then the lane-chain fmafs
     const int n32 = lane & 31, g32 = lane >> 5;
-    float acc32[RG][4][8];
+    float acc[RG][4][8];
 #pragma unroll
     for (int q = 0; q < RG; ++q)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int l = 0; l < 8; ++l) acc32[q][j][l] = 0.0f;
-    struct frag32 { xh8 a[RG][2]; xh8 b[2]; float dw[RG][4]; float da; };
-    auto ldfrag32 = [&](int b, frag32 &f) {
+            for (int l = 0; l < 8; ++l) acc[q][j][l] = 0.0f;
+    struct frag { xh8 a[RG][2]; xh8 b[2]; float dw[RG][4]; float da; };
+    auto ldfrag = [&](int b, frag &f) {
 #pragma unroll
         for (int q = 0; q < RG; ++q) {
-            if constexpr (CW) {
-                const uint2 *ab2 = a_ptr2 + b * a_bstride2 + q * a_rgoff2;
-                const uint2 v0 = ab2[0], v1 = ab2[a_hoff];
-                auto place = [&](uint2 v) {
-                    const uint4 u = a_hi ? make_uint4(0u, 0u, v.x, v.y) : make_uint4(v.x, v.y, 0u, 0u);
-                    return __builtin_bit_cast(xh8, u);
-                };
-                f.a[q][0] = place(v0);
-                f.a[q][1] = place(v1);
-                const float4 dwq = *(const float4 *)&dws[b][g32][wr / 2 + 4 * q];
-                f.dw[q][0] = dwq.x; f.dw[q][1] = dwq.y; f.dw[q][2] = dwq.z; f.dw[q][3] = dwq.w;
-                continue;
-            }
             const uint4 *ab = a_ptr + b * a_bstride + q * a_rgoff;
-#if GHIP_XMASK
-            const xh8 zh = {};
-            f.a[q][0] = a_act ? *(const xh8 *)ab : zh;  // inactive lanes: no LDS access (EXEC-masked)
-            f.a[q][1] = a_act ? *(const xh8 *)(ab + a_hoff) : zh;
-#else
             f.a[q][0] = *(const xh8 *)ab;
             f.a[q][1] = *(const xh8 *)(ab + a_hoff);
-#endif
             const float4 dwq = *(const float4 *)&dws[b][g32][wr / 2 + 4 * q];
             f.dw[q][0] = dwq.x; f.dw[q][1] = dwq.y; f.dw[q][2] = dwq.z; f.dw[q][3] = dwq.w;
         }
@@ -620,7 +502,7 @@ k_gemm_x(gemm_args g) {
         for (int h = 0; h < 2; ++h) f.b[h] = *(const xh8 *)(Xs + (wt + n32) * XS_ROW + b * 64 + h * 32 + g32 * 16);
         f.da = das[b][wt + n32];
     };
-    auto block32 = [&](const frag32 &f) {
+    auto block = [&](const frag &f) {
         const xf16v z = {};
         xf16v d[RG][2];
 #pragma unroll
@@ -634,8 +516,8 @@ k_gemm_x(gemm_args g) {
                 const float dd = f.dw[q][j] * f.da;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    acc32[q][j][i] = __builtin_fmaf(dd, d[q][0][4 * j + i], acc32[q][j][i]);
-                    acc32[q][j][4 + i] = __builtin_fmaf(dd, d[q][1][4 * j + i], acc32[q][j][4 + i]);
+                    acc[q][j][i] = __builtin_fmaf(dd, d[q][0][4 * j + i], acc[q][j][i]);
+                    acc[q][j][4 + i] = __builtin_fmaf(dd, d[q][1][4 * j + i], acc[q][j][4 + i]);
                 }
             }
     };
@@ -646,70 +528,23 @@ k_gemm_x(gemm_args g) {
         __syncthreads();
         if (kb0 + XKB < nb) gload(kb0 + XKB);
         const int nbs = (int)(nb - kb0 < XKB ? nb - kb0 : XKB);
-        if constexpr (W32) {
-#if GHIP_XPF
-            frag32 cur;
-            ldfrag32(0, cur);
-            for (int b = 0; b < nbs; ++b) {
-                frag32 nxt;
-                ldfrag32(b + 1 < nbs ? b + 1 : b, nxt);  // next block's operands in flight
-                block32(cur);
-                cur = nxt;
-            }
-#else
-            for (int b = 0; b < nbs; ++b) {
-                frag32 cur;
-                ldfrag32(b, cur);
-                block32(cur);
-            }
-#endif
-            __syncthreads();
-            continue;
-        }
-#if GHIP_XPF
-        frag cur;
-        ldfrag(0, cur);
-        for (int b = 0; b < nbs; ++b) {
-            frag nxt;
-            ldfrag(b + 1 < nbs ? b + 1 : b, nxt);  // next block's operands in flight
-            block(cur);
-            cur = nxt;
-        }
-#else
         for (int b = 0; b < nbs; ++b) {
             frag cur;
             ldfrag(b, cur);
             block(cur);
         }
-#endif
         __syncthreads();
     }
-    if constexpr (W32) {  // hsum in registers: ((a0+a4)+(a2+a6))+((a1+a5)+(a3+a7))
-        const int64_t t = t0 + wt + n32;
+    // hsum in registers: ((a0+a4)+(a2+a6))+((a1+a5)+(a3+a7))
+    const int64_t t = t0 + wt + n32;
 #pragma unroll
-        for (int q = 0; q < RG; ++q)
+    for (int q = 0; q < RG; ++q)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float *a = acc32[q][j];
-                float o = ((a[0] + a[4]) + (a[2] + a[6])) + ((a[1] + a[5]) + (a[3] + a[7]));
-                const int64_t r = r0 + wr + 8 * q + 2 * j + g32;
-                if (t >= g.T || r >= g.rows) continue;
-                if (EPI == EPI_ADD) o = o + g.resid[t * g.ldy + r];
-                g.y[t * g.ldy + r] = o;
-            }
-        return;
-    }
-    // hsum: lane kg even holds lanes 0-3 of (row, token), lane^16 lanes 4-7
-#pragma unroll
-    for (int rt = 0; rt < XRT; ++rt)
-#pragma unroll
-        for (int ct = 0; ct < XCT; ++ct) {
-            float p[4];
-#pragma unroll
-            for (int v = 0; v < 4; ++v) p[v] = acc[rt][ct][v] + __shfl_xor(acc[rt][ct][v], 16);
-            float o = (p[0] + p[2]) + (p[1] + p[3]);
-            const int64_t t = t0 + wt + ct * 16 + l16, r = r0 + wr + 2 * rt + (kg >> 1);
-            if ((kg & 1) || t >= g.T || r >= g.rows) continue;
+        for (int j = 0; j < 4; ++j) {
+            const float *a = acc[q][j];
+            float o = ((a[0] + a[4]) + (a[2] + a[6])) + ((a[1] + a[5]) + (a[3] + a[7]));
+            const int64_t r = r0 + wr + 8 * q + 2 * j + g32;
+            if (t >= g.T || r >= g.rows) continue;
             if (EPI == EPI_ADD) o = o + g.resid[t * g.ldy + r];
             g.y[t * g.ldy + r] = o;
         }
@@ -732,40 +567,22 @@ k_gemm_x(gemm_args g) {
 // bytes: conflict-free), tokens as k_gemm_x's padded f16 rows.
 typedef _Float16 xh4 __attribute__((ext_vector_type(4)));
 constexpr int X4_ACOL = 16 * 8;                          // bytes per (block, row group, lane) column
-#ifndef GHIP_X4_WPE
-#define GHIP_X4_WPE 3  // waves per SIMD the register budget must allow (LDS: 53 KB per workgroup fits 3 per CU)
-#endif
-#ifndef GHIP_X4_PF
-#define GHIP_X4_PF 0   // 1: the next stage's global loads in registers during the compute (k_gemm_x's form)
-#endif
-#ifndef GHIP_X4_OPF
-#define GHIP_X4_OPF 0  // 1: a block's LDS operands read one block ahead (measured 83.5 vs 70.9 ms: staging spills)
-#endif
-#ifndef GHIP_X4_SEQ
-#define GHIP_X4_SEQ 1  // 1: a block's two token groups one after the other (half the MFMA results live)
-#endif
 // RGS: row groups (16 rows) per workgroup — 2: 32 rows x 64 tokens, 4: 64 rows x 32 tokens (the token
 // image, re-read by every row tile, is the bulk of the staging: 64 rows halve it)
 // XI: the activation staged from the int8 Q8_0 image (g.xq, 32 B per block and token: half the
 // global / L2 bytes of the f16 image) and converted to f16 while it is written to LDS (q ^ 0x80
 // over bias 1152: exact), instead of read as the f16 image g.xh
+// 3 waves per SIMD: what the register budget must allow (LDS: 53 KB per workgroup fits 3 per CU)
 template <int WT, int EPI, int RGS, int XI = 0>
-__global__ void __launch_bounds__(XNT)
-#if GHIP_X4_WPE
-__attribute__((amdgpu_waves_per_eu(GHIP_X4_WPE, GHIP_X4_WPE)))
-#endif
-k_gemm_x4(gemm_args g) {
+__global__ void __launch_bounds__(XNT) __attribute__((amdgpu_waves_per_eu(3, 3))) k_gemm_x4(gemm_args g) {
     static_assert(XNT == 256 && (RGS == 2 || RGS == 4), "4 waves: RGS row groups x 4/RGS token groups");
     constexpr int M4 = 16 * RGS, N4 = 32 * (4 / RGS), X4_ABLK = RGS * 8 * X4_ACOL;
-    constexpr int XREC4 = N4 * XKB * (XI ? 32 : 64) / 16 / XNT, XDA4 = (N4 * XKB + XNT - 1) / XNT;
+    constexpr int XREC4 = N4 * XKB * (XI ? 32 : 64) / 16 / XNT;
     constexpr int XSEG = XKB * (XI ? 32 : 64) / 16;  // 16-B global records per token and stage
     __shared__ __attribute__((aligned(16))) uint8_t Wa[XKB * X4_ABLK];
     __shared__ __attribute__((aligned(16))) uint8_t Xs[N4 * XS_ROW];
     __shared__ __attribute__((aligned(16))) float dws[XKB][M4];
     __shared__ __attribute__((aligned(16))) float das[XKB][N4];
-    constexpr int BT = wfmt<WT>::BT;
-    constexpr int WRECS = (M4 / 8) * 64 * (WT == T_Q4_0 ? 1 : 2);  // 16-B weight records per stage
-    constexpr int WREC = (WRECS + XNT - 1) / XNT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int rg = wave % RGS, tg = wave / RGS;        // this wave: rows 16*rg.., tokens 32*tg..
     const int q = lane >> 4, l16 = lane & 15;
@@ -784,10 +601,13 @@ k_gemm_x4(gemm_args g) {
 #pragma unroll
             for (int p2 = 0; p2 < 2; ++p2) acc[c][l][p2] = xf2{0.0f, 0.0f};
 
-    typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+    constexpr int BT = wfmt<WT>::BT;
+    constexpr int WRECS = (M4 / 8) * 64 * (WT == T_Q4_0 ? 1 : 2);  // 16-B weight records per stage
+    constexpr int WREC = (WRECS + XNT - 1) / XNT;
+    constexpr int XDA4 = (N4 * XKB + XNT - 1) / XNT;
     u4v wq[WREC], ws[WREC], xr[XREC4];
     float xd[XDA4];
-    auto gload = [&](int64_t kb0) {  // k_gemm_x's stage loads
+    auto gload = [&](int64_t kb0) {
 #pragma unroll
         for (int k = 0; k < WREC; ++k) {
             const int rec = tid + XNT * k, tile_i = rec >> 6, ln = rec & 63, rr = ln >> 3;
@@ -818,6 +638,9 @@ k_gemm_x4(gemm_args g) {
         }
     };
     auto lstore = [&]() {
+        // A: row slot swizzled by the lane: (row & 15) ^ 2l, so each 16-lane group (rr 2 values x l 0..7)
+        // of a ds_write_b64 lands on 32 distinct banks (unswizzled: 8-way, 50 % of the LDS cycles
+        // conflicts in the PMC; scripts/lds_banks.py); a 16-row column stays one contiguous 128 B
 #pragma unroll
         for (int k = 0; k < WREC; ++k) {
             const int rec = tid + XNT * k, tile_i = rec >> 6, ln = rec & 63, rr = ln >> 3, l = ln & 7;
@@ -883,9 +706,8 @@ k_gemm_x4(gemm_args g) {
     const int qs_ = q ^ ((l16 >> 3) & 1);
     const uint8_t *b_base = Xs + (32 * tg + l16) * XS_ROW + (XI ? ((qs_ >> 1) & 1) * 256 + (qs_ & 1) * 8 : qs_ * 8);
     constexpr int BSTEP = XI ? 32 : 64, BHALF = XI ? 16 : 32;  // bytes per block, second AVX2 half
-    // one block's operands (A: 2 lanes' fragments, B: 2 token groups x 2, d_w of the lane's 4 rows, d_a
-    // of its 2 tokens), loaded a block ahead (GHIP_X4_OPF) so their LDS latency hides behind the
-    // previous block's MFMAs and chains
+    // one block's operands: A: 2 lanes' fragments, B: 2 token groups x 2, d_w of the lane's 4 rows, d_a
+    // of its 2 tokens
     struct x4ops {
         xh4 a0, a1, bb[2][2];
         float4 dw4;
@@ -922,35 +744,23 @@ k_gemm_x4(gemm_args g) {
                         acc[c][4 * h + bq][p2] = __builtin_elementwise_fma(dd[p2], dv, acc[c][4 * h + bq][p2]);
                     }
         };
+        // a block's two token groups one after the other (half the MFMA results live): token group
+        // 1's MFMAs after group 0's chains
         group(0);
-        if (GHIP_X4_SEQ) __builtin_amdgcn_sched_barrier(0);  // token group 1's MFMAs after group 0's chains
+        __builtin_amdgcn_sched_barrier(0);
         group(1);
     };
 
-    if (GHIP_X4_PF) gload(0);
     for (int64_t kb0 = 0; kb0 < nb; kb0 += XKB) {
-        if (!GHIP_X4_PF) gload(kb0);  // (no register prefetch: the other workgroups of the CU overlap)
+        gload(kb0);  // (no register prefetch: the other workgroups of the CU overlap)
         lstore();
         __syncthreads();
-        if (GHIP_X4_PF && kb0 + XKB < nb) gload(kb0 + XKB);
         const int nbs = (int)(nb - kb0 < XKB ? nb - kb0 : XKB);
-        if (GHIP_X4_OPF) {
+#pragma unroll 1
+        for (int b = 0; b < nbs; ++b) {
             x4ops cur;
-            ldops(0, cur);
-#pragma unroll 1
-            for (int b = 0; b < nbs; ++b) {
-                x4ops nxt;
-                ldops(b + 1 < nbs ? b + 1 : b, nxt);  // (the last block re-reads its own: no branch)
-                compute(cur);
-                cur = nxt;
-            }
-        } else {
-#pragma unroll 1
-            for (int b = 0; b < nbs; ++b) {
-                x4ops cur;
-                ldops(b, cur);
-                compute(cur);
-            }
+            ldops(b, cur);
+            compute(cur);
         }
         __syncthreads();
     }
@@ -1194,17 +1004,32 @@ int launch_quant_rows(int mode, const qrow_args &a, int T, hipStream_t s) {
     return 0;
 }
 
+// the run-time (weight type, epilogue) of a GEMM as compile-time constants: f(wt, ep) with
+// decltype(wt)::value = T_Q4_0 / T_Q8_0 and decltype(ep)::value = EPI_STORE / EPI_ADD; false (f not
+// called) for any other pair
+template <class F>
+static bool with_gemm_kind(int wtype, int epi, F f) {
+    auto with_epi = [&](auto wt) {
+        if (epi == EPI_STORE) f(wt, std::integral_constant<int, EPI_STORE>());
+        else if (epi == EPI_ADD) f(wt, std::integral_constant<int, EPI_ADD>());
+        else return false;
+        return true;
+    };
+    if (wtype == T_Q4_0) return with_epi(std::integral_constant<int, T_Q4_0>());
+    if (wtype == T_Q8_0) return with_epi(std::integral_constant<int, T_Q8_0>());
+    return false;
+}
+
 int launch_gemm_q(int wtype, int epi, const gemm_args &g, hipStream_t s) {
     if (g.ldq % 256 || g.nb * 32 > g.ldq) {
         set_error("gemm_q: activation image must be padded to 256 elements");
         return -1;
     }
     const dim3 grid((unsigned)((g.rows + GM - 1) / GM), (unsigned)((g.T + GN - 1) / GN));
-    if (wtype == T_Q4_0 && epi == EPI_STORE) hipLaunchKernelGGL((k_gemm_q<T_Q4_0, EPI_STORE>), grid, dim3(256), 0, s, g);
-    else if (wtype == T_Q4_0 && epi == EPI_ADD) hipLaunchKernelGGL((k_gemm_q<T_Q4_0, EPI_ADD>), grid, dim3(256), 0, s, g);
-    else if (wtype == T_Q8_0 && epi == EPI_STORE) hipLaunchKernelGGL((k_gemm_q<T_Q8_0, EPI_STORE>), grid, dim3(256), 0, s, g);
-    else if (wtype == T_Q8_0 && epi == EPI_ADD) hipLaunchKernelGGL((k_gemm_q<T_Q8_0, EPI_ADD>), grid, dim3(256), 0, s, g);
-    else {
+    const bool known = with_gemm_kind(wtype, epi, [&](auto wt, auto ep) {
+        hipLaunchKernelGGL((k_gemm_q<decltype(wt)::value, decltype(ep)::value>), grid, dim3(256), 0, s, g);
+    });
+    if (!known) {
         set_error("gemm_q: unsupported (type, epilogue)");
         return -1;
     }
@@ -1217,54 +1042,42 @@ int launch_gemm_q(int wtype, int epi, const gemm_args &g, hipStream_t s) {
 // 2 the same with 64 x 32 (72.3 ms), 3 = 1 with the activation staged from the int8 image (the
 // default: 68.0 vs 70.8 ms), 4 = 2 staged from the int8 image; same bits every way
 static std::atomic<int> g_gemm_x4{3};
-bool gemm_x4_on() { return g_gemm_x4.load() != 0; }
-bool gemm_x4_i8() { const int m = g_gemm_x4.load(); return m == 3 || m == 4; }  // staged from the int8 image
-int gemm_x4_mode() { return g_gemm_x4.load(); }  // 1: 32 rows x 64 tokens per workgroup, 2: 64 x 32
-void set_gemm_x4(int v) { g_gemm_x4.store(v); }
+void set_gemm_x4(int mode) {
+    if (mode < 0 || mode > 4) set_error("hpc_set_gemm_x4: mode " + std::to_string(mode) + " outside 0..4 (the form is unchanged)");
+    else g_gemm_x4.store(mode);
+}
+gemm_form gemm_form_now() {  // the only reader of the mode's numbering
+    const int mode = g_gemm_x4.load();
+    gemm_form f;
+    f.x4 = mode != 0;
+    f.rgs = (mode == 2 || mode == 4) ? 4 : 2;
+    f.i8 = mode == 3 || mode == 4;
+    return f;
+}
 
-int launch_gemm_exact(int wtype, int epi, const gemm_args &g, hipStream_t s) {
-    if (g.ldq % 256 || g.nb * 32 > g.ldq || g.T <= 0 || g.rows <= 0 || !(gemm_x4_i8() ? (const void *)g.xq : (const void *)g.xh)) {
+int launch_gemm_exact(int wtype, int epi, const gemm_form &form, const gemm_args &g, hipStream_t s) {
+    if (g.ldq % 256 || g.nb * 32 > g.ldq || g.T <= 0 || g.rows <= 0 || !(form.i8 ? (const void *)g.xq : (const void *)g.xh)) {
         set_error("gemm_exact: needs the activation image of its form (int8 or f16), padded to 256 elements");
         return -1;
     }
-    const int64_t gy = (g.rows + XM - 1) / XM;
+    // workgroup tile: k_gemm_x XM x XN, k_gemm_x4 16 * rgs rows x 32 * (4 / rgs) tokens; the row bound
+    // below is the form's own grid.y (the 64-row forms take twice the rows of the 32-row ones)
+    const int M = form.x4 ? 16 * form.rgs : XM, N = form.x4 ? 32 * (4 / form.rgs) : XN;
+    const int64_t gy = (g.rows + M - 1) / M;
     if (gy > 65535) {
         set_error("gemm_exact: too many rows");
         return -1;
     }
-    const dim3 grid((unsigned)((g.T + XN - 1) / XN), (unsigned)gy);
-    if (gemm_x4_on()) {  // the K = 4 multi-block MFMA form
-        const int mode = gemm_x4_mode(), rgs = (mode == 2 || mode == 4) ? 4 : 2, xi = mode >= 3;
-        if (xi && !g.xq) {
-            set_error("gemm_exact: the int8-staged form needs the int8 image");
-            return -1;
-        }
-        const dim3 grid4((unsigned)((g.T + 32 * (4 / rgs) - 1) / (32 * (4 / rgs))), (unsigned)((g.rows + 16 * rgs - 1) / (16 * rgs)));
-#define X4_GO(W, E)                                                                                          \
-    do {                                                                                                     \
-        if (rgs == 4 && xi) hipLaunchKernelGGL((k_gemm_x4<W, E, 4, 1>), grid4, dim3(XNT), 0, s, g);         \
-        else if (rgs == 4) hipLaunchKernelGGL((k_gemm_x4<W, E, 4>), grid4, dim3(XNT), 0, s, g);              \
-        else if (xi) hipLaunchKernelGGL((k_gemm_x4<W, E, 2, 1>), grid4, dim3(XNT), 0, s, g);                 \
-        else hipLaunchKernelGGL((k_gemm_x4<W, E, 2>), grid4, dim3(XNT), 0, s, g);                            \
-    } while (0)
-        if (wtype == T_Q4_0 && epi == EPI_STORE) X4_GO(T_Q4_0, EPI_STORE);
-        else if (wtype == T_Q4_0 && epi == EPI_ADD) X4_GO(T_Q4_0, EPI_ADD);
-        else if (wtype == T_Q8_0 && epi == EPI_STORE) X4_GO(T_Q8_0, EPI_STORE);
-        else if (wtype == T_Q8_0 && epi == EPI_ADD) X4_GO(T_Q8_0, EPI_ADD);
-#undef X4_GO
-        else {
-            set_error("gemm_exact: unsupported (type, epilogue)");
-            return -1;
-        }
-        GHIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    constexpr bool W32 = GHIP_X32 != 0;
-    if (wtype == T_Q4_0 && epi == EPI_STORE) hipLaunchKernelGGL((k_gemm_x<T_Q4_0, EPI_STORE, W32>), grid, dim3(XNT), 0, s, g);
-    else if (wtype == T_Q4_0 && epi == EPI_ADD) hipLaunchKernelGGL((k_gemm_x<T_Q4_0, EPI_ADD, W32>), grid, dim3(XNT), 0, s, g);
-    else if (wtype == T_Q8_0 && epi == EPI_STORE) hipLaunchKernelGGL((k_gemm_x<T_Q8_0, EPI_STORE, W32>), grid, dim3(XNT), 0, s, g);
-    else if (wtype == T_Q8_0 && epi == EPI_ADD) hipLaunchKernelGGL((k_gemm_x<T_Q8_0, EPI_ADD, W32>), grid, dim3(XNT), 0, s, g);
-    else {
+    const dim3 grid((unsigned)((g.T + N - 1) / N), (unsigned)gy);
+    const bool known = with_gemm_kind(wtype, epi, [&](auto wt, auto ep) {
+        constexpr int W = decltype(wt)::value, E = decltype(ep)::value;
+        if (!form.x4) hipLaunchKernelGGL((k_gemm_x<W, E>), grid, dim3(XNT), 0, s, g);
+        else if (form.rgs == 4 && form.i8) hipLaunchKernelGGL((k_gemm_x4<W, E, 4, 1>), grid, dim3(XNT), 0, s, g);
+        else if (form.rgs == 4) hipLaunchKernelGGL((k_gemm_x4<W, E, 4>), grid, dim3(XNT), 0, s, g);
+        else if (form.i8) hipLaunchKernelGGL((k_gemm_x4<W, E, 2, 1>), grid, dim3(XNT), 0, s, g);
+        else hipLaunchKernelGGL((k_gemm_x4<W, E, 2>), grid, dim3(XNT), 0, s, g);
+    });
+    if (!known) {
         set_error("gemm_exact: unsupported (type, epilogue)");
         return -1;
     }

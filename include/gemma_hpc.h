@@ -53,10 +53,12 @@ int gemma_hip_mem_live(int64_t *allocs, int64_t *bytes);
 /* columns from which K-quant mul_mats (and the K-quant engine prefill) run the MFMA GEMM
  * (prefill_kq.hip) instead of the dot4 kernels; -1 = GHIP_KQ_MFMA_MIN or 8 (tests: same bytes) */
 void hpc_set_kq_gemm_min(int min_cols);
-/* the exact Q4_0 / Q8_0 prefill GEMM's form: 1 (default) = K = 4 multi-block MFMA (k_gemm_x4, dense
-   lane fragments, 32 rows x 64 tokens per workgroup), 2 = the same with 64 x 32, 0 = the lane-masked
-   32x32x16 form (k_gemm_x); bit-identical every way */
-void hpc_set_gemm_x4(int on);
+/* the exact Q4_0 / Q8_0 prefill GEMM's form, modes 0-4: 1 = K = 4 multi-block MFMA (k_gemm_x4, dense
+   lane fragments, 32 rows x 64 tokens per workgroup), 2 = the same with 64 x 32, 3 (default) and 4 =
+   1 and 2 with the activation staged from the int8 image instead of the f16 one, 0 = the lane-masked
+   32x32x16 form (k_gemm_x); bit-identical every way.  Process-wide; a pass reads it once, at its
+   start.  Any other value leaves the form as it was and sets the last-error text (hpc_last_error) */
+void hpc_set_gemm_x4(int mode);
 
 /* ---- graph executor (SURVEY §8(b) `hpc_graph_compute(ggml_cgraph*)`): runs a graph built with the
  * ggml surface of include/ggml.h on the GPU; 0 = ok, else hpc_last_error() tells */

@@ -1,7 +1,9 @@
-"""The exact prefill GEMM on the K = 4 multi-block MFMA (prefill.hip k_gemm_x4, hpc_set_gemm_x4(1)):
-bit-identical to mul_mat's AVX2 lane order (the oracle's restatement of src/hpc.cpp:15-41 over
-ggml's vec_dot_q4_0_q8_0 / q8_0_q8_0) at ragged shapes, and whole exact prefills (every prompt row's
-logits, the decode that continues from the cache) equal to the oracle and to the W32 form."""
+"""The exact prefill GEMM in its five forms (hpc_set_gemm_x4 modes 0-4, default 3: prefill.hip k_gemm_x, the
+lane-masked W32 kernel, and k_gemm_x4, the K = 4 multi-block MFMA kernel with 32 x 64 or 64 x 32 tiles,
+staged from the f16 or the int8 image): bit-identical to mul_mat's AVX2 lane order (the oracle's
+restatement of src/hpc.cpp:15-41 over ggml's vec_dot_q4_0_q8_0 / q8_0_q8_0) at ragged shapes, and whole
+exact prefills (every prompt row's logits, the decode that continues from the cache) equal to the oracle
+and to the W32 form.  Modes outside 0-4 are rejected and leave the form as it was."""
 import numpy as np
 import pytest
 
@@ -17,7 +19,7 @@ DEFAULT = 3  # hpc_set_gemm_x4's default form
 @pytest.fixture(params=[0, 1, 2, 3, 4], ids=["w32", "x4_32x64", "x4_64x32", "x4_i8", "x4_64x32_i8"])
 def x4(request):
     """every exact GEMM form: the lane-masked W32 kernel (0), the K = 4 kernel with 32 rows x 64
-    tokens (1, the default) and 64 x 32 (2)"""
+    tokens (1) and 64 x 32 (2), and the same two staged from the int8 image (3, the default, and 4)"""
     import gemma_hip as G
     G.lib().hpc_set_gemm_x4(request.param)
     yield request.param
@@ -68,6 +70,40 @@ def test_gemm_x4_extreme_blocks(x4):
 
 
 @gpu
+def test_mode_outside_0_to_4_is_rejected_and_leaves_the_form():
+    """hpc_set_gemm_x4(5) and (-1) set the last-error text, which names the value, and change nothing:
+    a 16 x 256 x 17 Q8_0 product still equals the oracle bit for bit from the default form, and, from
+    mode 1 (the f16 image alone is written), so does a whole exact prefill, the path on which a stored
+    5 made the quantizer write the f16 image while the GEMM read the int8 one."""
+    import gemma_hip as G
+    L = G.lib()
+    rows, K, T = 16, 256, 17
+    rng = np.random.default_rng(5)
+    W = O.quantize((rng.standard_normal((rows, K)) * 0.05).astype(np.float32), "q8_0_ref")
+    X = rng.standard_normal((T, K)).astype(np.float32)
+    wdata, rs = O.mul_mat_init(O.Q8_0, X)
+    ref = O.mul_mat(W, O.Q8_0, rows, W.shape[1], K, wdata, rs, T)
+    try:
+        L.hpc_set_gemm_x4(DEFAULT)
+        for bad in (5, -1):
+            L.hpc_set_gemm_x4(bad)
+            err = G.last_error()
+            assert err != "" and str(bad) in err, (bad, err)
+            r, Y, _, _ = _gemm(L, O.Q8_0, W, X, rows, K, T, exact=True)  # (a successful call clears the text)
+            assert r == 0, G.last_error()
+            assert G.last_error() == ""
+            assert np.array_equal(Y.view(np.uint32), ref.view(np.uint32)), (bad, np.abs(Y - ref).max())
+        # the engine's pass writes only the image its form stages from: a stored 5 would not survive this
+        L.hpc_set_gemm_x4(1)
+        for bad in (5, -1):
+            L.hpc_set_gemm_x4(bad)
+            assert str(bad) in G.last_error(), bad
+        _prefill_exact_case(dict(O.TINY), 33, 128, n_decode=1)
+    finally:
+        L.hpc_set_gemm_x4(DEFAULT)
+
+
+@gpu
 def test_prefill_exact_x4_gemma2b_shapes(x4):
     _prefill_exact_case(dict(O.GEMMA_2B), 96, 256, n_decode=2)
 
@@ -79,8 +115,9 @@ def test_prefill_exact_x4_q8_0_gqa(x4):
 
 @gpu
 def test_prefill_x4_full_size_equals_w32():
-    """BASELINE config 3 at full size (Gemma-2B, T = 2048): every prompt row's logits from the K = 4
-    form equal the lane-masked W32 form's (both bit-exact restatements; a size-independent check)."""
+    """BASELINE config 3 at full size (Gemma-2B, T = 2048): the last row's logits and the decode that
+    follows from each K = 4 form (modes 1-4) equal the lane-masked W32 form's (mode 0; all bit-exact
+    restatements; a size-independent check)."""
     import gemma_hip as G
     T = 2048
     shape = dict(O.GEMMA_2B)
