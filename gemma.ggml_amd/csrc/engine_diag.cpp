@@ -932,6 +932,49 @@ extern "C" int gemma_test_attn_prefill(const uint16_t *q16, const uint16_t *kc, 
     return r;
 }
 
+// the same rows through the key-split matrix-core form (attn_mx_long.hip) as ONE call of its launcher.  Its
+// scratch goes in as a pass would find it after earlier ones, only worse: large finite words, so a stale word
+// that a kernel reads wins the max and changes the output
+extern "C" int gemma_test_attn_mx_long(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, int T, int p0, int H,
+                                       int Hkv, int hd, int ctx, int n_kv, int64_t ldo, float *out) {
+    set_error("");
+    if (!q16 || !kc || !vc || !out || T <= 0 || p0 < 0 || H <= 0 || Hkv <= 0 || hd <= 0 || ctx <= 0 || n_kv <= 0 ||
+        ldo < (int64_t)H * hd) {
+        set_error("gemma_test_attn_mx_long: bad arguments (ldo >= H * hd)");
+        return -1;
+    }
+    attnp_args a;
+    a.ldo = ldo; a.T = T; a.H = H; a.Hkv = Hkv; a.hd = hd; a.ctx = ctx; a.n_kv = n_kv; a.p0 = p0;
+    if (const char *why = attn_mx_long_unsupported(a)) {  // before anything is sized by the shape
+        set_error(std::string("attn_mx_long: ") + why);
+        return -1;
+    }
+    const size_t q_n = (size_t)T * H * hd, cache_n = (size_t)ctx * Hkv * hd, out_n = (size_t)T * ldo;
+    const int slab_rows = attn_mx_long_slab_rows(T);
+    const size_t sb_n = attn_mx_long_scratch(slab_rows, H, ctx, false) / 4;
+    dev_pool tmp;
+    uint16_t *d_q, *d_k, *d_v, *d_pb;
+    float *d_out, *d_sb;
+    if (tmp.get(&d_q, q_n * 2) || tmp.get(&d_k, cache_n * 2) || tmp.get(&d_v, cache_n * 2) || tmp.get(&d_out, out_n * 4) ||
+        tmp.get(&d_sb, sb_n * 4) || tmp.get(&d_pb, sb_n * 2))
+        return -1;
+    {
+        std::vector<float> sb(sb_n, GEMMA_TEST_ATTN_LONG_W_FILL);
+        std::vector<uint16_t> pb(sb_n, (uint16_t)GEMMA_TEST_ATTN_LONG_P_FILL);
+        GHIP_CHECK(hipMemcpy(d_sb, sb.data(), sb_n * 4, hipMemcpyHostToDevice));
+        GHIP_CHECK(hipMemcpy(d_pb, pb.data(), sb_n * 2, hipMemcpyHostToDevice));
+    }
+    GHIP_CHECK(hipMemcpy(d_q, q16, q_n * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_k, kc, cache_n * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_v, vc, cache_n * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_out, out, out_n * 4, hipMemcpyHostToDevice));
+    a.q16 = d_q; a.kc = d_k; a.vc = d_v; a.out = d_out;
+    const int r = launch_attn_mx_long(a, d_sb, d_pb, slab_rows, nullptr);
+    GHIP_CHECK(hipDeviceSynchronize());
+    if (r == 0) GHIP_CHECK(hipMemcpy(out, d_out, out_n * 4, hipMemcpyDeviceToHost));
+    return r;
+}
+
 // ---- per-op test entry: the decode attention's launch forms, R rows on host buffers (include/gemma_hpc.h) ----
 extern "C" int gemma_test_attn_decode_rows(gemma_test_attn_rows_args *t) {
     set_error("");

@@ -70,6 +70,11 @@ struct pf_scratch {
     // log-probabilities: the partials of a pass of more than 8 rows, [T][G] (the engine's scratch: made
     // while they are on; a wide batch's: always, so nothing moves while it is open); else null
     lse_part *LP = nullptr;
+    // the key-split exact attention's scores and P16 (attn_mx_long.hip), made when a pass first takes that form:
+    // att_rows slab rows x n_head x n_ctx words each
+    float *AS = nullptr;
+    uint16_t *AP = nullptr;
+    int att_rows = 0;
 };
 
 // ---- a sequence (engine.cpp) ---- ---------------------------------------------------
@@ -222,7 +227,8 @@ struct gemma_engine {
     // dims; option "att_dsplit"). Same box, decode tok/s: 1 / 2 / 4 -> 1,443 / 1,458 / 1,458; after the
     // batched K/V step loads 2 / 4 / 8 -> 1,470-1,482 / 1,491 / 1,355-1,369 (scripts/env_ab.sh)
     int att_dsplit = 4;
-    int att_mx = 1;  // option "att_mx": exact prefill attention on the f32 matrix cores (0: the row form)
+    int att_mx = 1;  // option "att_mx": exact prefill attention on the f32 matrix cores (0: the row form only; 2: the
+                     // key-split form wherever it is supported)
     // ---- activations ----
     float *x = nullptr, *qkv = nullptr, *attn = nullptr, *sa = nullptr, *h = nullptr, *logits = nullptr;
     // Q8_0 activation images written by their producers (attention, gate/up) for attn-out and down

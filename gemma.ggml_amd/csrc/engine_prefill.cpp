@@ -85,15 +85,37 @@ static int kq_expand(gemma_engine *e, pf_scratch &p, const uint8_t *x, int64_t l
 }
 
 // The exact prefill attention: on the f32 matrix cores where the shapes allow it (attn_mx.hip:
-// v_mfma_f32_16x16x4_f32 is an fmaf chain over K, so vec_dot_f16's chains ride it bit for bit),
-// else per row with v_fma_mix (k_attn_rows).  Option "att_mx" 0 forces the row form (tests, A/B).
-// The form is resolved once per prefill (att_mx_form): the option and the shape check do not
-// change between its layers.
-static bool att_mx_form(const gemma_engine *e, const attnp_args &at) {
-    return e->att_mx && !attn_mx_unsupported(at);
+// v_mfma_f32_16x16x4_f32 is an fmaf chain over K, so vec_dot_f16's chains ride it bit for bit); where its 16
+// score rows do not fit the LDS (more than 2556 keys) the key-split matrix-core form (attn_mx_long.hip, n_ctx
+// <= 8192); else per row with v_fma_mix (k_attn_rows).  Option "att_mx" 0 forces the row form, 2 the key-split
+// form wherever it is supported (tests, A/B).  The form is resolved once per prefill (att_mx_form): the option
+// and the shape check do not change between its layers.
+enum { ATT_ROWS = 0, ATT_MX = 1, ATT_MX_LONG = 2 };
+static int att_mx_form(const gemma_engine *e, const attnp_args &at) {
+    if (!e->att_mx) return ATT_ROWS;
+    if (e->att_mx != 2 && !attn_mx_unsupported(at)) return ATT_MX;
+    return attn_mx_long_unsupported(at) ? ATT_ROWS : ATT_MX_LONG;
 }
-static int launch_attn_exact(const attnp_args &at, bool mx, hipStream_t s) {
-    return mx ? launch_attn_mx(at, s) : launch_attn_rows(at, s);
+// the key-split form's scratch, in the prefill pool beside the pass scratch (a regrow of that drops both): made
+// when a pass first resolves to the form, before its first attention launch, never between its layers
+static int att_long_alloc(gemma_engine *e, int T) {
+    pf_scratch &p = e->pf;
+    const int rows = attn_mx_long_slab_rows(T), H = e->cfg.n_head, ctx = e->cfg.n_ctx;
+    if (p.att_rows >= rows) return 0;
+    e->pf_mem.put(p.AS);
+    e->pf_mem.put(p.AP);
+    p.att_rows = 0;
+    if (e->pf_mem.get(&p.AS, attn_mx_long_scratch(rows, H, ctx, false)) ||
+        e->pf_mem.get(&p.AP, attn_mx_long_scratch(rows, H, ctx, true))) {
+        e->pf_mem.put(p.AS);
+        return -1;
+    }
+    p.att_rows = rows;
+    return 0;
+}
+static int launch_attn_exact(gemma_engine *e, const attnp_args &at, int form, hipStream_t s) {
+    if (form == ATT_MX_LONG) return launch_attn_mx_long(at, e->pf.AS, e->pf.AP, e->pf.att_rows, s);
+    return form == ATT_MX ? launch_attn_mx(at, s) : launch_attn_rows(at, s);
 }
 
 // layer il of a T-row prefill of positions p0 .. p0+T-1, from pf.QKV: RoPE + K/V store into the
@@ -115,8 +137,11 @@ static int prefill_attention(gemma_engine *e, int il, int T, const pass_rows &ro
     at.q16 = p.Q16; at.kc = r.kc; at.vc = r.vc; at.out = p.ATT; at.ldo = e->qw;
     at.T = T; at.H = c.n_head; at.Hkv = c.n_head_kv; at.hd = c.head_dim; at.ctx = c.n_ctx; at.p0 = p0;
     at.n_kv = std::min(32 * ((p0 + T) / 32 + 1), c.n_ctx);  // src/gemma_model.cpp:429 with n_total = p0 + T
-    if (*mx_form < 0) *mx_form = att_mx_form(e, at);
-    return exact ? launch_attn_exact(at, *mx_form == 1, s) : launch_attn_prefill(at, s);
+    if (*mx_form < 0) {
+        *mx_form = att_mx_form(e, at);
+        if (exact && *mx_form == ATT_MX_LONG && att_long_alloc(e, T)) return -1;
+    }
+    return exact ? launch_attn_exact(e, at, *mx_form, s) : launch_attn_prefill(at, s);
 }
 
 // One batched pass over T rows.  Own rows (own_rows(e, p0)): hist[p0 .. p0+T), sequence positions

@@ -278,9 +278,17 @@ int launch_attn_rows(const attnp_args &a, hipStream_t s);
 // so vec_dot_f16's 32 chains ride K four steps at a time; "" when it runs the shapes
 const char *attn_mx_unsupported(const attnp_args &a);  // nullptr: the matrix-core form runs these shapes
 int launch_attn_mx(const attnp_args &a, hipStream_t s);
+// the same rows with no LDS bound on the key count (attn_mx_long.hip): scores, softmax and KQV as three launches
+// per slab of at most 256 rows, n_ctx <= 8192.  sbuf f32 / pbuf f16 hold slab_rows x H x n_ctx words each
+// (attn_mx_long_scratch bytes), slab_rows = attn_mx_long_slab_rows(T): min(256, T rounded up to 16)
+constexpr int ATTN_MX_LONG_MAX_CTX = 8192;
+const char *attn_mx_long_unsupported(const attnp_args &a);  // nullptr: the key-split form runs these shapes
+int attn_mx_long_slab_rows(int T);
+size_t attn_mx_long_scratch(int slab_rows, int H, int ctx, bool p16);
+int launch_attn_mx_long(const attnp_args &a, float *sbuf, uint16_t *pbuf, int slab_rows, hipStream_t s);
 // hipFuncAttributeMaxDynamicSharedMemorySize of a kernel raised to the CU's whole LDS, once per
 // (slot, device), thread-safe: slots LDS_SLOT_*
-enum { LDS_SLOT_ATTN_MX = 0, LDS_SLOT_GELU_LDS = 1, LDS_SLOTS = 2 };
+enum { LDS_SLOT_ATTN_MX = 0, LDS_SLOT_GELU_LDS = 1, LDS_SLOT_ATTN_MXL = 2, LDS_SLOTS = 3 };
 int allow_full_lds(const void *fn, int slot);
 // the `parts` partial argmax keys of each of `rows` rows (ld floats apart) in ONE launch, grid (parts,
 // rows): row r's keys at keys + r * parts

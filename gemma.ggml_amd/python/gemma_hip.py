@@ -48,7 +48,8 @@ EXPORTS = ["mul_mat", "hpc_init", "hpc_shutdown", "hpc_register_weight", "hpc_la
            "gemma_engine_set_logprobs", "gemma_engine_logprobs", "gemma_engine_batch_logprobs", "gemma_test_logprob",
            "gemma_engine_batch_set_sampler", "gemma_engine_batch_sampler", "gemma_engine_batch_fork",
            "gemma_test_sample_rows", "gemma_test_rope_kv_prefill", "gemma_test_rows_rope_kv",
-           "gemma_test_attn_prefill", "gemma_test_attn_decode_rows", "gemma_test_attn_long_rows"]
+           "gemma_test_attn_prefill", "gemma_test_attn_decode_rows", "gemma_test_attn_long_rows",
+           "gemma_test_attn_mx_long"]
 
 
 def build():

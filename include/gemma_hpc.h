@@ -421,7 +421,8 @@ int gemma_engine_set_att_o(gemma_engine *e, int on);
 /* The measured variants that stay selectable (tests, A/B), set through the API rather than the
    environment: "kq_fuse" (K-quant Q8_K INIT plan 0..6), "kq_dual" (gate+up one launch), "kq_pair"
    (q|k and v one launch), "kq_abl" (timing ablation, wrong results), "att_mx" (exact prefill attention
-   on the f32 matrix cores; 0 = the row form), "att_dsplit" (decode attention workgroups per head:
+   on the f32 matrix cores: 1 = the LDS form where it fits, the key-split form past 2556 keys, else the row form;
+   0 = the row form only; 2 = the key-split form wherever it is supported),"att_dsplit" (decode attention workgroups per head:
    1/2/4/8), "ks_small" / "ks_down" (launch-plan K split defaults), "grid_big", "bt_mfma_min" (rows
    from which a wide batch pass runs as one MFMA pass, [9, 65], 65 = never; default 29, measured), and the
    gemma_engine_time diagnostics "time_hot" / "ablate" (a non-zero "ablate" needs the -DGHIP_ABLATE=1
@@ -471,6 +472,12 @@ int gemma_test_rows_rope_kv(const float *qkv, int64_t ldqkv, int T, int p0, int 
  * the caller's values.  A shape the form refuses: non-zero with the launcher's message, out untouched */
 int gemma_test_attn_prefill(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, int T, int p0, int H, int Hkv,
                             int hd, int ctx, int n_kv, int64_t ldo, int form, float *out);
+/* the same rows through the key-split matrix-core form (attn_mx_long.hip: scores, softmax and KQV launches per slab
+ * of 256 rows; head_dim 256, n_ctx <= 8192, no bound on n_kv below it) as ONE call of its launcher; the arguments
+ * above without `form`.  Before the launches the entry fills the form's scores scratch with
+ * GEMMA_TEST_ATTN_LONG_W_FILL and its P16 scratch with GEMMA_TEST_ATTN_LONG_P_FILL (below) */
+int gemma_test_attn_mx_long(const uint16_t *q16, const uint16_t *kc, const uint16_t *vc, int T, int p0, int H, int Hkv,
+                            int hd, int ctx, int n_kv, int64_t ldo, float *out);
 /* per-op test entry: R decode-attention rows through ONE launch form on host buffers.
  * form 0 the per-head kernel (with dsplit), 1 the position-split kernel, 2 the batch pass's one-row-per-slot
  *      kernel, 3 the several-rows-per-slot pair (the K / V store launch, then the attention on cached K / V).
