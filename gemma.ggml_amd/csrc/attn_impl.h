@@ -55,6 +55,8 @@ constexpr int ATT_QUADS = ATT_THREADS / 4;  // one KQ (position, head) or KQV (d
 constexpr int ATT_VW = 256;                 // V positions staged in LDS per dimension row (n_kv <= 256)
 constexpr int ATT_STG = 2;                  // staging uint4 per thread for each of K and V
 constexpr int ATT_MAXWG = 256;              // co-resident workgroups (in-kernel hand-off)
+constexpr int ATT_PW = 1024;                // windowed split form (attn_decode_win.hip): positions of P16 per window
+constexpr int ATT_PWS = ATT_PW + 8;         // its row stride in halfs (16 B of pad: rows start in different banks)
 
 // ggml_vec_dot_f16 with accumulator row j = t4 held by lane t4 of a quad: fold the
 // quad exactly as sum0+=sum2, sum1+=sum3, sum0+=sum1 (xor-2 then xor-1), then halves and hadds.

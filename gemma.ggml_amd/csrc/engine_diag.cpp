@@ -309,7 +309,7 @@ extern "C" int gemma_engine_set_option(gemma_engine *e, const char *name, int va
     set_error("");
     const std::string n = name ? name : "";
     int *f = n == "kq_fuse" ? &e->kq_fuse : n == "kq_dual" ? &e->kq_dual : n == "kq_pair" ? &e->kq_pair
-           : n == "kq_abl" ? &e->kq_abl : n == "att_mx" ? &e->att_mx : n == "time_hot" ? &e->time_hot
+           : n == "kq_abl" ? &e->kq_abl : n == "att_mx" ? &e->att_mx : n == "att_win" ? &e->att_win : n == "time_hot" ? &e->time_hot
            : n == "ablate" ? &e->ablate : n == "ks_small" ? &e->ks_small : n == "ks_down" ? &e->ks_down : nullptr;
     if (n == "att_dsplit") {
         if (value < 1 || value > 8 || (value & (value - 1)) || e->cfg.head_dim % (32 * value)) {

@@ -229,6 +229,8 @@ struct gemma_engine {
     int att_dsplit = 4;
     int att_mx = 1;  // option "att_mx": exact prefill attention on the f32 matrix cores (0: the row form only; 2: the
                      // key-split form wherever it is supported)
+    int att_win = 0;  // option "att_win": 1 runs the windowed split form (k_attn_decode_win) wherever ATTN_SPLIT runs
+                      // (A/B timing); 0: only where the resident P16 image does not fit the LDS
     // ---- activations ----
     float *x = nullptr, *qkv = nullptr, *attn = nullptr, *sa = nullptr, *h = nullptr, *logits = nullptr;
     // Q8_0 activation images written by their producers (attention, gate/up) for attn-out and down
@@ -379,7 +381,7 @@ static inline attn_args attn_of(gemma_engine *e, int il) {
     t.pos = e->seq.pos; t.out = e->attn;
     t.H = c.n_head; t.Hkv = c.n_head_kv; t.hd = c.head_dim; t.ctx = c.n_ctx;
     t.q_scale = 1.0f / sqrtf((float)c.head_dim);
-    t.mode = e->att_mode;
+    t.mode = e->att_mode == ATTN_SPLIT && e->att_win ? ATTN_SPLIT_WIN : e->att_mode;
     t.nwg = e->ag.nwg; t.sbuf = e->att_sbuf; t.sync = e->att_sync; t.err = e->att_sync + e->ag.sync_ints;
     return t;
 }

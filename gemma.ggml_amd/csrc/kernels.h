@@ -304,7 +304,7 @@ int launch_synth_norm(float *dst, int64_t n, uint64_t key, float scale, hipStrea
 int launch_untile(const tiled_mat &m, uint8_t *dst_rowmajor, hipStream_t s);
 
 // ---- small decode ops (ops.hip) -----------------------------------------------------------------
-enum attn_mode { ATTN_PER_HEAD = 0, ATTN_SPLIT = 1 };
+enum attn_mode { ATTN_PER_HEAD = 0, ATTN_SPLIT = 1, ATTN_SPLIT_WIN = 2 };
 struct attn_args {
     const float *qkv;       // [q(H*hd) | k(Hkv*hd) | v(Hkv*hd)] for one token
     uint16_t *kc, *vc;      // layer caches: K [ctx][Hkv*hd], V [Hkv*hd][ctx] (f16 bits)
@@ -426,9 +426,15 @@ struct attn_geom {
     int nwg = 0, grid = 0;
     int img = 0;  // the split form can write the output's Q8_0 image (32-dim KQV slices)
     size_t lds = 0, sbuf_floats = 0, sync_ints = 0;
+    size_t lds_win = 0;  // LDS of the windowed form (attn_decode_win.hip): no term in ctx
 };
 attn_geom attn_geometry(int H, int Hkv, int hd, int ctx);
+// ATTN_SPLIT runs k_attn_decode while its resident P16 image fits the 160 KiB of a workgroup, else (n_ctx up to
+// ATTN_WIN_MAX_CTX) k_attn_decode_win: the same launch, scratch and results.  ATTN_SPLIT_WIN: the windowed form at
+// every shape the split form serves (engine option "att_win": A/B timing).
+constexpr int ATTN_WIN_MAX_CTX = 8192;
 int launch_attn_decode(const attn_args &a, hipStream_t s);
+int launch_attn_decode_win(const attn_args &a, const attn_geom &g, hipStream_t s);  // (through launch_attn_decode only)
 int launch_embed(const uint8_t *qs, const uint8_t *sc, int wtype, int64_t n_bt, const int *token, float scale,
                  float *out, int64_t E, hipStream_t s);
 // reduces the n_parts per-workgroup argmax keys, appends the token, advances the position

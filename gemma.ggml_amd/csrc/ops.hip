@@ -847,7 +847,10 @@ attn_geom attn_geometry(int H, int Hkv, int hd, int ctx) {
     const int na = (ctx + PS - 1) / PS;
     g.nwg = std::max(nb, std::min(na, std::min(32, ATT_MAXWG / Hkv)));
     g.grid = 8 * g.nwg * ((Hkv + 7) / 8);  // XCD-colocated groups (idle slots exit at once)
-    g.lds = (size_t)G * hd * 2 + (size_t)hd * 2 + (size_t)PS * hd * 2 + (size_t)DS * ATT_VW * 2 + (size_t)G * ctx * 2;
+    const size_t lds_stage = (size_t)G * hd * 2 + (size_t)hd * 2 + (size_t)PS * hd * 2 + (size_t)DS * ATT_VW * 2;
+    g.lds = lds_stage + (size_t)G * ctx * 2;
+    // windowed form: two windows of P16 and a max key (u32) + e sum (u64) per head; 70,496 B at G 8, head_dim 256
+    g.lds_win = (lds_stage + (size_t)2 * G * ATT_PWS * 2 + (size_t)G * 12 + 15) & ~(size_t)15;
     g.sbuf_floats = (size_t)Hkv * ctx * G;
     g.sync_ints = (size_t)Hkv * 2;
     g.img = DS == 32 && hd % 32 == 0;
@@ -913,9 +916,14 @@ int launch_attn_decode(const attn_args &a, hipStream_t s) {
         set_error("attn_decode: too many workgroups for the in-kernel hand-off");
         return -1;
     }
-    if (g.lds > 160 * 1024) {
-        set_error("attn_decode: context too long for the LDS image");
-        return -1;
+    // the windowed form (attn_decode_win.hip) where the resident P16 image does not fit, up to the cap of every
+    // long form here, or where the caller asks for it (its LDS has no term in n_ctx)
+    if (a.mode == ATTN_SPLIT_WIN || g.lds > 160 * 1024) {
+        if ((a.mode != ATTN_SPLIT_WIN && a.ctx > ATTN_WIN_MAX_CTX) || g.lds_win > 160 * 1024) {
+            set_error("attn_decode: context too long for the LDS image");
+            return -1;
+        }
+        return launch_attn_decode_win(a, g, s);
     }
     if (g.lds > 64 * 1024)
         GHIP_CHECK(hipFuncSetAttribute((const void *)k_attn_decode, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));

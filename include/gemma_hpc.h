@@ -422,7 +422,9 @@ int gemma_engine_set_att_o(gemma_engine *e, int on);
    environment: "kq_fuse" (K-quant Q8_K INIT plan 0..6), "kq_dual" (gate+up one launch), "kq_pair"
    (q|k and v one launch), "kq_abl" (timing ablation, wrong results), "att_mx" (exact prefill attention
    on the f32 matrix cores: 1 = the LDS form where it fits, the key-split form past 2556 keys, else the row form;
-   0 = the row form only; 2 = the key-split form wherever it is supported),"att_dsplit" (decode attention workgroups per head:
+   0 = the row form only; 2 = the key-split form wherever it is supported), "att_win" (the decode
+   step's split attention past n_ctx 2048: 0 = P16 in windows only where the resident image does not fit the LDS, 1 = in
+   windows wherever the split form runs; same bits), "att_dsplit" (decode attention workgroups per head:
    1/2/4/8), "ks_small" / "ks_down" (launch-plan K split defaults), "grid_big", "bt_mfma_min" (rows
    from which a wide batch pass runs as one MFMA pass, [9, 65], 65 = never; default 29, measured), and the
    gemma_engine_time diagnostics "time_hot" / "ablate" (a non-zero "ablate" needs the -DGHIP_ABLATE=1
