@@ -17,7 +17,8 @@
 // rejected rows' K / V cleared, all on the device; a slot may sit the pass out.
 // gemma_engine_batch_set_sampler gives a slot a sampler of its own (or its own greedy) beside slots that
 // follow the engine's: every row reads its parameters from its row-table entry, and the picks of a pass take
-// one, three or four launches by the mix of the participating slots; gemma_engine_batch_fork copies a slot.
+// one launch, a sampler's three or six, or every set some slot needs, by the mix of the participating slots;
+// gemma_engine_batch_fork copies a slot.
 //
 // The three pass entries (batch_step, batch_step_rows, batch_verify) share everything but their per-slot
 // tables and their advance.  Each describes its pass by a batch_pass {row table, row sources, tokens, T}
@@ -48,7 +49,7 @@ static bool slot_ok(const gemma_engine *e, int slot, const char *fn) {
 
 // A sampler per slot: the parameters the slot's rows carry (its own, else the engine's while that
 // sampler is on, else greedy), and which launches a pass's picks take, from the host mirror of the
-// participating slots' modes (n_sample of n_slots sample)
+// participating slots' modes (mode_count)
 static sampler_params slot_params(const gemma_engine *e, int slot) {
     const batch_state &b = e->bt;
     sampler_params p;  // temperature 0: greedy
@@ -60,9 +61,15 @@ static sampler_params slot_params(const gemma_engine *e, int slot) {
     }
     return p;
 }
-static int picks_mix(int n_sample, int n_slots) {
-    return n_sample == 0 ? PICKS_GREEDY : n_sample == n_slots ? PICKS_SAMPLE : PICKS_MIXED;
-}
+struct mode_count {  // of a pass's participating slots: all, those that sample, those of them over the whole vocabulary
+    int slots = 0, sample = 0, full = 0;
+    void add(const gemma_engine *e, int slot) {
+        ++slots;
+        sample += slot_samples(e, slot);
+        full += slot_samples_full(e, slot);
+    }
+    int mix() const { return picks_mix(slots, sample, full); }
+};
 
 static void batch_drop(gemma_engine *e) {
     e->bt_mem.clear();
@@ -219,7 +226,7 @@ extern "C" int gemma_engine_batch_set_sampler(gemma_engine *e, int slot, const g
     const std::string fn = "gemma_engine_batch_set_sampler";
     if (!slot_ok(e, slot, fn.c_str())) return -1;
     if (sp) {
-        const std::string why = sampler_invalid(*sp);
+        const std::string why = sampler_invalid(*sp, e->cfg.n_vocab);
         if (!why.empty()) {
             set_error(fn + ": " + why);
             return -1;
@@ -373,11 +380,12 @@ extern "C" int gemma_engine_batch_step(gemma_engine *e, int n, float *logits) {
         set_error("gemma_engine_batch_step: no batch is open (gemma_engine_batch_open)");
         return -1;
     }
-    int R = 0, n_sample = 0;
+    int R = 0;
+    mode_count modes;
     for (int i = 0; i < b.n_slots; ++i) {
         if (!b.slot[i].active) continue;
         ++R;
-        n_sample += slot_samples(e, i);
+        modes.add(e, i);
         if ((int64_t)b.slot[i].host_pos + n >= c.n_ctx) {
             set_error("gemma_engine_batch_step: context full (slot " + std::to_string(i) + " at position " +
                       std::to_string(b.slot[i].host_pos) + ", n = " + std::to_string(n) + ", n_ctx = " + std::to_string(c.n_ctx) + ")");
@@ -396,7 +404,7 @@ extern "C" int gemma_engine_batch_step(gemma_engine *e, int n, float *logits) {
     const batch_pass bp{b.rows, nullptr, b.row_tok, R};
     for (int i = 0; i < n; ++i) {
         row_picks pk;
-        if (batch_run_pass(e, bp, picks_mix(n_sample, R), logits ? logits + (size_t)i * R * c.n_vocab : nullptr, &pk)) return -1;
+        if (batch_run_pass(e, bp, modes.mix(), logits ? logits + (size_t)i * R * c.n_vocab : nullptr, &pk)) return -1;
         if (launch_batch_advance(b.rows, R, pk.keys, pk.n_parts, pk.stride, b.row_tok, c.n_ctx, rope_of(e), s)) return -1;
         if (enqueue_lp_finish(e, b.pf.LG, R, b.picks.lp_parts, nullptr, b.rows, nullptr)) return -1;
     }
@@ -453,12 +461,13 @@ extern "C" int gemma_engine_batch_step_rows(gemma_engine *e, int max_rows, float
         return -1;
     }
     int32_t need[NS], m_of[NS];
-    int R = 0, n_sample = 0;
+    int R = 0;
+    mode_count modes;
     for (int i = 0; i < b.n_slots; ++i) {
         const seq_state &S = b.slot[i];
         need[i] = S.active ? std::max(1, S.n_given - S.host_pos) : 0;
         R += S.active;
-        n_sample += S.active && slot_samples(e, i);
+        if (S.active) modes.add(e, i);
     }
     if (R == 0) {
         set_error(std::string(fn) + ": no slot is active (gemma_engine_batch_begin / _adopt)");
@@ -495,7 +504,7 @@ extern "C" int gemma_engine_batch_step_rows(gemma_engine *e, int max_rows, float
     // a pick from every row (one launch whatever T; only each slot's last row's is used)
     const batch_pass bp{b.mrows, b.msrc, b.row_tok, T};
     row_picks pk;
-    if (batch_run_pass(e, bp, picks_mix(n_sample, R), logits, &pk)) return -1;
+    if (batch_run_pass(e, bp, modes.mix(), logits, &pk)) return -1;
     if (launch_rows_advance(b.rows, b.mrows, b.mspans, R, pk.keys, pk.n_parts, pk.stride, b.row_tok, c.n_ctx, rope_of(e), s))
         return -1;
     if (enqueue_lp_finish(e, b.pf.LG, T, b.picks.lp_parts, nullptr, b.mrows, nullptr)) return -1;
@@ -528,7 +537,8 @@ extern "C" int gemma_engine_batch_verify(gemma_engine *e, const int32_t *draft, 
         set_error(fn + ": a null draft, k_of, out_tokens or n_out");
         return -1;
     }
-    int P = 0, T = 0, n_sample = 0;
+    int P = 0, T = 0;
+    mode_count modes;
     for (int i = 0; i < b.n_slots; ++i) {
         const seq_state &S = b.slot[i];
         if (!S.active) continue;
@@ -551,7 +561,7 @@ extern "C" int gemma_engine_batch_verify(gemma_engine *e, const int32_t *draft, 
         }
         ++P;
         T += 1 + k;
-        n_sample += slot_samples(e, i);
+        modes.add(e, i);
     }
     if (P == 0) {
         set_error(fn + ": no slot takes part (no active slot, or every k_of is -1)");
@@ -587,7 +597,7 @@ extern "C" int gemma_engine_batch_verify(gemma_engine *e, const int32_t *draft, 
     // 2. the pass over its own tokens, and a pick from every row: none advances
     const batch_pass bp{b.mrows, b.msrc, b.vtok, T};
     row_picks pk;
-    if (batch_run_pass(e, bp, picks_mix(n_sample, P), logits, &pk)) return -1;
+    if (batch_run_pass(e, bp, modes.mix(), logits, &pk)) return -1;
     // 3. accept + advance per slot; (log-probabilities on) rows 0 .. a_s score what the accept settled
     if (launch_bverify_accept(b.rows, b.mrows, b.vslots, P, pk.keys, pk.n_parts, pk.stride, b.row_tok, c.n_ctx, rope_of(e),
                               b.vout, s))

@@ -161,14 +161,16 @@ int enqueue_logits_q6k(gemma_engine *e, const uint8_t *x, int ncols, float *y) {
 }
 
 // The one place a token is picked.  Sampling off: k_advance reduces the greedy argmax keys, launch
-// for launch as before.  Sampling on: the sampler's three launches on the logits row, then the
+// for launch as before.  Sampling on: the sampler's three launches on the logits row (six when it draws
+// over the whole vocabulary: the node set of a captured step differs between the two), then the
 // unchanged k_advance on its one key (the p >= n_fixed guard, the RoPE row and the epoch bump stay).
 // enqueue_pick_keys is the pick without the advance (the verify pass picks every row, then advances
 // once over the accepted prefix).
 int enqueue_pick_keys(gemma_engine *e, const float *row, const int *pos, const unsigned long long **keys, int *n_parts) {
     if (!e->sampling) return 0;
     const sample_ws &w = e->smp_ws;
-    if (launch_sample(row, 0, 1, e->cfg.n_vocab, e->smp_dev, pos, nullptr, w, sample_dbg{}, e->stream)) return -1;
+    const int sets = engine_samples_full(e) ? PICKS_FULL : PICKS_TRUNC;
+    if (launch_sample(row, 0, 1, e->cfg.n_vocab, e->smp_dev, pos, nullptr, w, sample_dbg{}, e->stream, sets)) return -1;
     *keys = w.key;
     *n_parts = 1;
     return 0;
@@ -212,7 +214,8 @@ int enqueue_lp_finish(gemma_engine *e, const float *LG, int R, lse_part *own, co
 
 // The picks of a pass's T rows, none advancing: the verify pass then accepts a prefix, the batch pass
 // advances every row's slot.  The launch count does not depend on T: one row-argmax launch (greedy),
-// the sampler's three (sampling), or both (a batch pass whose slots differ), each with the row in grid.y.
+// the sampler's three or six (sampling), or every set some row needs (a batch pass whose slots differ),
+// each with the row in grid.y.
 int pick_buf_alloc(dev_pool &M, pick_buf &b, hipStream_t s) {
     return M.get_zeroed(&b.keys, (size_t)(PICK_MAX_ROWS * 256 + PICK_MAX_ROWS) * 8, s);
 }
@@ -227,7 +230,7 @@ int enqueue_row_picks(gemma_engine *e, const float *LG, int T, const int *pos, c
         set_error("row picks: a pass of " + std::to_string(T) + " rows");
         return -1;
     }
-    if (mix < 0) mix = e->sampling ? PICKS_SAMPLE : PICKS_GREEDY;
+    if (mix < 0) mix = picks_mix(1, e->sampling, engine_samples_full(e));
     if (enqueue_lp_parts(e, LG, T, b.lp_parts)) return -1;  // (the caller's advance is followed by enqueue_lp_finish)
     // every sampling row in its own workspace: the buffer's own (a wide batch's, or a narrow batch's on
     // an engine that has none), else the engine's 8

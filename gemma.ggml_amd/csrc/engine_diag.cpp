@@ -351,11 +351,12 @@ extern "C" int gemma_engine_set_option(gemma_engine *e, const char *name, int va
 // On-device sampling on / off and its parameters (include/gemma_hpc.h).  The parameters live in a
 // device struct the sampler's kernels read, and their launch geometry depends on n_vocab only: a new
 // seed, temperature, top_k or top_p is a stream-ordered copy and the captured graph is kept; only
-// turning sampling on or off changes the node set and drops the graph.
+// turning sampling on or off, or moving between the truncated sampler's three launches and the
+// whole-vocabulary sampler's six (top_k == GEMMA_TOP_K_ALL), changes the node set and drops the graph.
 extern "C" int gemma_engine_set_sampler(gemma_engine *e, const gemma_sampler *sp) {
     set_error("");
     if (sp) {
-        const std::string why = sampler_invalid(*sp);
+        const std::string why = sampler_invalid(*sp, e->cfg.n_vocab);
         if (!why.empty()) {
             set_error("gemma_engine_set_sampler: " + why);
             return -1;
@@ -385,8 +386,9 @@ extern "C" int gemma_engine_set_sampler(gemma_engine *e, const gemma_sampler *sp
         e->smp_host.seed = sp->seed;
         GHIP_CHECK(hipMemcpyAsync(e->smp_dev, &e->smp_host, sizeof(sampler_params), hipMemcpyHostToDevice, e->stream));
     }
+    const bool was_full = engine_samples_full(e);
     e->smp = sp ? *sp : gemma_sampler{0.0f, 0, 1.0f, 0};
-    if (on != e->sampling) {
+    if (on != e->sampling || (on && sampler_full(e->smp) != was_full)) {
         e->sampling = on;
         drop_graph(e);
     }
@@ -462,7 +464,7 @@ extern "C" int gemma_test_logprob(const float *logits, int rows, int n_vocab, co
     return 0;
 }
 
-// Test hook: the sampler's three launches on `rows` host rows of n_vocab logits, row r at sequence
+// Test hook: the sampler's launches (three, or the whole-vocabulary six) on `rows` host rows of n_vocab logits, row r at sequence
 // index positions[r]; the same kernels, scratch and device parameter struct as the engine's step.
 extern "C" int gemma_test_sample(const float *logits, int rows, int n_vocab, const gemma_sampler *sp, const int32_t *positions,
                                  int32_t *tokens, int32_t *cand, int32_t *n_cand, int32_t *n_kept) {
@@ -475,7 +477,7 @@ extern "C" int gemma_test_sample(const float *logits, int rows, int n_vocab, con
         set_error("gemma_test_sample: n_vocab must be >= 1");
         return -1;
     }
-    std::string why = sampler_invalid(*sp);
+    std::string why = sampler_invalid(*sp, n_vocab);
     if (why.empty() && !(sp->temperature > 0.0f)) why = "temperature must be > 0 (the sampler is off otherwise)";
     for (int r = 0; why.empty() && r < rows; ++r)
         if (positions[r] < 0 || positions[r] == INT32_MAX) why = "positions must be in [0, 2^31 - 1)";
@@ -505,7 +507,8 @@ extern "C" int gemma_test_sample(const float *logits, int rows, int n_vocab, con
     for (int r = 0; r < rows; r += chunk) {
         sample_dbg d;
         d.token = dtok + r; d.cand = dcand + (size_t)r * SAMPLE_MAX_K; d.n_cand = dnc + r; d.n_kept = dnk + r;
-        if (launch_sample(dl + (size_t)r * n_vocab, n_vocab, std::min(chunk, rows - r), n_vocab, dp, dpos + r, nullptr, ws, d, nullptr))
+        if (launch_sample(dl + (size_t)r * n_vocab, n_vocab, std::min(chunk, rows - r), n_vocab, dp, dpos + r, nullptr, ws, d, nullptr,
+                          sampler_full(*sp) ? PICKS_FULL : PICKS_TRUNC))
             return -1;
     }
     GHIP_CHECK(hipDeviceSynchronize());
@@ -517,7 +520,8 @@ extern "C" int gemma_test_sample(const float *logits, int rows, int n_vocab, con
 }
 
 // Test hook: gemma_test_sample with one sampler per row, through launch_picks: the launches a batch
-// pass takes for this mix of rows (none sample: the row argmax; all: the sampler's three; else both).
+// pass takes for this mix of rows (picks_mix: the row argmax when some row is greedy, and each sampler's
+// set of launches that some row needs).
 // Every row's token is its pick key reduced as the advance kernels reduce it.
 extern "C" int gemma_test_sample_rows(const float *logits, int rows, int n_vocab, const gemma_sampler *s_of,
                                       const int32_t *positions, int32_t *tokens, int32_t *cand, int32_t *n_cand,
@@ -528,17 +532,18 @@ extern "C" int gemma_test_sample_rows(const float *logits, int rows, int n_vocab
         set_error(fn + ": logits, samplers, positions, rows >= 1 and n_vocab >= 1 are required");
         return -1;
     }
-    int n_sample = 0;
+    int n_sample = 0, n_full = 0;
     for (int r = 0; r < rows; ++r) {
-        std::string why = sampler_invalid(s_of[r]);
+        std::string why = sampler_invalid(s_of[r], n_vocab);
         if (why.empty() && (positions[r] < 0 || positions[r] == INT32_MAX)) why = "positions must be in [0, 2^31 - 1)";
         if (!why.empty()) {
             set_error(fn + ": row " + std::to_string(r) + ": " + why);
             return -1;
         }
         n_sample += s_of[r].temperature > 0.0f;
+        n_full += sampler_full(s_of[r]);
     }
-    const int mix = n_sample == 0 ? PICKS_GREEDY : n_sample == rows ? PICKS_SAMPLE : PICKS_MIXED;
+    const int mix = picks_mix(rows, n_sample, n_full);
     dev_pool tmp;
     sample_ws ws;
     const int chunk = std::min(rows, (int)PICK_MAX_ROWS);

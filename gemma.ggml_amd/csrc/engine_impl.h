@@ -329,6 +329,12 @@ static inline bool row_split(const gemma_engine *e) { return e->tp_n > 1 || e->c
 static inline bool slot_samples(const gemma_engine *e, int slot) {
     return e->bt.smp_own[slot] ? e->bt.smp[slot].temperature > 0.0f : e->sampling;
 }
+// the sampler in force draws over the whole vocabulary (top_k == GEMMA_TOP_K_ALL): the engine's, a slot's
+static inline bool sampler_full(const gemma_sampler &s) { return s.temperature > 0.0f && s.top_k == GEMMA_TOP_K_ALL; }
+static inline bool engine_samples_full(const gemma_engine *e) { return e->sampling && sampler_full(e->smp); }
+static inline bool slot_samples_full(const gemma_engine *e, int slot) {
+    return e->bt.smp_own[slot] ? sampler_full(e->bt.smp[slot]) : engine_samples_full(e);
+}
 
 // attention can hand attn-out the Q8_0 image of its output (per-head form; split form with 32-dim slices)
 static inline bool att_img_ok(const gemma_engine *e) { return e->att_mode == ATTN_PER_HEAD || e->ag.img; }
@@ -395,9 +401,16 @@ static inline rope_row rope_of(const gemma_engine *e) {
 }
 
 // what is wrong with a sampler's fields ("" = valid); the message names the field
-static inline std::string sampler_invalid(const gemma_sampler &s) {
+// (n_vocab: the rows the sampler will see; top_k == GEMMA_TOP_K_ALL, the whole-vocabulary sampler, takes
+// rows of at most 2^23 logits)
+static_assert(GEMMA_TOP_K_ALL == SAMPLE_TOP_K_ALL, "one value on both sides of the C interface");
+static inline std::string sampler_invalid(const gemma_sampler &s, int64_t n_vocab) {
     if (!std::isfinite(s.temperature)) return "temperature is not finite";
-    if (s.top_k < 0 || s.top_k > SAMPLE_MAX_K) return "top_k outside [0, " + std::to_string(SAMPLE_MAX_K) + "]";
+    if (s.top_k == GEMMA_TOP_K_ALL) {
+        if (n_vocab > SAMPLE_FULL_MAX_V) return "top_k = GEMMA_TOP_K_ALL with n_vocab above " + std::to_string(SAMPLE_FULL_MAX_V);
+    } else if (s.top_k < 0 || s.top_k > SAMPLE_MAX_K) {
+        return "top_k outside [0, " + std::to_string(SAMPLE_MAX_K) + "]";
+    }
     if (!std::isfinite(s.top_p) || !(s.top_p > 0.0f) || s.top_p > 1.0f) return "top_p outside (0, 1]";
     return "";
 }
@@ -438,7 +451,7 @@ int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *ke
 int enqueue_pick_keys(gemma_engine *e, const float *row, const int *pos, const unsigned long long **keys, int *n_parts);
 // The pick of every row of a pass: LG [T][n_vocab], T <= 64; the device position word of row t is
 // tab[t].pos when the pass has a row table, else pos + t (its token is that sequence's index *pos_t + 1).
-// Enqueues the sampler's draws (sampling on: three launches) or the row argmaxes (one launch) into b
+// Enqueues the sampler's draws (sampling on: three launches, six over the whole vocabulary) or the row argmaxes (one launch) into b
 // and returns what the advance kernel takes: row t's n_parts keys at keys + t * stride
 struct row_picks {
     const unsigned long long *keys = nullptr;
@@ -455,8 +468,8 @@ int enqueue_lp_finish(gemma_engine *e, const float *LG, int R, lse_part *own, co
                       const int *acc);
 // lp[p0 .. p0 + n) of S into out after one synchronise; fn names the caller in the range error
 int seq_logprobs(gemma_engine *e, const seq_state &S, int p0, int n, double *out, const char *fn);
-// mix: PICKS_GREEDY / _SAMPLE / _MIXED from the caller's mirror of its rows' modes (a batch pass: each row
-// reads its parameters from tab[t].smp); -1: the engine's sampler for every row
+// mix: picks_mix of the caller's mirror of its rows' modes (a batch pass: each row reads its parameters
+// from tab[t].smp); -1: the engine's sampler for every row
 int enqueue_row_picks(gemma_engine *e, const float *LG, int T, const int *pos, const slot_row *tab, const pick_buf &b,
                       row_picks *out, int mix = -1);
 int tok_prepare(gemma_engine *e);

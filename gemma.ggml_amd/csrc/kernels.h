@@ -562,41 +562,66 @@ int launch_bverify_accept(const slot_row *rows, const slot_row *mrows, const bv_
 int launch_bverify_clean(const slot_row *rows, const bv_slot *vs, int P, const int *out, int n_layer, int64_t layer_stride,
                          int ctx, int kvw, hipStream_t s);
 
-// ---- on-device sampling (sample.hip; the rule: include/gemma_hpc.h, DESIGN.md §5b″) ------------
-constexpr int SAMPLE_MAX_K = 1024;  // candidates at most (top_k == 0 means this many)
+// ---- on-device sampling (sample.hip, sample_full.hip; the rules: include/gemma_hpc.h, DESIGN.md §5b″) ----
+constexpr int SAMPLE_MAX_K = 1024;  // candidates at most of the truncated sampler (top_k == 0 means this many)
+constexpr int SAMPLE_TOP_K_ALL = 0x7FFFFFFF;  // top_k of the whole-vocabulary sampler (GEMMA_TOP_K_ALL)
 // (sampler_params, above slot_row: the engine's lives in device memory, a change is a stream-ordered copy)
 constexpr int SAMPLE_WS_HIST = 4096 + 16;  // words of one row's histogram and list cursors
-struct sample_ws {  // scratch of `rows` samplers, one per row of a launch (sample_ws_alloc); the tail
-                    // launch leaves every row's hist and cur zero
+// the whole-vocabulary sampler: a workgroup pass covers SAMPLE_FULL_CHUNK consecutive indices; a row's
+// workspace, in u64: [0] the maximum key (its low word), [2 ..) the mass histograms over the key's top 12,
+// next 10 and last 10 bits, then the kept mass and the kept count of every chunk
+constexpr int SAMPLE_FULL_CHUNK = 2048;
+constexpr int64_t SAMPLE_FULL_MAX_V = 1 << 23;  // 2^23 masses of at most 2^40 each stay below 2^63
+constexpr int SAMPLE_FULL_H1 = 2, SAMPLE_FULL_H2 = SAMPLE_FULL_H1 + 4096, SAMPLE_FULL_H3 = SAMPLE_FULL_H2 + 1024,
+              SAMPLE_FULL_HDR = SAMPLE_FULL_H3 + 1024;
+struct sample_ws {  // scratch of `rows` samplers, one per row of a launch (sample_ws_alloc); a row's last
+                    // launch leaves its hist, cur and the first SAMPLE_FULL_HDR words of its `full` zero
     int rows = 0;
     unsigned *hist = nullptr, *cur = nullptr;  // [rows][SAMPLE_WS_HIST]: key histogram [4096], list cursors [2] (cur = hist + 4096)
-    unsigned long long *list_a = nullptr, *list_b = nullptr;  // [rows][SAMPLE_MAX_K], [rows][cap_b] (key << 32 | ~index)
+    // [rows][SAMPLE_MAX_K], [rows][cap_b] (key << 32 | ~index); a whole-vocabulary row keeps its masses q_i in list_b
+    unsigned long long *list_a = nullptr, *list_b = nullptr;
     int64_t cap_b = 0;                                        // = n_vocab
+    unsigned long long *full = nullptr;  // [rows][full_stride], full_stride = SAMPLE_FULL_HDR + 2 * ceil(n_vocab / SAMPLE_FULL_CHUNK)
+    int64_t full_stride = 0;
     unsigned long long *key = nullptr;  // [rows] the drawn tokens, each one argmax key (launch_advance(key, 1, ...))
 };
 struct sample_dbg {  // optional outputs (tests), per row: token [rows], cand [rows][SAMPLE_MAX_K] (-1 past K), K, m [rows]
+                     // (a whole-vocabulary row: K = n, m = the nucleus size, cand all -1)
     int *token = nullptr, *cand = nullptr, *n_cand = nullptr, *n_kept = nullptr;
 };
-int sample_ws_alloc(dev_pool &mem, sample_ws *w, int64_t n_vocab, hipStream_t s, int rows = 1);  // all four buffers, or none
+int sample_ws_alloc(dev_pool &mem, sample_ws *w, int64_t n_vocab, hipStream_t s, int rows = 1);  // all five buffers, or none
 void sample_ws_free(dev_pool &mem, sample_ws *w);
-// The rows of a pass, three launches in all (grid.y = row): row r's token for sequence index
-// *pos_r + 1 from lg[r * ld .. + n) into w.key[r], in row r's own workspace.  pos_r is tab[r].pos when
-// a row table is given, else pos + r.  prm, pos and tab are device pointers read by the kernels; the
-// geometry depends on n and rows only.
-// Parameters per row: with a row table row r's parameters are tab[r].smp (prm is not read); a row
-// whose temperature is <= 0 is greedy: it leaves all three kernels before its first
-// atomic, its workspace stays zero and its key slot is not written.  key_parts > 1: row r's key slot
-// is w.key + r * key_parts and the tail fills it [pick, 0, 0, ...]: the layout of the row-argmax
+// Which launches a pass's picks take, decided on the host from the samplers of its rows as given:
+//   PICKS_GREEDY  no row samples: the one row-argmax launch, 256 partial keys per row at keys
+//   PICKS_SAMPLE  every row samples: the samplers' launches, one key per row at keys + rows_cap * 256
+//   PICKS_MIXED   both: the row argmax over every row, then the samplers, whose last launch
+//                 overwrites a sampling row's 256 partial keys with [pick, 0 ...]
+// and, or-ed in when some row samples, the sets of sampler launches that some row needs:
+//   PICKS_TRUNC   the truncated sampler's three (sample.hip)
+//   PICKS_FULL    the whole-vocabulary sampler's six (sample_full.hip)
+enum { PICKS_GREEDY = 0, PICKS_SAMPLE = 1, PICKS_MIXED = 2, PICKS_KIND = 3, PICKS_TRUNC = 4, PICKS_FULL = 8 };
+// ... of `rows` rows of which n_sample sample, n_full of those over the whole vocabulary
+static inline int picks_mix(int rows, int n_sample, int n_full) {
+    if (n_sample == 0) return PICKS_GREEDY;
+    return (n_sample == rows ? PICKS_SAMPLE : PICKS_MIXED) | (n_sample > n_full ? PICKS_TRUNC : 0) | (n_full ? PICKS_FULL : 0);
+}
+// The rows of a pass (grid.y = row): row r's token for sequence index *pos_r + 1 from lg[r * ld .. + n)
+// into w.key[r], in row r's own workspace.  pos_r is tab[r].pos when a row table is given, else pos + r.
+// prm, pos and tab are device pointers read by the kernels; the geometry depends on n and rows only.
+// sets: PICKS_TRUNC and / or PICKS_FULL, the launches enqueued: three and / or six.
+// Parameters per row: with a row table row r's parameters are tab[r].smp (prm is not read); every row
+// leaves the kernels of a set that is not its own (a greedy row: both) before its first atomic, its
+// workspace stays zero and its key slot is not written.  Without a table every row has the one
+// sampler *prm, and `sets` names its set alone.  key_parts > 1: row r's key slot
+// is w.key + r * key_parts and the set's last launch fills it [pick, 0, 0, ...]: the layout of the row-argmax
 // partial keys, so an advance kernel reduces greedy and sampling rows of one pass alike.
 int launch_sample(const float *lg, int64_t ld, int rows, int64_t n, const sampler_params *prm, const int *pos,
-                  const slot_row *tab, const sample_ws &w, const sample_dbg &dbg, hipStream_t s, int key_parts = 1);
-// The picks of a pass's rows, one key layout per pass, the launch count by `mix` alone:
-//   PICKS_GREEDY  no row samples: the one row-argmax launch, 256 partial keys per row at keys
-//   PICKS_SAMPLE  every row samples: the sampler's three launches, one key per row at keys + rows_cap * 256
-//   PICKS_MIXED   both, four launches: the row argmax over every row, then the sampler, whose tail
-//                 overwrites a sampling row's 256 partial keys with [pick, 0 ...]
+                  const slot_row *tab, const sample_ws &w, const sample_dbg &dbg, hipStream_t s, int sets, int key_parts = 1);
+// the whole-vocabulary set alone (sample_full.hip; launch_sample checks the arguments)
+int launch_sample_full(const float *lg, int64_t ld, int rows, int64_t n, const sampler_params *prm, const int *pos,
+                       const slot_row *tab, const sample_ws &w, const sample_dbg &dbg, hipStream_t s, int key_parts);
+// The picks of a pass's rows, one key layout per pass, the launches by `mix` alone (picks_mix).
 // keys: [rows_cap * 256 + rows_cap] u64.  out_*: what the advance kernel takes
-enum { PICKS_GREEDY = 0, PICKS_SAMPLE = 1, PICKS_MIXED = 2 };
 int launch_picks(int mix, const float *lg, int64_t ld, int rows, int64_t n, const sampler_params *prm, const int *pos,
                  const slot_row *tab, const sample_ws &w, unsigned long long *keys, int rows_cap, const sample_dbg &dbg,
                  hipStream_t s, const unsigned long long **out_keys, int *out_parts, int *out_stride);

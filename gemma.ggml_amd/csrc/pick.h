@@ -1,5 +1,5 @@
 // pick.h — the token pick on the device, stated once (device inlines only; included by ops.hip,
-// batch.hip, verify.hip, prefill.hip, sample.hip and matvec_impl.h).
+// batch.hip, verify.hip, prefill.hip, sample_impl.h and matvec_impl.h).
 //
 //  * the key: a candidate (value, index) as one u64, (ordered float << 32) | ~index.  "Larger key" is
 //    larger value, then smaller index: the maximum key is the strict '>' argmax whose first maximum

@@ -28,43 +28,29 @@
 // depend on top_k (it is read from the device struct), so only sampling on / off changes a graph.
 #include <algorithm>
 
-#include "kernels.h"
-#include "pick.h"
+#include "sample_impl.h"
 
 namespace ghip {
 namespace {
 
 constexpr int SM_BINS = 4096, SM_SHIFT = 20;  // histogram over the key's top 12 bits
-constexpr int SM_TH = 256, SM_PER = 8, SM_CHUNK = SM_TH * SM_PER;  // logits per workgroup pass
-constexpr int SM_GRID_MAX = 1024;
 constexpr int SM_TAIL = 1024;  // the tail workgroup: one thread per candidate
 constexpr int SM_CAP = 2048;   // entries the tail sorts (>= SAMPLE_MAX_K)
 static_assert(SM_TAIL == SAMPLE_MAX_K && SM_CAP >= SAMPLE_MAX_K && SM_BINS == 16 * SM_TH, "sampler geometry");
 
-// monotone key of a logit: the argmax key's high word (pick.h) with -0 made +0
-__device__ __forceinline__ uint32_t logit_key(float v) {
-    uint32_t u = __builtin_bit_cast(uint32_t, v);
-    if (u == 0x80000000u) u = 0;
-    return ordered_bits(u);
-}
 __device__ __forceinline__ int sample_k(const sampler_params &p, int64_t n) {
     const int k = p.top_k > 0 ? p.top_k : SAMPLE_MAX_K;
     return (int)(n < (int64_t)k ? n : (int64_t)k);
 }
 
-// All three kernels: grid.y = the row of the pass.  A row's logits are lg + row * ld and its
-// workspace the row-th of each sample_ws array; the offsets are wave-uniform (scalar registers).
-// the row's parameters: its table entry's, else the launch's one struct
-__device__ __forceinline__ sampler_params row_params(const sampler_params *prm, const slot_row *tab) {
-    return tab ? tab[blockIdx.y].smp : *prm;
-}
-
+// (logit_key, row_params and the draw's uniform: sample_impl.h, shared with the whole-vocabulary sampler)
 __global__ void __launch_bounds__(SM_TH) k_sample_hist(const float *lg, int64_t ld, int64_t n, const slot_row *tab,
                                                        unsigned *ghist) {
     __shared__ unsigned h[SM_BINS];
     const int tid = threadIdx.x;
-    // a greedy row of a mixed pass leaves here (rows without a table always sample, nothing is read)
-    if (tab && !(tab[blockIdx.y].smp.temperature > 0.0f)) return;
+    // a greedy or whole-vocabulary row of a mixed pass leaves here (rows without a table always sample,
+    // nothing is read)
+    if (tab && !samples_truncated(tab[blockIdx.y].smp)) return;
     const float *row = lg + (int64_t)blockIdx.y * ld;
     ghist += (int64_t)blockIdx.y * SAMPLE_WS_HIST;
     for (int i = tid; i < SM_BINS; i += SM_TH) h[i] = 0;
@@ -97,7 +83,7 @@ __global__ void __launch_bounds__(SM_TH) k_sample_compact(const float *lg, int64
     list_a += r * SAMPLE_MAX_K;
     list_b += r * cap_b;
     const sampler_params P = row_params(prm, tab);
-    if (tab && !(P.temperature > 0.0f)) return;  // a greedy row: before the first barrier and atomic
+    if (tab && !samples_truncated(P)) return;  // a greedy or whole-vocabulary row: before the first barrier and atomic
     const unsigned K = (unsigned)sample_k(P, n);
     // b*: the bin with (entries in bins above it) < K <= (those + its own); thread t owns bins 16t .. 16t+15
     unsigned loc[16], sum = 0;
@@ -165,18 +151,12 @@ __global__ void __launch_bounds__(SM_TH) k_sample_compact(const float *lg, int64
     }
 }
 
-__device__ __forceinline__ uint64_t splitmix64_mix(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 __global__ void __launch_bounds__(SM_TAIL) k_sample_tail(const sampler_params *prm, const int *pos, const slot_row *tab, int64_t n,
                                                          unsigned *ghist, unsigned *cur, const unsigned long long *list_a,
                                                          const unsigned long long *list_b, int64_t cap_b,
                                                          unsigned long long *key_out, int key_parts, sample_dbg dbg) {
     const sampler_params P = row_params(prm, tab);
-    if (tab && !(P.temperature > 0.0f)) return;  // a greedy row: workspace and key slot untouched
+    if (tab && !samples_truncated(P)) return;  // a greedy or whole-vocabulary row: workspace and key slot untouched
     {  // this row's position word, workspace, key slot and debug outputs
         const int64_t r = blockIdx.y;
         pos = tab ? tab[r].pos : pos + r;
@@ -316,9 +296,7 @@ __global__ void __launch_bounds__(SM_TAIL) k_sample_tail(const sampler_params *p
     const int m = s_m;
     if (tid == 0) s_j = m - 1;
     __syncthreads();
-    const uint64_t z = P.seed + (uint64_t)(int64_t)(p + 1) * 0x9E3779B97F4A7C15ull;
-    const double u = (double)(splitmix64_mix(z) >> 11) * 0x1.0p-53;
-    const double r = u * cs[m - 1];
+    const double r = draw_uniform(P.seed, p) * cs[m - 1];
     if (tid < m && c_i > r && (tid == 0 || cs[tid - 1] <= r)) s_j = tid;
     __syncthreads();
     const unsigned long long pick = ks[s_j];
@@ -341,9 +319,11 @@ int sample_ws_alloc(dev_pool &mem, sample_ws *w, int64_t n_vocab, hipStream_t s,
     }
     *w = sample_ws{};
     w->cap_b = n_vocab;
+    w->full_stride = SAMPLE_FULL_HDR + 2 * ((n_vocab + SAMPLE_FULL_CHUNK - 1) / SAMPLE_FULL_CHUNK);
     const size_t R = (size_t)rows;
     if (mem.get_zeroed(&w->hist, R * SAMPLE_WS_HIST * 4, s) || mem.get(&w->list_a, R * SAMPLE_MAX_K * 8) ||
-        mem.get(&w->list_b, R * (size_t)n_vocab * 8) || mem.get_zeroed(&w->key, R * 8, s)) {
+        mem.get(&w->list_b, R * (size_t)n_vocab * 8) || mem.get_zeroed(&w->full, R * (size_t)w->full_stride * 8, s) ||
+        mem.get_zeroed(&w->key, R * 8, s)) {
         sample_ws_free(mem, w);
         return -1;
     }
@@ -356,44 +336,54 @@ void sample_ws_free(dev_pool &mem, sample_ws *w) {
     mem.put(w->hist);
     mem.put(w->list_a);
     mem.put(w->list_b);
+    mem.put(w->full);
     mem.put(w->key);
     *w = sample_ws{};
 }
 
 int launch_sample(const float *lg, int64_t ld, int rows, int64_t n, const sampler_params *prm, const int *pos,
-                  const slot_row *tab, const sample_ws &w, const sample_dbg &dbg, hipStream_t s, int key_parts) {
+                  const slot_row *tab, const sample_ws &w, const sample_dbg &dbg, hipStream_t s, int sets, int key_parts) {
     if (!w.hist || n <= 0 || n > w.cap_b || rows < 1 || rows > w.rows || (!pos && !tab) || (!prm && !tab) || key_parts < 1 ||
-        key_parts > SM_TAIL) {
+        key_parts > SM_TAIL || !(sets & (PICKS_TRUNC | PICKS_FULL))) {
         set_error("sampler: scratch not sized for these rows");
         return -1;
     }
-    const int grid = (int)std::min<int64_t>((n + SM_CHUNK - 1) / SM_CHUNK, SM_GRID_MAX);
-    hipLaunchKernelGGL(k_sample_hist, dim3(grid, rows), dim3(SM_TH), 0, s, lg, ld, n, tab, w.hist);
-    hipLaunchKernelGGL(k_sample_compact, dim3(grid, rows), dim3(SM_TH), 0, s, lg, ld, n, prm, tab, (const unsigned *)w.hist,
-                       w.cur, w.list_a, w.list_b, w.cap_b);
-    hipLaunchKernelGGL(k_sample_tail, dim3(1, rows), dim3(SM_TAIL), 0, s, prm, pos, tab, n, w.hist, w.cur,
-                       (const unsigned long long *)w.list_a, (const unsigned long long *)w.list_b, w.cap_b, w.key, key_parts, dbg);
-    GHIP_CHECK(hipGetLastError());
+    if ((sets & PICKS_FULL) && n > SAMPLE_FULL_MAX_V) {
+        set_error("sampler: the whole-vocabulary sampler takes rows of at most 2^23 logits");
+        return -1;
+    }
+    if (sets & PICKS_TRUNC) {
+        const int grid = (int)std::min<int64_t>((n + SM_CHUNK - 1) / SM_CHUNK, SM_GRID_MAX);
+        hipLaunchKernelGGL(k_sample_hist, dim3(grid, rows), dim3(SM_TH), 0, s, lg, ld, n, tab, w.hist);
+        hipLaunchKernelGGL(k_sample_compact, dim3(grid, rows), dim3(SM_TH), 0, s, lg, ld, n, prm, tab, (const unsigned *)w.hist,
+                           w.cur, w.list_a, w.list_b, w.cap_b);
+        hipLaunchKernelGGL(k_sample_tail, dim3(1, rows), dim3(SM_TAIL), 0, s, prm, pos, tab, n, w.hist, w.cur,
+                           (const unsigned long long *)w.list_a, (const unsigned long long *)w.list_b, w.cap_b, w.key, key_parts, dbg);
+        GHIP_CHECK(hipGetLastError());
+    }
+    if (sets & PICKS_FULL) return launch_sample_full(lg, ld, rows, n, prm, pos, tab, w, dbg, s, key_parts);
     return 0;
 }
 
 int launch_picks(int mix, const float *lg, int64_t ld, int rows, int64_t n, const sampler_params *prm, const int *pos,
                  const slot_row *tab, const sample_ws &w, unsigned long long *keys, int rows_cap, const sample_dbg &dbg,
                  hipStream_t s, const unsigned long long **out_keys, int *out_parts, int *out_stride) {
-    if (!keys || rows < 1 || rows > rows_cap || mix < PICKS_GREEDY || mix > PICKS_MIXED) {
+    const int kind = mix & PICKS_KIND, sets = mix & (PICKS_TRUNC | PICKS_FULL);
+    if (!keys || rows < 1 || rows > rows_cap || mix < 0 || kind > PICKS_MIXED || mix != (kind | sets) ||
+        (kind == PICKS_GREEDY) != (sets == 0)) {
         set_error("picks: no key buffer, or a pass outside its rows");
         return -1;
     }
     constexpr int PARTS = 256;  // the row argmax's partial keys per row
-    if (mix != PICKS_SAMPLE && launch_row_argmax(lg, n, keys, PARTS, s, rows, ld)) return -1;
-    if (mix == PICKS_GREEDY || mix == PICKS_MIXED) {
+    if (kind != PICKS_SAMPLE && launch_row_argmax(lg, n, keys, PARTS, s, rows, ld)) return -1;
+    if (kind == PICKS_GREEDY || kind == PICKS_MIXED) {
         *out_keys = keys; *out_parts = PARTS; *out_stride = PARTS;
     }
-    if (mix == PICKS_GREEDY) return 0;
+    if (kind == PICKS_GREEDY) return 0;
     sample_ws v = w;
-    v.key = mix == PICKS_MIXED ? keys : keys + (size_t)rows_cap * PARTS;
-    if (launch_sample(lg, ld, rows, n, prm, pos, tab, v, dbg, s, mix == PICKS_MIXED ? PARTS : 1)) return -1;
-    if (mix == PICKS_SAMPLE) {
+    v.key = kind == PICKS_MIXED ? keys : keys + (size_t)rows_cap * PARTS;
+    if (launch_sample(lg, ld, rows, n, prm, pos, tab, v, dbg, s, sets, kind == PICKS_MIXED ? PARTS : 1)) return -1;
+    if (kind == PICKS_SAMPLE) {
         *out_keys = v.key; *out_parts = 1; *out_stride = 1;
     }
     return 0;

@@ -73,6 +73,7 @@ class GemmaSampler(C.Structure):
 
 
 SAMPLE_MAX_K = 1024  # candidates at most (top_k == 0 means this many)
+TOP_K_ALL = 0x7FFFFFFF  # top_k of the whole-vocabulary sampler (GEMMA_TOP_K_ALL): every entry a candidate, nothing sorted
 VERIFY_MAX_DRAFT = 7  # include/gemma_hpc.h GEMMA_VERIFY_MAX_DRAFT
 BATCH_MAX_SLOTS = 8   # include/gemma_hpc.h GEMMA_BATCH_MAX_SLOTS
 BATCH_WIDE_MAX_SLOTS = 64  # include/gemma_hpc.h GEMMA_BATCH_WIDE_MAX_SLOTS
@@ -643,7 +644,8 @@ class Engine:
     def set_sampler(self, temperature=0.0, top_k=0, top_p=1.0, seed=0):
         """Seeded temperature / top-k / top-p sampling inside the decode step (include/gemma_hpc.h
         has the rule).  temperature <= 0 or None: greedy, the default.  top_k 0 = 1024 candidates
-        (the most there are).  A change of parameters keeps the captured graph; on / off drops it."""
+        (the most the truncated rule takes), TOP_K_ALL = the whole-vocabulary sampler (temperature and
+        top_p over every entry of the row).  A change of parameters keeps the captured graph; on / off drops it."""
         if temperature is None:
             r = self.L.gemma_engine_set_sampler(self.h, None)
         else:
@@ -750,7 +752,8 @@ class Engine:
 def test_sample(rows, sampler, positions):
     """The sampler's kernels on host logits rows [R][V] (gemma_test_sample): row r is drawn at sequence
     index positions[r].  sampler: dict(temperature, top_k, top_p, seed).  Returns (tokens [R],
-    cand [R][1024] candidate ids in order with -1 past K, n_cand [R] = K, n_kept [R] = m);
+    cand [R][1024] candidate ids in order with -1 past K, n_cand [R] = K, n_kept [R] = m; with
+    top_k = TOP_K_ALL: cand all -1, n_cand = V, n_kept = the nucleus size);
     raises RuntimeError with the library's message on a refused argument."""
     x = np.ascontiguousarray(rows, dtype=np.float32)
     if x.ndim == 1:

@@ -156,15 +156,39 @@ int gemma_engine_prefill_next(gemma_engine *e, int n, int exact, float *logits_l
  * not on call count, graph or eager, batching, or a rewind.  Steps, prefill and prefill_next all pick
  * through it; given (prompt) positions are never overwritten.
  * Changing the parameters of a running sampler is a stream-ordered copy and keeps the captured decode
- * graph (the launch geometry does not depend on top_k); turning sampling on or off drops it. */
+ * graph (the launch geometry does not depend on top_k); turning sampling on or off drops it.
+ *
+ * top_k == GEMMA_TOP_K_ALL: the whole-vocabulary sampler, another rule (V <= 2^23): every entry of the
+ * row is a candidate, nothing is sorted and nothing is truncated, so top_p cuts the model's own
+ * tempered distribution.
+ *  1. key_i = the monotone u32 key of l_i (the float's bits made to order as the float does, -0 folded
+ *     into +0); l_max = the logit of the largest key.
+ *  2. q_i = (u64) floor(exp(((double)l_i - (double)l_max) / (double)temperature) * 2^40): the maximum
+ *     has q = 2^40; an entry more than about 27.7 * temperature below it has mass 0, as has -inf.
+ *     W = sum_i q_i, an exact integer below 2^63.
+ *  3. the threshold key t: top_p == 1: t = 0, every entry is kept.  Else P = max((u64)((double)top_p *
+ *     (double)W), 1) and t = the largest key value with sum_{key_i >= t} q_i >= P.  The nucleus is N =
+ *     {i : key_i >= t}: a run of equal logits at the boundary is kept whole, there is no tie-break by
+ *     index.  M = sum_{i in N} q_i.
+ *  4. u as above; r = min((u64)(u * (double)M), M - 1); the token is the smallest index j in N whose
+ *     prefix sum in index order satisfies sum_{i in N, i <= j} q_i > r.
+ * After the exp everything is integer arithmetic: the draw depends on the row and the parameters only.
+ * The draw walks the entries in index order, not in sorted order as the truncated rule does: the
+ * distribution is the same, the token a given (seed, p) yields is not.  Rows with a NaN or whose
+ * maximum is -inf are outside the contract.  Inside this mode a change of temperature, top_p or seed
+ * keeps the captured decode graph; entering or leaving it (six launches a token in place of three)
+ * drops it, as turning sampling on or off does. */
+#define GEMMA_TOP_K_ALL 0x7FFFFFFF
 typedef struct gemma_sampler { float temperature; int top_k; float top_p; uint64_t seed; } gemma_sampler;
 /* NULL or temperature <= 0: greedy (the default).  -1 + hpc_last_error, state untouched, on
- * top_k outside [0, 1024], top_p outside (0, 1], a non-finite field, or a row-split engine. */
+ * top_k outside [0, 1024] and not GEMMA_TOP_K_ALL (or that with n_vocab above 2^23), top_p outside
+ * (0, 1], a non-finite field, or a row-split engine. */
 int gemma_engine_set_sampler(gemma_engine *e, const gemma_sampler *s);
 int gemma_engine_sampler(const gemma_engine *e, gemma_sampler *out);   /* 1 = sampling on, 0 = greedy */
 /* per-op test entry: the sampler on host rows.  positions[r] = the p of row r.  Outputs (any may be
  * NULL): tokens[rows]; cand[rows][1024] candidate ids in order, -1 past K; n_cand[rows] = K;
- * n_kept[rows] = m */
+ * n_kept[rows] = m.  top_k == GEMMA_TOP_K_ALL: n_cand = V, n_kept = |N| and cand all -1 (there is no
+ * ordered list) */
 int gemma_test_sample(const float *logits, int rows, int n_vocab, const gemma_sampler *s,
                       const int32_t *positions, int32_t *tokens, int32_t *cand, int32_t *n_cand, int32_t *n_kept);
 /* the same with one sampler per row, s_of[rows], all rows through one set of launches (those of a batch
@@ -318,7 +342,9 @@ int gemma_engine_kv_read(gemma_engine *e, int layer, int p0, int n, uint16_t *k_
  * slot's pick is the engine's greedy pick as it stands, not the sampler with top_k = 1: the two orders
  * differ on a signed-zero tie (the sampler's key folds -0 into +0, the argmax key does not).
  * The pick launches of a pass depend on the mix alone, decided on the host: no participating slot
- * samples, the one row-argmax launch; all sample, the sampler's three; else both, four. */
+ * samples, the one row-argmax launch; all sample, the sampler's three (the whole-vocabulary sampler's
+ * six; both sets when slots of both kinds take part, every row leaving the set that is not its own);
+ * else the row argmax and those. */
 #define GEMMA_BATCH_MAX_SLOTS 8
 #define GEMMA_BATCH_WIDE_MAX_SLOTS 64
 int gemma_engine_batch_open(gemma_engine *e, int n_slots);

@@ -1,18 +1,19 @@
 """What on-device sampling costs: Gemma-2B Q4_0 (synthetic weights, the BASELINE config 2 shape),
 one engine, one process.
 
-    python scripts/sample_bench.py [--steps 512] [--reps 3] [--prompt 128] [--legs greedy,k40,k1024,host]
+    python scripts/sample_bench.py [--steps 512] [--reps 3] [--prompt 128] [--legs greedy,k40,k1024,all,host]
 
 Legs, alternated `reps` times, each from the same state (begin, the prompt and 8 warm-up steps by
 graph replay, then `steps` timed graph replays with no host sync in between):
     greedy   the default: k_advance on the logits launch's argmax keys
     k40      set_sampler(T = 0.8, top_k = 40, top_p = 0.95)
     k1024    set_sampler(T = 0.8, top_k = 1024, top_p = 1)
+    all      set_sampler(T = 0.8, top_k = TOP_K_ALL, top_p = 0.95): the whole-vocabulary sampler
     host     the only way to sample without the feature: step(1, want_logits) per token, a numpy draw
              on the host (T = 0.8, top_k = 40, top_p = 0.95), the token fed back through extend()
 Prints one line per timed leg and a JSON summary (tok/s median and spread, launches per token).
 Under `rocprofv3 --kernel-trace --stats` run one short sampled leg (--legs k40 --reps 1 --steps 64):
-the k_sample_* rows of the kernel stats are the sampler's own time."""
+the k_sample_* (leg all: k_full_*) rows of the kernel stats are the sampler's own time."""
 import argparse
 import json
 import os
@@ -30,7 +31,8 @@ import gemma_hip as G  # noqa: E402
 from bench import GEMMA_2B, make_prompt  # noqa: E402
 
 SAMPLERS = {"greedy": None, "k40": dict(temperature=0.8, top_k=40, top_p=0.95, seed=1),
-            "k1024": dict(temperature=0.8, top_k=1024, top_p=1.0, seed=1)}
+            "k1024": dict(temperature=0.8, top_k=1024, top_p=1.0, seed=1),
+            "all": dict(temperature=0.8, top_k=G.TOP_K_ALL, top_p=0.95, seed=1)}
 
 
 def host_draw(row, rng, temperature=0.8, top_k=40, top_p=0.95):
@@ -49,7 +51,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--legs", default="greedy,k40,k1024,host")
+    ap.add_argument("--legs", default="greedy,k40,k1024,all,host")
     ap.add_argument("--no-tune", action="store_true")
     args = ap.parse_args()
     legs = args.legs.split(",")
