@@ -783,6 +783,21 @@ int seq_alloc(gemma_engine *e, dev_pool &M, seq_state &S, bool caches, int *toke
     return token_word ? 0 : M.get_zeroed(&S.token, 4, s);
 }
 
+// all-ones bytes from sequence index `from` on: token -1 and an f64 NaN, "no alternatives"
+static int seq_alt_clear(gemma_engine *e, seq_state &S, int from) {
+    if (!S.alt_tok) return 0;
+    const size_t o = (size_t)from * GEMMA_TOP_LOGPROBS_MAX, cnt = (size_t)(e->cfg.n_ctx + 1 - from) * GEMMA_TOP_LOGPROBS_MAX;
+    GHIP_CHECK(hipMemsetAsync(S.alt_tok + o, 0xFF, cnt * 4, e->stream));
+    GHIP_CHECK(hipMemsetAsync(S.alt_lp + o, 0xFF, cnt * 8, e->stream));
+    return 0;
+}
+
+int seq_alt_alloc(gemma_engine *e, dev_pool &M, seq_state &S) {
+    const gemma_hip_config &c = e->cfg;
+    if (M.get(&S.alt_tok, (size_t)(c.n_ctx + 1) * GEMMA_TOP_LOGPROBS_MAX * 4) || M.get(&S.alt_lp, (size_t)(c.n_ctx + 1) * GEMMA_TOP_LOGPROBS_MAX * 8)) return -1;
+    return seq_alt_clear(e, S, 0);
+}
+
 int seq_begin(gemma_engine *e, seq_state &S, const int32_t *tokens, int n) {
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
@@ -798,6 +813,7 @@ int seq_begin(gemma_engine *e, seq_state &S, const int32_t *tokens, int n) {
     GHIP_CHECK(hipMemsetAsync(S.hist, 0, (size_t)(c.n_ctx + 1) * 4, s));
     GHIP_CHECK(hipMemcpyAsync(S.hist, tokens, (size_t)n * 4, hipMemcpyHostToDevice, s));
     GHIP_CHECK(hipMemsetAsync(S.lp, 0xFF, (size_t)(c.n_ctx + 1) * 8, s));  // all-ones bytes: an f64 NaN, "not scored"
+    if (seq_alt_clear(e, S, 0)) return -1;
     GHIP_CHECK(hipMemsetAsync(S.pos, 0, 4, s));
     const size_t half = (size_t)c.head_dim / 2;  // RoPE row of position 0
     GHIP_CHECK(hipMemcpyAsync(S.rope, e->rope_cos, half * 4, hipMemcpyDeviceToDevice, s));
@@ -820,6 +836,10 @@ int seq_copy(gemma_engine *e, seq_state &dst, const seq_state &src) {
     }
     GHIP_CHECK(hipMemcpyAsync(dst.hist, src.hist, (size_t)(c.n_ctx + 1) * 4, hipMemcpyDeviceToDevice, s));
     GHIP_CHECK(hipMemcpyAsync(dst.lp, src.lp, (size_t)(c.n_ctx + 1) * 8, hipMemcpyDeviceToDevice, s));
+    if (dst.alt_tok && src.alt_tok) {  // (a destination with alternatives has a source with them: the setting is fixed while a batch is open)
+        GHIP_CHECK(hipMemcpyAsync(dst.alt_tok, src.alt_tok, (size_t)(c.n_ctx + 1) * GEMMA_TOP_LOGPROBS_MAX * 4, hipMemcpyDeviceToDevice, s));
+        GHIP_CHECK(hipMemcpyAsync(dst.alt_lp, src.alt_lp, (size_t)(c.n_ctx + 1) * GEMMA_TOP_LOGPROBS_MAX * 8, hipMemcpyDeviceToDevice, s));
+    }
     GHIP_CHECK(hipMemcpyAsync(dst.pos, src.pos, 4, hipMemcpyDeviceToDevice, s));
     GHIP_CHECK(hipMemcpyAsync(dst.nfix, src.nfix, 4, hipMemcpyDeviceToDevice, s));
     GHIP_CHECK(hipMemcpyAsync(dst.token, src.hist + src.host_pos, 4, hipMemcpyDeviceToDevice, s));
@@ -857,6 +877,34 @@ int seq_logprobs(gemma_engine *e, const seq_state &S, int p0, int n, double *out
     (void)hipSetDevice(e->device);
     GHIP_CHECK(hipStreamSynchronize(e->stream));
     if (n) GHIP_CHECK(hipMemcpy(out, S.lp + p0, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return n;
+}
+
+int seq_top_logprobs(gemma_engine *e, const seq_state &S, int p0, int n, int32_t *tokens, double *lps, const char *fn) {
+    if (!e->top_lp || !S.alt_tok) {
+        set_error(std::string(fn) + ": the alternatives are off (gemma_engine_set_top_logprobs)");
+        return -1;
+    }
+    const int n_seq = std::max(S.host_pos + 1, S.n_given);
+    if (p0 < 0 || n < 0 || (int64_t)p0 + n > n_seq || (n > 0 && (!tokens || !lps))) {
+        set_error(std::string(fn) + ": [" + std::to_string(p0) + ", " + std::to_string((int64_t)p0 + n) + ") outside [0, n_seq = " +
+                  std::to_string(n_seq) + "), or a null buffer");
+        return -1;
+    }
+    (void)hipSetDevice(e->device);
+    GHIP_CHECK(hipStreamSynchronize(e->stream));
+    if (!n) return 0;
+    // the device keeps GEMMA_TOP_LOGPROBS_MAX entries per index, the caller gets the first top_lp of each: one
+    // contiguous copy per array, narrowed here (a pitched copy goes row by row: 28 ms for 2,047 indices)
+    const size_t w = (size_t)e->top_lp, W = GEMMA_TOP_LOGPROBS_MAX, o = (size_t)p0 * W;
+    std::vector<int32_t> ht((size_t)n * W);
+    std::vector<double> hl((size_t)n * W);
+    GHIP_CHECK(hipMemcpy(ht.data(), S.alt_tok + o, ht.size() * 4, hipMemcpyDeviceToHost));
+    GHIP_CHECK(hipMemcpy(hl.data(), S.alt_lp + o, hl.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < (size_t)n; ++i) {
+        memcpy(tokens + i * w, ht.data() + i * W, w * 4);
+        memcpy(lps + i * w, hl.data() + i * W, w * 8);
+    }
     return n;
 }
 
@@ -910,6 +958,7 @@ extern "C" int gemma_engine_extend(gemma_engine *e, int keep, const int32_t *tok
     GHIP_CHECK(hipMemcpyAsync(e->seq.hist + keep, tokens, (size_t)n * 4, hipMemcpyHostToDevice, s));
     // row keep - 1 is not recomputed: lp[keep] is "not scored" with everything behind it
     GHIP_CHECK(hipMemsetAsync(e->seq.lp + keep, 0xFF, (ctx + 1 - (size_t)keep) * 8, s));
+    if (seq_alt_clear(e, e->seq, keep)) return -1;
     GHIP_CHECK(hipMemsetAsync(e->key, 0, (size_t)e->grid_big * 8, s));
     // *pos = keep, its RoPE row with the position word, *n_fixed = keep + n, the epoch bump
     if (launch_set_position(tokens[0], keep, e->seq.pos, e->seq.hist, e->seq.nfix, keep + n, rope_of(e), s)) return -1;
@@ -1000,6 +1049,11 @@ extern "C" int gemma_engine_tokens(gemma_engine *e, int32_t *out, int cap) {
 }
 
 extern "C" int gemma_engine_pos(gemma_engine *e) { return e->seq.host_pos; }
+
+extern "C" int gemma_engine_top_logprobs(gemma_engine *e, int p0, int cnt, int32_t *tokens, double *lps) {
+    set_error("");
+    return seq_top_logprobs(e, e->seq, p0, cnt, tokens, lps, "gemma_engine_top_logprobs");
+}
 
 extern "C" int gemma_engine_logprobs(gemma_engine *e, int p0, int n, double *out) {
     set_error("");

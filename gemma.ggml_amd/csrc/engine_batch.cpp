@@ -105,7 +105,8 @@ static int batch_open(gemma_engine *e, int n_slots, int max_slots, int rows, con
     const size_t rope_words = (size_t)e->cfg.head_dim + 4;
     const size_t mtab = NS * (sizeof(slot_row) + sizeof(row_src) + sizeof(slot_span));
     bool bad = batch_scratch_alloc(e, rows) != 0 || M.get_zeroed(&b.last, NS * 4, s);
-    for (int i = 0; i < n_slots && !bad; ++i) bad = seq_alloc(e, M, b.slot[i], true, b.last + i) != 0;
+    for (int i = 0; i < n_slots && !bad; ++i)  // (the alternatives: by the setting now, which cannot change while the batch is open)
+        bad = seq_alloc(e, M, b.slot[i], true, b.last + i) != 0 || (e->top_lp && seq_alt_alloc(e, M, b.slot[i]));
     bad = bad || M.get_zeroed(&b.rows, NS * sizeof(slot_row), s) || M.get_zeroed(&b.row_tok, NS * 4, s) ||
           pick_buf_alloc(M, b.picks, s) || M.get(&b.stage, NS * sizeof(slot_row), MEM_PINNED) ||
           // more rows than the engine's sampler has workspaces: the batch brings its own, one per row
@@ -292,7 +293,7 @@ static slot_row batch_row(const gemma_engine *e, int slot, int t, bool own) {
     r.kc = S.kc; r.vc = S.vc;
     r.rope = own ? b.mrope + (size_t)t * (e->cfg.head_dim + 4) : S.rope;
     r.pos = own ? (int *)(r.rope + e->cfg.head_dim) : S.pos;  // a RoPE row ends with its position word
-    r.hist = S.hist; r.nfix = S.nfix; r.last = S.token; r.lp = S.lp;
+    r.hist = S.hist; r.nfix = S.nfix; r.last = S.token; r.lp = S.lp; r.alt_tok = S.alt_tok; r.alt_lp = S.alt_lp;
     r.smp = slot_params(e, slot);
     return r;
 }
@@ -693,6 +694,16 @@ extern "C" int gemma_engine_batch_kv_read(gemma_engine *e, int slot, int layer, 
     set_error("");
     if (!slot_ok(e, slot, "gemma_engine_batch_kv_read")) return -1;
     return seq_kv_read(e, e->bt.slot[slot], layer, p0, n, k_rows, v_rows, "gemma_engine_batch_kv_read");
+}
+
+extern "C" int gemma_engine_batch_top_logprobs(gemma_engine *e, int slot, int p0, int cnt, int32_t *tokens, double *lps) {
+    set_error("");
+    if (!slot_ok(e, slot, "gemma_engine_batch_top_logprobs")) return -1;
+    if (!e->bt.slot[slot].active) {
+        set_error("gemma_engine_batch_top_logprobs: slot " + std::to_string(slot) + " is not active");
+        return -1;
+    }
+    return seq_top_logprobs(e, e->bt.slot[slot], p0, cnt, tokens, lps, "gemma_engine_batch_top_logprobs");
 }
 
 extern "C" int gemma_engine_batch_logprobs(gemma_engine *e, int slot, int p0, int n, double *out) {

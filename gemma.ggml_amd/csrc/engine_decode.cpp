@@ -177,7 +177,7 @@ int enqueue_pick_keys(gemma_engine *e, const float *row, const int *pos, const u
 }
 
 int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *keys, int n_parts, const float *rows0, int R,
-                 lse_part *own) {
+                 lp_scratch own) {
     if (!rows0) { rows0 = row; R = 1; }
     if (enqueue_lp_parts(e, rows0, R, own)) return -1;
     if (enqueue_pick_keys(e, row, e->seq.pos, &keys, &n_parts)) return -1;
@@ -187,29 +187,38 @@ int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *ke
 
 // The log-probabilities of a pass's rows (logprob.hip): the partials need the rows only and go right
 // behind the logits launch; the finish reads the token the advance settled.  Off: nothing is launched.
-static lse_part *lp_parts_of(gemma_engine *e, int R, lse_part *own) {
-    if (own) return own;
-    if (R <= GEMM_SKINNY_MAX_T && e->lp_parts) return e->lp_parts;
+// With the alternatives on (toplogprob.hip) each of the two is followed by its twin, k_topn_parts and
+// k_topn_finish, on the candidate scratch that sits beside the partials.
+static bool lp_scratch_of(gemma_engine *e, int R, lp_scratch own, lp_scratch *out) {
+    *out = own.parts ? own : e->lp_parts;
+    if ((own.parts || R <= GEMM_SKINNY_MAX_T) && out->parts && (!e->top_lp || out->top)) return true;
     set_error("logprobs: no partials for a pass of " + std::to_string(R) + " rows");
-    return nullptr;
+    return false;
 }
 
-int enqueue_lp_parts(gemma_engine *e, const float *LG, int R, lse_part *own) {
+int enqueue_lp_parts(gemma_engine *e, const float *LG, int R, lp_scratch own) {
     if (!e->logprobs) return 0;
-    lse_part *parts = lp_parts_of(e, R, own);
-    return parts ? launch_lse_parts(LG, e->cfg.n_vocab, R, e->cfg.n_vocab, parts, e->stream) : -1;
+    const int64_t V = e->cfg.n_vocab;
+    lp_scratch w;
+    if (!lp_scratch_of(e, R, own, &w) || launch_lse_parts(LG, V, R, V, w.parts, e->stream)) return -1;
+    return e->top_lp ? launch_topn_parts(LG, V, R, V, e->top_lp, w.top, e->stream) : 0;
 }
 
-int enqueue_lp_finish(gemma_engine *e, const float *LG, int R, lse_part *own, const seq_state *S, const slot_row *tab,
+int enqueue_lp_finish(gemma_engine *e, const float *LG, int R, lp_scratch own, const seq_state *S, const slot_row *tab,
                       const int *acc) {
     if (!e->logprobs) return 0;
+    lp_scratch w;
+    if (!lp_scratch_of(e, R, own, &w)) return -1;
     lse_finish_args a;
     a.lg = LG; a.ld = e->cfg.n_vocab; a.n = e->cfg.n_vocab; a.R = R; a.G = lse_grid(e->cfg.n_vocab); a.n_ctx = e->cfg.n_ctx;
-    a.parts = lp_parts_of(e, R, own);
-    if (!a.parts) return -1;
+    a.parts = w.parts;
     a.tab = tab; a.acc = acc;
-    if (S) { a.pos = S->pos; a.hist = S->hist; a.lp = S->lp; }
-    return launch_lse_finish(a, e->stream);
+    if (S) { a.pos = S->pos; a.hist = S->hist; a.lp = S->lp; a.alt_tok = S->alt_tok; a.alt_lp = S->alt_lp; }
+    if (launch_lse_finish(a, e->stream)) return -1;
+    if (!e->top_lp) return 0;
+    topn_finish_args t;
+    t.l = a; t.tparts = w.top; t.Gt = topn_grid(e->cfg.n_vocab); t.top = e->top_lp;
+    return launch_topn_finish(t, e->stream);
 }
 
 // The picks of a pass's T rows, none advancing: the verify pass then accepts a prefix, the batch pass

@@ -417,14 +417,93 @@ extern "C" int gemma_engine_set_logprobs(gemma_engine *e, int on) {
         return -1;
     }
     (void)hipSetDevice(e->device);
-    if (on && !e->lp_parts &&
-        e->mem.get(&e->lp_parts, (size_t)GEMM_SKINNY_MAX_T * lse_grid(e->cfg.n_vocab) * sizeof(lse_part)))
+    if (on && !e->lp_parts.parts &&
+        e->mem.get(&e->lp_parts.parts, (size_t)GEMM_SKINNY_MAX_T * lse_grid(e->cfg.n_vocab) * sizeof(lse_part)))
         return -1;
+    if (!on && e->top_lp && gemma_engine_set_top_logprobs(e, 0) < 0) return -1;  // the alternatives need them
     if ((on != 0) != e->logprobs) {
         e->logprobs = on != 0;
         drop_graph(e);
     }
     return e->logprobs ? 1 : 0;
+}
+
+// The n most likely tokens of every scored position (include/gemma_hpc.h), 0 = off.  On adds k_topn_parts
+// and k_topn_finish behind the log-probability pair; n is a kernel argument, so any change drops the
+// decode graph.  Made when first turned on and kept, sized for GEMMA_TOP_LOGPROBS_MAX (the captured graph
+// holds them): the engine's 8 rows of candidates and its own sequence's alternatives.  A batch's slots
+// and a wide batch's candidates are made at batch_open by the setting then, so it stays while one is open.
+extern "C" int gemma_engine_set_top_logprobs(gemma_engine *e, int n) {
+    set_error("");
+    const std::string fn = "gemma_engine_set_top_logprobs";
+    if (n < 0) return e->top_lp;
+    if (n > GEMMA_TOP_LOGPROBS_MAX) {
+        set_error(fn + ": n = " + std::to_string(n) + " outside [0, " + std::to_string(GEMMA_TOP_LOGPROBS_MAX) + "]");
+        return -1;
+    }
+    if (n == e->top_lp) return n;
+    if (n && row_split(e)) {
+        set_error(fn + ": row-split engines hold a vocabulary shard per rank (single-GPU engines only)");
+        return -1;
+    }
+    if (n && !e->logprobs) {
+        set_error(fn + ": the alternatives come with the log-probabilities: turn those on first (gemma_engine_set_logprobs)");
+        return -1;
+    }
+    if (e->bt.open) {
+        set_error(fn + ": a batch is open: its slots were made for the setting it was opened with (gemma_engine_batch_close)");
+        return -1;
+    }
+    (void)hipSetDevice(e->device);
+    if (n && !e->lp_parts.top &&
+        e->mem.get(&e->lp_parts.top, (size_t)GEMM_SKINNY_MAX_T * topn_grid(e->cfg.n_vocab) * GEMMA_TOP_LOGPROBS_MAX * 8))
+        return -1;
+    if (n && !e->seq.alt_tok) {
+        if (seq_alt_alloc(e, e->mem, e->seq)) return -1;
+        GHIP_CHECK(hipStreamSynchronize(e->stream));
+    }
+    e->top_lp = n;
+    drop_graph(e);
+    return n;
+}
+
+// Test hook: the alternatives of `rows` host rows through the four kernels (the log-probability pair and
+// the top-n pair), the rows as one sequence: row r predicts sequence index r + 1
+extern "C" int gemma_test_top_logprobs(const float *logits, int rows, int n_vocab, int n, int32_t *tokens, double *lps) {
+    set_error("");
+    if (!logits || !tokens || !lps || rows < 1 || rows > 65535 || n_vocab < 1 || n_vocab > LSE_MAX_G * LSE_CHUNK || n < 1 ||
+        n > GEMMA_TOP_LOGPROBS_MAX) {
+        set_error("gemma_test_top_logprobs: logits, tokens, lps, rows in [1, 65535], n_vocab in [1, " +
+                  std::to_string(LSE_MAX_G * LSE_CHUNK) + "] and n in [1, " + std::to_string(GEMMA_TOP_LOGPROBS_MAX) + "] are required");
+        return -1;
+    }
+    dev_pool tmp;
+    float *dl = nullptr;
+    int *dpos = nullptr;
+    int32_t *dtok = nullptr;
+    double *dlp = nullptr;
+    lse_part *dp = nullptr;
+    unsigned long long *dt = nullptr;
+    const size_t row_b = (size_t)n_vocab * 4, alt = (size_t)(rows + 1) * GEMMA_TOP_LOGPROBS_MAX;
+    if (tmp.get(&dl, row_b * rows) || tmp.get(&dpos, 4) || tmp.get(&dtok, alt * 4) || tmp.get(&dlp, alt * 8) ||
+        tmp.get(&dp, (size_t)rows * lse_grid(n_vocab) * sizeof(lse_part)) || tmp.get(&dt, (size_t)rows * topn_grid(n_vocab) * n * 8))
+        return -1;
+    GHIP_CHECK(hipMemcpy(dl, logits, row_b * rows, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(dpos, &rows, 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemset(dtok, 0xFF, alt * 4));
+    GHIP_CHECK(hipMemset(dlp, 0xFF, alt * 8));
+    topn_finish_args a;
+    a.l.lg = dl; a.l.ld = n_vocab; a.l.n = n_vocab; a.l.R = rows; a.l.G = lse_grid(n_vocab); a.l.n_ctx = rows;
+    a.l.parts = dp; a.l.pos = dpos; a.l.alt_tok = dtok; a.l.alt_lp = dlp;
+    a.tparts = dt; a.Gt = topn_grid(n_vocab); a.top = n;
+    if (launch_lse_parts(dl, n_vocab, rows, n_vocab, dp, nullptr) || launch_topn_parts(dl, n_vocab, rows, n_vocab, n, dt, nullptr) ||
+        launch_topn_finish(a, nullptr))
+        return -1;
+    GHIP_CHECK(hipDeviceSynchronize());
+    const size_t W = GEMMA_TOP_LOGPROBS_MAX;
+    GHIP_CHECK(hipMemcpy2D(tokens, (size_t)n * 4, dtok + W, W * 4, (size_t)n * 4, (size_t)rows, hipMemcpyDeviceToHost));
+    GHIP_CHECK(hipMemcpy2D(lps, (size_t)n * 8, dlp + W, W * 8, (size_t)n * 8, (size_t)rows, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // Test hook: logprob(rows[r], tokens[r]) through the two kernels, the rows as one sequence: row r

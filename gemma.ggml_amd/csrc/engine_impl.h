@@ -54,6 +54,13 @@ struct launch_plan {
     int img = 0;  // attn-out / down: read the producer-written Q8_0 image (PRO_IMG) instead of f32
 };
 
+// the per-row scratch of the log-probability kernels: k_lse_parts' partials [rows][G] and, while the
+// alternatives are on, k_topn_parts' candidate keys [rows][Gt][GEMMA_TOP_LOGPROBS_MAX] (else null)
+struct lp_scratch {
+    lse_part *parts = nullptr;
+    unsigned long long *top = nullptr;
+};
+
 // scratch of a batched pass, every buffer indexed by the row t of the pass (lazily sized for the
 // largest pass seen: prefill_alloc)
 struct pf_scratch {
@@ -68,8 +75,9 @@ struct pf_scratch {
     uint8_t *XQ8K = nullptr;  // Q6_K head: the T Q8_K rows of rms_norm(x)*out_norm
     void *keys = nullptr;
     // log-probabilities: the partials of a pass of more than 8 rows, [T][G] (the engine's scratch: made
-    // while they are on; a wide batch's: always, so nothing moves while it is open); else null
-    lse_part *LP = nullptr;
+    // while they are on; a wide batch's: always, so nothing moves while it is open); else null.  With them,
+    // the alternatives' candidates while those are on (a batch's: on when it was opened)
+    lp_scratch LP;
     // the key-split exact attention's scores and P16 (attn_mx_long.hip), made when a pass first takes that form:
     // att_rows slab rows x n_head x n_ctx words each
     float *AS = nullptr;
@@ -86,6 +94,10 @@ struct seq_state {
     uint16_t *kc = nullptr, *vc = nullptr;  // [L][ctx][kvw], [L][kvw][ctx] (null: the engine's own on external caches)
     int *hist = nullptr;                    // [ctx + 1] the tokens by position
     double *lp = nullptr;                   // [ctx + 1] log-probability of hist[i] under the row before it (NaN: not scored)
+    // [ctx + 1][GEMMA_TOP_LOGPROBS_MAX] the alternatives at index i under the row before it (-1 / NaN: none).  Null
+    // until the alternatives are first turned on (the engine's own), or in a batch opened with them off
+    int32_t *alt_tok = nullptr;
+    double *alt_lp = nullptr;
     int *pos = nullptr, *nfix = nullptr;    // processed positions; given tokens (hist below *nfix is never overwritten)
     // the token word.  The engine's own: always the last pick (also inside the given tokens).  A
     // slot's: the pending token hist[*pos] (-1: inactive), a word of batch_state::last
@@ -101,7 +113,7 @@ struct pick_buf {
     unsigned long long *keys = nullptr;  // device: [64][256] greedy partial keys, then [64] sampler key slots
     sample_ws ws;                        // a batch's own sampler workspaces: a wide batch's, or a narrow one's made by
                                          // batch_set_sampler on an engine that has none (else the engine's 8: smp_ws)
-    lse_part *lp_parts = nullptr;        // a wide batch's own log-probability partials (else the engine's 8 rows: lp_parts)
+    lp_scratch lp_parts;                 // a wide batch's own log-probability scratch (else the engine's 8 rows: lp_parts)
 };
 
 // ---- batched decode (engine_batch.cpp, DESIGN.md §5b⁗) ------------------------------------------
@@ -273,7 +285,8 @@ struct gemma_engine {
     sample_ws smp_ws;                     // allocated when sampling is first turned on
     // per-token log-probabilities (gemma_engine_set_logprobs; logprob.hip): off = nothing below is used
     bool logprobs = false;
-    lse_part *lp_parts = nullptr;         // [8][G] partials (step, verify, narrow batch); allocated when first turned on
+    lp_scratch lp_parts;                  // 8 rows (step, verify, narrow batch); each part allocated when first turned on
+    int top_lp = 0;                       // alternatives per scored position (gemma_engine_set_top_logprobs; toplogprob.hip); 0 = off
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     // flow control of gemma_engine_step: an event every FC_EVERY graph launches, FC_SLOTS of them
@@ -444,7 +457,7 @@ int enqueue_step(gemma_engine *e);
 // the greedy argmax keys (n_parts of them) exactly as before
 // rows0 / R: the pass's R rows that end with `row` (a prefill), all scored when log-probabilities are on
 int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *keys, int n_parts, const float *rows0 = nullptr,
-                 int R = 1, lse_part *own = nullptr);
+                 int R = 1, lp_scratch own = {});
 // the pick alone, no advance: with sampling on, the sampler's draw for sequence index *pos + 1 from
 // `row` into the sampler's own key slot, *keys / *n_parts set to that one key; sampling off: nothing
 // is launched and the caller's greedy keys stand
@@ -460,14 +473,19 @@ struct row_picks {
 int pick_buf_alloc(dev_pool &M, pick_buf &b, hipStream_t s);  // zeroed on s
 // Log-probabilities of a pass's R rows LG [R][n_vocab] (nothing is launched while they are off).
 // enqueue_lp_parts: the rows' partials, right after the logits (enqueue_pick and enqueue_row_picks
-// issue it); own: partials of the pass's own, else the engine's 8 rows.  enqueue_lp_finish: after the
+// issue it); own: scratch of the pass's own, else the engine's 8 rows.  enqueue_lp_finish: after the
 // advance, lp[q] of every row; the rows are a row table's (tab), or consecutive positions of S ending
-// at *S.pos (acc: the device word of a verify pass's accepted count, rows past it are not scored)
-int enqueue_lp_parts(gemma_engine *e, const float *LG, int R, lse_part *own);
-int enqueue_lp_finish(gemma_engine *e, const float *LG, int R, lse_part *own, const seq_state *S, const slot_row *tab,
+// at *S.pos (acc: the device word of a verify pass's accepted count, rows past it are not scored).
+// With the alternatives on (top_lp > 0) each enqueues its kernel of toplogprob.hip behind its own.
+int enqueue_lp_parts(gemma_engine *e, const float *LG, int R, lp_scratch own);
+int enqueue_lp_finish(gemma_engine *e, const float *LG, int R, lp_scratch own, const seq_state *S, const slot_row *tab,
                       const int *acc);
 // lp[p0 .. p0 + n) of S into out after one synchronise; fn names the caller in the range error
 int seq_logprobs(gemma_engine *e, const seq_state &S, int p0, int n, double *out, const char *fn);
+// the alternatives of the same range, [n][top_lp] each; the same checks, and they must be on
+int seq_top_logprobs(gemma_engine *e, const seq_state &S, int p0, int n, int32_t *tokens, double *lps, const char *fn);
+// S's alternatives from pool M, filled with "none" (all-ones bytes: token -1, an f64 NaN)
+int seq_alt_alloc(gemma_engine *e, dev_pool &M, seq_state &S);
 // mix: picks_mix of the caller's mirror of its rows' modes (a batch pass: each row reads its parameters
 // from tab[t].smp); -1: the engine's sampler for every row
 int enqueue_row_picks(gemma_engine *e, const float *LG, int T, const int *pos, const slot_row *tab, const pick_buf &b,

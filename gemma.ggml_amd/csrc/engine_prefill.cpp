@@ -8,9 +8,11 @@
 // prefill buffers (lazily sized for the largest pass seen: the prompt, or a gemma_engine_prefill_next
 // chunk).  A regrow drops the whole scratch and makes it anew; pf.T is set last, so a failed regrow
 // leaves T = 0 and no pointer to freed memory.
-// parts: the scratch also holds the log-probability partials of its rows (passes of more than 8 rows)
+// parts: the scratch also holds the log-probability partials of its rows (passes of more than 8 rows),
+// and the alternatives' candidates when those are on
 static int scratch_alloc(gemma_engine *e, dev_pool &M, pf_scratch &p, int T, bool parts) {
-    if (p.T >= T && (!parts || p.LP)) return 0;
+    const bool top = parts && e->top_lp > 0;
+    if (p.T >= T && (!parts || p.LP.parts) && (!top || p.LP.top)) return 0;
     T = std::max(T, p.T);
     M.clear();
     p = {};
@@ -26,7 +28,8 @@ static int scratch_alloc(gemma_engine *e, dev_pool &M, pf_scratch &p, int T, boo
         M.get(&p.XQ, (size_t)T * (e->kq ? p.ldq / 256 * 292 : p.ldq)) || M.get(&p.XH, (size_t)T * p.ldq * 2) ||
         M.get(&p.XM, (size_t)T * (p.ldq / 256) * 32) || M.get(&p.keys, 256 * 8) ||
         (e->out_type == T_Q6_K && M.get(&p.XQ8K, (size_t)T * (E / 256) * 292)) ||
-        (parts && M.get(&p.LP, (size_t)T * lse_grid(c.n_vocab) * sizeof(lse_part)))) {
+        (parts && M.get(&p.LP.parts, (size_t)T * lse_grid(c.n_vocab) * sizeof(lse_part))) ||
+        (top && M.get(&p.LP.top, (size_t)T * topn_grid(c.n_vocab) * GEMMA_TOP_LOGPROBS_MAX * 8))) {
         M.clear();
         p = {};
         return -1;
@@ -68,7 +71,8 @@ static pf_scratch scratch_of(gemma_engine *e, const pass_rows &rows) {
     p.XQ += r * (e->kq ? p.ldq / 256 * 292 : p.ldq); p.XH += r * p.ldq;
     p.XM += r * (p.ldq / 256) * 16;  // 32 bytes per 256 values
     if (p.XQ8K) p.XQ8K += r * (c.n_embd / 256) * 292;
-    if (p.LP) p.LP += r * lse_grid(c.n_vocab);
+    if (p.LP.parts) p.LP.parts += r * lse_grid(c.n_vocab);
+    if (p.LP.top) p.LP.top += r * topn_grid(c.n_vocab) * e->top_lp;  // [row][chunk][top_lp]
     return p;
 }
 
@@ -234,7 +238,7 @@ static int enqueue_prefill(gemma_engine *e, int T, const pass_rows &rows, bool e
     const int last = p0 + T - 1;
     GHIP_CHECK(hipMemcpyAsync(e->seq.pos, &last, 4, hipMemcpyHostToDevice, s));
     // (log-probabilities on: all T rows are scored, row t against hist[p0 + t + 1])
-    return enqueue_pick(e, last_row, (const unsigned long long *)p.keys, 256, p.LG, T, T > GEMM_SKINNY_MAX_T ? p.LP : nullptr);
+    return enqueue_pick(e, last_row, (const unsigned long long *)p.keys, 256, p.LG, T, T > GEMM_SKINNY_MAX_T ? p.LP : lp_scratch{});
 }
 
 // Batched prefill for K-quant layers (the reference's shipped Q4_K_M model, src/app.cpp:36): the

@@ -486,6 +486,8 @@ struct slot_row {
     int *hist = nullptr, *pos = nullptr, *last = nullptr;
     const int *nfix = nullptr;
     double *lp = nullptr;        // the slot's log-probabilities by sequence index (k_lse_finish)
+    int32_t *alt_tok = nullptr;  // the slot's alternatives by sequence index, [TOPN_MAX] each (k_topn_finish; null: it has none)
+    double *alt_lp = nullptr;
     // the sampler in force on the row's slot, by value (the slot's own, else the engine's; temperature
     // <= 0: greedy): the sampler's kernels of a pass with a row table read it with the entry, one load
     sampler_params smp;
@@ -649,8 +651,24 @@ struct lse_finish_args {  // grid (1, R): lp[q_r] = logprob(row r, hist[q_r]) on
     const slot_row *tab = nullptr;
     const int *pos = nullptr, *hist = nullptr, *acc = nullptr;
     double *lp = nullptr;
+    int32_t *alt_tok = nullptr;  // that sequence's alternatives (k_topn_finish alone reads the two)
+    double *alt_lp = nullptr;
 };
 int launch_lse_finish(const lse_finish_args &a, hipStream_t s);
+
+// ---- the n most likely tokens of every scored row (toplogprob.hip; the rule: include/gemma_hpc.h) ----
+constexpr int TOPN_MAX = 32;       // alternatives per position at most (GEMMA_TOP_LOGPROBS_MAX): a key per lane of half a wave
+constexpr int TOPN_CHUNK = 4096;   // logits per workgroup of k_topn_parts: Gt = ceil(n_vocab / TOPN_CHUNK), n_vocab alone
+int topn_grid(int64_t n_vocab);
+// tparts[r][g][0 .. n): the n largest pick keys of chunk g of row lg + r * ld, descending, key 0 where the
+// chunk has fewer; grid (Gt, rows); needs no token and no position.  n in [1, TOPN_MAX], n_vocab <= 2^20
+int launch_topn_parts(const float *lg, int64_t ld, int rows, int64_t n_vocab, int n, unsigned long long *tparts, hipStream_t s);
+struct topn_finish_args {  // grid (1, R): alt_tok / alt_lp [q_r][0 .. top) of every row that k_lse_finish scores
+    lse_finish_args l;     // the rows, their partials and where each row writes (lg, hist and lp are not read)
+    const unsigned long long *tparts = nullptr;
+    int Gt = 0, top = 0;
+};
+int launch_topn_finish(const topn_finish_args &a, hipStream_t s);
 
 // ---- generic ggml-op kernels used by the C-ABI and the ggml-compatible executor ----------------
 int launch_mul_mat_f16(const uint16_t *src0, int64_t nb01_elems, int64_t ne01, const uint16_t *src1,

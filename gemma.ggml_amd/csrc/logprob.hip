@@ -9,24 +9,19 @@
 //                 only: no token, no position.
 //   k_lse_finish  grid (1, R), after the advance has settled the token: M = max_g m_g, S = sum_g
 //                 s_g * exp((double)m_g - (double)M) in ascending g, then the row's sequence index q,
-//                 t = hist[q] and lp[q].
+//                 t = hist[q] and lp[q] (the rules it shares with k_topn_finish: lse_impl.h).
 // The value is a function of (row, token) alone, bit for bit: G and the chunks depend on n_vocab only,
 // a thread sums its four terms in index order, a wave reduces by a fixed xor butterfly (IEEE addition
 // is commutative, so every lane holds the same bits), the four waves and the G partials are added in
 // index order.  max is exact and order-free.
-#include "kernels.h"
+#include "lse_impl.h"
 
 namespace ghip {
 namespace {
 
-constexpr int LSE_TH = 256, LSE_PER = 4;
+constexpr int LSE_PER = 4;
 static_assert(LSE_CHUNK == LSE_TH * LSE_PER, "one 16-byte load per thread and chunk");
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
@@ -72,46 +67,18 @@ __global__ void __launch_bounds__(LSE_TH) k_lse_parts(const float *lg, int64_t l
 }
 
 __global__ void __launch_bounds__(LSE_TH) k_lse_finish(lse_finish_args a) {
-    __shared__ float wm[LSE_TH / 64];
-    __shared__ double term[LSE_MAX_G];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ lse_merge_lds L;
     const int r = blockIdx.y;
-    // the rows that count: all of them, or 0 .. *acc of a verify pass (the accepted prefix)
-    const int last = a.acc ? *a.acc : a.R - 1;
+    const int last = lse_last_row(a);
     if (r > last || last >= a.R) return;
-    const lse_part *parts = a.parts + (int64_t)r * a.G;
-    const float ninf = -__builtin_inff();
-    float m = ninf;
-    for (int g = tid; g < a.G; g += LSE_TH) m = fmaxf(m, parts[g].m);
-    m = wave_max(m);
-    if (lane == 0) wm[wave] = m;
-    __syncthreads();
-    const float M = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
-    for (int g = tid; g < a.G; g += LSE_TH) {
-        const lse_part p = parts[g];
-        term[g] = p.m == ninf ? 0.0 : p.s * exp((double)p.m - (double)M);
-    }
-    __syncthreads();
-    if (tid != 0) return;
-    double S = 0.0;
-    for (int g = 0; g < a.G; ++g) S += term[g];  // ascending g
-    // the sequence index the row predicts: the slot's position after its advance, or the rows of a
-    // pass of consecutive positions that ends at *pos
-    const int *hist = a.hist;
-    double *lp = a.lp;
-    int q;
-    if (a.tab) {
-        const slot_row sr = a.tab[r];
-        hist = sr.hist; lp = sr.lp;
-        q = *sr.pos;
-    } else {
-        q = *a.pos - (last - r);
-    }
-    if (q < 1 || q > a.n_ctx) return;
-    const int t = hist[q];
-    if (t < 0 || t >= a.n) return;
-    const float lt = a.lg[(int64_t)r * a.ld + t];
-    lp[q] = ((double)lt - (double)M) - log(S);
+    double S;
+    const float M = lse_merge(a.parts + (int64_t)r * a.G, a.G, L, &S);
+    if (threadIdx.x != 0) return;
+    lse_target t;
+    if (!lse_target_of(a, r, last, &t)) return;
+    const int tok = t.hist[t.q];
+    if (tok < 0 || tok >= a.n) return;
+    t.lp[t.q] = lse_value(a.lg[(int64_t)r * a.ld + tok], M, S);
 }
 
 }  // namespace

@@ -46,6 +46,7 @@ EXPORTS = ["mul_mat", "hpc_init", "hpc_shutdown", "hpc_register_weight", "hpc_la
            "gemma_engine_batch_last_n", "gemma_batch_plan_rows", "gemma_engine_batch_open_rows",
            "gemma_engine_batch_step_rows", "gemma_engine_batch_verify", "gemma_engine_batch_generate_lookup",
            "gemma_engine_set_logprobs", "gemma_engine_logprobs", "gemma_engine_batch_logprobs", "gemma_test_logprob",
+           "gemma_engine_set_top_logprobs", "gemma_engine_top_logprobs", "gemma_engine_batch_top_logprobs", "gemma_test_top_logprobs",
            "gemma_engine_batch_set_sampler", "gemma_engine_batch_sampler", "gemma_engine_batch_fork",
            "gemma_test_sample_rows", "gemma_test_rope_kv_prefill", "gemma_test_rows_rope_kv",
            "gemma_test_attn_prefill", "gemma_test_attn_decode_rows", "gemma_test_attn_long_rows",
@@ -228,6 +229,14 @@ def lib():
     L.gemma_engine_batch_logprobs.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
     L.gemma_test_logprob.restype = C.c_int
     L.gemma_test_logprob.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+    L.gemma_engine_set_top_logprobs.restype = C.c_int
+    L.gemma_engine_set_top_logprobs.argtypes = [vp, C.c_int]
+    L.gemma_engine_top_logprobs.restype = C.c_int
+    L.gemma_engine_top_logprobs.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+    L.gemma_engine_batch_top_logprobs.restype = C.c_int
+    L.gemma_engine_batch_top_logprobs.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.gemma_test_top_logprobs.restype = C.c_int
+    L.gemma_test_top_logprobs.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
     # GGUF reader (include/ggml.h)
     L.gguf_init_from_file.restype = vp
     L.gguf_init_from_file.argtypes = [C.c_char_p, GGUFInitParams]
@@ -687,6 +696,39 @@ class Engine:
             raise RuntimeError("batch_logprobs failed: " + last_error())
         return out
 
+    def set_top_logprobs(self, n=-1):
+        """The n most likely tokens of every scored position with their log-probabilities
+        (include/gemma_hpc.h has the rule): n in [0, TOP_LOGPROBS_MAX], 0 off, -1 keep; returns the
+        setting.  A change drops the captured graph; raises while log-probabilities are off, on a
+        row-split engine and while a batch is open."""
+        r = self.L.gemma_engine_set_top_logprobs(self.h, int(n))
+        if r < 0:
+            raise RuntimeError("set_top_logprobs failed: " + last_error())
+        return r
+
+    def _top_logprobs(self, call, what, p0, cnt):
+        n = self.set_top_logprobs()
+        tok = np.zeros((max(int(cnt), 0), n), dtype=np.int32)
+        lps = np.zeros(tok.shape, dtype=np.float64)
+        if call(int(p0), int(cnt), _p(tok), _p(lps)) < 0:
+            raise RuntimeError(what + " failed: " + last_error())
+        return tok, lps
+
+    def top_logprobs(self, p0=0, cnt=None):
+        """the alternatives of sequence indices [p0, p0+cnt) of the engine's sequence (cnt=None: through
+        its end): (tokens i32 [cnt][n], lps f64 [cnt][n]) in descending order; -1 / NaN where the row has
+        fewer entries or no scored row predicted the index."""
+        if cnt is None:
+            cnt = max(self.pos() + 1, getattr(self, "_n_seq", 0)) - int(p0)
+        return self._top_logprobs(lambda *a: self.L.gemma_engine_top_logprobs(self.h, *a), "top_logprobs", p0, cnt)
+
+    def batch_top_logprobs(self, slot, p0=0, cnt=None):
+        """top_logprobs() of an active slot of the open batch"""
+        if cnt is None:
+            cnt = self.batch_pos(slot) + 1 - int(p0)
+        return self._top_logprobs(lambda *a: self.L.gemma_engine_batch_top_logprobs(self.h, int(slot), *a),
+                                  "batch_top_logprobs", p0, cnt)
+
     def set_att_o(self, on=-1):
         """decode attention + attn-out in one launch per layer: on 1 / off 0 / keep -1; returns the setting"""
         return self.L.gemma_engine_set_att_o(self.h, on) == 1
@@ -826,6 +868,27 @@ def test_logprob(rows, tokens):
 
 
 test_logprob.__test__ = False  # a library wrapper, not a pytest test
+
+
+TOP_LOGPROBS_MAX = 32  # GEMMA_TOP_LOGPROBS_MAX
+
+
+def test_top_logprobs(rows, n):
+    """The n most likely tokens of host logits rows [R][V] with their log-probabilities through the
+    engine's kernels (gemma_test_top_logprobs); returns (tokens i32 [R][n], lps f64 [R][n]); raises
+    RuntimeError with the library's message on a refused argument."""
+    x = np.ascontiguousarray(rows, dtype=np.float32)
+    if x.ndim == 1:
+        x = x[None, :]
+    R, V = x.shape
+    tok = np.zeros((R, max(int(n), 0)), dtype=np.int32)
+    lps = np.zeros(tok.shape, dtype=np.float64)
+    if lib().gemma_test_top_logprobs(_p(x), R, V, int(n), _p(tok), _p(lps)) != 0:
+        raise RuntimeError("gemma_test_top_logprobs failed: " + last_error())
+    return tok, lps
+
+
+test_top_logprobs.__test__ = False  # a library wrapper, not a pytest test
 
 
 def batch_plan_rows(need, max_rows):

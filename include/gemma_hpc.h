@@ -221,6 +221,33 @@ int gemma_engine_set_logprobs(gemma_engine *e, int on);
 int gemma_engine_logprobs(gemma_engine *e, int p0, int n, double *out);
 /* the same for an active slot of the open batch */
 int gemma_engine_batch_logprobs(gemma_engine *e, int slot, int p0, int n, double *out);
+/* The n most likely tokens at every scored position, with their log-probabilities (an OpenAI-style
+ * top_logprobs; DESIGN.md §5b⁗′ "Alternatives").  For a logits row l[0..V) (f32) and 1 <= n <=
+ * GEMMA_TOP_LOGPROBS_MAX: every entry i has the pick key (ordered bits of l[i], ~i), where the ordered
+ * bits of a float u are ~u for a set sign bit and u | 0x80000000 otherwise; the alternatives are the
+ * min(n, V) entries with the largest keys, in descending key order: larger value first, -0 below +0, the
+ * smaller index first among equal bits.  Alternative 0 is therefore the greedy pick of the row, and -inf
+ * entries are ordinary candidates.  Alternative i carries logprob(l, t_i) by the rule above, computed by
+ * the same device code; where the scored token hist[q] is among the alternatives of q, its value there
+ * has the bits of lp[q].  Entries i >= min(n, V) are token -1, value NaN.  Rows with a NaN or whose
+ * maximum is -inf are outside the contract.  The result is a function of (row, n) alone, bit for bit.
+ * Which row writes which sequence index is the rule lp has: the row that processed index p writes
+ * position p + 1 after the advance, a verify pass only its accepted rows; positions no row has written
+ * (since begin, or from `keep` on after extend) hold -1 / NaN.
+ * Needs the log-probabilities on (turning those off turns this off); two more kernels per decoded
+ * token; any change drops the captured decode graph.  n in [0, GEMMA_TOP_LOGPROBS_MAX], 0 = off, -1 =
+ * keep; returns the setting.  -1 + hpc_last_error: log-probabilities off, a row-split engine, or a
+ * batch open (its slots were made for the setting it was opened with). */
+#define GEMMA_TOP_LOGPROBS_MAX 32
+int gemma_engine_set_top_logprobs(gemma_engine *e, int n);
+/* the alternatives of sequence indices [p0, p0+cnt) into tokens and lps, [cnt][n] each with n the
+ * setting; ranges, return value and errors as gemma_engine_logprobs; -1 while the alternatives are off */
+int gemma_engine_top_logprobs(gemma_engine *e, int p0, int cnt, int32_t *tokens, double *lps);
+/* the same for an active slot of the open batch */
+int gemma_engine_batch_top_logprobs(gemma_engine *e, int slot, int p0, int cnt, int32_t *tokens, double *lps);
+/* per-op test entry: the alternatives of host rows [rows][n_vocab] through the engine's kernels into
+ * tokens and lps [rows][n] (rows <= 65535, n_vocab <= 2^20, n in [1, GEMMA_TOP_LOGPROBS_MAX]) */
+int gemma_test_top_logprobs(const float *logits, int rows, int n_vocab, int n, int32_t *tokens, double *lps);
 /* per-op test entry: out[r] = logprob(rows[r], tokens[r]) on host rows [rows][n_vocab] through the two
  * kernels of the engine (rows <= 65535, n_vocab <= 2^20, ids in [0, n_vocab)) */
 int gemma_test_logprob(const float *logits, int rows, int n_vocab, const int32_t *tokens, double *out);

@@ -6,17 +6,20 @@ process.
     python scripts/logprob_bench.py trace
     python scripts/logprob_bench.py table --csv <rocprofv3 ..._kernel_trace.csv>
 
-decode  the scripts/sample_bench.py set-up: legs greedy / greedy+lp / k40 / k40+lp alternated `reps`
-        times, each from the same state (begin, the prompt and 8 warm-up steps by graph replay, then
+decode  the scripts/sample_bench.py set-up: legs greedy / greedy+lp / greedy+lp+top20 / k40 / k40+lp
+        alternated `reps` times (top20: the 20 most likely tokens per position, gemma_engine_set_top_logprobs), each from the same state (begin, the prompt and 8 warm-up steps by graph replay, then
         `steps` timed graph replays with no host sync in between).  tok/s, us per token, launches.
 score   a T-token text, three ways `reps` times after one warm-up round, their order rotating: `plain` the exact
         prefill alone; `device` the exact prefill with log-probabilities on and the T f64 values read
         back; `host` the exact prefill with logits_all copied to the host and the rule restated in
-        numpy f64 there.  ms per way, the largest |device - host|, both perplexities.
+        numpy f64 there.  ms per way, the largest |device - host|, both perplexities.  With --top N the
+        device way also selects and reads back the N alternatives of every token and the host way takes
+        them from logits_all by numpy argpartition; the bytes each way returns are reported.
 trace   one call of every pass form with log-probabilities on, for `rocprofv3 --kernel-trace --stats`:
         R = 1 (8 decode steps), R = 8 (a verify pass of 7 drafts), R = 64 (a wide batch pass),
-        R = 2048 (a prefill).  The k_lse_parts / k_lse_finish rows of the trace are the feature's time.
-table   the k_lse_* launches of such a trace (and the decode logits launch beside them) by rows per
+        R = 2048 (a prefill).  The k_lse_parts / k_lse_finish rows of the trace are the feature's time;
+        with --top N the alternatives are on too and k_topn_parts / k_topn_finish are theirs.
+table   the k_lse_* and k_topn_* launches of such a trace (and the decode logits launch beside them) by rows per
         launch: calls, min / median / max microseconds.
 Prints one JSON line per mode (table: text)."""
 import argparse
@@ -45,16 +48,18 @@ def stats(v):
 
 
 def decode(args):
-    legs = [("greedy", None, 0), ("greedy+lp", None, 1), ("k40", K40, 0), ("k40+lp", K40, 1)]
+    legs = [("greedy", None, 0, 0), ("greedy+lp", None, 1, 0), ("greedy+lp+top20", None, 1, 20), ("k40", K40, 0, 0), ("k40+lp", K40, 1, 0)]
     warm = 8
     e = G.Engine(GEMMA_2B, n_ctx=((args.prompt + warm + args.steps + 64) // 32 + 1) * 32)
     e.tune(8)
     prompt = make_prompt(args.prompt, V)
-    us, launches = {k: [] for k, _, _ in legs}, {}
+    us, launches = {k[0]: [] for k in legs}, {}
     for rep in range(args.reps):
-        for name, smp, lp in legs:
+        for name, smp, lp, top in legs:
             e.set_sampler(**smp) if smp else e.set_sampler(None)
             e.set_logprobs(lp)
+            if lp:
+                e.set_top_logprobs(top)
             e.begin(prompt)
             e.step(args.prompt + warm, use_graph=True)
             e.sync()
@@ -71,6 +76,7 @@ def decode(args):
     out = {k: dict(us_per_token=stats(v), tok_s_median=round(1e6 / stats(v)["median"], 1), launches_per_token=launches[k])
            for k, v in us.items()}
     out["added_us_per_token"] = {"greedy": round(out["greedy+lp"]["us_per_token"]["median"] - out["greedy"]["us_per_token"]["median"], 2),
+                                 "top20_over_lp": round(out["greedy+lp+top20"]["us_per_token"]["median"] - out["greedy+lp"]["us_per_token"]["median"], 2),
                                  "k40": round(out["k40+lp"]["us_per_token"]["median"] - out["k40"]["us_per_token"]["median"], 2)}
     print(json.dumps(dict(mode="decode", steps=args.steps, reps=args.reps, prompt=args.prompt, legs=out)), flush=True)
 
@@ -86,33 +92,63 @@ def host_rule(rows, tokens):
     return out
 
 
+def host_top(rows, n):
+    """the n largest entries of every row but the last, descending (argpartition, then a sort of the n) and their
+    log-probabilities by the rule: what a caller of logits_all has to do for the alternatives"""
+    tok = np.empty((len(rows) - 1, n), dtype=np.int32)
+    lps = np.empty((len(rows) - 1, n))
+    for r0 in range(0, len(tok), 64):
+        blk = rows[r0:min(r0 + 64, len(tok))]
+        part = np.argpartition(blk, -n, axis=1)[:, -n:]
+        vals = np.take_along_axis(blk, part, axis=1)
+        order = np.lexsort((part, -vals), axis=1)
+        tok[r0:r0 + len(blk)] = np.take_along_axis(part, order, axis=1)
+        d = blk.astype(np.float64)
+        d -= d.max(axis=1, keepdims=True)
+        lps[r0:r0 + len(blk)] = np.take_along_axis(d, tok[r0:r0 + len(blk)].astype(np.int64), axis=1) - np.log(np.exp(d).sum(axis=1))[:, None]
+    return tok, lps
+
+
 def score(args):
     T = args.T
     e = G.Engine(GEMMA_2B, n_ctx=T + 64)
     text = [int(t) for t in make_prompt(T, V)]
     ms = {"plain": [], "device": [], "host": []}
-    dev = host = None
+    dev = host = dev_top = host_top_ = None
     ways = ["plain", "device", "host"]
     for rep in range(args.reps + 1):  # the first round warms up (scratch, code objects) and is dropped
         # the order rotates: the leg behind `host` starts on a GPU that idled through seconds of numpy
         for way in ways[rep % 3:] + ways[:rep % 3]:
             e.set_logprobs(1 if way == "device" else 0)
+            if way == "device":
+                e.set_top_logprobs(args.top)
             e.begin(text)
             e.sync()
             t0 = time.perf_counter()
             if way == "host":
-                host = host_rule(e.prefill(T, want_all=True)[2], text)
+                rows = e.prefill(T, want_all=True)[2]
+                host = host_rule(rows, text)
+                if args.top:
+                    host_top_ = host_top(rows, args.top)
             else:
                 e.prefill(T)
                 if way == "device":
                     dev = e.logprobs(1, T - 1)
+                    if args.top:
+                        dev_top = e.top_logprobs(1, T - 1)
             dt = (time.perf_counter() - t0) * 1e3
             if rep:
                 ms[way].append(dt)
             print(f"rep {rep} {way:7s} {dt:10.2f} ms", flush=True)
     e.close()
     res = {k: stats(v) for k, v in ms.items()}
-    print(json.dumps(dict(mode="score", T=T, reps=args.reps, ms=res,
+    extra = {}
+    if args.top:  # (random logits hold no ties, so argpartition's order is the rule's)
+        extra = dict(top=args.top, host_over_device=round(res["host"]["median"] / res["device"]["median"], 2),
+                     bytes_device=int(dev.nbytes + dev_top[0].nbytes + dev_top[1].nbytes), bytes_host=int(T * V * 4),
+                     top_tokens_equal=bool(np.array_equal(dev_top[0], host_top_[0])),
+                     max_abs_top_lp_diff=float(np.abs(dev_top[1] - host_top_[1]).max()))
+    print(json.dumps(dict(mode="score", T=T, reps=args.reps, ms=res, **extra,
                           added_over_plain_ms=round(res["device"]["median"] - res["plain"]["median"], 2),
                           max_abs_lp_diff=float(np.abs(dev - host).max()),
                           perplexity_device=float(np.exp(-dev.mean())), perplexity_host=float(np.exp(-host.mean())))), flush=True)
@@ -121,6 +157,7 @@ def score(args):
 def trace(args):
     e = G.Engine(GEMMA_2B, n_ctx=512)
     e.set_logprobs(1)
+    e.set_top_logprobs(args.top)
     prompt = make_prompt(32, V)
     e.begin(prompt)
     e.prefill(32)
@@ -135,6 +172,7 @@ def trace(args):
     e.close()
     e = G.Engine(GEMMA_2B, n_ctx=2048 + 64)
     e.set_logprobs(1)
+    e.set_top_logprobs(args.top)
     e.begin(make_prompt(2048, V))
     e.prefill(2048)                                  # R = 2048
     n2 = int(np.isfinite(e.logprobs(0, 2049)).sum())
@@ -149,6 +187,7 @@ def table(args):
     for r in csv.DictReader(open(args.csv)):
         n = r["Kernel_Name"]
         name = ("k_lse_parts" if "k_lse_parts" in n else "k_lse_finish" if "k_lse_finish" in n
+                else "k_topn_parts" if "k_topn_parts" in n else "k_topn_finish" if "k_topn_finish" in n
                 else "logits launch (k_matvec, argmax epilogue)" if "k_matvec<2, 1, 1, 3" in n else None)
         if name:
             key = (name, int(r["Grid_Size_X"]) // int(r["Workgroup_Size_X"]), int(r["Grid_Size_Y"]) // int(r["Workgroup_Size_Y"]))
@@ -167,6 +206,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--T", type=int, default=2048)
+    ap.add_argument("--top", type=int, default=0)
     args = ap.parse_args()
     {"decode": decode, "score": score, "trace": trace, "table": table}[args.mode](args)
 

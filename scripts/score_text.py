@@ -1,7 +1,7 @@
 """Log-likelihood and perplexity of a token-id text, scored on the device.
 
     python scripts/score_text.py --tokens ids.txt (--gguf model.gguf | --shape tiny|gemma2b|'{json}')
-                                 [--wtype q4_0|q8_0] [--chunk 512] [--fast] [--check]
+                                 [--wtype q4_0|q8_0] [--chunk 512] [--fast] [--check] [--top N]
 
 The text is fed by chunked prefill_next passes with log-probabilities on (gemma_engine_set_logprobs):
 every logits row is scored on the device against the token that follows it, and only the T f64 values
@@ -13,6 +13,9 @@ exp(-mean(lp[1..T))).  Token 0 has no row before it and is not scored.
 Tokenizing is not done here.  --shape runs synthetic weights of that shape (the test
 and benchmark shapes, or a JSON object of n_layer, n_embd, n_head, n_head_kv, head_dim, n_ff, n_vocab).
 --fast scores the rows of the MFMA tolerance prefill instead of the exact one.
+--top N (1 .. 32) adds the N most likely tokens at every scored position with their log-probabilities,
+selected on the device too (gemma_engine_set_top_logprobs): "top_logprobs" in the JSON, one list of
+[token, logprob] pairs per token of the text from token 1 on.
 --check also takes logits_all of the same passes to the host, restates the rule in numpy f64 and
 prints the largest |device - numpy| and both perplexities (a test of this script, at small shapes).
 Prints one JSON line."""
@@ -45,10 +48,12 @@ def host_logprob(row, t):
     return d[t] - np.log(np.exp(d).sum())
 
 
-def score(e, tokens, chunk, exact=True, check=False):
-    """(lp [T] f64 with lp[0] = NaN, host restatement [T] or None)"""
+def score(e, tokens, chunk, exact=True, check=False, top=0):
+    """(lp [T] f64 with lp[0] = NaN, host restatement [T] or None); with top > 0 the engine also keeps the
+    alternatives of every scored position (e.top_logprobs)"""
     T = len(tokens)
     e.set_logprobs(1)
+    e.set_top_logprobs(top)
     e.begin(tokens)
     host = np.full(T, np.nan) if check else None
     while e.pos() < T:
@@ -70,25 +75,29 @@ def main():
     ap.add_argument("--chunk", type=int, default=512)
     ap.add_argument("--fast", action="store_true")
     ap.add_argument("--check", action="store_true")
+    ap.add_argument("--top", type=int, default=0)
     args = ap.parse_args()
     if (args.gguf is None) == (args.shape is None):
         ap.error("give exactly one of --gguf and --shape")
     tokens = read_tokens(args.tokens)
     T = len(tokens)
-    if T < 2 or args.chunk < 1:
-        ap.error("the text needs at least 2 tokens and --chunk at least 1")
+    if T < 2 or args.chunk < 1 or not 0 <= args.top <= G.TOP_LOGPROBS_MAX:
+        ap.error("the text needs at least 2 tokens, --chunk at least 1 and --top in [0, %d]" % G.TOP_LOGPROBS_MAX)
     n_ctx = (T // 32 + 2) * 32
     if args.gguf:
         e = G.Engine.from_gguf(args.gguf, n_ctx=n_ctx)
     else:
         shape = SHAPES[args.shape] if args.shape in SHAPES else json.loads(args.shape)
         e = G.Engine(shape, n_ctx=n_ctx, wtype=WTYPES[args.wtype])
-    lp, host = score(e, tokens, args.chunk, exact=not args.fast, check=args.check)
+    lp, host = score(e, tokens, args.chunk, exact=not args.fast, check=args.check, top=args.top)
+    alts = e.top_logprobs(1, T - 1) if args.top else None
     e.close()
     if np.isnan(lp[1:]).any():
         raise SystemExit("score_text: tokens %s were not scored" % np.flatnonzero(np.isnan(lp[1:]))[:8])
     res = {"tokens": T, "scored": T - 1, "log_likelihood": float(lp[1:].sum()), "perplexity": float(np.exp(-lp[1:].mean())),
            "path": "fast" if args.fast else "exact", "chunk": args.chunk}
+    if alts:
+        res["top_logprobs"] = [[[int(t), float(v)] for t, v in zip(*row) if t >= 0] for row in zip(*alts)]
     if args.check:
         res["host_perplexity"] = float(np.exp(-host[1:].mean()))
         res["max_abs_lp_diff"] = float(np.abs(lp[1:] - host[1:]).max())
