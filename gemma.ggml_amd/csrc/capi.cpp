@@ -456,6 +456,45 @@ extern "C" int gemma_test_gemm_skinny(int type, int64_t rows, int64_t K, int64_t
     return r;
 }
 
+// the skinny exact K-quant GEMM (tests/test_gpu_gemm_skinny_kq.py): W raw ggml Q4_K / Q6_K rows (tiled:
+// a device copy re-tiled by launch_kq_retile), X [T][K] through the device's Q8_K INIT, then
+// launch_gemm_skinny_kq with the residual epilogue when resid [T][rows] is given.  Refusals touch nothing
+extern "C" int gemma_test_gemm_skinny_kq(int type, int64_t rows, int64_t K, int64_t T, int tiled, const void *W,
+                                         const float *X, float *Y, const float *resid) {
+    set_error("");
+    if ((type != T_Q4_K && type != T_Q6_K) || K <= 0 || K % 256 || rows <= 0 || !W || !X || !Y) {
+        set_error("gemma_test_gemm_skinny_kq: Q4_K / Q6_K rows with K % 256 == 0");
+        return -1;
+    }
+    if (T < 1 || T > GEMM_SKINNY_MAX_T) {
+        set_error("gemma_test_gemm_skinny_kq: T = " + std::to_string(T) + " outside [1, " + std::to_string(GEMM_SKINNY_MAX_T) + "]");
+        return -1;
+    }
+    if (tiled && type == T_Q6_K && K % 2048) {
+        set_error("gemma_test_gemm_skinny_kq: the lane-contiguous Q6_K layout needs K % 2048 == 0");
+        return -1;
+    }
+    const int64_t rb = kq_row_bytes(type, K), ld = K / 256 * 292;
+    uint8_t *d_w = nullptr, *d_t = nullptr, *d_q = nullptr;
+    float *d_x = nullptr, *d_y = nullptr, *d_r = nullptr;
+    dev_pool tmp;
+    if (tmp.get(&d_w, (size_t)(rb * rows)) || (tiled && tmp.get(&d_t, (size_t)(rb * rows))) || tmp.get(&d_x, (size_t)(T * K * 4)) ||
+        tmp.get(&d_q, (size_t)(T * ld)) || tmp.get(&d_y, (size_t)(T * rows * 4)) || tmp.get(&d_r, (size_t)(T * rows * 4)))
+        return -1;
+    GHIP_CHECK(hipMemcpy(d_w, W, (size_t)(rb * rows), hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_x, X, (size_t)(T * K * 4), hipMemcpyHostToDevice));
+    if (resid) GHIP_CHECK(hipMemcpy(d_r, resid, (size_t)(T * rows * 4), hipMemcpyHostToDevice));
+    int r = tiled ? launch_kq_retile(type, d_w, d_t, rows, K, true, nullptr) : 0;
+    if (r == 0) r = launch_quant_q8_K(d_x, K, K, (int)T, d_q, ld, nullptr);
+    kq_args a;
+    a.w = tiled ? d_t : d_w; a.tiled = tiled ? 1 : 0; a.row_bytes = rb; a.rows = rows; a.nsb = (int)(K / 256);
+    a.x = d_q; a.x_col_stride = ld; a.y = d_y; a.y_col_stride = rows; a.ncols = (int)T; a.resid = resid ? d_r : nullptr;
+    if (r == 0) r = launch_gemm_skinny_kq(type, a, nullptr);
+    if (r == 0) GHIP_CHECK(hipDeviceSynchronize());
+    if (r == 0) GHIP_CHECK(hipMemcpy(Y, d_y, (size_t)(T * rows * 4), hipMemcpyDeviceToHost));
+    return r;
+}
+
 // ---- per-op test entry for the decode matvec (tests/test_gpu_kernarg_args.py) ---------------------
 // One launch_matvec with every field of its mv_args supplied by the caller (include/gemma_hpc.h).
 // gelu_clamp, and img_act u32 [ceil(rows / 128) * 32] + img_da f32 [rows / 32] (the Q8_0 image of y that

@@ -308,7 +308,7 @@ extern "C" int gemma_engine_persist_err(gemma_engine *e, int *out3, int reset) {
 extern "C" int gemma_engine_set_option(gemma_engine *e, const char *name, int value) {
     set_error("");
     const std::string n = name ? name : "";
-    int *f = n == "kq_fuse" ? &e->kq_fuse : n == "kq_dual" ? &e->kq_dual : n == "kq_pair" ? &e->kq_pair
+    int *f = n == "kq_fuse" ? &e->kq_fuse : n == "kq_dual" ? &e->kq_dual : n == "kq_pair" ? &e->kq_pair : n == "kq_skinny" ? &e->kq_skinny
            : n == "kq_abl" ? &e->kq_abl : n == "att_mx" ? &e->att_mx : n == "att_win" ? &e->att_win : n == "time_hot" ? &e->time_hot
            : n == "ablate" ? &e->ablate : n == "ks_small" ? &e->ks_small : n == "ks_down" ? &e->ks_down : nullptr;
     if (n == "att_dsplit") {

@@ -205,6 +205,9 @@ struct gemma_engine {
     // K-quant step options (gemma_engine_set_option): kq_fuse = the plan for where ggml's Q8_K INIT
     // runs (enqueue_step_kq, 0..6); kq_dual: gate+up in one launch; kq_pair: q|k and v in one launch
     int kq_fuse = 5, kq_dual = 1, kq_pair = 1;
+    // kq_skinny: skinny passes (T <= 8) send K-quant matrices and the Q6_K head through launch_gemm_skinny_kq:
+    // 1 at every T, 0 never, 2 (default) from 4 rows, where it measured faster
+    int kq_skinny = 2;
     int kq_abl = 0;  // option "kq_abl": hand-off timing ablation (kq_args::q8_abl; wrong results)
     // ---- TP + p2p ----
     // row-split tensor parallelism: this rank's contiguous row range of every

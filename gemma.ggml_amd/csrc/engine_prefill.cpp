@@ -76,8 +76,6 @@ static pf_scratch scratch_of(gemma_engine *e, const pass_rows &rows) {
     return p;
 }
 
-static int enqueue_prefill_kq(gemma_engine *e, int T, const pass_rows &rows);
-
 // the K-quant prefill's MFMA GEMM (prefill_kq.hip) for T prompt rows (kq_gemm_min: default 8)
 static bool kq_prefill_mfma(int T) { return T >= kq_gemm_min(); }
 // T Q8_K columns of K values (ld bytes apart) -> the GEMM's f16 image in the prefill scratch
@@ -160,6 +158,13 @@ static int prefill_attention(gemma_engine *e, int il, int T, const pass_rows &ro
 struct pass_end {
     bool logits_only = false, skinny = false;
 };
+static int enqueue_prefill_kq(gemma_engine *e, int T, const pass_rows &rows, const pass_end &end);
+// a skinny pass's K-quant matrices on launch_gemm_skinny_kq (option "kq_skinny": 1 always, 0 never; the
+// default 2 from 4 rows: Gemma-2B Q4_K_M verify passes of 2 / 3 / 4 / 6 / 8 rows took 2.24 / 2.32 / 2.41 /
+// 2.83 / 3.12 ms on it against 1.77 / 2.08 / 3.20 / 3.37 / 4.75 ms on the T-column / MFMA kernels)
+static bool kq_skinny_pass(const gemma_engine *e, const pass_end &end, int T) {
+    return end.skinny && (e->kq_skinny == 1 || (e->kq_skinny == 2 && T >= 4));
+}
 static int enqueue_prefill(gemma_engine *e, int T, const pass_rows &rows, bool exact, float *taps = nullptr, pass_end end = {}) {
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
@@ -193,7 +198,7 @@ static int enqueue_prefill(gemma_engine *e, int T, const pass_rows &rows, bool e
             set_error("gemma_engine_prefill_fast: K-quant layer engines have the exact batched prefill only");
             return -1;
         }
-        if (enqueue_prefill_kq(e, T, rows)) return -1;
+        if (enqueue_prefill_kq(e, T, rows, end)) return -1;
     } else if (q6 && launch_embed_q6K(e->embd_q6k, e->embd_row_bytes, rows.tokens, nullptr, T, (int)E, sqrtf((float)E), p.X, s, e->embd_tiled)) {
         return -1;
     }
@@ -214,7 +219,12 @@ static int enqueue_prefill(gemma_engine *e, int T, const pass_rows &rows, bool e
     if (q6) {  // Q6_K tied output: Q8_K INIT of every row, then the K-quant dot per (vocab row, position)
         const int64_t ld = E / 256 * 292;
         if (launch_norm_q8K(p.X, E, e->out_norm, (int)E, c.eps, T, p.XQ8K, ld, s)) return -1;
-        if (exact && kq_prefill_mfma(T) && e->embd_tiled && E % 2048 == 0) {  // the MFMA GEMM (prefill_kq.hip)
+        if (kq_skinny_pass(e, end, T)) {  // every head super-block loaded once for the T rows (gemm_skinny_kq.hip)
+            kq_args k;
+            k.w = e->embd_q6k; k.tiled = e->embd_tiled; k.row_bytes = e->embd_row_bytes; k.rows = c.n_vocab; k.nsb = (int)(E / 256);
+            k.x = p.XQ8K; k.x_col_stride = ld; k.y = p.LG; k.y_col_stride = c.n_vocab; k.ncols = T;
+            if (launch_gemm_skinny_kq(T_Q6_K, k, s)) return -1;
+        } else if (exact && kq_prefill_mfma(T) && e->embd_tiled && E % 2048 == 0) {  // the MFMA GEMM (prefill_kq.hip)
             if (kq_expand(e, p, p.XQ8K, ld, E, T)) return -1;
             kqg_args g;
             g.w = e->embd_q6k; g.row_bytes = e->embd_row_bytes; g.rows = c.n_vocab; g.nsb = (int)(E / 256); g.T = T;
@@ -247,7 +257,7 @@ static int enqueue_prefill(gemma_engine *e, int T, const pass_rows &rows, bool e
 // column's Q8_K INIT — every K-quant launch covers all T columns (grid.y) — and the exact per-row
 // attention of the Q4_0 prefill (k_rope_kv_prefill + k_attn_rows).  Bit-identical to the token
 // loop and to the CPU path: no operation depends on the batching.
-static int enqueue_prefill_kq(gemma_engine *e, int T, const pass_rows &rows) {
+static int enqueue_prefill_kq(gemma_engine *e, int T, const pass_rows &rows, const pass_end &end) {
     const gemma_hip_config &c = e->cfg;
     hipStream_t s = e->stream;
     int mx_form = -1;  // the exact attention's form, resolved at the first layer
@@ -258,7 +268,10 @@ static int enqueue_prefill_kq(gemma_engine *e, int T, const pass_rows &rows) {
     // T >= kq_gemm_min() (default 8): the lane-tiled matrices go through the MFMA GEMM
     // (prefill_kq.hip) against the f16 image each Q8_K INIT is expanded to; below, or with
     // GHIP_KQ_MFMA=0, the dot4 T-column kernel.  Same bytes either way (tests/test_gpu_engine_gguf.py).
-    const bool mfma = kq_prefill_mfma(T);
+    // A skinny pass (kq_skinny_pass): every matrix through the skinny K-quant GEMM
+    // (gemm_skinny_kq.hip), gate then up with gate_in; no f16 image is needed.
+    const bool skinny = kq_skinny_pass(e, end, T);
+    const bool mfma = !skinny && kq_prefill_mfma(T);
     auto mfma_ok = [&](const kq_mat &W) { return mfma && W.tiled && (W.type == T_Q4_K || W.K % 2048 == 0); };
     auto expand = [&](int64_t K) { return mfma ? kq_expand(e, p, img, ldk, K, T) : 0; };
     auto mv = [&](const kq_mat &W, float *y, int64_t ldy, const float *resid, const float *gate_in, const kq_mat *up) {
@@ -274,6 +287,7 @@ static int enqueue_prefill_kq(gemma_engine *e, int T, const pass_rows &rows) {
         k.x = img; k.x_col_stride = ldk; k.y = y; k.y_col_stride = ldy; k.ncols = T;
         k.tiled = W.tiled;
         k.resid = resid; k.gate_in = gate_in; k.gelu_tab = e->gelu_tab; k.gelu_clamp = c.gelu_clamp;
+        if (skinny) return launch_gemm_skinny_kq(W.type, k, s);
         if (up) k.w2 = up->w;
         return launch_matvec_kq(W.type, k, s);
     };
@@ -296,7 +310,7 @@ static int enqueue_prefill_kq(gemma_engine *e, int T, const pass_rows &rows) {
         if (launch_quant_q8_K(p.ATT, e->qw, e->qw, T, img, ldk, s) || expand(e->qw)) return -1;
         if (mv(K.o, p.SA, E, p.X, nullptr, nullptr)) return -1;  // + inpL
         if (launch_norm_q8K(p.SA, E, L.ffn_norm, (int)E, c.eps, T, img, ldk, s) || expand(E)) return -1;
-        if (K.gate.type == K.up.type && K.gate.rows == K.up.rows && K.gate.K == K.up.K && e->kq_dual &&
+        if (K.gate.type == K.up.type && K.gate.rows == K.up.rows && K.gate.K == K.up.K && e->kq_dual && !skinny &&
             !(mfma_ok(K.gate) && mfma_ok(K.up))) {
             if (mv(K.gate, p.U, F, nullptr, nullptr, &K.up)) return -1;  // gelu(gate)*up
         } else if (mv(K.gate, p.G, F, nullptr, nullptr, nullptr) || mv(K.up, p.U, F, nullptr, p.G, nullptr)) {

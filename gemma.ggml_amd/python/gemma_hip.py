@@ -39,7 +39,7 @@ EXPORTS = ["mul_mat", "hpc_init", "hpc_shutdown", "hpc_register_weight", "hpc_la
            "gemma_engine_create_from_gguf", "gemma_engine_config",
            "gemma_engine_set_sampler", "gemma_engine_sampler", "gemma_test_sample",
            "gemma_engine_verify", "gemma_engine_kv_read", "gemma_lookup_draft", "gemma_engine_generate_lookup",
-           "gemma_test_gemm_skinny", "gemma_test_matvec", "gemma_hip_mem_live",
+           "gemma_test_gemm_skinny", "gemma_test_gemm_skinny_kq", "gemma_test_matvec", "gemma_hip_mem_live",
            "gemma_engine_batch_open", "gemma_engine_batch_close", "gemma_engine_batch_begin", "gemma_engine_batch_adopt",
            "gemma_engine_batch_release", "gemma_engine_batch_step", "gemma_engine_batch_pos", "gemma_engine_batch_tokens",
            "gemma_engine_batch_last", "gemma_engine_batch_kv_read", "gemma_engine_batch_open_wide",
@@ -209,6 +209,8 @@ def lib():
     L.gemma_engine_generate_lookup.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(SpecStats)]
     L.gemma_test_gemm_skinny.restype = C.c_int
     L.gemma_test_gemm_skinny.argtypes = [C.c_int, i64, i64, i64, vp, vp, vp, vp]
+    L.gemma_test_gemm_skinny_kq.restype = C.c_int
+    L.gemma_test_gemm_skinny_kq.argtypes = [C.c_int, i64, i64, i64, C.c_int, vp, vp, vp, vp]
     for fn, at in (("open", [C.c_int]), ("close", []), ("begin", [C.c_int, vp, C.c_int]), ("adopt", [C.c_int]),
                    ("release", [C.c_int]), ("step", [C.c_int, vp]), ("pos", [C.c_int]), ("tokens", [C.c_int, vp, C.c_int]),
                    ("last", [vp]), ("kv_read", [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
@@ -923,6 +925,21 @@ def gemm_skinny(wtype, W, rows, X, resid=None):
     rc = lib().gemma_test_gemm_skinny(int(wtype), rows, K, T, _p(w), _p(x), None if r is None else _p(r), _p(y))
     if rc != 0:
         raise RuntimeError("gemma_test_gemm_skinny failed: " + last_error())
+    return y
+
+
+def gemm_skinny_kq(wtype, W, rows, X, resid=None, tiled=0):
+    """The skinny exact K-quant GEMM on host buffers (gemma_test_gemm_skinny_kq): W raw ggml Q4_K /
+    Q6_K rows, X [T][K] f32, resid [T][rows] or None, tiled 1 = the lane-contiguous layout; returns
+    Y [T][rows]."""
+    x = np.ascontiguousarray(X, dtype=np.float32)
+    T, K = x.shape
+    y = np.zeros((T, rows), dtype=np.float32)
+    r = None if resid is None else np.ascontiguousarray(resid, dtype=np.float32)
+    w = np.ascontiguousarray(W)
+    rc = lib().gemma_test_gemm_skinny_kq(int(wtype), rows, K, T, int(tiled), _p(w), _p(x), _p(y), None if r is None else _p(r))
+    if rc != 0:
+        raise RuntimeError("gemma_test_gemm_skinny_kq failed: " + last_error())
     return y
 
 

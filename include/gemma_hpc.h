@@ -473,7 +473,10 @@ int gemma_engine_set_fuse(gemma_engine *e, int fuse_front); /* fused layer front
 int gemma_engine_set_att_o(gemma_engine *e, int on);
 /* The measured variants that stay selectable (tests, A/B), set through the API rather than the
    environment: "kq_fuse" (K-quant Q8_K INIT plan 0..6), "kq_dual" (gate+up one launch), "kq_pair"
-   (q|k and v one launch), "kq_abl" (timing ablation, wrong results), "att_mx" (exact prefill attention
+   (q|k and v one launch), "kq_skinny" (K-quant matrices and the Q6_K head in passes of up to 8 rows —
+   verify, narrow batch passes and groups: 1 = the skinny K-quant GEMM, every super-block loaded once
+   for all rows; 0 = the T-column / MFMA kernels; default 2 = the skinny GEMM from 4 rows, where it
+   measured faster; same bits), "kq_abl" (timing ablation, wrong results), "att_mx" (exact prefill attention
    on the f32 matrix cores: 1 = the LDS form where it fits, the key-split form past 2556 keys, else the row form;
    0 = the row form only; 2 = the key-split form wherever it is supported), "att_win" (the decode
    step's split attention past n_ctx 2048: 0 = P16 in windows only where the resident image does not fit the LDS, 1 = in
@@ -589,6 +592,13 @@ int gemma_test_gemm_exact(int type, int64_t rows, int64_t K, int64_t T, const vo
  * bit-identical to gemma_test_gemm_exact and mul_mat.  T outside [1, 8]: -1 with hpc_last_error */
 int gemma_test_gemm_skinny(int type, int64_t rows, int64_t K, int64_t T, const void *W, const float *X,
                            const float *resid, float *Y);
+/* the K-quant counterpart (the skinny exact Q4_K / Q6_K GEMM of skinny passes on K-quant layers and the
+ * Q6_K output head: each weight super-block loaded and decoded once for all T columns): W raw ggml rows
+ * of `type` (tiled = 1: a device copy in the engine's lane-contiguous layout), Y[T][rows] = W x Q8_K(X)
+ * (+ resid [T][rows], may be NULL); bit-identical to mul_mat.  T outside [1, 8], K % 256 != 0, or tiled
+ * Q6_K with K % 2048 != 0: -1 with hpc_last_error, nothing touched */
+int gemma_test_gemm_skinny_kq(int type, int64_t rows, int64_t K, int64_t T, int tiled, const void *W, const float *X,
+                              float *Y, const float *resid);
 /* per-op test entry: ONE decode matvec launch (either form) on host buffers, every argument of the
  * launch set by the caller, so that a test can make each of them distinguishable.
  * pro: 0 x = ncols columns of K floats (x_stride floats apart), 1 the same through rms_norm * norm_w,
