@@ -111,6 +111,8 @@ static int batch_open(gemma_engine *e, int n_slots, int max_slots, int rows, con
           pick_buf_alloc(M, b.picks, s) || M.get(&b.stage, NS * sizeof(slot_row), MEM_PINNED) ||
           // more rows than the engine's sampler has workspaces: the batch brings its own, one per row
           (rows > NARROW && sample_ws_alloc(M, &b.picks.ws, e->cfg.n_vocab, s, rows)) ||
+          // and, while penalties are on, more save lists than the engine's 8 (else made when they are turned on)
+          (e->penalising && b.pf.T > NARROW && penalty_ws_alloc(M, &b.picks.pen, s, b.pf.T)) ||
           // the tables of a pass with several rows per slot (gemma_engine_batch_step_rows)
           M.get_zeroed(&b.mrows, NS * sizeof(slot_row), s) || M.get_zeroed(&b.msrc, NS * sizeof(row_src), s) ||
           M.get_zeroed(&b.mspans, NS * sizeof(slot_span), s) || M.get_zeroed(&b.mrope, NS * rope_words * 4, s) ||
@@ -135,6 +137,13 @@ static int batch_open(gemma_engine *e, int n_slots, int max_slots, int rows, con
     b.n_slots = n_slots;
     b.open = true;
     return 0;
+}
+
+// gemma_engine_set_penalties with a batch open: the batch's own save lists, one per row of its widest pass
+int batch_penalty_ws(gemma_engine *e) {
+    batch_state &b = e->bt;
+    if (!e->penalising || !b.open || b.pf.T <= NARROW || b.picks.pen.list) return 0;
+    return penalty_ws_alloc(e->bt_mem, &b.picks.pen, e->stream, b.pf.T);
 }
 
 extern "C" int gemma_engine_batch_open(gemma_engine *e, int n_slots) {
@@ -530,6 +539,7 @@ extern "C" int gemma_engine_batch_verify(gemma_engine *e, const int32_t *draft, 
     const gemma_hip_config &c = e->cfg;
     batch_state &b = e->bt;
     constexpr int KD = GEMMA_VERIFY_MAX_DRAFT;
+    if (penalties_refuse(e, fn.c_str())) return -1;
     if (!b.open) {
         set_error(fn + ": no batch is open (gemma_engine_batch_open)");
         return -1;

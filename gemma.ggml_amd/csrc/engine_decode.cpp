@@ -176,11 +176,30 @@ int enqueue_pick_keys(gemma_engine *e, const float *row, const int *pos, const u
     return 0;
 }
 
+// The penalties around a pass's picks (penalty.hip): the rows LG changed in place over each row's own
+// window, and put back once the pick kernels have read them.  Off: nothing is launched.
+static penalty_args penalty_of(gemma_engine *e, const float *LG, int T, const int *pos, const slot_row *tab) {
+    penalty_args a;
+    a.lg = const_cast<float *>(LG); a.ld = e->cfg.n_vocab; a.n_vocab = e->cfg.n_vocab; a.rows = T;
+    a.prm = e->pen_dev; a.tab = tab; a.pos = pos; a.hist = e->seq.hist; a.hist_cap = e->cfg.n_ctx + 1;
+    return a;
+}
+
 int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *keys, int n_parts, const float *rows0, int R,
                  lp_scratch own) {
     if (!rows0) { rows0 = row; R = 1; }
     if (enqueue_lp_parts(e, rows0, R, own)) return -1;
+    const penalty_args pa = penalty_of(e, row, 1, e->seq.pos, nullptr);
+    if (e->penalising) {
+        if (launch_penalty_apply(pa, e->pen_ws, e->stream)) return -1;
+        // the caller's greedy keys are the raw row's: the row argmax of the penalised row instead
+        if (!e->sampling) {
+            if (launch_row_argmax(row, e->cfg.n_vocab, e->key, 256, e->stream)) return -1;
+            keys = e->key; n_parts = 256;
+        }
+    }
     if (enqueue_pick_keys(e, row, e->seq.pos, &keys, &n_parts)) return -1;
+    if (e->penalising && launch_penalty_restore(pa, e->pen_ws, e->stream)) return -1;
     if (launch_advance(keys, n_parts, e->seq.token, e->seq.pos, e->seq.hist, e->cfg.n_ctx, e->seq.nfix, rope_of(e), e->stream)) return -1;
     return enqueue_lp_finish(e, rows0, R, own, &e->seq, nullptr, nullptr);
 }
@@ -244,8 +263,15 @@ int enqueue_row_picks(gemma_engine *e, const float *LG, int T, const int *pos, c
     // every sampling row in its own workspace: the buffer's own (a wide batch's, or a narrow batch's on
     // an engine that has none), else the engine's 8
     const sample_ws &w = b.ws.hist ? b.ws : e->smp_ws;
-    return launch_picks(mix, LG, V, T, V, e->smp_dev, pos, tab, w, b.keys, PICK_MAX_ROWS, sample_dbg{}, e->stream, &out->keys,
-                        &out->n_parts, &out->stride);
+    // penalties: every row over its own window (through the row table: its slot's history, its own position
+    // word), the raw rows back before the caller's advance, logits copy and enqueue_lp_finish
+    const penalty_args pa = penalty_of(e, LG, T, pos, tab);
+    const penalty_ws &pw = b.pen.list ? b.pen : e->pen_ws;
+    if (e->penalising && launch_penalty_apply(pa, pw, e->stream)) return -1;
+    if (launch_picks(mix, LG, V, T, V, e->smp_dev, pos, tab, w, b.keys, PICK_MAX_ROWS, sample_dbg{}, e->stream, &out->keys,
+                     &out->n_parts, &out->stride))
+        return -1;
+    return e->penalising ? launch_penalty_restore(pa, pw, e->stream) : 0;
 }
 
 // the decode tail of a Q6_K tied output: rms_norm*out_norm -> Q8_K (have_img: the last down handed
@@ -256,7 +282,8 @@ static int step_tail_q6k(gemma_engine *e, bool have_img) {
     const int E = c.n_embd;
     if (!have_img && launch_norm_q8K(e->x, E, e->out_norm, E, c.eps, 1, e->xq8k, (E / 256) * 292, s)) return -1;
     if (enqueue_logits_q6k(e, e->xq8k, 1, e->logits)) return -1;
-    if (!e->sampling && launch_row_argmax(e->logits, c.n_vocab, e->key, 256, s)) return -1;
+    // (penalties on: enqueue_pick runs the row argmax itself, on the penalised row)
+    if (!e->sampling && !e->penalising && launch_row_argmax(e->logits, c.n_vocab, e->key, 256, s)) return -1;
     return enqueue_pick(e, e->logits, e->key, 256);
 }
 

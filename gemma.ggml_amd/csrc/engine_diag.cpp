@@ -272,6 +272,10 @@ extern "C" int gemma_engine_graph_kernels(gemma_engine *e) {
 extern "C" int gemma_engine_set_persist(gemma_engine *e, int on) {
     set_error("");
     (void)hipSetDevice(e->device);
+    if (on > 0 && e->penalising) {
+        set_error("gemma_engine_set_persist: penalties are on (gemma_engine_set_penalties): they run with the per-layer launches");
+        return -1;
+    }
     if (on >= 0 && on != e->persist) {
         e->persist = on;
         drop_graph(e);
@@ -399,6 +403,116 @@ extern "C" int gemma_engine_set_sampler(gemma_engine *e, const gemma_sampler *sp
 extern "C" int gemma_engine_sampler(const gemma_engine *e, gemma_sampler *out) {
     if (out) *out = e->smp;
     return e->sampling ? 1 : 0;
+}
+
+// Penalties on / off and their values (include/gemma_hpc.h).  The values live in a device struct the two
+// kernels of penalty.hip read, and their geometry is the row count alone: new values or a new last_n are
+// a stream-ordered copy and the captured graph is kept; on / off changes the node set and drops it.
+extern "C" int gemma_engine_set_penalties(gemma_engine *e, const gemma_penalties *p) {
+    set_error("");
+    const std::string fn = "gemma_engine_set_penalties";
+    if (p) {
+        const std::string why = penalties_invalid(*p);
+        if (!why.empty()) {
+            set_error(fn + ": " + why);
+            return -1;
+        }
+    }
+    const bool on = p && !penalties_off(*p);
+    if (on && (row_split(e) || e->tp_n_keys)) {
+        set_error(fn + ": row-split engines hold a vocabulary shard per rank; a penalised pick needs the whole row "
+                  "(single-GPU engines only)");
+        return -1;
+    }
+    if (on && e->persist) {
+        set_error(fn + ": the persistent token launch is on (gemma_engine_set_persist): penalties run with the per-layer launches");
+        return -1;
+    }
+    (void)hipSetDevice(e->device);
+    if (on) {
+        if (!e->pen_dev) {  // made once and kept for the engine's lifetime (the captured graph holds both)
+            if (penalty_ws_alloc(e->mem, &e->pen_ws, e->stream, GEMM_SKINNY_MAX_T)) return -1;
+            if (e->mem.get(&e->pen_dev, sizeof(penalty_params))) {
+                penalty_ws_free(e->mem, &e->pen_ws);
+                return -1;
+            }
+        }
+        // the copy's source must outlive the call: wait for an earlier copy before rewriting it
+        GHIP_CHECK(hipStreamSynchronize(e->stream));
+        e->pen_host.repeat = p->repeat; e->pen_host.presence = p->presence; e->pen_host.frequency = p->frequency;
+        e->pen_host.last_n = p->last_n;
+        GHIP_CHECK(hipMemcpyAsync(e->pen_dev, &e->pen_host, sizeof(penalty_params), hipMemcpyHostToDevice, e->stream));
+    }
+    e->pen = p ? *p : gemma_penalties{1.0f, 0.0f, 0.0f, 64};
+    if (on != e->penalising) {
+        e->penalising = on;
+        drop_graph(e);
+    }
+    return batch_penalty_ws(e);  // an open batch with wider passes than the engine's 8 rows: its own lists
+}
+
+extern "C" int gemma_engine_penalties(const gemma_engine *e, gemma_penalties *out) {
+    if (out) *out = e->pen;
+    return e->penalising ? 1 : 0;
+}
+
+// Test hook: k_penalty_apply and k_penalty_restore on `rows` host rows, each with a history and a position
+// of its own through a row table (as a batch pass reads them), up to 64 rows a launch; the rows are
+// copied out after each kernel
+extern "C" int gemma_test_penalize(const float *logits, int rows, int n_vocab, const int32_t *hist, int hist_ld,
+                                   const int32_t *positions, const gemma_penalties *p, float *penalised, float *restored,
+                                   int32_t *n_saved) {
+    set_error("");
+    const std::string fn = "gemma_test_penalize";
+    if (!logits || !hist || !positions || !penalised || !restored || !n_saved || rows < 1 || n_vocab < 1 || hist_ld < 1) {
+        set_error(fn + ": logits, hist, positions, the three outputs, rows >= 1, n_vocab >= 1 and hist_ld >= 1 are required");
+        return -1;
+    }
+    std::string why = p ? penalties_invalid(*p) : "";
+    for (int r = 0; why.empty() && r < rows; ++r)
+        if (positions[r] < 0 || positions[r] >= hist_ld) why = "positions must be in [0, hist_ld)";
+    if (!why.empty()) {
+        set_error(fn + ": " + why);
+        return -1;
+    }
+    dev_pool tmp;
+    penalty_ws ws;
+    penalty_params hp, *dp = nullptr;  // off unless a setting is given
+    if (p) { hp.repeat = p->repeat; hp.presence = p->presence; hp.frequency = p->frequency; hp.last_n = p->last_n; }
+    const int chunk = std::min(rows, (int)PICK_MAX_ROWS);
+    const size_t row_b = (size_t)n_vocab * 4;
+    float *dl = nullptr;
+    int *dh = nullptr, *dpos = nullptr;
+    slot_row *dtab = nullptr;
+    if (penalty_ws_alloc(tmp, &ws, nullptr, chunk)) return -1;
+    if (tmp.get(&dp, sizeof(hp)) || tmp.get(&dl, row_b * rows) || tmp.get(&dh, (size_t)rows * hist_ld * 4) ||
+        tmp.get(&dpos, (size_t)rows * 4) || tmp.get(&dtab, (size_t)rows * sizeof(slot_row)))
+        return -1;
+    std::vector<slot_row> htab(rows);
+    for (int r = 0; r < rows; ++r) {
+        htab[r].hist = dh + (size_t)r * hist_ld;
+        htab[r].pos = dpos + r;
+    }
+    GHIP_CHECK(hipMemcpy(dp, &hp, sizeof(hp), hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(dl, logits, row_b * rows, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(dh, hist, (size_t)rows * hist_ld * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(dpos, positions, (size_t)rows * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(dtab, htab.data(), (size_t)rows * sizeof(slot_row), hipMemcpyHostToDevice));
+    GHIP_CHECK(hipDeviceSynchronize());  // (the workspace's counts were zeroed on the null stream)
+    for (int r = 0; r < rows; r += chunk) {
+        const int T = std::min(chunk, rows - r);
+        penalty_args a;
+        a.lg = dl + (size_t)r * n_vocab; a.ld = n_vocab; a.n_vocab = n_vocab; a.rows = T; a.prm = dp; a.tab = dtab + r;
+        a.hist_cap = hist_ld;
+        if (launch_penalty_apply(a, ws, nullptr)) return -1;
+        GHIP_CHECK(hipDeviceSynchronize());
+        GHIP_CHECK(hipMemcpy(penalised + (size_t)r * n_vocab, a.lg, row_b * T, hipMemcpyDeviceToHost));
+        GHIP_CHECK(hipMemcpy(n_saved + r, ws.count, (size_t)T * 4, hipMemcpyDeviceToHost));
+        if (launch_penalty_restore(a, ws, nullptr)) return -1;
+        GHIP_CHECK(hipDeviceSynchronize());
+        GHIP_CHECK(hipMemcpy(restored + (size_t)r * n_vocab, a.lg, row_b * T, hipMemcpyDeviceToHost));
+    }
+    return 0;
 }
 
 // Per-token log-probabilities on / off (include/gemma_hpc.h).  On adds k_lse_parts and k_lse_finish

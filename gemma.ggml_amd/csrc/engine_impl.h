@@ -114,6 +114,7 @@ struct pick_buf {
     sample_ws ws;                        // a batch's own sampler workspaces: a wide batch's, or a narrow one's made by
                                          // batch_set_sampler on an engine that has none (else the engine's 8: smp_ws)
     lp_scratch lp_parts;                 // a wide batch's own log-probability scratch (else the engine's 8 rows: lp_parts)
+    penalty_ws pen;                      // a batch's own save lists when its passes have more than 8 rows (else the engine's 8: pen_ws)
 };
 
 // ---- batched decode (engine_batch.cpp, DESIGN.md §5b⁗) ------------------------------------------
@@ -286,6 +287,12 @@ struct gemma_engine {
     sampler_params smp_host;              // their device form (source of the stream-ordered copy)
     sampler_params *smp_dev = nullptr;
     sample_ws smp_ws;                     // allocated when sampling is first turned on
+    // penalties on the tokens of the sequence so far (gemma_engine_set_penalties; penalty.hip): off = nothing below is used
+    bool penalising = false;
+    gemma_penalties pen{1.0f, 0.0f, 0.0f, 64};  // the setting as given
+    penalty_params pen_host;              // its device form (source of the stream-ordered copy)
+    penalty_params *pen_dev = nullptr;
+    penalty_ws pen_ws;                    // 8 rows, allocated when penalties are first turned on
     // per-token log-probabilities (gemma_engine_set_logprobs; logprob.hip): off = nothing below is used
     bool logprobs = false;
     lp_scratch lp_parts;                  // 8 rows (step, verify, narrow batch); each part allocated when first turned on
@@ -431,6 +438,23 @@ static inline std::string sampler_invalid(const gemma_sampler &s, int64_t n_voca
     return "";
 }
 
+// what is wrong with a penalty setting's fields ("" = valid); the message names the field
+static_assert(GEMMA_PENALTY_MAX_LAST_N == PENALTY_MAX_N, "one value on both sides of the C interface");
+static inline std::string penalties_invalid(const gemma_penalties &p) {
+    if (!std::isfinite(p.repeat) || !std::isfinite(p.presence) || !std::isfinite(p.frequency)) return "a field is not finite";
+    if (!(p.repeat > 0.0f)) return "repeat must be > 0";
+    if (p.last_n < 1 || p.last_n > PENALTY_MAX_N) return "last_n outside [1, " + std::to_string(PENALTY_MAX_N) + "]";
+    return "";
+}
+static inline bool penalties_off(const gemma_penalties &p) { return p.repeat == 1.0f && p.presence == 0.0f && p.frequency == 0.0f; }
+// the entries that stage drafts in the history refuse while penalties are on (fn: the entry's name)
+static inline bool penalties_refuse(const gemma_engine *e, const char *fn) {
+    if (!e->penalising) return false;
+    set_error(std::string(fn) + ": penalties are on (gemma_engine_set_penalties): a draft row's window would sit on staged "
+              "history; turn them off for speculative passes");
+    return true;
+}
+
 // ---- functions that cross translation units (internal: not part of the library's surface) -------
 #pragma GCC visibility push(hidden)
 // engine.cpp
@@ -465,6 +489,8 @@ int enqueue_pick(gemma_engine *e, const float *row, const unsigned long long *ke
 // `row` into the sampler's own key slot, *keys / *n_parts set to that one key; sampling off: nothing
 // is launched and the caller's greedy keys stand
 int enqueue_pick_keys(gemma_engine *e, const float *row, const int *pos, const unsigned long long **keys, int *n_parts);
+// a batch's own save lists (bt.picks.pen) once penalties are on and its passes can have more than 8 rows
+int batch_penalty_ws(gemma_engine *e);
 // The pick of every row of a pass: LG [T][n_vocab], T <= 64; the device position word of row t is
 // tab[t].pos when the pass has a row table, else pos + t (its token is that sequence's index *pos_t + 1).
 // Enqueues the sampler's draws (sampling on: three launches, six over the whole vocabulary) or the row argmaxes (one launch) into b

@@ -244,7 +244,8 @@ static int enqueue_prefill(gemma_engine *e, int T, const pass_rows &rows, bool e
     // that is still a given token (k_advance's p >= n_fixed guard: a pass that ends mid-prompt)
     // (with the sampler on: its draw at position p0+T from the same row, after *pos is in place)
     const float *last_row = p.LG + (size_t)(T - 1) * c.n_vocab;
-    if (!e->sampling && launch_row_argmax(last_row, c.n_vocab, (unsigned long long *)p.keys, 256, s)) return -1;
+    // (penalties on: enqueue_pick runs the row argmax itself, on the penalised row)
+    if (!e->sampling && !e->penalising && launch_row_argmax(last_row, c.n_vocab, (unsigned long long *)p.keys, 256, s)) return -1;
     const int last = p0 + T - 1;
     GHIP_CHECK(hipMemcpyAsync(e->seq.pos, &last, 4, hipMemcpyHostToDevice, s));
     // (log-probabilities on: all T rows are scored, row t against hist[p0 + t + 1])

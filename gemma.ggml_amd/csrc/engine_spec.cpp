@@ -21,6 +21,7 @@ extern "C" int gemma_engine_verify(gemma_engine *e, const int32_t *draft, int k,
     set_error("");
     const gemma_hip_config &c = e->cfg;
     const int p0 = e->seq.host_pos;
+    if (penalties_refuse(e, "gemma_engine_verify")) return -1;
     if (row_split(e)) {
         set_error("gemma_engine_verify: single-GPU engines only (row-split engines decode token by token)");
         return -1;
@@ -131,6 +132,7 @@ extern "C" int gemma_engine_generate_lookup(gemma_engine *e, int n_new, int k, i
     set_error("");
     const gemma_hip_config &c = e->cfg;
     gemma_spec_stats st{0, 0, 0, 0};
+    if (penalties_refuse(e, "gemma_engine_generate_lookup")) return -1;
     if (n_new < 0 || (n_new > 0 && !out) || k < 1 || k > GEMMA_VERIFY_MAX_DRAFT || ngram_max < 1) {
         set_error("gemma_engine_generate_lookup: needs n_new >= 0, 1 <= k <= " + std::to_string(GEMMA_VERIFY_MAX_DRAFT) +
                   " and ngram_max >= 1");
@@ -180,6 +182,7 @@ extern "C" int gemma_engine_batch_generate_lookup(gemma_engine *e, int n_new, in
     const gemma_hip_config &c = e->cfg;
     batch_state &b = e->bt;
     constexpr int KD = GEMMA_VERIFY_MAX_DRAFT, NS = GEMMA_BATCH_WIDE_MAX_SLOTS;
+    if (penalties_refuse(e, fn.c_str())) return -1;
     if (!b.open) {
         set_error(fn + ": no batch is open (gemma_engine_batch_open)");
         return -1;

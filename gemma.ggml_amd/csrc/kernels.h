@@ -632,6 +632,37 @@ int launch_picks(int mix, const float *lg, int64_t ld, int rows, int64_t n, cons
                  const slot_row *tab, const sample_ws &w, unsigned long long *keys, int rows_cap, const sample_dbg &dbg,
                  hipStream_t s, const unsigned long long **out_keys, int *out_parts, int *out_stride);
 
+// ---- repetition / presence / frequency penalties (penalty.hip; the rule: include/gemma_hpc.h, DESIGN.md §5b″) ----
+constexpr int PENALTY_MAX_N = 8192;  // window entries at most (GEMMA_PENALTY_MAX_LAST_N): 32 KiB of LDS as u32
+struct penalty_params {  // the setting as the kernels read it (device memory; a change is a stream-ordered copy)
+    float repeat = 1.0f, presence = 0.0f, frequency = 0.0f;
+    int last_n = 0;      // 0: off (as is repeat 1, presence 0, frequency 0): the row is left as it is
+};
+struct penalty_ws {      // the save lists of `rows` rows of a launch (penalty_ws_alloc)
+    int rows = 0;
+    uint2 *list = nullptr;      // [rows][PENALTY_MAX_N] (token, raw logit bits) of every logit k_penalty_apply changed
+    unsigned *count = nullptr;  // [rows] entries of each list; k_penalty_restore leaves it zero
+};
+int penalty_ws_alloc(dev_pool &mem, penalty_ws *w, hipStream_t s, int rows);  // both buffers, or none
+void penalty_ws_free(dev_pool &mem, penalty_ws *w);
+// The rows of a pass (grid.x = row, 1,024 threads): row r is lg + r * ld, n_vocab logits, changed in place.
+// It processed sequence index p_r of the history h_r: tab[r].pos / tab[r].hist when a row table is given,
+// else pos[r] and hist + r * hist_ld.  h_r holds hist_cap words; a p_r outside [0, hist_cap) leaves the row alone.
+struct penalty_args {
+    float *lg = nullptr;
+    int64_t ld = 0;
+    int n_vocab = 0, rows = 0;
+    const penalty_params *prm = nullptr;  // device: one setting for every row
+    const slot_row *tab = nullptr;
+    const int *pos = nullptr, *hist = nullptr;
+    int64_t hist_ld = 0;
+    int hist_cap = 0;
+};
+// apply: l'[t] for every in-range token t of row r's window, the raw bits saved in w; restore: the raw
+// bits back, w's counts zero.  Always in pairs on the same arguments, the picks of the rows between them.
+int launch_penalty_apply(const penalty_args &a, const penalty_ws &w, hipStream_t s);
+int launch_penalty_restore(const penalty_args &a, const penalty_ws &w, hipStream_t s);
+
 // ---- per-token log-probabilities (logprob.hip; the rule: include/gemma_hpc.h, DESIGN.md §5b⁗′) ----
 constexpr int LSE_CHUNK = 1024;  // logits per workgroup of k_lse_parts: G = ceil(n_vocab / LSE_CHUNK), n_vocab alone
 constexpr int LSE_MAX_G = 1024;  // partials k_lse_finish merges (n_vocab <= 2^20)

@@ -50,7 +50,8 @@ EXPORTS = ["mul_mat", "hpc_init", "hpc_shutdown", "hpc_register_weight", "hpc_la
            "gemma_engine_batch_set_sampler", "gemma_engine_batch_sampler", "gemma_engine_batch_fork",
            "gemma_test_sample_rows", "gemma_test_rope_kv_prefill", "gemma_test_rows_rope_kv",
            "gemma_test_attn_prefill", "gemma_test_attn_decode_rows", "gemma_test_attn_long_rows",
-           "gemma_test_attn_mx_long"]
+           "gemma_test_attn_mx_long",
+           "gemma_engine_set_penalties", "gemma_engine_penalties", "gemma_test_penalize"]
 
 
 def build():
@@ -73,6 +74,12 @@ class GemmaSampler(C.Structure):
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("seed", C.c_uint64)]
 
 
+class GemmaPenalties(C.Structure):
+    """struct gemma_penalties (include/gemma_hpc.h): repeat 1, presence 0, frequency 0 is off."""
+    _fields_ = [("repeat", C.c_float), ("presence", C.c_float), ("frequency", C.c_float), ("last_n", C.c_int)]
+
+
+PENALTY_MAX_LAST_N = 8192  # include/gemma_hpc.h GEMMA_PENALTY_MAX_LAST_N
 SAMPLE_MAX_K = 1024  # candidates at most (top_k == 0 means this many)
 TOP_K_ALL = 0x7FFFFFFF  # top_k of the whole-vocabulary sampler (GEMMA_TOP_K_ALL): every entry a candidate, nothing sorted
 VERIFY_MAX_DRAFT = 7  # include/gemma_hpc.h GEMMA_VERIFY_MAX_DRAFT
@@ -199,6 +206,12 @@ def lib():
     L.gemma_test_sample.argtypes = [vp, C.c_int, C.c_int, C.POINTER(GemmaSampler), vp, vp, vp, vp, vp]
     L.gemma_test_sample_rows.restype = C.c_int
     L.gemma_test_sample_rows.argtypes = [vp, C.c_int, C.c_int, C.POINTER(GemmaSampler), vp, vp, vp, vp, vp]
+    L.gemma_engine_set_penalties.restype = C.c_int
+    L.gemma_engine_set_penalties.argtypes = [vp, C.POINTER(GemmaPenalties)]
+    L.gemma_engine_penalties.restype = C.c_int
+    L.gemma_engine_penalties.argtypes = [vp, C.POINTER(GemmaPenalties)]
+    L.gemma_test_penalize.restype = C.c_int
+    L.gemma_test_penalize.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.POINTER(GemmaPenalties), vp, vp, vp]
     L.gemma_engine_verify.restype = C.c_int
     L.gemma_engine_verify.argtypes = [vp, vp, C.c_int, vp, vp]
     L.gemma_engine_kv_read.restype = C.c_int
@@ -670,6 +683,24 @@ class Engine:
         on = self.L.gemma_engine_sampler(self.h, C.byref(s))
         return on == 1, dict(temperature=s.temperature, top_k=s.top_k, top_p=s.top_p, seed=s.seed)
 
+    def set_penalties(self, repeat=1.0, presence=0.0, frequency=0.0, last_n=64):
+        """Repetition, presence and frequency penalties over the last last_n tokens of the sequence, applied
+        on the device ahead of every pick (include/gemma_hpc.h has the rule).  repeat None, or the defaults
+        (1, 0, 0): off.  A change of values or of last_n keeps the captured graph; on / off drops it.
+        Raises on a refused setting, a row-split engine or the persistent launch."""
+        if repeat is None:
+            r = self.L.gemma_engine_set_penalties(self.h, None)
+        else:
+            p = GemmaPenalties(float(repeat), float(presence), float(frequency), int(last_n))
+            r = self.L.gemma_engine_set_penalties(self.h, C.byref(p))
+        self._chk(r, "set_penalties")
+
+    def penalties(self):
+        """(penalties on, {repeat, presence, frequency, last_n} as last set)"""
+        p = GemmaPenalties()
+        on = self.L.gemma_engine_penalties(self.h, C.byref(p))
+        return on == 1, dict(repeat=p.repeat, presence=p.presence, frequency=p.frequency, last_n=p.last_n)
+
     def set_logprobs(self, on=-1):
         """Per-token log-probabilities under the raw softmax of every logits row a pass computes
         (include/gemma_hpc.h has the rule): on 1 / off 0 / keep -1; returns the setting.  On / off drops
@@ -850,6 +881,36 @@ def test_sample_rows(rows, samplers, positions):
 
 
 test_sample_rows.__test__ = False
+
+
+def _penalties(p):
+    """dict(repeat, presence, frequency, last_n) or a tuple in that order -> GemmaPenalties"""
+    if isinstance(p, dict):
+        p = (p.get("repeat", 1.0), p.get("presence", 0.0), p.get("frequency", 0.0), p.get("last_n", 64))
+    return GemmaPenalties(float(p[0]), float(p[1]), float(p[2]), int(p[3]))
+
+
+def test_penalize(rows, hist, positions, penalties, out=None):
+    """The two penalty kernels on host logits rows [R][V] (gemma_test_penalize): row r processed sequence
+    index positions[r] of its own history hist[r] ([R][H] int32, H > every position).  penalties:
+    dict(repeat, presence, frequency, last_n), such a tuple, or None for a setting that is off.  Returns
+    (penalised [R][V], restored [R][V], n_saved [R]), written into `out` when that triple is given;
+    raises RuntimeError with the library's message on a refused argument (the outputs are then untouched)."""
+    x = np.ascontiguousarray(rows, dtype=np.float32)
+    h = np.ascontiguousarray(hist, dtype=np.int32)
+    R, V = x.shape
+    pos = np.ascontiguousarray(positions, dtype=np.int32)
+    if pos.shape != (R,) or h.ndim != 2 or h.shape[0] != R:
+        raise ValueError("positions and hist: one per row")
+    pen, res, n_saved = out if out is not None else (np.zeros_like(x), np.zeros_like(x), np.zeros(R, dtype=np.int32))
+    p = None if penalties is None else C.byref(_penalties(penalties))
+    r = lib().gemma_test_penalize(_p(x), R, V, _p(h), h.shape[1], _p(pos), p, _p(pen), _p(res), _p(n_saved))
+    if r != 0:
+        raise RuntimeError("gemma_test_penalize failed: " + last_error())
+    return pen, res, n_saved
+
+
+test_penalize.__test__ = False
 
 
 def test_logprob(rows, tokens):

@@ -196,6 +196,38 @@ int gemma_test_sample(const float *logits, int rows, int n_vocab, const gemma_sa
  * the launch the engine uses) with n_cand = n_kept = 0 and cand[r][*] = -1 */
 int gemma_test_sample_rows(const float *logits, int rows, int n_vocab, const gemma_sampler *s_of,
                            const int32_t *positions, int32_t *tokens, int32_t *cand, int32_t *n_cand, int32_t *n_kept);
+/* Repetition, presence and frequency penalties inside the pick (no host round trip; DESIGN.md §5b″
+ * "Penalties").  With penalties on, the logits row l[0..V) that processed sequence index p (it gives the
+ * token of index p + 1) is penalised over the window W = hist[max(0, p + 1 - last_n) .. p] before the
+ * pick reads it: with c_t the number of occurrences of token t in W, every t in [0, V) with c_t > 0 gets
+ *     a     = (l[t] <= 0) ? l[t] * repeat : l[t] / repeat          (-0 takes the first arm)
+ *     pen   = ((float)c_t * frequency) + presence
+ *     l'[t] = a - pen
+ * each an f32 operation rounded once to nearest (no fused multiply-add, the correctly rounded division);
+ * ids outside [0, V) are ignored and every other entry is unchanged.  The pick then runs on l' exactly as
+ * it runs on l without penalties: greedy (larger logit, then smaller index) or either sampler rule above.
+ * The row is changed in place and put back right after the pick: log-probabilities and alternatives score
+ * the raw row, and every logits copy to the host (step, prefill, batch_step) is the raw row bit for bit.
+ * The engine's setting covers its own sequence (step, eager and graph; the final pick of prefill,
+ * prefill_fast and prefill_next) and every slot of a batch (batch_step, batch_step_rows: each row over its
+ * own slot's history at its own position).  While penalties are on, gemma_engine_verify,
+ * gemma_engine_generate_lookup, gemma_engine_batch_verify and gemma_engine_batch_generate_lookup return -1
+ * (their draft rows sit on staged history).  Changing the values of a running setting, last_n included, is
+ * a stream-ordered copy and keeps the captured decode graph; turning penalties on or off drops it. */
+#define GEMMA_PENALTY_MAX_LAST_N 8192
+typedef struct gemma_penalties { float repeat; float presence; float frequency; int last_n; } gemma_penalties;
+/* NULL, or repeat == 1 && presence == 0 && frequency == 0: off (the default; nothing is launched).  -1 +
+ * hpc_last_error, state untouched, on repeat <= 0, a non-finite field, last_n outside [1, 8192], a
+ * row-split engine, or an engine with the persistent launch on. */
+int gemma_engine_set_penalties(gemma_engine *e, const gemma_penalties *p);
+int gemma_engine_penalties(const gemma_engine *e, gemma_penalties *out);   /* 1 = on, 0 = off */
+/* per-op test entry: the two kernels on host rows.  Row r is logits + r * n_vocab, its history
+ * hist + r * hist_ld (hist_ld > max position), and it processed sequence index positions[r] >= 0.
+ * penalised[rows][n_vocab]: the rows after k_penalty_apply; restored: after k_penalty_restore; n_saved[r]:
+ * the save count apply left (the distinct in-range tokens of the window).  p == NULL: the setting is off */
+int gemma_test_penalize(const float *logits, int rows, int n_vocab, const int32_t *hist, int hist_ld,
+                        const int32_t *positions, const gemma_penalties *p,
+                        float *penalised, float *restored, int32_t *n_saved);
 /* Per-token log-probabilities on the device (DESIGN.md §5b⁗′).  For a logits row l[0..V) (f32) and a
  * token t: M = max_i l[i] compared as floats (-0 == +0); S = sum_i exp((double)l[i] - (double)M) in
  * f64 (an -inf entry contributes 0; S >= 1); logprob(l, t) = ((double)l[t] - (double)M) - log(S), -inf
