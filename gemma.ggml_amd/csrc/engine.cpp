@@ -968,6 +968,55 @@ extern "C" int gemma_engine_extend(gemma_engine *e, int keep, const int32_t *tok
     return 0;
 }
 
+// The context shift of a sequence, the engine's own or a slot (DESIGN.md §5b′ "Context shift"): positions
+// [keep, keep + discard) leave, the rest moves down (kv_shift.hip: K rotated back by `discard`, V as
+// bits, hist with the pending token), and from pos - discard on the state is what a rewind to that
+// position leaves.  The per-position records (log-probabilities, alternatives) are dropped from `keep`
+// on, as gemma_engine_extend(keep) drops them: the row that scored index keep is gone.  own: the engine's
+// own sequence (the epoch, the decode step's argmax keys).  Returns the new position, -1 with the state
+// untouched.  No buffer moves: the captured decode graph is kept.
+int seq_shift(gemma_engine *e, seq_state &S, int keep, int discard, bool own, const char *fn) {
+    const gemma_hip_config &c = e->cfg;
+    const int pos = S.host_pos;
+    auto refuse = [&](const std::string &why) {
+        set_error(std::string(fn) + ": " + why);
+        return -1;
+    };
+    if (keep < 0 || discard < 1 || (int64_t)keep + discard > pos)
+        return refuse("keep = " + std::to_string(keep) + ", discard = " + std::to_string(discard) +
+                      " need 0 <= keep, 1 <= discard, keep + discard <= pos = " + std::to_string(pos));
+    if (S.n_given > pos) return refuse(std::to_string(S.n_given - pos) + " given tokens are not processed yet (prefill or step first)");
+    if (row_split(e)) return refuse("single-GPU engines only (row-split engines are out of scope)");
+    if (!S.kc) return refuse("the caches are external (ggml executor path)");
+    if (own && persist_on(e)) return refuse("the persistent launch is on (gemma_engine_set_persist)");
+    if (const char *why = kv_shift_unsupported(c.n_ctx, c.n_head_kv, c.head_dim)) return refuse(why);
+    (void)hipSetDevice(e->device);
+    hipStream_t s = e->stream;
+    const size_t half = (size_t)c.head_dim / 2, ctx = (size_t)c.n_ctx;
+    kv_shift_args a;
+    a.kc = S.kc; a.vc = S.vc; a.n_layer = c.n_layer; a.layer_stride = (int64_t)c.n_ctx * e->kvw;
+    a.ctx = c.n_ctx; a.Hkv = c.n_head_kv; a.hd = c.head_dim; a.pos = pos; a.keep = keep; a.discard = discard;
+    a.cs = e->rope_cos + (size_t)discard * half; a.sn = e->rope_sin + (size_t)discard * half;  // the query's row of position `discard`
+    if (launch_kv_shift(a, s)) return -1;
+    // given tokens below keep stay given, those behind the dropped span move with it (at least hist[0]: a sequence has one)
+    const int fixed = std::max(1, S.n_given <= keep ? S.n_given : std::max(keep, S.n_given - discard));
+    rope_row rr = rope_of(e);
+    rr.cur = S.rope;
+    if (!own) rr.epoch = nullptr;  // neither the epoch nor the decode step's keys belong to a slot
+    if (launch_seq_shift(S.hist, S.pos, S.nfix, fixed, pos, keep, discard, rr, own ? e->key : nullptr, own ? e->grid_big : 0, s)) return -1;
+    GHIP_CHECK(hipMemsetAsync(S.lp + keep, 0xFF, (ctx + 1 - (size_t)keep) * 8, s));
+    if (seq_alt_clear(e, S, keep)) return -1;
+    GHIP_CHECK(hipStreamSynchronize(s));
+    S.n_given = fixed;
+    S.host_pos = pos - discard;
+    return S.host_pos;
+}
+
+extern "C" int gemma_engine_shift(gemma_engine *e, int keep, int discard) {
+    set_error("");
+    return seq_shift(e, e->seq, keep, discard, true, "gemma_engine_shift");
+}
+
 // the decode step captured once in a hipGraph (after a first eager step has set the kernels' LDS attributes)
 int ensure_graph(gemma_engine *e) {
     if (e->graph_exec) return 0;

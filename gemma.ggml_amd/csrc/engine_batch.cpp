@@ -649,6 +649,18 @@ extern "C" int gemma_engine_batch_pos(gemma_engine *e, int slot) {
     return e->bt.slot[slot].host_pos;
 }
 
+// gemma_engine_shift for a slot: the same launchers on the slot's sequence.  The pending token moves with
+// the history, so the slot's token word, its row token and the row table stand as they are
+extern "C" int gemma_engine_batch_shift(gemma_engine *e, int slot, int keep, int discard) {
+    set_error("");
+    if (!slot_ok(e, slot, "gemma_engine_batch_shift")) return -1;
+    if (!e->bt.slot[slot].active) {
+        set_error("gemma_engine_batch_shift: slot " + std::to_string(slot) + " is not active");
+        return -1;
+    }
+    return seq_shift(e, e->bt.slot[slot], keep, discard, false, "gemma_engine_batch_shift");
+}
+
 extern "C" int gemma_engine_batch_tokens(gemma_engine *e, int slot, int32_t *out, int cap) {
     set_error("");
     if (!slot_ok(e, slot, "gemma_engine_batch_tokens")) return -1;

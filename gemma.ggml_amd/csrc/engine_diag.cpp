@@ -1095,6 +1095,38 @@ extern "C" int gemma_test_rows_rope_kv(const float *qkv, int64_t ldqkv, int T, i
     return r;
 }
 
+// the context shift's two cache launches (kv_shift.hip) on one layer's images, whole in and whole out; the RoPE row
+// of position `discard` is the last row of the engine's table builder
+extern "C" int gemma_test_kv_shift(uint16_t *kc_inout, uint16_t *vc_inout, int ctx, int Hkv, int hd, int pos, int keep,
+                                   int discard, float rope_base) {
+    set_error("");
+    if (!kc_inout || !vc_inout || ctx <= 0 || Hkv <= 0 || hd <= 0 || hd % 2 || discard < 1 || discard >= ctx) {
+        set_error("gemma_test_kv_shift: bad arguments (images, shapes, 1 <= discard < ctx)");
+        return -1;
+    }
+    const size_t cache_n = (size_t)ctx * Hkv * hd, half = (size_t)hd / 2;
+    std::vector<float> rc, rs;
+    build_rope(discard + 1, hd, rope_base, rc, rs);
+    dev_pool tmp;
+    float *d_c, *d_s;
+    uint16_t *d_k, *d_v;
+    if (tmp.get(&d_c, half * 4) || tmp.get(&d_s, half * 4) || tmp.get(&d_k, cache_n * 2) || tmp.get(&d_v, cache_n * 2)) return -1;
+    GHIP_CHECK(hipMemcpy(d_c, rc.data() + (size_t)discard * half, half * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_s, rs.data() + (size_t)discard * half, half * 4, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_k, kc_inout, cache_n * 2, hipMemcpyHostToDevice));
+    GHIP_CHECK(hipMemcpy(d_v, vc_inout, cache_n * 2, hipMemcpyHostToDevice));
+    kv_shift_args a;
+    a.kc = d_k; a.vc = d_v; a.n_layer = 1; a.layer_stride = (int64_t)cache_n; a.ctx = ctx; a.Hkv = Hkv; a.hd = hd;
+    a.pos = pos; a.keep = keep; a.discard = discard; a.cs = d_c; a.sn = d_s;
+    const int r = launch_kv_shift(a, nullptr);
+    GHIP_CHECK(hipDeviceSynchronize());
+    if (r == 0) {
+        GHIP_CHECK(hipMemcpy(kc_inout, d_k, cache_n * 2, hipMemcpyDeviceToHost));
+        GHIP_CHECK(hipMemcpy(vc_inout, d_v, cache_n * 2, hipMemcpyDeviceToHost));
+    }
+    return r;
+}
+
 // q16 [T][H][hd], kc [ctx][Hkv*hd], vc [Hkv*hd][ctx] f16; out [T][ldo] f32, copied in before the launch
 // and back after it (columns past H*hd keep what the caller put there).  form 0 k_attn_rows, 1 k_attn_mx,
 // 2 k_attn_prefill; a shape the form's launcher refuses: non-zero with its message, out untouched

@@ -476,6 +476,9 @@ int seq_copy(gemma_engine *e, seq_state &dst, const seq_state &src);
 // K rows / V columns p0 .. p0+n of one layer as [n][kvw] each; fn names the caller in the range error
 int seq_kv_read(gemma_engine *e, const seq_state &S, int layer, int p0, int n, uint16_t *k_rows, uint16_t *v_rows,
                 const char *fn);
+// the context shift: positions [keep, keep + discard) of S dropped, the rest moved down and K re-rotated
+// (kv_shift.hip); own: S is the engine's own sequence.  Returns the new position; synchronises
+int seq_shift(gemma_engine *e, seq_state &S, int keep, int discard, bool own, const char *fn);
 // hist[0 .. min(cap, host_pos + 1)): the pending token included; returns the count
 int seq_tokens(const seq_state &S, int32_t *out, int cap);
 // engine_decode.cpp

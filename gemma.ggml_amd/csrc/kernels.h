@@ -472,6 +472,28 @@ int launch_verify_accept(const verify_args &v, hipStream_t s);
 int launch_verify_clean(uint16_t *kc, uint16_t *vc, int n_layer, int64_t layer_stride, int ctx, int kvw, int p0, int k,
                         const int *accepted, hipStream_t s);
 
+// ---- context shift (kv_shift.hip; gemma_engine_shift, DESIGN.md §5b′ "Context shift") -------------
+// Positions [keep, keep + discard) of a sequence of `pos` processed positions are dropped, in place, in
+// n_layer caches layer_stride elements apart: for x in [keep, pos), V[j][x] = V[j][x + discard] and
+// K[x] = K[x + discard] rotated back by `discard` positions (cs | sn: the RoPE row of position `discard`,
+// hd / 2 floats each, device), zero from pos - discard on.  Two launches, the layer in the grid; every
+// word's reader and writer are one workgroup walking ascending, so nothing orders workgroups.
+struct kv_shift_args {
+    uint16_t *kc = nullptr, *vc = nullptr;  // K [ctx][Hkv*hd], V [Hkv*hd][ctx] of layer 0
+    int n_layer = 1;
+    int64_t layer_stride = 0;
+    int ctx = 0, Hkv = 0, hd = 0;
+    int pos = 0, keep = 0, discard = 0;     // 0 <= keep, 1 <= discard, keep + discard <= pos < ctx
+    const float *cs = nullptr, *sn = nullptr;
+};
+const char *kv_shift_unsupported(int ctx, int Hkv, int hd);  // nullptr: the kernels run these shapes (hd % 16, ctx % 8)
+int launch_kv_shift(const kv_shift_args &a, hipStream_t s);
+// the sequence's words, one launch: hist[x] = hist[x + discard] for x in [keep, pos - discard] (the pending
+// token included), zero behind it up to pos; *pos_word = pos - discard with its RoPE row as k_advance
+// publishes it, *nfix = fixed, the epoch bump, and n_zero argmax keys zeroed (null / 0: none)
+int launch_seq_shift(int *hist, int *pos_word, int *nfix, int fixed, int pos, int keep, int discard, const rope_row &r,
+                     unsigned long long *zero_keys, int n_zero, hipStream_t s);
+
 // ---- batched decode (batch.hip; gemma_engine_batch_*, DESIGN.md §5b⁗) ---------------------------
 // One row of a batch pass: the next token of its own sequence (slot).  The table lives in device
 // memory and is rewritten when the set of active slots changes; no entry depends on a position.

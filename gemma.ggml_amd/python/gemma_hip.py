@@ -51,7 +51,8 @@ EXPORTS = ["mul_mat", "hpc_init", "hpc_shutdown", "hpc_register_weight", "hpc_la
            "gemma_test_sample_rows", "gemma_test_rope_kv_prefill", "gemma_test_rows_rope_kv",
            "gemma_test_attn_prefill", "gemma_test_attn_decode_rows", "gemma_test_attn_long_rows",
            "gemma_test_attn_mx_long",
-           "gemma_engine_set_penalties", "gemma_engine_penalties", "gemma_test_penalize"]
+           "gemma_engine_set_penalties", "gemma_engine_penalties", "gemma_test_penalize",
+           "gemma_engine_shift", "gemma_engine_batch_shift", "gemma_test_kv_shift"]
 
 
 def build():
@@ -212,6 +213,12 @@ def lib():
     L.gemma_engine_penalties.argtypes = [vp, C.POINTER(GemmaPenalties)]
     L.gemma_test_penalize.restype = C.c_int
     L.gemma_test_penalize.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.POINTER(GemmaPenalties), vp, vp, vp]
+    L.gemma_engine_shift.restype = C.c_int
+    L.gemma_engine_shift.argtypes = [vp, C.c_int, C.c_int]
+    L.gemma_engine_batch_shift.restype = C.c_int
+    L.gemma_engine_batch_shift.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.gemma_test_kv_shift.restype = C.c_int
+    L.gemma_test_kv_shift.argtypes = [vp, vp] + [C.c_int] * 6 + [C.c_float]
     L.gemma_engine_verify.restype = C.c_int
     L.gemma_engine_verify.argtypes = [vp, vp, C.c_int, vp, vp]
     L.gemma_engine_kv_read.restype = C.c_int
@@ -392,6 +399,16 @@ class Engine:
         self._chk(self.L.gemma_engine_extend(self.h, int(keep), _p(a), len(a)), "extend")
         self._n_seq = int(keep) + len(a)
 
+    def shift(self, keep, discard):
+        """Context shift (gemma_engine_shift): positions [keep, keep + discard) are dropped, the rest of
+        the caches and of the history moves down and K is rotated back by `discard`; returns the new pos."""
+        n = self.L.gemma_engine_shift(self.h, int(keep), int(discard))
+        if n < 0:
+            raise RuntimeError("shift failed: " + last_error())
+        g = getattr(self, "_n_seq", 0)  # given tokens behind the dropped span move with it
+        self._n_seq = g if g <= keep else max(int(keep), g - int(discard))
+        return n
+
     def prefill_next(self, n=0, want_all=False, exact=True):
         """One batched pass over the next n given tokens (0: all that remain) from the current
         position; returns (token, last-row logits[, the pass's rows]) like prefill().  The token is
@@ -533,6 +550,13 @@ class Engine:
         """Slot dst becomes a device-to-device copy of the active slot src's sequence (caches, history,
         position, pending and unprocessed given tokens); each slot keeps its own sampler setting."""
         self._chk(self.L.gemma_engine_batch_fork(self.h, int(src), int(dst)), "batch_fork")
+
+    def batch_shift(self, slot, keep, discard):
+        """shift() for an active slot (gemma_engine_batch_shift); returns the slot's new pos"""
+        n = self.L.gemma_engine_batch_shift(self.h, int(slot), int(keep), int(discard))
+        if n < 0:
+            raise RuntimeError("batch_shift failed: " + last_error())
+        return n
 
     def batch_close(self):
         self._chk(self.L.gemma_engine_batch_close(self.h), "batch_close")
@@ -888,6 +912,16 @@ def _penalties(p):
     if isinstance(p, dict):
         p = (p.get("repeat", 1.0), p.get("presence", 0.0), p.get("frequency", 0.0), p.get("last_n", 64))
     return GemmaPenalties(float(p[0]), float(p[1]), float(p[2]), int(p[3]))
+
+
+def test_kv_shift(kc, vc, pos, keep, discard, Hkv, hd, rope_base=10000.0):
+    """The context shift's cache kernels on one layer's images, in place (gemma_test_kv_shift): kc
+    [ctx][Hkv*hd], vc [Hkv*hd][ctx], C-contiguous uint16 (f16 bits).  A refusal raises and leaves both as given."""
+    for a in (kc, vc):
+        if a.dtype != np.uint16 or not a.flags.c_contiguous:
+            raise ValueError("test_kv_shift: C-contiguous uint16 images")
+    if lib().gemma_test_kv_shift(_p(kc), _p(vc), kc.shape[0], int(Hkv), int(hd), int(pos), int(keep), int(discard), float(rope_base)) != 0:
+        raise RuntimeError("gemma_test_kv_shift failed: " + last_error())
 
 
 def test_penalize(rows, hist, positions, penalties, out=None):

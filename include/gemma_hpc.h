@@ -136,6 +136,23 @@ int gemma_engine_prefill_fast(gemma_engine *e, float *logits_last, float *logits
  * gemma_engine_step consumes the tokens one by one or gemma_engine_prefill_next in batches.
  * -1 with hpc_last_error and the state untouched on a bad argument. */
 int gemma_engine_extend(gemma_engine *e, int keep, const int32_t *tokens, int n);
+/* Context shift (llama.cpp's n_keep / n_discard; DESIGN.md §5b′ "Context shift"): a sequence outlives
+ * n_ctx.  With pos processed positions (and possibly the pending token at index pos): positions [0, keep)
+ * stay, [keep, keep + discard) are dropped, [keep + discard, pos) move down by `discard` in every layer's
+ * caches, on the device and in place.  V moves as bits.  K is stored after RoPE, so a moved row is rotated
+ * back by `discard` positions: with c | s the RoPE row of position `discard` as a query gets it, for the
+ * pair (x0, x1) = (K[p][i], K[p][i + head_dim/2]) the new row p - discard holds f16(x0 c + x1 s) and
+ * f16(x1 c - x0 s), every product and sum one f32 operation (ggml's f16 rope at position -discard).
+ * Afterwards pos' = pos - discard; the tokens (gemma_engine_tokens) are the old ones without the dropped
+ * span, the pending token included; K rows / V columns and history from pos' on are what
+ * gemma_engine_extend(pos') leaves (zero).  Read straight off this state: a sampler's draws are keyed by
+ * (seed, p) with the new p, and a penalty window reads the shifted history.  The per-position records
+ * (gemma_engine_logprobs, gemma_engine_top_logprobs) are dropped from `keep` on ("not scored"), as
+ * gemma_engine_extend(keep) drops them; new steps score again.  The captured decode graph is kept.
+ * Needs 0 <= keep, 1 <= discard, keep + discard <= pos, every given token processed, head_dim % 16 == 0
+ * and n_ctx % 8 == 0; refused on row-split engines, on external caches and while the persistent launch
+ * is on.  Returns pos', or -1 with hpc_last_error and the state untouched. */
+int gemma_engine_shift(gemma_engine *e, int keep, int discard);
 /* One batched pass over the next `n` given-but-unprocessed tokens, positions [pos, pos+n)
  * (n == 0: all that remain; 1 <= n <= n_seq - pos), against the caches of [0, pos).  exact != 0:
  * bit-identical to the CPU path and to the token-by-token steps; 0: the MFMA tolerance path.
@@ -424,6 +441,9 @@ int gemma_engine_batch_step_rows(gemma_engine *e, int max_rows, float *logits, i
 int gemma_engine_batch_set_sampler(gemma_engine *e, int slot, const gemma_sampler *s);
 int gemma_engine_batch_sampler(gemma_engine *e, int slot, gemma_sampler *out, int *own);
 int gemma_engine_batch_fork(gemma_engine *e, int src, int dst);
+/* gemma_engine_shift for an active slot: the same rule and refusals; gemma_engine_batch_pos,
+ * gemma_engine_batch_tokens and the slot's pending token (gemma_engine_batch_last) follow it */
+int gemma_engine_batch_shift(gemma_engine *e, int slot, int keep, int discard);
 /* Drafts in the batch (DESIGN.md §5b⁗ "Drafts in the batch"): gemma_engine_verify for the slots of the
  * open batch, all in one exact pass.  draft is [n_slots][GEMMA_VERIFY_MAX_DRAFT], k_of [n_slots]; k_of[s]
  * is read for active slots only:
@@ -555,6 +575,11 @@ int gemma_test_rope_kv_prefill(const float *qkv, int64_t ldqkv, int T, int p0, i
  * per row, 1 <= T <= 64, every row on the same caches; q is not touched by that kernel */
 int gemma_test_rows_rope_kv(const float *qkv, int64_t ldqkv, int T, int p0, int H, int Hkv, int hd, int ctx,
                             float rope_base, uint16_t *kc_inout, uint16_t *vc_inout);
+/* per-op test entry: the context shift's cache kernels (kv_shift.hip) on one layer's host images.  kc_inout
+ * [ctx][Hkv*hd] and vc_inout [Hkv*hd][ctx] f16 are copied in whole, shifted once (gemma_engine_shift's rule
+ * for `pos` processed positions) and copied back whole.  A refusal leaves both as given */
+int gemma_test_kv_shift(uint16_t *kc_inout, uint16_t *vc_inout, int ctx, int Hkv, int hd, int pos, int keep, int discard,
+                        float rope_base);
 /* per-op test entry: one causal prefill attention launch on host buffers.  q16 [T][H][hd], kc [ctx][Hkv*hd],
  * vc [Hkv*hd][ctx] f16; row t is position p0 + t; n_kv = the padded key count of the last row (<= ctx).
  * form 0 = the exact rows kernel, 1 = the exact f32 matrix-core kernel, 2 = the approximate f16 MFMA kernel.
